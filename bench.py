@@ -2,10 +2,17 @@
 """bench.py -- BilateralSliceApply forward throughput on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p|1080p_b4|hdrp] [--split rows]
+                    [--full] [--dump-outputs DIR]
     python bench.py --workload train_1080p_b4 [--gpus N]    BASELINE config #4 as stated: training step, 4 x 1080p per GPU,
                                                             ONE flat-bucket gradient all-reduce over the N ranks
     python bench.py --workload hdrp_u16 [--gpus N]          BASELINE config #5 as stated: uint16 / 32767 wire format,
                                                             4000x3000, grid 32x32x8x12, one image per GPU
+
+A plain run sets up, pre-rolls and warms up, times the K steps and prints the JSON line; every measurement beside the
+headline that takes launches of its own (the `sustained` and `pipelined` blocks, `extra.ops`, `cpu_baseline`; for
+train_1080p_b4 the all-reduce alone and the static-feed step) runs only with `--full`.  `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy (dump_outputs()); the inputs are seeded, so two builds of the
+project run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 from a bare shell re-launches itself as N ranks under
 torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1); launched by the driver under
@@ -34,9 +41,9 @@ torch.cuda.synchronize() pairs -- always the wall clock, whatever K is; `value` 
 max over ranks.  Defaults K = 2000, W = 1000.  HIP events on the launch stream bracket the same K launches and give the
 `roofline` block its average kernel duration.  Under SUSTAINED load some boxes alternate between a fast
 state and a ~17 % slower one in episodes of 50-200 ms (profiles/r02/exp35): the `sustained` block
-(N = 1) reports the mean and the spread of 100-launch windows over a further 0.5 s, and
+(N = 1, `--full`) reports the mean and the spread of 100-launch windows over a further 0.5 s, and
 `roofline.frac_sustained` is the roofline fraction at that mean; its `power` entry is the socket power and shader
-clock read beside it (the kernel runs at the package power cap).  The `pipelined` block (N = 1) is the same frames
+clock read beside it (the kernel runs at the package power cap).  The `pipelined` block (N = 1, `--full`) is the same frames
 issued round-robin on TWO streams -- the next frame's pipeline fill under the previous frame's drain, what a
 pipeline of independent frames gets (hdrnet_amd.runtime.FramePipeline) -- reported beside the headline, never as
 `value`.
@@ -46,9 +53,9 @@ Adds to the JSON line:
                   stream around the timed region) vs the 8 TB/s HBM3E peak; `traffic` = HBM bytes
                   per launch from the committed rocprofv3 PMC passes, only if they were collected
                   on the SAME kernel sources (digest of hdrnet_amd/csrc), else null
-  sustained    -- 0.5 s of back-to-back launches after the timed region: mean, fastest / slowest
-                  100-launch window, fraction of windows > 8 % slower than the fastest
-  cpu_baseline -- the reference's own CPU op (oracle/_ref, kind "reference") on ONE core (value),
+  sustained    -- (--full) 0.5 s of back-to-back launches after the timed region: mean, fastest /
+                  slowest 100-launch window, fraction of windows > 8 % slower than the fastest
+  cpu_baseline -- (--full) the reference's own CPU op (oracle/_ref, kind "reference") on ONE core (value),
                   plus legs: nproc whole-image processes of it, and the numpy restatement of
                   jax/bilateral_slice.py; bounded samples, rank 0, N = 1 only
 """
@@ -232,6 +239,37 @@ def emit(result):
         sys.stdout.flush()
     else:
         os.write(_JSON_FD, line)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # everything one `--dump-outputs` run writes, all ranks together
+DUMP_SAMPLE_ELEMENTS = 4 * 2 ** 20  # elements kept of an array larger than its share of the limit
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(outdir, arrays, rank=0, world=1):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, DIR/<name>.npy per array a caller of that
+    path receives (`_rank<r>` appended when N > 1), float32 (float64 stays float64).  An array larger than its share of
+    DUMP_LIMIT_BYTES is written as a fixed sample of its flattened elements: DUMP_SAMPLE_ELEMENTS indices drawn without
+    replacement by a generator seeded with DUMP_SAMPLE_SEED, in ascending order -- the same elements on every run with
+    the same arguments.  Returns {file: what was written} for stderr."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (len(arrays) * world)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.to(torch.float32)
+        n, esz = t.numel(), t.element_size()
+        if n * esz > share:
+            k = min(DUMP_SAMPLE_ELEMENTS, share // esz)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            what = f"sample of {k} of {n} elements (seed {DUMP_SAMPLE_SEED}, ascending flat indices)"
+        else:
+            what = f"all of {tuple(t.shape)}"
+        fname = name + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(outdir, fname), t.cpu().numpy())
+        written[fname] = f"{what}, {t.dtype}".replace("torch.", "")
+    return written
 
 
 def timed(step_fn, steps, dist_on, dev):
@@ -534,6 +572,14 @@ def main():
                     help="images (default): every rank slices its OWN frames, weak scaling.  rows: every frame "
                          "is split into N row bands, one per rank (hdrnet_bilateral_slice_apply_rows_f32), strong "
                          "scaling -- the total work is fixed")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take the measurements that need launches or processes of their "
+                         "own: the `sustained` and `pipelined` blocks, `extra.ops` and `cpu_baseline` (the --no-* "
+                         "options below leave single ones out); train_1080p_b4: the all-reduce alone and the "
+                         "static-feed step.  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; an array over its share "
+                         "of 64 MB as a fixed seeded sample of its elements)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipelined", action="store_true",
                     help="skip the two-stream `pipelined` block: its overlapping launches have longer per-kernel durations "
@@ -559,6 +605,8 @@ def main():
                          "(the dry run of what the driver launches; tests/test_gpu_bench_dryrun.py)")
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)  # tests: gloo + a stub timed body
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -618,6 +666,11 @@ def main():
     wall, gpu_s = timed(step, args.steps, dist_on, dev)
 
     wall_max, gpu_max = hd.max_over_ranks([wall, gpu_s], device=dev if backend == "nccl" else torch.device("cpu"))
+    if args.dump_outputs:
+        out = sets[(args.steps - 1) % nsets][3]  # the buffer set of timed step K - 1
+        if band is not None:
+            out = out[:, band[0]:band[0] + band[1]]
+        print("dump-outputs:", dump_outputs(args.dump_outputs, {"out": out}, rank, world), file=sys.stderr)
 
     # `value`: always the wall clock of the K launches (max over ranks).  images: every rank did K frames
     # of its own; rows: the N ranks together did K frames.
@@ -639,7 +692,7 @@ def main():
         "value": round(value, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(wall_max / args.steps * 1e3, 5),
         "higher_is_better": True, "scaling": "strong" if band else "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic", "clock": "wall",
+        "data": "synthetic", "clock": "wall", "full": bool(args.full),
         "preroll_launches": n_pre, "preroll_ms": round(pre_s * 1e3, 1),
         "config": {"workload": desc, "images_per_gpu_per_step": B if not band else round(1.0 / world, 4),
                    "layout": "NHWC fp32",
@@ -660,12 +713,12 @@ def main():
                      "timing": "achieved = algorithmic bytes per launch / (wall clock of the K timed launches / K): the "
                                "clock of `value`; frac_events = the same bytes over HIP events on the launch stream "
                                "around the same K launches / K; frac_sustained = over the mean of 100-launch event "
-                               "windows during a further 0.5 s (N = 1)",
+                               "windows during a further 0.5 s (N = 1, --full)",
                      "frac_events": round(achieved_events / HBM_PEAK_GBPS, 4),
                      "event_us_per_launch": round(avg_kernel_s * 1e6, 3)},
     }
 
-    if world == 1:
+    if world == 1 and args.full:
         # ~0.5 s more of back-to-back launches in 100-launch HIP-event windows: what a long-running caller
         # gets on this box, and how much it wanders (profiles/r02/exp35).
         sus = sustained(step, dev, est_us=avg_kernel_s * 1e6, smi_index=dev.index or 0)
@@ -697,12 +750,12 @@ def main():
             extra["smooth_guide_avg_kernel_us"] = round(g3 / args.steps * 1e6, 3)
             extra["smooth_guide_hbm_frac"] = round(abytes / (g3 / args.steps) / 1e9 / HBM_PEAK_GBPS, 4)
             del s3
-        if not args.no_extra_ops:
+        if args.full and not args.no_extra_ops:
             t_x = time.perf_counter()
             extra["ops"] = extra_ops(lib, dev)
             extra["ops_seconds"] = round(time.perf_counter() - t_x, 2)
         result["extra"] = extra
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(H, W, GH, GW, GD)
     if rank == 0:
         emit(result)
@@ -792,23 +845,30 @@ def main_train(args, rank, world, local_rank, stub=False):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        loss = run()
     sync()
     wall = time.perf_counter() - t0
     if dist_on:
         hd.barrier()
-    # the collective alone
-    n_ar = max(10, min(200, args.steps))
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(n_ar):
-        step.bucket.allreduce(force=force)
-    sync()
-    ar = (time.perf_counter() - t1) / n_ar
+    if args.dump_outputs:
+        # the last step's loss, the gradients it all-reduced (the flat bucket) and the parameters Adam left
+        params = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        print("dump-outputs:", dump_outputs(args.dump_outputs, {"loss": loss, "grad": step.bucket.flat, "params": params},
+                                            rank, world), file=sys.stderr)
+    # the collective alone (--full)
+    ar = 0.0
+    if args.full:
+        n_ar = max(10, min(200, args.steps))
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(n_ar):
+            step.bucket.allreduce(force=force)
+        sync()
+        ar = (time.perf_counter() - t1) / n_ar
     # the same step fed from the graph's own input buffers (a loader that writes the batch where the graph reads it):
-    # without the three staging copies of the timed loop above (reported beside `value`, not instead of it)
+    # without the three staging copies of the timed loop above (reported beside `value`, not instead of it; --full)
     static_ms = None
-    if not stub:
+    if args.full and not stub:
         feed_in, feed_tgt = step.static_inputs, step.static_targets
         for _ in range(min(args.warmup, 20)):
             step(feed_in, feed_tgt)
@@ -828,9 +888,9 @@ def main_train(args, rank, world, local_rank, stub=False):
         "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic", "clock": "wall",
         "per_gpu_MPps": round(args.steps * mp / wall_max, 1),
+        "full": bool(args.full),
         "ms_per_step_static_feed": None if static_ms is None else round(static_ms, 4),
-        "allreduce": {"ms": round(ar_max * 1e3, 4), "share_of_step": round(ar_max * 1e3 / ms, 4),
-                      "bucket_elements": int(step.bucket.flat.numel()), "collectives_per_step": 1 if (world > 1 or force) else 0,
+        "allreduce": {"bucket_elements": int(step.bucket.flat.numel()), "collectives_per_step": 1 if (world > 1 or force) else 0,
                       "forced_at_world_1": force,
                       "backend": backend if dist_on else None},
         "config": {"workload": EXTRA_WORKLOADS["train_1080p_b4"].format(
@@ -839,6 +899,8 @@ def main_train(args, rank, world, local_rank, stub=False):
                    "global_batch": B * world, "parallelism": f"dp{world} (image shards)", "kernel": kernel,
                    "batch_norm": bool(args.batch_norm)},
     }
+    if args.full:
+        result["allreduce"].update(ms=round(ar_max * 1e3, 4), share_of_step=round(ar_max * 1e3 / ms, 4))
     _finish(result, rank, dist_on)
 
 
@@ -882,6 +944,9 @@ def main_hdrp_u16(args, rank, world, local_rank):
     step(args.warmup, 0)
     wall, gpu_s = timed(step, args.steps, dist_on, dev)
     wall_max, gpu_max = hd.max_over_ranks([wall, gpu_s], device=dev if backend == "nccl" else torch.device("cpu"))
+    if args.dump_outputs:
+        print("dump-outputs:", dump_outputs(args.dump_outputs, {"out": sets[(args.steps - 1) % nsets][3]}, rank, world),
+              file=sys.stderr)
     mp = B * H * W / 1e6
     avg = gpu_max / args.steps
     wall_l = wall_max / args.steps  # the clock of `value` (main(): one clock for the line)
@@ -890,6 +955,7 @@ def main_hdrp_u16(args, rank, world, local_rank):
         "value": round(world * args.steps * mp / wall_max, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(wall_max / args.steps * 1e3, 5), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32 (uint16 in)", "data": "synthetic", "clock": "wall",
+        "full": bool(args.full),
         "preroll_launches": n_pre, "preroll_ms": round(pre_s * 1e3, 1), "per_gpu_MPps": round(args.steps * mp / wall_max, 1),
         "config": {"workload": EXTRA_WORKLOADS["hdrp_u16"], "images_per_gpu_per_step": B, "global_batch": B * world,
                    "rotating_buffer_sets": nsets, "parallelism": f"image-shard x{world}", "kernel": kernel},

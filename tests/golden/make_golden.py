@@ -47,6 +47,41 @@ SLICE_CASES = {
     "slice_guide_out_of_range": (2, 17, 23, 5, 4, 3, 5, -0.5, 1.5),
 }
 
+# tests/test_oracle_pinning.py::test_port_matches_compiled_reference: (B, H, W, GH, GW, GD, Cin, Cout, has_offset), its
+# inputs drawn as that test drew them; stored with the reference's outputs in ref_shapes.npz under "<shape>/<array>"
+REF_SHAPES = [
+    (1, 1, 1, 1, 1, 1, 1, 1, True),
+    (2, 5, 7, 3, 2, 4, 3, 3, True),
+    (1, 33, 65, 16, 16, 8, 3, 3, True),
+    (2, 9, 4, 12, 12, 8, 1, 3, True),
+    (1, 16, 16, 2, 2, 1, 4, 2, False),
+    (1, 40, 24, 5, 3, 2, 2, 5, True),
+]
+
+
+def ref_shapes_key(shape):
+    return "x".join(str(int(v)) for v in shape)
+
+
+def make_ref_shapes(R):
+    arrays = {}
+    for shape in REF_SHAPES:
+        B, H, W, GH, GW, GD, Cin, Cout, ho = shape
+        rng = np.random.default_rng(hash(shape) & 0xFFFF)
+        Cj = Cin + int(ho)
+        grid = rng.standard_normal((B, GH, GW, GD, Cout * Cj)).astype(np.float32)
+        guide = (rng.random((B, H, W)) * 1.6 - 0.3).astype(np.float32)
+        inp = rng.random((B, H, W, Cin)).astype(np.float32)
+        dout = rng.standard_normal((B, H, W, Cout)).astype(np.float32)
+        dgrid, dguide, dinput = R.bilateral_slice_apply_grad(grid, guide, inp, dout, ho)
+        d2 = rng.standard_normal((B, H, W, Cout * Cj)).astype(np.float32)
+        slice_dgrid, slice_dguide = R.bilateral_slice_grad(grid, guide, d2)
+        for k, v in dict(grid=grid, guide=guide, input=inp, dout=dout, out=R.bilateral_slice_apply(grid, guide, inp, ho),
+                         dgrid=dgrid, dguide=dguide, dinput=dinput, slice_out=R.bilateral_slice(grid, guide),
+                         slice_dout=d2, slice_dgrid=slice_dgrid, slice_dguide=slice_dguide).items():
+            arrays[ref_shapes_key(shape) + "/" + k] = v
+    np.savez_compressed(os.path.join(HERE, "ref_shapes.npz"), **arrays)
+
 
 def main():
     R = oracle.ref()
@@ -85,6 +120,7 @@ def main():
         guide = (((val + 0.5) / (1.0 * d)) * np.ones((3, 5, 9))).astype(np.float32)
         outs.append(R.bilateral_slice(grid, guide))
     np.savez_compressed(os.path.join(HERE, "slice_interpolate_kat.npz"), grid=grid, outs=np.stack(outs))
+    make_ref_shapes(R)
     for k, v in out.items():
         print(f"{k}: max|out| = {v:.4f}")
     print("bytes:", sum(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if f.endswith(".npz")))

@@ -43,6 +43,35 @@ REFERENCE = "/root/reference"
 OUT = os.path.join(HERE, "tf_shim")
 
 
+MAX_FILE_BYTES = 1000 * 1024  # every committed file stays under 1 MiB
+
+
+def save_fixture(out_dir, name, arrays):
+    """np.savez_compressed as <name>.npz; a fixture larger than MAX_FILE_BYTES is split into <name>.npz and
+    <name>.part1.npz, <name>.part2.npz, ... (first fit by each array's compressed size;
+    tests/test_tf_shim_fixtures.py::_load merges them back).  Returns the bytes written."""
+    import glob
+    import zlib
+    for f in glob.glob(os.path.join(out_dir, glob.escape(name) + ".part*.npz")):
+        os.remove(f)
+    size = {k: len(zlib.compress(np.ascontiguousarray(v).tobytes())) + 200 for k, v in arrays.items()}
+    bins = []
+    for k in sorted(arrays, key=lambda k: -size[k]):
+        for b in bins:
+            if sum(size[x] for x in b) + size[k] <= MAX_FILE_BYTES * 0.95:
+                b.append(k)
+                break
+        else:
+            bins.append([k])
+    total = 0
+    for i, b in enumerate(bins):
+        path = os.path.join(out_dir, name + (".part%d" % i if i else "") + ".npz")
+        np.savez_compressed(path, **{k: arrays[k] for k in b})
+        assert os.path.getsize(path) <= MAX_FILE_BYTES, path
+        total += os.path.getsize(path)
+    return total
+
+
 def _sha(path):
     with open(path, "rb") as f:
         return hashlib.sha256(f.read()).hexdigest()
@@ -295,11 +324,10 @@ def main():
                   model=np.asarray(cls), params_json=np.asarray(json.dumps(params, sort_keys=True)),
                   source=np.asarray("oracle/tf1_shim (eager numpy stand-in for TensorFlow 1.x) + oracle/_ref"),
                   reference_sha256=np.asarray(json.dumps(hashes, sort_keys=True)))
-        path = os.path.join(out_dir, name + ".npz")
-        np.savez_compressed(path, **fx)
+        nbytes = save_fixture(out_dir, name, fx)
         nvar = sum(k.startswith("var/") for k in fx)
         print("%-50s %3d variables  coefficients %s  output %s  %.0f KiB" % (
-            name, nvar, fx["bilateral_coefficients"].shape, fx["output"].shape, os.path.getsize(path) / 1024))
+            name, nvar, fx["bilateral_coefficients"].shape, fx["output"].shape, nbytes / 1024))
 
     # the 6-D wrappers of hdrnet/layers.py:99-148, :153-199 on their own: slice + apply == slice_apply
     rng = np.random.RandomState(99)

@@ -86,7 +86,7 @@ def test_train_workload_two_ranks_gloo():
     """`--workload train_1080p_b4 --gpus 2` (BASELINE config #4 as stated): the harness -- per-rank train step with the
     flat gradient bucket, ONE all-reduce per step, max-over-ranks timing, the all-reduce's share -- on CPU / gloo
     with a stand-in torch-only model (the HIP kernels have no CPU path)."""
-    out = _run(["--gpus", "2", "--workload", "train_1080p_b4"])
+    out = _run(["--gpus", "2", "--workload", "train_1080p_b4", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["unit"] == "MP/s"
     ar = out["allreduce"]
     assert ar["collectives_per_step"] == 1 and ar["backend"] == "gloo" and ar["bucket_elements"] == 12 * 32 + 32 + 32 * 3 + 3
@@ -126,3 +126,45 @@ def test_traffic_record_is_refused_when_sources_differ(tmp_path, monkeypatch):
     (tmp_path / "hdrnet_amd" / "csrc" / "common.h").write_text("changed")
     got, why = bench.measured_traffic("4k", "k")
     assert got is None and "other kernel sources" in why
+
+
+def test_train_stub_plain_run_and_full_run():
+    """A plain run times the steps and prints the line; the all-reduce alone is timed only with --full."""
+    plain = _run(["--gpus", "1", "--workload", "train_1080p_b4"])
+    assert plain["full"] is False and plain["steps"] == 4 and plain["ms_per_step"] > 0
+    assert "ms" not in plain["allreduce"] and "share_of_step" not in plain["allreduce"]
+    full = _run(["--gpus", "1", "--workload", "train_1080p_b4", "--full"])
+    assert full["full"] is True and full["allreduce"]["ms"] >= 0 and "share_of_step" in full["allreduce"]
+
+
+def test_dump_outputs_of_the_train_stub_are_the_same_on_every_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's loss, gradients and parameters, float32, identical from run to run."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        _run(["--gpus", "1", "--workload", "train_1080p_b4", "--dump-outputs", str(d)])
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["grad.npy", "loss.npy", "params.npy"] and sorted(os.listdir(dirs[1])) == names
+    for f in names:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), f
+    assert np.load(dirs[0] / "loss.npy").shape == ()
+    assert np.load(dirs[0] / "grad.npy").size == np.load(dirs[0] / "params.npy").size == 12 * 32 + 32 + 32 * 3 + 3
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_a_large_array(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMENTS", 100)
+    arrays = {"big": torch.arange(5000, dtype=torch.float32), "small": torch.ones((3, 4), dtype=torch.float16)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.dtype == np.float32 and big.shape == (100,) and (np.diff(big) > 0).all()  # ascending, no repeats
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float32 and small.shape == (3, 4) and (small == 1).all()
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 4000 + 2 * 128  # the limit plus the two .npy headers

@@ -58,3 +58,34 @@ def test_bench_under_the_launcher_with_a_one_rank_communicator_equals_the_plain_
     # the verdict's bar is 1 %; the assertion leaves room for the drift of a box between two runs (profiles/r05:
     # four default runs on one box span 1.2 %)
     assert abs(b / a - 1.0) < 0.025, (a, b)
+
+
+def test_plain_run_dumps_what_its_last_timed_step_computed(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: a plain run (none of --full's blocks) whose `ms_per_step` is
+    the wall clock of the K timed steps, and whose dump -- a seeded sample of the last step's 4K frame -- is the same on
+    every run and is what the op computes from the same seeded inputs."""
+    import numpy as np
+    import torch
+
+    import bench
+    from hdrnet_amd import hdrnet_ops as ops
+    K = 20
+    dumps = []
+    for d in ("a", "b"):
+        out, _ = _line([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", "5",
+                        "--dump-outputs", str(tmp_path / d)])
+        assert out["steps"] == K and out["full"] is False and out["unit"] == "MP/s" and out["ms_per_step"] > 0
+        assert not {"sustained", "pipelined", "cpu_baseline"} & set(out) and "ops" not in out.get("extra", {})
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 / (3840 * 2160 / 1e6) - 1) < 1e-3
+        assert sorted(os.listdir(tmp_path / d)) == ["out.npy"]
+        dumps.append(np.load(tmp_path / d / "out.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE_ELEMENTS,) and np.array_equal(a, b)
+    # the inputs of timed step K - 1, drawn again by bench.py's own seeded generator
+    dev = torch.device("cuda:0")
+    B, H, W, GH, GW, GD, _ = bench.WORKLOADS["4k"]
+    nsets = max(3, -(-int(bench.CACHE_BYTES * 1.5) // bench.algorithmic_bytes(B, H, W, GH, GW, GD)))
+    grid, guide, inp, _ = bench.make_sets(dev, nsets, B, H, W, GH, GW, GD, seed=1234)[(K - 1) % nsets]
+    want = ops.bilateral_slice_apply(grid, guide, inp, has_offset=True).reshape(-1)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(want.numel(), size=a.size, replace=False))
+    np.testing.assert_array_equal(a, want[torch.from_numpy(idx).to(dev)].cpu().numpy())

@@ -30,9 +30,15 @@ MODEL_FIXTURES = ["HDRNetCurves", "HDRNetPointwiseNNGuide", "HDRNetGaussianPyrNN
 REFERENCE = "/root/reference"
 
 
-def _load(name):
-    with np.load(os.path.join(FIXTURES, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
+def _load(name, where=FIXTURES):
+    """A fixture's arrays: <name>.npz and the parts <name>.partN.npz of one larger than a committed file may be
+    (tests/golden/make_tf_shim_fixtures.py: save_fixture)."""
+    out = {}
+    for f in [name + ".npz"] + sorted(f for f in os.listdir(where) if f.startswith(name + ".part") and f.endswith(".npz")):
+        with np.load(os.path.join(where, f)) as z:
+            assert not set(z.files) & set(out), f
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 def _model(fx):
@@ -193,13 +199,13 @@ def test_committed_fixtures_are_what_the_script_computes(tmp_path):
                     "--out", str(tmp_path), "--only", name], check=True, timeout=300,
                    stdout=subprocess.DEVNULL)
     want = _load(name)
-    with np.load(os.path.join(str(tmp_path), name + ".npz")) as z:
-        assert sorted(z.files) == sorted(want)
-        for k in z.files:
-            if z[k].dtype.kind == "f":   # (bit-identical on this machine; a BLAS with another thread count may differ by an ulp)
-                np.testing.assert_allclose(z[k], want[k], rtol=1e-6, atol=1e-7, err_msg=k)
-            else:
-                np.testing.assert_array_equal(z[k], want[k], err_msg=k)
+    z = _load(name, str(tmp_path))
+    assert sorted(z) == sorted(want)
+    for k in z:
+        if z[k].dtype.kind == "f":   # (bit-identical on this machine; a BLAS with another thread count may differ by an ulp)
+            np.testing.assert_allclose(z[k], want[k], rtol=1e-6, atol=1e-7, err_msg=k)
+        else:
+            np.testing.assert_array_equal(z[k], want[k], err_msg=k)
     for fixture in MODEL_FIXTURES + ["layers_wrappers", "metrics", "gradients_fd", "gradients_fd_training",
                                      "gradients_fd_curves", "gradients_fd_pyramid"]:
         for rel, digest in json.loads(str(_load(fixture)["reference_sha256"])).items():

@@ -54,24 +54,24 @@ tail -40 $O/fwd_pmc.txt; tail -25 $O/traffic.log
 exit 0
 fi
 # 2. the default bench command, un-profiled and under rocprofv3 --kernel-trace --stats
-python $R/bench.py > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 # ... and, on the same box, the whole -m gpu suite with its printed error figures (-s) and the smoke entry point
 (cd $R && python -m pytest tests -q -m gpu -s 2>&1 | grep -v amdgpu.ids > $O/gpu_suite.txt; python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" >> $O/gpu_suite.txt 2>&1)
 # the same command under rocprofv3 --kernel-trace --stats (its per-kernel average must agree with the line above)
-rocprofv3 --kernel-trace --stats -d $O/stats -o fwd --output-format csv -- python $R/bench.py --no-cpu-baseline --no-pipelined > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats -o fwd --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-pipelined > $O/bench_under_rocprof.log 2>&1
 grep '^{"metric' $O/bench_under_rocprof.log > $O/bench_under_rocprof.json
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/fwd_kernel_stats.csv \;
 rm -rf $O/stats
 for i in 1 2 3; do python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-ops; done > $O/bench_steps20.txt 2>> $O/bench.err
-python $R/bench.py --workload 1080p --no-cpu-baseline > $O/bench_1080p.json 2>> $O/bench.err
-python $R/bench.py --workload 1080p_b4 --no-cpu-baseline > $O/bench_1080p_b4.json 2>> $O/bench.err
-python $R/bench.py --workload hdrp --no-cpu-baseline > $O/bench_hdrp.json 2>> $O/bench.err
+python $R/bench.py --full --workload 1080p --no-cpu-baseline > $O/bench_1080p.json 2>> $O/bench.err
+python $R/bench.py --full --workload 1080p_b4 --no-cpu-baseline > $O/bench_1080p_b4.json 2>> $O/bench.err
+python $R/bench.py --full --workload hdrp --no-cpu-baseline > $O/bench_hdrp.json 2>> $O/bench.err
 python $R/bench.py --workload hdrp_u16 > $O/bench_hdrp_u16.json 2>> $O/bench.err
-python $R/bench.py --workload train_1080p_b4 --steps 100 --warmup 20 > $O/bench_train_1080p_b4.json 2>> $O/bench.err
-python $R/bench.py --workload train_1080p_b4 --batch-norm --steps 100 --warmup 20 > $O/bench_train_1080p_b4_batch_norm.json 2>> $O/bench.err
-for i in 1 2 3; do python $R/bench.py --no-cpu-baseline; done > $O/bench_repeat.txt 2>> $O/bench.err
+python $R/bench.py --full --workload train_1080p_b4 --steps 100 --warmup 20 > $O/bench_train_1080p_b4.json 2>> $O/bench.err
+python $R/bench.py --full --workload train_1080p_b4 --batch-norm --steps 100 --warmup 20 > $O/bench_train_1080p_b4_batch_norm.json 2>> $O/bench.err
+for i in 1 2 3; do python $R/bench.py --full --no-cpu-baseline; done > $O/bench_repeat.txt 2>> $O/bench.err
 # the smooth-guide pair SURVEY.md section 8d asks for beside U[0,1) (+ the cache-resident rate), same protocol
-python $R/bench.py --extra --no-cpu-baseline --no-pipelined > $O/bench_extra_smooth_guide.json 2>> $O/bench.err
+python $R/bench.py --full --extra --no-cpu-baseline --no-pipelined > $O/bench_extra_smooth_guide.json 2>> $O/bench.err
 # 3. every entry point, all sizes; A/B of the forward variants; this build vs the previous round's; end to end
 cd $R
 python tools/op_bench.py --tools --workload 4k --json $O/ops_4k.json > $O/ops_4k.txt 2>&1
