@@ -876,7 +876,9 @@ hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char**
   static thread_local char label[64];
   const int kind = a.guide ? kGuideMap : (a.guide_shifts ? kGuideCurves : kGuideNN);
   const bool cells = kind == kGuideCurves && a.guide_prepared && a.n_feats <= kCurveMaxKnots;
-  snprintf(label, sizeof label, "apply_fwd_io/%s%s%s", io[a.input_dtype][a.output_dtype], suffix[kind], cells ? "/cells" : "");
+  const bool scan = kind == kGuideCurves && a.n_feats > kCurveMaxKnots;  // knot by knot (kGuideCurvesScan)
+  snprintf(label, sizeof label, "apply_fwd_io/%s%s%s", io[a.input_dtype][a.output_dtype], suffix[kind],
+           cells ? "/cells" : scan ? "/scan" : "");
   *name = label;
   if (kind == kGuideCurves) {
     if (a.n_feats > kCurveMaxKnots) return dispatch_types<kGuideCurvesScan>(a, pl, s);
