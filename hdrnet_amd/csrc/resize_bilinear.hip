@@ -115,16 +115,17 @@ __global__ __launch_bounds__(256) void resize_bilinear_grad_ac(const float* __re
   const int yhi = (int)fminf(ceilf((float)(ys + 1) * inv_sh) + 1.0f, (float)(Hout - 1));
   const int xlo = (int)fmaxf(floorf((float)(xs - 1) * inv_sw) - 1.0f, 0.0f);
   const int xhi = (int)fminf(ceilf((float)(xs + 1) * inv_sw) + 1.0f, (float)(Wout - 1));
-  // the column weights do not depend on the row: kept for windows of <= 8 columns (up-sampling by two: <= 7)
+  // the column weights do not depend on the row: kept for windows of <= 8 columns (up-sampling n -> 2 n: 8 -- the scale
+  // is just under 1 / 2, (xs - 1, xs + 1) / scale just over 4 wide: 6 columns after floor / ceil, 8 with the slack)
   constexpr int kW = 8;
   float wxs[kW];
   const bool cached = xhi - xlo + 1 <= kW;
 #pragma unroll
   for (int i = 0; i < kW; ++i) wxs[i] = (cached && xlo + i <= xhi) ? tap_weight(xlo + i, xs, sw, Win) : 0.0f;
   for (int c0 = 0; c0 < nc; c0 += kMaxC) {  // (one round unless C is dynamic and > 4)
-    float acc[kMaxC];
+    float acc[kMaxC], comp[kMaxC];
 #pragma unroll
-    for (int c = 0; c < kMaxC; ++c) acc[c] = 0.0f;
+    for (int c = 0; c < kMaxC; ++c) acc[c] = comp[c] = 0.0f;
     for (int y = ylo; y <= yhi; ++y) {
       const float wy = tap_weight(y, ys, sh, Hin);
       if (wy == 0.0f) continue;
@@ -140,12 +141,19 @@ __global__ __launch_bounds__(256) void resize_bilinear_grad_ac(const float* __re
           }
         }
       } else {
+        // a window this wide can hold up to the whole destination per source pixel (one source row -> 1080 x 1920: 2 M terms,
+        // beyond what a plain float32 running sum keeps to 2e-6 of the result): compensated, still in a fixed order
         for (int x = xlo; x <= xhi; ++x) {
           const float w = wy * tap_weight(x, xs, sw, Win);
           if (w == 0.0f) continue;
 #pragma unroll
           for (int c = 0; c < kMaxC; ++c)
-            if (c0 + c < nc) acc[c] = __builtin_fmaf(w, row[(size_t)x * nc + c0 + c], acc[c]);
+            if (c0 + c < nc) {
+              const float t = __builtin_fmaf(w, row[(size_t)x * nc + c0 + c], -comp[c]);
+              const float sum = acc[c] + t;
+              comp[c] = (sum - acc[c]) - t;
+              acc[c] = sum;
+            }
         }
       }
     }

@@ -66,12 +66,7 @@ def resize_bilinear_align_corners(x, height, width):
     x = np.asarray(x, np.float32)
     B, Hin, Win, C = x.shape
 
-    def axis(n_in, n_out):
-        scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(n_in) / np.float32(n_out)
-        src = (np.arange(n_out, dtype=np.float32) * scale).astype(np.float32)
-        lo = np.floor(src)
-        hi = np.minimum(np.ceil(src), n_in - 1)
-        return lo.astype(np.int64), hi.astype(np.int64), (src - lo).astype(np.float32)
+    from .f64_train import resize_taps as axis  # (lower, upper, lerp) per destination index, in float32
 
     y0, y1, ly = axis(Hin, int(height))
     x0, x1, lx = axis(Win, int(width))

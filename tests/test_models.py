@@ -586,7 +586,12 @@ def test_graphed_train_step_split_form_matches_one_graph():
 def test_upsample_add_and_its_vjp_vs_torch_float64(shape):
     """hdrnet_ops.upsample_add = resize(coarse, align_corners) + fine (hdrnet/models.py:283-287) and its two gradients
     against torch's interpolate in float64: up-sampling by two and by odd ratios, one source row, DOWN-sampling, equal
-    sizes, a channel count without a specialisation; the gather-form transpose is bit-reproducible."""
+    sizes, a channel count without a specialisation; the gather-form transpose is bit-reproducible.
+
+    torch's float64 interpolate forms the source coordinate i * scale in float64; the op forms it in float32, which is part
+    of its semantics (oracle.resize_bilinear_align_corners).  At these extents the two coordinates agree to 2^-23 x extent
+    and the reference is valid; at frame size it is not (2.8e-4 in the output at 960 -> 1920 on randn data).  There
+    tests/test_gpu_train_fullsize.py compares with oracle/f64_train.py: float32 coordinates, float64 sums."""
     from hdrnet_amd import hdrnet_ops
     B, ih, iw, oh, ow, C = shape
     torch.manual_seed(sum(shape))

@@ -399,3 +399,114 @@ def test_reference_float32_noise_floor_of_the_per_pixel_vjps():
     print(r)
     assert r["dinput"][0] < 0.2 * DINPUT_ATOL
     assert 0.25e-5 < r["dguide"][0] < DGUIDE_ATOL
+
+
+# ---- the float64 references of the training step's kernels (oracle/f64_train.py) ---------------------------------------
+@pytest.mark.parametrize("dims", [(270, 480, 540, 960), (540, 960, 1080, 1920), (539, 959, 1080, 1920),
+                                  (1080, 1920, 270, 480), (1, 2, 1080, 1920)])
+def test_f64_upsample_add_equals_the_float32_restatement_at_frame_sizes(dims):
+    """Float32 coordinates, float64 sums: within float32 rounding of oracle.resize_bilinear_align_corners, which forms the
+    same taps and evaluates three lerps a + (b - a) l in float32 -- five roundings of at most 2^-24 max|x| each per
+    lerp, the row lerp on top of the two column lerps: 10 x 2^-24 max|x|."""
+    import oracle
+    from oracle import f64_train
+    h, w, H, W = dims
+    rng = np.random.default_rng(sum(dims))
+    x = rng.standard_normal((1, h, w, 2)).astype(np.float32)
+    fine = rng.standard_normal((1, H, W, 2)).astype(np.float32)
+    got = f64_train.upsample_add_f64(x, fine) - fine
+    want = oracle.resize_bilinear_align_corners(x, H, W)
+    err = np.abs(got - want).max()
+    bar = 10 * 2.0 ** -24 * np.abs(x).max()
+    print(f"{dims}: max|f64 sums - float32 restatement| = {err:.3e}, bar {bar:.3e}")
+    assert err <= bar
+
+
+@pytest.mark.parametrize("shape", [(2, 17, 23, 34, 46, 3), (1, 5, 7, 11, 13, 3), (2, 8, 8, 16, 16, 1), (1, 1, 4, 3, 9, 3),
+                                   (1, 12, 10, 6, 5, 3), (1, 6, 6, 6, 6, 5)])
+def test_f64_upsample_add_equals_torch_float64_at_small_extents(shape):
+    """At the extents of test_models.py::test_upsample_add_and_its_vjp_vs_torch_float64 the float32 source coordinate
+    is within 2^-23 x extent of torch's float64 one (the scale's rounding and the product's), which moves the output
+    by at most that times the largest step between neighbours (2 max|x|) per axis; the transpose likewise."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import f64_train
+    B, h, w, H, W, C = shape
+    rng = np.random.default_rng(sum(shape))
+    x = rng.standard_normal((B, h, w, C)).astype(np.float32)
+    fine = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    g = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    c64 = torch.from_numpy(x).double().requires_grad_(True)
+    ref = F.interpolate(c64.permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=True).permute(0, 2, 3, 1) \
+        + torch.from_numpy(fine).double()
+    (ref * torch.from_numpy(g).double()).sum().backward()
+    bar = 2.0 ** -23 * (h + w) * 2 * np.abs(x).max()
+    err = np.abs(f64_train.upsample_add_f64(x, fine) - ref.detach().numpy()).max()
+    assert err <= bar, (err, bar)
+    # the transpose sums up to (H / h + 2) (W / w + 2) destination pixels per source pixel, each moved as above
+    taps = (H / h + 2) * (W / w + 2)
+    gbar = 2.0 ** -23 * (h + w) * taps * np.abs(g).max()
+    gerr = np.abs(f64_train.upsample_vjp_f64(g, h, w) - c64.grad.numpy()).max()
+    print(f"{shape}: forward {err:.3e} (bar {bar:.3e}), transpose {gerr:.3e} (bar {gbar:.3e})")
+    assert gerr <= gbar, (gerr, gbar)
+
+
+@pytest.mark.parametrize("dims", [(5, 7, 11, 13), (270, 480, 1080, 1920), (1080, 1920, 270, 480), (1, 2, 33, 65)])
+def test_f64_upsample_vjp_is_the_adjoint(dims):
+    """<W x, g> == <x, W^T g> to float64 rounding; every row of a tap matrix sums to one and has at most two entries;
+    the float32 matrices (the planted-spike tests' expectation) are the float64 ones rounded."""
+    from oracle import f64_train
+    h, w, H, W = dims
+    rng = np.random.default_rng(sum(dims))
+    x = rng.standard_normal((2, h, w, 3)).astype(np.float32)
+    g = rng.standard_normal((2, H, W, 3)).astype(np.float32)
+    zero = np.zeros((2, H, W, 3), np.float32)
+    lhs = float((f64_train.upsample_add_f64(x, zero) * g).sum())
+    rhs = float((x * f64_train.upsample_vjp_f64(g, h, w)).sum())
+    scale = float(np.abs(x).max() * np.abs(g).sum())
+    assert abs(lhs - rhs) <= 1e-13 * scale, (lhs, rhs)
+    for n_in, n_out in ((h, H), (w, W)):
+        M = f64_train.resize_matrix(n_in, n_out)
+        assert np.array_equal(M.sum(1), np.ones(n_out)) and ((M != 0).sum(1) <= 2).all() and (M >= 0).all()
+        M32 = f64_train.resize_matrix(n_in, n_out, np.float32)
+        assert M32.dtype == np.float32 and np.abs(M32 - M).max() <= 2.0 ** -24
+        lo, hi, l = f64_train.resize_taps(n_in, n_out)
+        assert lo[0] == 0 and hi.max() == n_in - 1 and (hi - lo <= 1).all() and (0 <= l).all() and (l < 1).all()
+
+
+@pytest.mark.parametrize("epsilon_hat", [False, True])
+def test_f64_adam_restatement_equals_torch_adam_in_float64(epsilon_hat):
+    """oracle.f64_train.adam_step in float64 against torch.optim.Adam on float64 tensors with the same (float32-valued)
+    hyper-parameters.  TensorFlow's placement of epsilon is torch's with eps / sqrt(1 - b2^t), set per step.  The
+    float32 form of the same restatement stays within 1e-5 (relative to the update of an element whose gradients do not
+    cancel) of it, and the moving average of |g| equals |exp_avg| for gradients of one sign."""
+    import torch
+    from oracle import f64_train
+    lr, b1, b2, eps = f64_train.adam_hyper(1e-4, 0.9, 0.999, 1e-8)
+    assert b2 == float(np.float32(0.999)) and abs((1 - b2) / (1 - 0.999) - 1) > 1e-5   # (not the double's 0.999)
+    rng = np.random.default_rng(3)
+    n = 1000
+    p0 = rng.standard_normal(n)
+    w = torch.from_numpy(p0.copy()).requires_grad_(True)
+    opt = torch.optim.Adam([w], lr=float(lr), betas=(float(b1), float(b2)), eps=float(eps))
+    p, m, v, s = p0.copy(), np.zeros(n), np.zeros(n), None
+    p32, m32, v32 = p0.astype(np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    for t in range(1, 8):
+        g = (rng.standard_normal(n) * 1e-2).astype(np.float32)
+        g[:10] = 0
+        g[10:20] = 1e-20
+        g[20:40] = np.abs(g[20:40])
+        if epsilon_hat:
+            opt.param_groups[0]["eps"] = float(eps) / (1 - float(b2) ** t) ** 0.5
+        w.grad = torch.from_numpy(g).double()
+        opt.step()
+        p, m, v, upd, s, unit = f64_train.adam_step(p, m, v, g, t, 1e-4, 0.9, 0.999, 1e-8, epsilon_hat, s=s)
+        p32, m32, v32, upd32, _, _ = f64_train.adam_step(p32, m32, v32, g, t, 1e-4, 0.9, 0.999, 1e-8, epsilon_hat,
+                                                         dtype=np.float32)
+        assert p32.dtype == m32.dtype == v32.dtype == upd32.dtype == np.float32
+        np.testing.assert_allclose(p, w.detach().numpy(), rtol=1e-13, atol=0)
+        assert (np.abs(m - opt.state[w]["exp_avg"].numpy()) <= 1e-13 * s).all()   # (gradients cancel in exp_avg)
+        np.testing.assert_allclose(v, opt.state[w]["exp_avg_sq"].numpy(), rtol=1e-13, atol=0)
+        assert np.abs(upd32 - upd).max() <= 1e-5 * unit.max()
+        np.testing.assert_allclose(s[20:40], np.abs(m[20:40]), rtol=1e-13)
+        assert (np.abs(upd) <= unit * (1 + 1e-13)).all()
