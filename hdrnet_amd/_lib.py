@@ -20,6 +20,7 @@ GUIDE_SIGMOID_FAST = 0x10000  # HDRNET_GUIDE_SIGMOID_FAST (flags of the guide-ne
 GUIDE_RELU_PRESCALED = 0x20000  # HDRNET_GUIDE_RELU_PRESCALED: conv1 / conv2 are hdrnet_guide_nn_prescale_f32's arrays
 KERNEL_GENERIC = 1
 KERNEL_FAST = 2
+SAMPLE_EVEN_TURNS_ONLY = 1  # HDRNET_SAMPLE_EVEN_TURNS_ONLY (hdrnet_prepare_batch, include/hdrnet_amd_train.h)
 
 _FP = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 _I = ctypes.c_int
@@ -73,6 +74,7 @@ SIGNATURES = {
     "hdrnet_bilateral_slice_grad_workspace_bytes": (_SZ, [_I] * 7),
     "hdrnet_bilateral_slice_grad_f32": (_I, [_FP] * 5 + [_I] * 7 + [_VP, _SZ, _VP]),
     "hdrnet_bilateral_slice_grad_f32_ex": (_I, [_FP] * 5 + [_I] * 7 + [_VP, _SZ, _U, _VP]),
+    "hdrnet_lowres_input": (_I, [_FP, _I, ctypes.c_float] + [_I] * 3 + [_FP, _I, _VP]),
 }
 
 
@@ -118,6 +120,7 @@ TRAIN_SIGNATURES = {
     "hdrnet_resize_bilinear_grad_f32": (_I, [_FP, _FP] + [_I] * 6 + [_VP]),
     "hdrnet_adam_step_f32": (_I, [_FP, _FP, _FP, _FP, ctypes.c_longlong, _FP] + [ctypes.c_float] * 4 + [_VP]),
     "hdrnet_adam_step_tf_f32": (_I, [_FP, _FP, _FP, _FP, ctypes.c_longlong, _FP] + [ctypes.c_float] * 4 + [_VP]),
+    "hdrnet_prepare_batch": (_I, [_FP, _I, ctypes.c_float] * 2 + [_I] * 3 + [_FP, _I, _FP, _FP, _I, _I, _FP, _I, _U, _VP]),
 }
 
 _lock = threading.Lock()

@@ -47,6 +47,7 @@ SOURCES = [
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
     ("metrics.hip", []),
+    ("sample_prep.hip", []),
 ]
 TOOLS_ONLY_SOURCES = [
     ("apply_fwd_variants.hip", ["-fno-slp-vectorize"]),
@@ -96,7 +97,7 @@ def _usable_flags(cc: str, extra: List[str]) -> List[str]:
 
 
 def _deps() -> List[str]:
-    out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.abspath(__file__)]
+    out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"), os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):
             out.append(os.path.join(CSRC, f))

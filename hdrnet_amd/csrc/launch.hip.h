@@ -181,6 +181,23 @@ hipError_t launch_apply_fwd_upadd(const ApplyArgs& a, const float* coarse, int H
 hipError_t launch_resize_bilinear(const float* in, float* out, int B, int Hin, int Win, int Hout,
                                   int Wout, int C, hipStream_t s, const char** name);
 
+// Sample preparation (sample_prep.hip): wire-format sources -> the fp32 NHWC tensors of a batch, one launch.
+struct SamplePrepArgs {
+  const void* src_input;   // [N][Hs][Ws][3], input_dtype: 0 f32, 1 u8, 2 u16
+  const void* src_target;  // same extents, target_dtype; null without image_target
+  int input_dtype, target_dtype;
+  float input_white_level, target_white_level;
+  int N, Hs, Ws;
+  const int* ops;  // device [B][8] = {index, flip_lr, flip_ud, rot90, crop_y, crop_x, 0, 0}; null: identity, index = b
+  int B, H, W;
+  float* image_input;   // [B][H][W][3] or null
+  float* image_target;  // [B][H][W][3] or null
+  float* lowres_input;  // [B][n][n][3] or null
+  int n;
+  bool even_turns_only;
+};
+hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
+
 bool apply_fwd_io_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char** name);
 // the curves guide's uniform cell tables (apply_fwd_io.hip: CurveCells), prepared once per parameter set

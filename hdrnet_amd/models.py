@@ -514,6 +514,47 @@ class HDRNetCurves(nn.Module):
         return layers.bilateral_slice_apply(coeffs, guide, fullres_input, has_offset=True, name="slice")
 
 
+    # ---- frame in, frame out --------------------------------------------------------------------------------------------
+    _process_dtypes = (torch.float32, torch.uint8, torch.uint16)
+
+    def _process_guide_args(self) -> Dict:
+        """The guide arguments of ``hdrnet_ops.bilateral_slice_apply_io`` for this model's inference choices."""
+        arrays = self.guide.exported()
+        return {"guide_curves": arrays, "curves_prepared": self.guide.prepared() if self.prepare_curves else None}
+
+    def process(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
+                white_level: Optional[float] = None) -> torch.Tensor:
+        """Frame in, frame out (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on the device ->
+        ``data.lowres_input`` -> the coefficient network -> the fused guide + slice-apply, with the wire formats converted
+        in registers (``hdrnet_ops.bilateral_slice_apply_io``): ``value / white_level`` in (255 / 65535 / 1 by default),
+        float32 or uint8 ``= (uint8)(255 * clip(out, 0, 1))`` out (hdrnet/bin/run.py:95; default float32).  The guide
+        parameters and the ``fast_sigmoid`` / ``prescale_guide`` / ``prepare_curves`` choices are the model's own.  For a
+        float32 frame with float32 out the result is exactly ``forward(data.lowres_input(frame), frame)``."""
+        from . import data, hdrnet_ops
+        if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] != 3:
+            raise ValueError("frame should be [B, H, W, 3]")
+        if frame.dtype not in self._process_dtypes:
+            raise TypeError(f"{type(self).__name__}.process takes "
+                            f"{' / '.join(str(d).replace('torch.', '') for d in self._process_dtypes)} frames, got {frame.dtype}")
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+        if out_dtype != torch.float32 and self._process_dtypes == (torch.float32,):
+            raise TypeError(f"{type(self).__name__}.process returns float32 frames only")
+        if self.training:
+            raise RuntimeError("process() is inference: call eval() first")
+        with torch.no_grad():
+            frame = frame.contiguous()
+            lowres = data.lowres_input(frame, self.params["net_input_size"], white_level)
+            if frame.dtype == torch.float32 and out_dtype == torch.float32:  # float32 is never scaled
+                return self.forward(lowres, frame)
+            coeffs = self.coefficients(lowres)
+            gs = coeffs.shape
+            return hdrnet_ops.bilateral_slice_apply_io(
+                coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), frame, input_white_level=white_level,
+                out_dtype=out_dtype, has_offset=True, **self._process_guide_args())
+
+
 class HDRNetPointwiseNNGuide(HDRNetCurves):
     """``hdrnet/models.py:199-210``.  The guide network is FUSED into the slice-apply kernel
     (SURVEY.md section 8f row 2): the 16-channel full-resolution intermediate is never
@@ -561,6 +602,11 @@ class HDRNetPointwiseNNGuide(HDRNetCurves):
             prescaled=prescaled)
 
 
+    def _process_guide_args(self) -> Dict:
+        conv1, conv2, prescaled = self.guide.inference_params(self.prescale_guide)
+        return {"guide_conv1": conv1, "guide_conv2": conv2, "prescaled": prescaled, "fast_sigmoid": self.fast_sigmoid}
+
+
 class _SplitLevels(torch.autograd.Function):
     """The pyramid's per-level coefficient grids, ``coeffs[:, :, :, :, 3 l : 3 l + 3, :]`` flattened to 12 channels
     (hdrnet/models.py:280), as contiguous tensors in ONE copy (level-major), and their gradients put back with ONE stack:
@@ -591,6 +637,9 @@ class HDRNetGaussianPyrNN(HDRNetPointwiseNNGuide):
 
     n_scales = 3
     n_out, n_in = 9, 4
+
+    # process(): the pyramid is built from a float32 frame (no wire-format variant of the per-level kernels)
+    _process_dtypes = (torch.float32,)
 
     def __init__(self, params: Optional[Dict] = None):
         super().__init__(params)

@@ -76,6 +76,28 @@ class GraphedInference:
         return self.static_output
 
 
+class _Process(torch.nn.Module):
+    """``model.process`` as the module a ``GraphedInference`` captures (parameters and buffers are the model's)."""
+
+    def __init__(self, model: torch.nn.Module, out_dtype, white_level):
+        super().__init__()
+        self.model, self.out_dtype, self.white_level = model, out_dtype, white_level
+
+    def forward(self, frame: torch.Tensor) -> torch.Tensor:
+        return self.model.process(frame, self.out_dtype, self.white_level)
+
+
+class FrameInference(GraphedInference):
+    """Frame in, frame out from a hipGraph: a ``GraphedInference`` whose captured callable is ``model.process`` (low-res
+    input, coefficient network, fused guide + slice-apply with the wire formats in registers).  One input, the frame
+    (uint8 / uint16 / float32 ``[B, H, W, 3]``); ``out_dtype`` float32 (default) or uint8."""
+
+    def __init__(self, model: torch.nn.Module, example_frame: torch.Tensor, out_dtype=None, white_level=None,
+                 warmup: int = 3, check_parameters: bool = True):
+        super().__init__(_Process(model.eval(), out_dtype, white_level), [example_frame], warmup=warmup,
+                         check_parameters=check_parameters)
+
+
 class FramePipeline:
     """Independent frames round-robin over ``depth`` HIP streams.
 

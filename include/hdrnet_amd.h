@@ -85,7 +85,8 @@ extern "C" {
  *        gather kernel under HDRNET_KERNEL_AUTO prints one line on stderr per process.
  *   251  4 -> 4 with offset (20 grid channels): dgrid runs on the fast pass as two channel windows; the workspace bound of
  *        that shape is no longer 0 (..._grad_workspace_bytes).  dguide of a call with dgrid == NULL changes in its last
- *        bits (contraction of the grid's z difference: closer to the float64 value than before). */
+ *        bits (contraction of the grid's z difference: closer to the float64 value than before).
+ *   260  + hdrnet_lowres_input, and hdrnet_prepare_batch in hdrnet_amd_train.h (sample preparation from u8 / u16 / f32). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */
@@ -481,6 +482,15 @@ int hdrnet_coefficients_grad_f32(const float* lowres, const hdrnet_coeff_net* ne
 
 int hdrnet_coefficients_f32(const float* lowres, const hdrnet_coeff_net* net, float* coeffs, int B,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* The low-resolution input of a whole frame (the inference case of hdrnet_prepare_batch, include/hdrnet_amd_train.h:
+ * identity geometry; the reference's `downsampling` / `convert_to_float` stages, benchmark/src/processor.cc:109-122):
+ *   lowres[b, y, x, :] = frames[b, min(floor(y * (H / (float)n)), H - 1), min(floor(x * (W / (float)n)), W - 1), :] / white_level
+ * frames [B][H][W][3] of dtype 0 f32 (copied unscaled), 1 u8, 2 u16 (4-byte aligned); lowres [B][n][n][3] fp32 (16-byte
+ * aligned), n = net_input_size.  Nearest neighbour as TF1's ResizeNearestNeighbor(align_corners=False) and OpenCV's
+ * INTER_NEAREST -- not the centre-aligned skimage resize of hdrnet/bin/run.py:166-169.  B == 0 is a no-op. */
+int hdrnet_lowres_input(const void* frames, int dtype, float white_level, int B, int H, int W, float* lowres,
+                        int net_input_size, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

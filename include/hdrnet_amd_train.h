@@ -51,6 +51,34 @@ int hdrnet_adam_step_f32(float* param, const float* grad, float* exp_avg, float*
 int hdrnet_adam_step_tf_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                             float* step, float lr, float beta1, float beta2, float eps, void* stream);
 
+/* Sample preparation (csrc/sample_prep.hip): one launch turns wire-format source images that sit in device memory into
+ * the fp32 NHWC tensors a training step consumes -- the reference's hdrnet/data_pipeline.py:126-171 (`_augment_data`),
+ * :228-241, :267-287 on the device.  For each output sample b a 32-byte record of the DEVICE table
+ *   ops[b] = {index, flip_lr, flip_ud, rot90, crop_y, crop_x, 0, 0}   (int32)
+ * selects source image `index` and the geometry, in the reference's order:
+ *   s   = source[index]                                        [Hs][Ws][3], dtype 0 f32, 1 u8, 2 u16
+ *   s   = s[:, ::-1] if flip_lr;  s = s[::-1] if flip_ud;  s = rot90(s, rot90)   (counter-clockwise, tf.image.rot90)
+ *   out = s[crop_y : crop_y + H, crop_x : crop_x + W] / white_level   (fp32, rounded as the IEEE division; f32 sources are
+ *                                                                      copied unscaled)
+ *   low[y, x] = out[min(floor(y * (H / (float)n)), H - 1), min(floor(x * (W / (float)n)), W - 1)],  n = net_input_size
+ * (TF1 ResizeNearestNeighbor, align_corners=False; fp32 scale and product).  Outputs, each optional (NULL = skipped):
+ * image_input [B][H][W][3] from src_input, image_target [B][H][W][3] from src_target (same table, its own dtype and white
+ * level; src_target may be NULL when image_target is), lowres_input [B][n][n][3] from src_input.  ops == NULL is the
+ * identity with index = b: it needs B <= N and (H, W) == (Hs, Ws).
+ * The table is read on the device, so a captured graph replays with new draws after a copy into it.  Memory safety does
+ * not depend on its contents: index is clamped to [0, N), the crop offsets to [0, extent - size] of the turned source,
+ * rot90 is masked with 3 and the flips with 1 -- such a record is a caller error whose result is the clamped sample,
+ * never an out-of-bounds access.  A crop that does not fit the source turned by a quarter (H > Ws or W > Hs) is refused
+ * when a table is given, unless HDRNET_SAMPLE_EVEN_TURNS_ONLY is set: the device then reads rot90 & 2.
+ * W % 4 == 0 when a full-resolution output is requested; outputs 16-byte, sources and table 4-byte aligned; the sources
+ * are read as aligned dwords (an allocation ends on a dword boundary).  Validation precedes any HIP call: 0, or 1 with
+ * hdrnet_last_error() set (include/hdrnet_amd.h).  B == 0 is a no-op.  No workspace, no atomics, asynchronous on `stream`. */
+#define HDRNET_SAMPLE_EVEN_TURNS_ONLY 1u
+int hdrnet_prepare_batch(const void* src_input, int input_dtype, float input_white_level, const void* src_target,
+                         int target_dtype, float target_white_level, int N, int Hs, int Ws, const int* ops, int B,
+                         float* image_input, float* image_target, int H, int W, float* lowres_input,
+                         int net_input_size, unsigned flags, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

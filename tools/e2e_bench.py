@@ -2,11 +2,14 @@
 """End-to-end timings of the reference's model graphs with the HIP hot path inside
 (BASELINE.json configs #3 and #4 on ONE MI355X; the 8-GPU runs are the driver's).
 
-    python tools/e2e_bench.py [--steps 20]
+    python tools/e2e_bench.py [--steps 20] [--feed]
 
 config #3: HDRNetPointwiseNNGuide inference, 3840x2160, batch 1 (coefficient net + guide in
            PyTorch-ROCm ops, slice-apply in the HIP kernel).
 config #4: training step (fwd + bwd + Adam) at 1920x1080, 4 images per GPU (= 32 / 8).
+--feed:    only config #4's graph-captured step, fed three ways, interleaved: from its own static buffers (no feed), by
+           pre-made f32 tensors through the staging copy, and by data.DeviceDataset.feed (u8 pairs on the device, drawn
+           and prepared into the static buffers each step).
 """
 import argparse
 import os
@@ -33,12 +36,46 @@ def timeit(fn, steps):
     return (time.perf_counter() - t) / steps
 
 
+def feed_bench(dev, steps):
+    """Config #4's step (as bench.py builds it) fed by a DeviceDataset beside the staging copy of pre-made tensors."""
+    import statistics
+
+    from hdrnet_amd import data
+    from hdrnet_amd.runtime import GraphedTrainStep
+    B, H, W, N, S = 4, 1080, 1920, 8, 2048
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    low = torch.rand((B, 256, 256, 3), device=dev, generator=gen)
+    full = torch.rand((B, H, W, 3), device=dev, generator=gen)
+    target = torch.rand((B, H, W, 3), device=dev, generator=gen)
+    ds = data.DeviceDataset(torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen),
+                            torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen),
+                            output_resolution=(H, W), generator=torch.Generator().manual_seed(1))
+    model = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).train()
+    opt = optim.FlatAdam([p for p in model.parameters() if p.requires_grad], lr=1e-4, epsilon_hat=True)
+    step = GraphedTrainStep(model, lambda out, tgt: metrics.l2_loss(tgt, out), opt, [low, full], [target], flat_bucket=True)
+    ways = {"own static buffers (no feed)": lambda: step(step.static_inputs, step.static_targets),
+            "pre-made f32 tensors, staging copy": lambda: step([low, full], [target]),
+            "DeviceDataset.feed (u8 pairs, all turns)": lambda: step(*ds.feed(step))}
+    for _ in range(100):  # pre-roll
+        step(step.static_inputs, step.static_targets)
+    res = {k: [] for k in ways}
+    for _ in range(5):
+        for k, fn in ways.items():
+            res[k].append(timeit(fn, steps))
+    for k, v in res.items():
+        t = statistics.median(v)
+        print(f"config #4  step fed by {k:42s}: {t * 1e3:.3f} ms/step (min {min(v) * 1e3:.3f}) = {B * H * W / 1e6 / t:.0f} MP/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--feed", action="store_true", help="only config #4's step, fed three ways (see the module text)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.feed:
+        return feed_bench(dev, args.steps)
 
     m = models.HDRNetPointwiseNNGuide().to(dev).eval()
     low = torch.rand(1, 256, 256, 3, device=dev)

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench] [--steps 50] [--json out.json] [--tools]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep] [--steps 50] [--json out.json] [--tools]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
 (hdrnet/hdrnet_ops_jax_tf2_test.py:56-65: batch 4, guide 4 x 1024 x 768 (h x w), grid 16 x 12 x 8 (gh x gw x gd), 2 channels, BilateralSlice,
-10 burn-in + 100 timed iterations there).  --tools loads the tools build and adds the round-1
+10 burn-in + 100 timed iterations there); `prep` = sample preparation (hdrnet_prepare_batch at 4 x 1080p from u8 and from
+u16 / 32767 + u8, hdrnet_lowres_input of a 4K u8 frame), each interleaved round by round with the stock-torch chain
+index -> flip -> rot90 -> crop -> .float() / wl -> nearest resize.  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -71,6 +73,8 @@ def main():
     lib.hdrnet_enable_kernel_names(1)
     if args.workload == "refbench":
         return refbench(lib, dev, args)
+    if args.workload == "prep":
+        return prep(dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -304,6 +308,90 @@ def refbench(lib, dev, args):
     if args.json:
         json.dump(dict(workload="refbench", rows=[dict(op="slice fwd", kernel=kern, us=round(med, 2), us_min=round(mn, 2),
                                                        GBps=round(nbytes / med / 1e3, 1))]), open(args.json, "w"), indent=1)
+
+
+def prep(dev, args):
+    """hdrnet_prepare_batch / hdrnet_lowres_input against the stock-torch chain a user would write today, interleaved
+    (kernel round, torch round, kernel round, ...) after a pre-roll, medians of 5 rounds each."""
+    from hdrnet_amd import data
+    B, H, W, n, N, S = 4, 1080, 1920, 256, 8, 2048
+    gen = torch.Generator(device=dev).manual_seed(1)
+    src8 = torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen)
+    tgt8 = torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen)
+    src16 = torch.randint(0, 32768, (N, S, S, 3), device=dev, dtype=torch.int32, generator=gen).to(torch.uint16)
+    outs = [(torch.empty((B, n, n, 3), device=dev), torch.empty((B, H, W, 3), device=dev), torch.empty((B, H, W, 3), device=dev))
+            for _ in range(2)]
+    ry, rx = S - H, S - W  # square sources: the same room after an odd turn
+
+    def table(geos):  # one record per sample: (flip_lr, flip_ud, rot90), different sources, offsets off every alignment
+        return torch.tensor([[(3 * b + 1) % N, flr, fud, rot, (37 * b + 5) % (ry + 1), (11 * b + 3) % (rx + 1), 0, 0]
+                             for b, (flr, fud, rot) in enumerate(geos)], dtype=torch.int32)
+
+    cases = {"identity geometry": table([(0, 0, 0)] * 4), "flips + even turns": table([(1, 0, 0), (0, 1, 2), (1, 1, 0), (0, 0, 2)]),
+             "mixed, odd turns included": table([(0, 0, 1), (1, 0, 3), (0, 1, 2), (1, 1, 1)]), "odd turns only": table([(0, 0, 1), (1, 0, 3), (0, 1, 3), (1, 1, 1)])}
+    sy = torch.tensor(H, dtype=torch.float32) / torch.tensor(n, dtype=torch.float32)
+    sx = torch.tensor(W, dtype=torch.float32) / torch.tensor(n, dtype=torch.float32)
+    ar = torch.arange(n, dtype=torch.float32)
+    ys = torch.clamp((ar * sy).floor().long(), max=H - 1).to(dev)
+    xs = torch.clamp((ar * sx).floor().long(), max=W - 1).to(dev)
+
+    def as_float(t):
+        return t.view(torch.uint16).float() if t.dtype == torch.int16 else t.float()
+
+    def chain(src, tgt, wl_in, wl_tg, ops, out):
+        low, full, target = out
+        for b, (idx, flr, fud, rot, cy, cx, _, _) in enumerate(ops):
+            for s_all, wl, dst in ((src, wl_in, full), (tgt, wl_tg, target)):
+                s = s_all[idx]
+                if s.dtype == torch.uint16:
+                    s = s.view(torch.int16)  # flips / rot90 of the same bits where uint16 has no kernel
+                if flr:
+                    s = s.flip(1)
+                if fud:
+                    s = s.flip(0)
+                if rot:
+                    s = torch.rot90(s, rot, (0, 1))
+                torch.div(as_float(s[cy:cy + H, cx:cx + W]), wl, out=dst[b])
+            low[b] = full[b].index_select(0, ys).index_select(1, xs)
+
+    rows = []
+
+    def ab(name, kernel, torch_chain, nbytes):
+        for k in range(400):  # pre-roll (~60 ms of launches)
+            kernel(k)
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(5):
+            a.append(timeit(kernel, args.steps, rounds=1)[0])
+            b.append(timeit(torch_chain, max(3, args.steps // 5), rounds=1)[0])
+        ka, tb = statistics.median(a), statistics.median(b)
+        rows.append(dict(op=name, us=round(ka, 2), us_torch_chain=round(tb, 2), algorithmic_MB=round(nbytes / 1e6, 1),
+                         GBps=round(nbytes / ka / 1e3, 1), hbm_frac=round(nbytes / ka / 1e3 / 8000, 4)))
+        print(f"{name:46s} kernel {ka:8.2f} us = {nbytes / ka / 1e3:7.1f} GB/s ({nbytes / ka / 1e3 / 80:5.1f}% of 8 TB/s)   "
+              f"torch chain {tb:9.2f} us ({nbytes / tb / 1e3 / 80:5.1f}%)   x{tb / ka:6.1f}   {nbytes / 1e6:6.1f} MB")
+
+    print(f"sample preparation: {B} x {H} x {W} crops of {N} sources of {S} x {S}, net_input_size {n}")
+    for fmt, (src, tgt, wl_in, wl_tg) in {"u8 / 255 + u8 / 255": (src8, tgt8, 255.0, 255.0),
+                                          "u16 / 32767 + u8 / 255": (src16, tgt8, 32767.0, 255.0)}.items():
+        nbytes = B * H * W * 3 * (src.element_size() + tgt.element_size() + 8) + B * n * n * 3 * (4 + src.element_size())
+        for cname, ops in cases.items():
+            dtab, ltab = ops.to(dev), ops.tolist()
+            ab(f"prepare_batch {fmt}, {cname}",
+               lambda k: data.prepare_batch(src, tgt, dtab, (H, W), n, wl_in, wl_tg, out=outs[k % 2]),
+               lambda k: chain(src, tgt, wl_in, wl_tg, ltab, outs[k % 2]), nbytes)
+    FH, FW = 2160, 3840
+    frames = [torch.randint(0, 256, (1, FH, FW, 3), device=dev, dtype=torch.uint8, generator=gen) for _ in range(12)]
+    lows = [torch.empty((1, n, n, 3), device=dev) for _ in range(2)]
+    ar = torch.arange(n, dtype=torch.float32)
+    fy = torch.clamp((ar * (torch.tensor(FH, dtype=torch.float32) / n)).floor().long(), max=FH - 1).to(dev)
+    fx = torch.clamp((ar * (torch.tensor(FW, dtype=torch.float32) / n)).floor().long(), max=FW - 1).to(dev)
+
+    def low_chain(k):
+        torch.div(frames[k % 12][0].index_select(0, fy).index_select(1, fx).float(), 255.0, out=lows[k % 2][0])
+
+    ab("lowres_input 4K u8", lambda k: data.lowres_input(frames[k % 12], n, out=lows[k % 2]), low_chain, n * n * 3 * (4 + 1))
+    if args.json:
+        json.dump(dict(workload="prep", rows=rows), open(args.json, "w"), indent=1)
 
 
 if __name__ == "__main__":
