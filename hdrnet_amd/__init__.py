@@ -13,7 +13,8 @@ Compute is hand-written HIP for gfx950 behind the C-ABI of ``include/hdrnet_amd.
 and ``torch.distributed`` only.
 """
 from . import data, hdrnet_ops, layers  # noqa: F401
-from .data import DeviceDataset, draw_ops, lowres_input, prepare_batch  # noqa: F401
+from .data import (DeviceDataset, RaggedDeviceDataset, draw_ops, lowres_input, pack_images, prepare_batch,  # noqa: F401
+                   prepare_batch_ragged)
 from .hdrnet_ops import bilateral_slice, bilateral_slice_apply  # noqa: F401
 
 __version__ = "0.1.0"

@@ -121,6 +121,8 @@ TRAIN_SIGNATURES = {
     "hdrnet_adam_step_f32": (_I, [_FP, _FP, _FP, _FP, ctypes.c_longlong, _FP] + [ctypes.c_float] * 4 + [_VP]),
     "hdrnet_adam_step_tf_f32": (_I, [_FP, _FP, _FP, _FP, ctypes.c_longlong, _FP] + [ctypes.c_float] * 4 + [_VP]),
     "hdrnet_prepare_batch": (_I, [_FP, _I, ctypes.c_float] * 2 + [_I] * 3 + [_FP, _I, _FP, _FP, _I, _I, _FP, _I, _U, _VP]),
+    "hdrnet_prepare_batch_ragged": (_I, [_FP, _I, ctypes.c_float] * 2 + [ctypes.c_longlong, _FP, _I] +
+                                    [_FP, _I, _FP, _FP, _I, _I, _FP, _I, _U, _VP]),
 }
 
 _lock = threading.Lock()

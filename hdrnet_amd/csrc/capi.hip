@@ -139,7 +139,9 @@ extern "C" {
 // 0.2.5.1: 4 -> 4 with offset (C = 20): dgrid on the contraction pass as two channel windows (the workspace bound doubles
 //          for that shape: query again); apply_vjp_seg's dguide in the z-difference form (bits change; closer to float64)
 // 0.2.6.0: + hdrnet_prepare_batch (include/hdrnet_amd_train.h), hdrnet_lowres_input: sample preparation from u8 / u16 / f32
-int hdrnet_version(void) { return 260; }
+// 0.2.7.0: + hdrnet_prepare_batch_ragged (include/hdrnet_amd_train.h): sample preparation from a packed set of images of
+//          mixed extents
+int hdrnet_version(void) { return 270; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -668,12 +670,16 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
   return rc;
 }
 
-// Sample preparation (sample_prep.hip).  Everything is checked before any HIP call.
+// Sample preparation (sample_prep.hip).  Everything is checked before any HIP call.  `ragged`: the sources are flat
+// buffers of n_samples samples with the descriptor table `images` (hdrnet_prepare_batch_ragged); Hs / Ws are then unused
+// and the fit of the crop is a matter of the table (the device clamps).
 static int prepare_impl(const char* what, const void* src_input, int input_dtype, float input_white_level,
                         const void* src_target, int target_dtype, float target_white_level, int N, int Hs, int Ws,
                         const int* ops, int B, float* image_input, float* image_target, int H, int W,
-                        float* lowres_input, int net_input_size, unsigned flags, void* stream) {
+                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged = false,
+                        long long n_samples = 0, const int* images = nullptr) {
   using namespace hdrnet_amd;
+  if (ragged) Hs = Ws = 1;  // unused
   if (flags & ~HDRNET_SAMPLE_EVEN_TURNS_ONLY)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown flags 0x%x (takes HDRNET_SAMPLE_EVEN_TURNS_ONLY)", what, flags);
   if (input_dtype < 0 || input_dtype > 2 || (src_target && (target_dtype < 0 || target_dtype > 2)))
@@ -682,21 +688,24 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
   if (!(input_white_level > 0.0f) || !(input_white_level <= 3.4028234e38f) ||
       (src_target && (!(target_white_level > 0.0f) || !(target_white_level <= 3.4028234e38f))))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: white levels must be positive and finite", what);
+  if (ragged && N <= 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: the image table is empty (N=%d)", what, N);
+  if (ragged && n_samples <= 0)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the source buffers are empty (n_samples=%lld)", what, n_samples);
   if (B < 0 || N <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || (lowres_input && net_input_size <= 0))
     return fail(HDRNET_INVALID_ARGUMENT,
                 "%s: non-positive extent (N=%d, Hs=%d, Ws=%d, B=%d, H=%d, W=%d, net_input_size=%d)", what, N, Hs, Ws, B,
                 H, W, net_input_size);
-  if (H > Hs || W > Ws)
+  if (!ragged && (H > Hs || W > Ws))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the crop %d x %d does not fit the %d x %d source", what, H, W, Hs, Ws);
-  if (!(flags & HDRNET_SAMPLE_EVEN_TURNS_ONLY) && ops && (H > Ws || W > Hs))
+  if (!ragged && !(flags & HDRNET_SAMPLE_EVEN_TURNS_ONLY) && ops && (H > Ws || W > Hs))
     return fail(HDRNET_INVALID_ARGUMENT,
                 "%s: the crop %d x %d does not fit the source turned by 90 degrees (%d x %d); pass "
                 "HDRNET_SAMPLE_EVEN_TURNS_ONLY", what, H, W, Ws, Hs);
-  if (!ops && (B > N || H != Hs || W != Ws))
+  if (!ragged && !ops && (B > N || H != Hs || W != Ws))
     return fail(HDRNET_INVALID_ARGUMENT,
                 "%s: ops == NULL is the identity (sample b = source b, whole image): needs B <= N and (H, W) == (Hs, Ws)",
                 what);
-  if ((long long)Hs * Ws * 12 >= (1LL << 31) || (long long)net_input_size * net_input_size * 12 >= (1LL << 31) || B > 65535)
+  if ((long long)Hs * Ws * 12 >= (1LL << 31) || (long long)H * W * 12 >= (1LL << 31) || (long long)net_input_size * net_input_size * 12 >= (1LL << 31) || B > 65535)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large", what);
   if (B == 0) {
     set_kernel("noop");
@@ -704,6 +713,9 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
     return HDRNET_OK;
   }
   if (!src_input) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (the input sources)", what);
+  if (ragged && !images) return fail(HDRNET_INVALID_ARGUMENT, "%s: null image table (images)", what);
+  if (ragged && !ops)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null ops: there is no identity geometry over images of mixed extents", what);
   if (image_target && !src_target)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: image_target given without src_target", what);
   if (!image_input && !image_target && !lowres_input)
@@ -714,11 +726,15 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
     return fail(HDRNET_INVALID_ARGUMENT, "%s: outputs must be 16-B aligned", what);
   if (((uintptr_t)src_input | (uintptr_t)src_target | (uintptr_t)ops) & 3u)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: sources and ops must be 4-B aligned", what);
-  const SamplePrepArgs a{src_input, src_target, input_dtype, src_target ? target_dtype : 0, input_white_level,
+  if ((uintptr_t)images & 15u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image table must be 16-B aligned (one 16-byte read per descriptor)", what);
+  SamplePrepArgs a{src_input, src_target, input_dtype, src_target ? target_dtype : 0, input_white_level,
                          src_target ? target_white_level : 1.0f, N, Hs, Ws, ops, B, H, W, image_input, image_target,
                          lowres_input, lowres_input ? net_input_size : 0, (flags & HDRNET_SAMPLE_EVEN_TURNS_ONLY) != 0};
+  a.images = images;
+  a.n_samples = n_samples;
   const int rc = check_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what);
-  if (rc == HDRNET_OK) set_kernel("sample_prep");
+  if (rc == HDRNET_OK) set_kernel(ragged ? "sample_prep_ragged" : "sample_prep");
   return rc;
 }
 
@@ -729,6 +745,15 @@ int hdrnet_prepare_batch(const void* src_input, int input_dtype, float input_whi
   return prepare_impl("hdrnet_prepare_batch", src_input, input_dtype, input_white_level, src_target, target_dtype,
                       target_white_level, N, Hs, Ws, ops, B, image_input, image_target, H, W, lowres_input,
                       net_input_size, flags, stream);
+}
+
+int hdrnet_prepare_batch_ragged(const void* src_input, int input_dtype, float input_white_level, const void* src_target,
+                                int target_dtype, float target_white_level, long long n_samples, const int* images, int N,
+                                const int* ops, int B, float* image_input, float* image_target, int H, int W,
+                                float* lowres_input, int net_input_size, unsigned flags, void* stream) {
+  return prepare_impl("hdrnet_prepare_batch_ragged", src_input, input_dtype, input_white_level, src_target, target_dtype,
+                      target_white_level, N, 0, 0, ops, B, image_input, image_target, H, W, lowres_input, net_input_size,
+                      flags, stream, true, n_samples, images);
 }
 
 int hdrnet_lowres_input(const void* frames, int dtype, float white_level, int B, int H, int W, float* lowres,

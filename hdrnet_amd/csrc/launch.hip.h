@@ -195,6 +195,10 @@ struct SamplePrepArgs {
   float* lowres_input;  // [B][n][n][3] or null
   int n;
   bool even_turns_only;
+  // the ragged flavour (images != null): src_* are flat buffers of n_samples samples each, images back to back, and
+  // Hs / Ws are unused
+  const int* images = nullptr;  // device [N][4] = {offset_lo, offset_hi, Hs, Ws}, the offset in samples
+  long long n_samples = 0;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 

@@ -32,6 +32,14 @@
 // rot90 is masked with 3 (2 with HDRNET_SAMPLE_EVEN_TURNS_ONLY) and the flips with 1.  Such a record is a caller error
 // whose result is the clamped sample.  Every load is of an aligned dword that contains at least one byte of the
 // source buffer (dword indices are clamped to the buffer's last dword).
+//
+// The RAGGED flavour (hdrnet_prepare_batch_ragged) reads a set of images of mixed extents: the sources are two flat
+// buffers, images back to back without padding, and a device table images[N][4] = {offset_lo, offset_hi, Hs, Ws} (the
+// offset in samples, the same for both buffers) takes the place of the uniform (Hs, Ws).  A workgroup reads its record's
+// descriptor with one wave-uniform 16-byte load through the constant address space; everything after make_geom is the
+// same code with the image's own pitch.  An image then starts at any byte (u8) or even byte (u16), which the unaligned
+// row machinery covers already.  Safety does not depend on the descriptors either: EVERY dword index of this flavour
+// is clamped to the flat buffer, so a bad descriptor gives a wrong sample, never an access outside the buffer.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -62,21 +70,27 @@ struct PrepParams {
   float scale_y, scale_x;  // H / (float)n, W / (float)n
   int tiles_x, tiles;      // full-res tiles per sample
   int even_only;
+  const int* images;    // RAGGED: device [N][4] = {offset_lo, offset_hi, Hs, Ws}, the offset in samples
+  long long n_samples;  // RAGGED: samples of each flat source buffer
 };
 
 typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
 struct u32x3a { uint32_t x, y, z; };  // 12 bytes exactly (a 3-vector type may be loaded as 4 dwords)
 typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const i32x4 ci32x4;  // wave-uniform descriptor: s_load_dwordx4
 
 // source (row, col) of output pixel (y, x):  even turns  row = r0 + rs * y, col = c0 + cs * x
 //                                            odd turns   row = r0 + rs * x, col = c0 + cs * y
 struct Geom {
   long long image;  // first sample of source image `index`
   int odd, r0, rs, c0, cs;
+  int Ws;  // pixels per source row of that image
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+template <bool RAGGED>
 __device__ __forceinline__ Geom make_geom(const PrepParams& p, int b) {
   int index = b, flr = 0, fud = 0, rot = 0, cy = 0, cx = 0;
   if (p.ops) {
@@ -87,25 +101,41 @@ __device__ __forceinline__ Geom make_geom(const PrepParams& p, int b) {
   }
   index = clampi(index, 0, p.N - 1);
   Geom g;
+  int Hs = p.Hs, Ws = p.Ws;
+  if constexpr (RAGGED) {
+    // the record is the same for the whole workgroup: the descriptor is one scalar 16-byte load
+    const i32x4 d = *((ci32x4*)p.images + __builtin_amdgcn_readfirstlane(index));
+    g.image = (long long)(((unsigned long long)(uint32_t)d.y << 32) | (uint32_t)d.x);
+    Hs = d.z; Ws = d.w;
+  } else {
+    g.image = (long long)index * p.Hs * p.Ws * 3;
+  }
+  g.Ws = Ws;
   g.odd = rot & 1;
-  cy = clampi(cy, 0, (g.odd ? p.Ws : p.Hs) - p.H);
-  cx = clampi(cx, 0, (g.odd ? p.Hs : p.Ws) - p.W);
+  cy = clampi(cy, 0, (g.odd ? Ws : Hs) - p.H);
+  cx = clampi(cx, 0, (g.odd ? Hs : Ws) - p.W);
   // the turn, in terms of (Y, X) = (cy + y, cx + x)
   const bool r_down = rot == 2 || rot == 3;  // row = Hs-1 - (Y or X)
   const bool c_down = rot == 1 || rot == 2;  // col = Ws-1 - (Y or X)
   g.rs = r_down ? -1 : 1;
-  g.r0 = r_down ? p.Hs - 1 : 0;
+  g.r0 = r_down ? Hs - 1 : 0;
   g.cs = c_down ? -1 : 1;
-  g.c0 = c_down ? p.Ws - 1 : 0;
+  g.c0 = c_down ? Ws - 1 : 0;
   g.r0 += g.rs * (g.odd ? cx : cy);
   g.c0 += g.cs * (g.odd ? cy : cx);
-  if (fud) { g.r0 = p.Hs - 1 - g.r0; g.rs = -g.rs; }
-  if (flr) { g.c0 = p.Ws - 1 - g.c0; g.cs = -g.cs; }
-  g.image = (long long)index * p.Hs * p.Ws * 3;
+  if (fud) { g.r0 = Hs - 1 - g.r0; g.rs = -g.rs; }
+  if (flr) { g.c0 = Ws - 1 - g.c0; g.cs = -g.cs; }
   return g;
 }
 
 __device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// index of the last dword of a source buffer of element type T
+template <typename T, bool RAGGED>
+__device__ __forceinline__ long long last_dword(const PrepParams& p) {
+  const long long samples = RAGGED ? p.n_samples : (long long)p.N * p.Hs * p.Ws * 3;
+  return ((samples * (long long)sizeof(T)) - 1) >> 2;
+}
 
 // 12 consecutive samples (4 pixels) starting at sample index e of the source, as floats / white level.  `last` is the
 // index of the source buffer's last dword.  A group at a tile's edge may be valid in part only, and its span may then
@@ -156,19 +186,21 @@ __device__ __forceinline__ void load_4px(const void* src, long long e, long long
   }
 }
 
-// one pixel (3 samples) at sample index e
-template <typename T>
+// one pixel (3 samples) at sample index e.  CLAMP: the pixel's position comes from a descriptor table that is not
+// trusted, so every dword index is clamped (the uniform flavour's positions are inside the buffer by construction).
+template <typename T, bool CLAMP>
 __device__ __forceinline__ void load_1px(const void* src, long long e, long long last, const WhiteLevel& wl, float (&v)[3]) {
   const uint32_t* base = static_cast<const uint32_t*>(src);
   if constexpr (sizeof(T) == 4) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = __uint_as_float(base[e + c]);
+    for (int c = 0; c < 3; ++c) v[c] = __uint_as_float(base[CLAMP ? clampll(e + c, 0, last) : e + c]);
   } else {
     const long long o = e * (long long)sizeof(T);
     const long long d = o >> 2;
     const uint32_t shift = (uint32_t)o & 3u;
     // u8: 3 bytes, inside one dword unless shift >= 2;  u16: 6 bytes, always exactly two dwords
-    const uint32_t w0 = base[d], w1 = base[d + 1 < last ? d + 1 : last];
+    const uint32_t w0 = base[CLAMP ? clampll(d, 0, last) : d];
+    const uint32_t w1 = base[CLAMP ? clampll(d + 1, 0, last) : (d + 1 < last ? d + 1 : last)];
     if constexpr (sizeof(T) == 1) {
       const uint32_t a = __builtin_amdgcn_alignbyte(w1, w0, shift);
 #pragma unroll
@@ -187,12 +219,12 @@ __device__ __forceinline__ int tile_addr(int ty, int e) {  // float index of ele
   return ty * kPitch + ((((e >> 2) ^ ((ty >> 2) & 7)) << 2) | (e & 3));
 }
 
-template <typename T>
+template <typename T, bool RAGGED>
 __device__ __forceinline__ void full_tile(const PrepParams& p, const PrepJob& job, const Geom& g, int b, int tile_id,
                                           float* __restrict__ tile) {
   const int ty0 = (tile_id / p.tiles_x) * kTileH, tx0 = (tile_id % p.tiles_x) * kTileW;
   const int tid = threadIdx.x;
-  const long long last = (((long long)p.N * p.Hs * p.Ws * 3 * (long long)sizeof(T)) - 1) >> 2;
+  const long long last = last_dword<T, RAGGED>(p);
   const bool rev = g.cs < 0;  // the 4 pixels of a group run against the source columns
   constexpr int kGroups = kTileH * kTileW / 4 / kThreads;
   float v[kGroups][12];
@@ -202,7 +234,7 @@ __device__ __forceinline__ void full_tile(const PrepParams& p, const PrepJob& jo
     for (int it = 0; it < kGroups; ++it) {
       const int grp = tid + kThreads * it, ty = grp / (kTileW / 4), x = tx0 + 4 * (grp % (kTileW / 4));
       const int row = g.r0 + g.rs * (ty0 + ty), col = g.c0 + g.cs * x - (rev ? 3 : 0);
-      load_4px<T>(job.src, g.image + ((long long)row * p.Ws + col) * 3, last, job.white, v[it]);
+      load_4px<T>(job.src, g.image + ((long long)row * g.Ws + col) * 3, last, job.white, v[it]);
     }
 #pragma unroll
     for (int it = 0; it < kGroups; ++it) {
@@ -227,7 +259,7 @@ __device__ __forceinline__ void full_tile(const PrepParams& p, const PrepJob& jo
     for (int it = 0; it < kGroups; ++it) {
       const int grp = tid + kThreads * it, tx = grp / (kTileH / 4), y = ty0 + 4 * (grp % (kTileH / 4));
       const int row = g.r0 + g.rs * (tx0 + tx), col = g.c0 + g.cs * y - (rev ? 3 : 0);
-      load_4px<T>(job.src, g.image + ((long long)row * p.Ws + col) * 3, last, job.white, v[it]);
+      load_4px<T>(job.src, g.image + ((long long)row * g.Ws + col) * 3, last, job.white, v[it]);
     }
 #pragma unroll
     for (int it = 0; it < kGroups; ++it) {
@@ -256,9 +288,9 @@ __device__ __forceinline__ void full_tile(const PrepParams& p, const PrepJob& jo
   }
 }
 
-template <typename T>
+template <typename T, bool RAGGED>
 __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& job, const Geom& g, int b) {
-  const long long last = (((long long)p.N * p.Hs * p.Ws * 3 * (long long)sizeof(T)) - 1) >> 2;
+  const long long last = last_dword<T, RAGGED>(p);
   const int npx = p.n * p.n;
   float* out = job.dst + (long long)b * npx * 3;
   const bool vec = (npx & 3) == 0;  // then every sample starts on a 16-byte boundary
@@ -272,7 +304,7 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
       y = y < p.H - 1 ? y : p.H - 1;
       x = x < p.W - 1 ? x : p.W - 1;
       const int row = g.r0 + g.rs * (g.odd ? x : y), col = g.c0 + g.cs * (g.odd ? y : x);
-      load_1px<T>(job.src, g.image + ((long long)row * p.Ws + col) * 3, last, job.white, v[j]);
+      load_1px<T, RAGGED>(job.src, g.image + ((long long)row * g.Ws + col) * 3, last, job.white, v[j]);
     }
     if (vec) {
       const float* f = &v[0][0];
@@ -291,21 +323,22 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
   }
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(kThreads) void sample_prep_kernel(const PrepParams p) {
   __shared__ __attribute__((aligned(16))) float tile[kTileH * kPitch];
   const PrepJob& job = p.job[blockIdx.z];
   const int b = blockIdx.y;
-  const Geom g = make_geom(p, b);
+  const Geom g = make_geom<RAGGED>(p, b);
   if (job.lowres) {
-    if (job.dtype == 1) lowres_job<uint8_t>(p, job, g, b);
-    else if (job.dtype == 2) lowres_job<uint16_t>(p, job, g, b);
-    else lowres_job<float>(p, job, g, b);
+    if (job.dtype == 1) lowres_job<uint8_t, RAGGED>(p, job, g, b);
+    else if (job.dtype == 2) lowres_job<uint16_t, RAGGED>(p, job, g, b);
+    else lowres_job<float, RAGGED>(p, job, g, b);
     return;
   }
   if ((int)blockIdx.x >= p.tiles) return;
-  if (job.dtype == 1) full_tile<uint8_t>(p, job, g, b, blockIdx.x, tile);
-  else if (job.dtype == 2) full_tile<uint16_t>(p, job, g, b, blockIdx.x, tile);
-  else full_tile<float>(p, job, g, b, blockIdx.x, tile);
+  if (job.dtype == 1) full_tile<uint8_t, RAGGED>(p, job, g, b, blockIdx.x, tile);
+  else if (job.dtype == 2) full_tile<uint16_t, RAGGED>(p, job, g, b, blockIdx.x, tile);
+  else full_tile<float, RAGGED>(p, job, g, b, blockIdx.x, tile);
 }
 
 }  // namespace
@@ -325,9 +358,13 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.tiles_x = (a.W + kTileW - 1) / kTileW;
   p.tiles = p.tiles_x * ((a.H + kTileH - 1) / kTileH);
   p.even_only = a.even_turns_only ? 1 : 0;
+  p.images = a.images;
+  p.n_samples = a.n_samples;
   const long long low_blocks = ((long long)a.n * a.n + 4 * kThreads - 1) / (4 * kThreads);
   const long long gx = full ? p.tiles : low_blocks;
-  sample_prep_kernel<<<dim3((unsigned)gx, (unsigned)a.B, (unsigned)nj), kThreads, 0, s>>>(p);
+  const dim3 grid((unsigned)gx, (unsigned)a.B, (unsigned)nj);
+  if (a.images) sample_prep_kernel<true><<<grid, kThreads, 0, s>>>(p);
+  else sample_prep_kernel<false><<<grid, kThreads, 0, s>>>(p);
   return hipGetLastError();
 }
 

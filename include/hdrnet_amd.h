@@ -86,7 +86,8 @@ extern "C" {
  *   251  4 -> 4 with offset (20 grid channels): dgrid runs on the fast pass as two channel windows; the workspace bound of
  *        that shape is no longer 0 (..._grad_workspace_bytes).  dguide of a call with dgrid == NULL changes in its last
  *        bits (contraction of the grid's z difference: closer to the float64 value than before).
- *   260  + hdrnet_lowres_input, and hdrnet_prepare_batch in hdrnet_amd_train.h (sample preparation from u8 / u16 / f32). */
+ *   260  + hdrnet_lowres_input, and hdrnet_prepare_batch in hdrnet_amd_train.h (sample preparation from u8 / u16 / f32).
+ *   270  + hdrnet_prepare_batch_ragged in hdrnet_amd_train.h (the same from a packed set of images of mixed extents). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

@@ -79,6 +79,25 @@ int hdrnet_prepare_batch(const void* src_input, int input_dtype, float input_whi
                          float* image_input, float* image_target, int H, int W, float* lowres_input,
                          int net_input_size, unsigned flags, void* stream);
 
+/* The same from a set of images of MIXED extents (photographs of many sizes and both orientations, as the reference's
+ * ImageFilesDataPipeline / HDRpDataPipeline decode them, data_pipeline.py:183-287).  src_input / src_target are FLAT
+ * buffers of n_samples samples each (3 per pixel): the images back to back with no padding between them, so an image
+ * starts at any byte (u8) or even byte (u16).  The DEVICE table
+ *   images[i] = {offset_lo, offset_hi, Hs, Ws}   (int32; 16-byte aligned)
+ * gives image i's first sample (a 64-bit count of SAMPLES split in two words, the same for both buffers: a pair has
+ * equal extents, only the element size differs) and its extents.  ops[b] is hdrnet_prepare_batch's record; the crop
+ * offsets are clamped to the room of the record's OWN image, [0, (odd turn ? Ws_i : Hs_i) - H] and so on.  `ops` is
+ * required: there is no identity geometry over mixed extents.  That every image holds the crop (turned too, unless
+ * HDRNET_SAMPLE_EVEN_TURNS_ONLY) is the table builder's business (hdrnet_amd/data.py checks it); memory safety depends
+ * on neither table: index is clamped to [0, N), turns and flips are masked, and every dword index is clamped to the flat
+ * buffer, so a bad record or descriptor gives a wrong sample, never an access outside the buffer.
+ * Dtype codes, white levels, the flag, W % 4 == 0, the alignment rules, the return codes, "validation precedes any HIP
+ * call" and the B == 0 no-op are hdrnet_prepare_batch's.  One launch, no workspace, no atomics, capturable. */
+int hdrnet_prepare_batch_ragged(const void* src_input, int input_dtype, float input_white_level, const void* src_target,
+                                int target_dtype, float target_white_level, long long n_samples, const int* images, int N,
+                                const int* ops, int B, float* image_input, float* image_target, int H, int W,
+                                float* lowres_input, int net_input_size, unsigned flags, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep] [--steps 50] [--json out.json] [--tools]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
 (hdrnet/hdrnet_ops_jax_tf2_test.py:56-65: batch 4, guide 4 x 1024 x 768 (h x w), grid 16 x 12 x 8 (gh x gw x gd), 2 channels, BilateralSlice,
 10 burn-in + 100 timed iterations there); `prep` = sample preparation (hdrnet_prepare_batch at 4 x 1080p from u8 and from
 u16 / 32767 + u8, hdrnet_lowres_input of a 4K u8 frame), each interleaved round by round with the stock-torch chain
-index -> flip -> rot90 -> crop -> .float() / wl -> nearest resize.  --tools loads the tools build and adds the round-1
+index -> flip -> rot90 -> crop -> .float() / wl -> nearest resize; `prep --ragged` instead times the same u8 batch from a
+packed set of images of mixed extents (hdrnet_prepare_batch_ragged) against the uniform call, interleaved.  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -66,6 +67,8 @@ def main():
     ap.add_argument("--luma-bins", type=int, default=None, help="override the grid depth GD (hdrnet/bin/train.py:235)")
     ap.add_argument("--smooth-guide", action="store_true",
                     help="an image-like guide (bench.make_sets' low-pass ramp + 2 %% noise) instead of U[0, 1)")
+    ap.add_argument("--ragged", action="store_true",
+                    help="with --workload prep: hdrnet_prepare_batch_ragged against hdrnet_prepare_batch, interleaved")
     ap.add_argument("--only", default=None, help="comma-separated substrings: run only the ops whose name contains one")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -74,7 +77,7 @@ def main():
     if args.workload == "refbench":
         return refbench(lib, dev, args)
     if args.workload == "prep":
-        return prep(dev, args)
+        return prep_ragged(dev, args) if args.ragged else prep(dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -392,6 +395,73 @@ def prep(dev, args):
     ab("lowres_input 4K u8", lambda k: data.lowres_input(frames[k % 12], n, out=lows[k % 2]), low_chain, n * n * 3 * (4 + 1))
     if args.json:
         json.dump(dict(workload="prep", rows=rows), open(args.json, "w"), indent=1)
+
+
+def prep_ragged(dev, args):
+    """hdrnet_prepare_batch_ragged from a packed set of u8 photographs of mixed extents against hdrnet_prepare_batch from
+    8 sources of 2048 x 2048: the same batch (4 crops of 1080 x 1920, the same records, u8 / 255 in and out, n = 256),
+    interleaved (uniform round, ragged round, ...) after a pre-roll; per case the median of the rounds and their spread.
+    A third column runs the ragged entry point on the UNIFORM call's own 8 x 2048 x 2048 sources, packed: same bytes at the
+    same pitch, so it separates the cost of the descriptor read from the effect of other images and row pitches."""
+    from hdrnet_amd import data
+    B, H, W, n, N, S, rounds = 4, 1080, 1920, 256, 8, 2048, 7
+    sizes = [(2048, 2048), (2160, 3840), (3840, 2160), (2048, 2731), (2731, 2049), (2049, 2051), (3000, 2000), (2000, 3000)]
+    gen = torch.Generator(device=dev).manual_seed(1)
+    src8 = torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen)
+    tgt8 = torch.randint(0, 256, (N, S, S, 3), device=dev, dtype=torch.uint8, generator=gen)
+    flat_in, images = data.pack_images([torch.randint(0, 256, (h, w, 3), device=dev, dtype=torch.uint8, generator=gen)
+                                        for h, w in sizes])
+    flat_tg, _ = data.pack_images([torch.randint(0, 256, (h, w, 3), device=dev, dtype=torch.uint8, generator=gen)
+                                   for h, w in sizes])
+    outs = [(torch.empty((B, n, n, 3), device=dev), torch.empty((B, H, W, 3), device=dev), torch.empty((B, H, W, 3), device=dev))
+            for _ in range(2)]
+
+    def table(geos):  # prep()'s records: they fit every image of `sizes` under every turn as well
+        return torch.tensor([[(3 * b + 1) % N, flr, fud, rot, 37 * b + 5, 11 * b + 3, 0, 0]
+                             for b, (flr, fud, rot) in enumerate(geos)], dtype=torch.int32)
+
+    cases = {"identity geometry": table([(0, 0, 0)] * 4), "flips + even turns": table([(1, 0, 0), (0, 1, 2), (1, 1, 0), (0, 0, 2)]),
+             "mixed, odd turns included": table([(0, 0, 1), (1, 0, 3), (0, 1, 2), (1, 1, 1)]), "odd turns only": table([(0, 0, 1), (1, 0, 3), (0, 1, 3), (1, 1, 1)])}
+    nbytes = B * H * W * 3 * (1 + 1 + 8) + B * n * n * 3 * (4 + 1)
+    dimages = images.to(dev)
+    same_images = data.pack_images([src8[0]] * N)[1].to(dev)  # src8 / tgt8 flattened ARE the packed 2048 x 2048 set
+    rows = []
+    print(f"sample preparation, u8 / 255 + u8 / 255: {B} x {H} x {W} crops of {N} sources of {S} x {S} (uniform) and of a packed "
+          f"set of {N} images of {min(sizes)} .. {max(sizes)} (ragged), net_input_size {n}; {rounds} interleaved rounds of {args.steps}")
+    for cname, ops in cases.items():
+        data.check_ops(ops, N, (S, S), (H, W))
+        data.check_ops(ops, N, images[:, 2:], (H, W))
+        dtab = ops.to(dev)
+
+        def uniform(k):
+            data.prepare_batch(src8, tgt8, dtab, (H, W), n, 255.0, 255.0, out=outs[k % 2])
+
+        def ragged(k):
+            data.prepare_batch_ragged(flat_in, flat_tg, dimages, dtab, (H, W), n, 255.0, 255.0, out=outs[k % 2])
+
+        def ragged_same(k):
+            data.prepare_batch_ragged(src8.view(-1), tgt8.view(-1), same_images, dtab, (H, W), n, 255.0, 255.0, out=outs[k % 2])
+
+        for k in range(200):  # pre-roll
+            uniform(k)
+            ragged(k)
+            ragged_same(k)
+        torch.cuda.synchronize()
+        u, r, q = [], [], []
+        for _ in range(rounds):
+            u.append(timeit(uniform, args.steps, rounds=1)[0])
+            r.append(timeit(ragged, args.steps, rounds=1)[0])
+            q.append(timeit(ragged_same, args.steps, rounds=1)[0])
+        mu, mr, mq = statistics.median(u), statistics.median(r), statistics.median(q)
+        rows.append(dict(op=cname, us_uniform=round(mu, 2), us_uniform_min=round(min(u), 2), us_uniform_max=round(max(u), 2),
+                         us_ragged=round(mr, 2), us_ragged_min=round(min(r), 2), us_ragged_max=round(max(r), 2),
+                         us_ragged_same_set=round(mq, 2), us_ragged_same_set_min=round(min(q), 2), us_ragged_same_set_max=round(max(q), 2),
+                         algorithmic_MB=round(nbytes / 1e6, 1), ragged_inside_uniform_spread=bool(min(u) <= mr <= max(u))))
+        print(f"{cname:28s} uniform {mu:8.2f} us ({min(u):8.2f} .. {max(u):8.2f}) = {nbytes / mu / 1e3:7.1f} GB/s   "
+              f"ragged {mr:8.2f} us ({min(r):8.2f} .. {max(r):8.2f}) = {nbytes / mr / 1e3:7.1f} GB/s   ragged / uniform {mr / mu:6.3f}   "
+              f"ragged on the uniform set {mq:8.2f} us ({min(q):8.2f} .. {max(q):8.2f}), / uniform {mq / mu:6.3f}")
+    if args.json:
+        json.dump(dict(workload="prep --ragged", rows=rows), open(args.json, "w"), indent=1)
 
 
 if __name__ == "__main__":
