@@ -47,6 +47,7 @@ SOURCES = [
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
     ("metrics.hip", []),
+    ("loss_psnr.hip", []),
     ("sample_prep.hip", []),
 ]
 TOOLS_ONLY_SOURCES = [

@@ -141,7 +141,7 @@ extern "C" {
 // 0.2.6.0: + hdrnet_prepare_batch (include/hdrnet_amd_train.h), hdrnet_lowres_input: sample preparation from u8 / u16 / f32
 // 0.2.7.0: + hdrnet_prepare_batch_ragged (include/hdrnet_amd_train.h): sample preparation from a packed set of images of
 //          mixed extents
-int hdrnet_version(void) { return 270; }
+int hdrnet_version(void) { return 280; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 

@@ -464,8 +464,8 @@ class DeviceDataset:
     launch; ``feed(step)`` does so straight into a ``runtime.GraphedTrainStep``'s static buffers.
 
     ``inputs`` / ``targets``: ``[N, Hs, Ws, 3]`` uint8 / uint16 / float32 device tensors (``targets`` may be ``None``);
-    ``output_resolution``: the crop ``(H, W)``; the augmentation switches are ``draw_ops``'s.  With ``rotate='even'`` the
-    crop may exceed the source's transposed extents (the kernel then masks odd turns).  ``order``: how the source
+    ``output_resolution``: the crop ``(H, W)``; the augmentation switches are ``draw_ops``'s.  With ``rotate='even'`` or
+    ``rotate=False`` the crop may exceed the source's transposed extents (the kernel then masks odd turns).  ``order``: how the source
     indices are chosen, ``"random"`` (uniform draws), ``"epoch"`` or ``"sequential"`` (see ``_Walk``).
     ``DeviceDataset.from_images`` holds a set of images of mixed extents instead."""
 
@@ -512,14 +512,22 @@ class DeviceDataset:
         """Draw ``batch`` records (or take the CPU table ``ops``) and prepare them:
         ``(lowres_input, image_input, image_target)``, into ``out`` if given."""
         table = self.draw(batch) if ops is None else ops
-        check_ops(table, len(self), self.source_hw, self.output_resolution, _rotate_mode(self.rotate) == "even")
+        even = self._even_turns_only()
+        check_ops(table, len(self), self.source_hw, self.output_resolution, even)
         dev_table = self._tables.get(batch)
         if dev_table is None:
             dev_table = self._tables[batch] = torch.zeros((batch, 8), dtype=torch.int32, device=self.inputs.device)
         dev_table.copy_(table, non_blocking=True)
         return prepare_batch(self.inputs, self.targets, dev_table, self.output_resolution, self.net_input_size,
-                             self.input_white_level, self.target_white_level, out=out,
-                             even_turns_only=_rotate_mode(self.rotate) == "even")
+                             self.input_white_level, self.target_white_level, out=out, even_turns_only=even)
+
+    def _even_turns_only(self) -> bool:
+        """May the device mask odd turns?  With ``rotate='even'``; and with ``rotate=False`` where the crop does not fit
+        the source turned by 90 degrees (no turn is drawn, and the kernel refuses such a crop otherwise: the evaluation
+        pipeline's 1080 x 1920 frames).  A crop that fits both ways keeps the full check of a caller's own table."""
+        mode = _rotate_mode(self.rotate)
+        (Hs, Ws), (H, W) = self.source_hw, self.output_resolution
+        return mode == "even" or (mode == "none" and (H > Ws or W > Hs))
 
     def feed(self, step, ops: Optional[torch.Tensor] = None):
         """Prepare the next batch INTO ``step``'s current static buffers (``static_inputs = [lowres, fullres]``,

@@ -87,7 +87,9 @@ extern "C" {
  *        that shape is no longer 0 (..._grad_workspace_bytes).  dguide of a call with dgrid == NULL changes in its last
  *        bits (contraction of the grid's z difference: closer to the float64 value than before).
  *   260  + hdrnet_lowres_input, and hdrnet_prepare_batch in hdrnet_amd_train.h (sample preparation from u8 / u16 / f32).
- *   270  + hdrnet_prepare_batch_ragged in hdrnet_amd_train.h (the same from a packed set of images of mixed extents). */
+ *   270  + hdrnet_prepare_batch_ragged in hdrnet_amd_train.h (the same from a packed set of images of mixed extents).
+ *   280  + hdrnet_loss_psnr_f32 / hdrnet_loss_psnr_workspace_bytes in hdrnet_amd_train.h (loss, per-image PSNR and their
+ *        running averages in the loss's own pass). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

@@ -35,6 +35,33 @@ int hdrnet_l2_loss_with_grad_f32(const float* prediction, const float* target, l
                                  float* dprediction_unit, void* workspace, size_t workspace_bytes, void* stream);
 int hdrnet_l2_loss_grad_scale_f32(float* dprediction, const float* grad_output, long long n, void* stream);
 
+/* The training loop's monitors in the loss's own pass (csrc/loss_psnr.hip; hdrnet/bin/train.py:95-96, 117-125, 160-174):
+ * prediction / target are [batch][n / batch] fp32.  ONE pass over both leaves the sum of squared differences per image and,
+ * with dprediction_unit given, hdrnet_l2_loss_with_grad_f32's unit gradient (2 / n)(prediction - target); a second,
+ * one-workgroup launch finishes in double:
+ *   image_mse[b] = float(S_b / (n / batch))                             (optional output, [batch])
+ *   loss[0]      = float(sum_b S_b / n)
+ *   psnr[0]      = float(mean_b(-10 / ln 10 * log(image_mse[b])))       (hdrnet/metrics.py:27-33; S_b == 0 gives +inf)
+ *   ema          (optional, DEVICE fp32 {ema_loss, ema_psnr, updates}): s <- s - (1 - decay)(s - value) for the loss and
+ *                the psnr just stored, in double from the stored floats, rounded once; updates += 1.  The shadow is
+ *                whatever the block held (start it at 0) and is not debiased: tf.train.ExponentialMovingAverage(decay)
+ *                .apply([tensor]) of TF 1.x as remembered, not confirmed against TensorFlow.  s / (1 - decay^updates)
+ *                is the debiased reading.  decay in [0, 1).
+ *   totals       (optional, DEVICE float64 {sum of per-image psnr, sum of image_mse, images}): accumulated in place, image
+ *                by image in index order -- an evaluation set's running sums, whatever the batch size.
+ * No atomics: every partial sum belongs to one image and is added in a fixed order, so results are bit-repeatable.  Nothing
+ * is read from the host between calls: a captured hipGraph replays correctly.  n % batch == 0; n / batch need not be a
+ * multiple of 4.  prediction, target, dprediction_unit and workspace 16-byte aligned, totals 8-byte, the other outputs
+ * 4-byte; `workspace`: hdrnet_loss_psnr_workspace_bytes(n, batch) bytes (0 for arguments the call refuses).  Validation
+ * precedes any HIP call: 1 for a null required buffer, n <= 0, batch <= 0, n % batch != 0, a short workspace, a misaligned
+ * pointer, or decay outside [0, 1) with ema given; 2 for a launch failure; else 0.  The backward stays
+ * hdrnet_l2_loss_grad_scale_f32 (first) / hdrnet_l2_loss_grad_f32 (again, through a retained graph). */
+size_t hdrnet_loss_psnr_workspace_bytes(long long n, int batch);
+int hdrnet_loss_psnr_f32(const float* prediction, const float* target, long long n, int batch, float* loss, float* psnr,
+                         float* image_mse /*opt*/, float* dprediction_unit /*opt*/, float* ema /*opt, 3 floats*/,
+                         float decay, double* totals /*opt, 3 doubles*/, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* The pyramid model's up-add and its VJP (hdrnet/models.py:283-287: `current = tf.image.resize_images(current, sz, BILINEAR,
  * align_corners=True) + out_lvl`), NHWC fp32, the resize of hdrnet_resize_bilinear_f32 (include/hdrnet_amd.h):
  *   hdrnet_resize_add_f32            output[B, OH, OW, C] = resize(coarse[B, IH, IW, C]) + fine[B, OH, OW, C], one pass

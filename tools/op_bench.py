@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -9,7 +9,9 @@ format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own mic
 10 burn-in + 100 timed iterations there); `prep` = sample preparation (hdrnet_prepare_batch at 4 x 1080p from u8 and from
 u16 / 32767 + u8, hdrnet_lowres_input of a 4K u8 frame), each interleaved round by round with the stock-torch chain
 index -> flip -> rot90 -> crop -> .float() / wl -> nearest resize; `prep --ragged` instead times the same u8 batch from a
-packed set of images of mixed extents (hdrnet_prepare_batch_ragged) against the uniform call, interleaved.  --tools loads the tools build and adds the round-1
+packed set of images of mixed extents (hdrnet_prepare_batch_ragged) against the uniform call, interleaved; `metrics` =
+the training step's loss at 4 x 1080p three ways, interleaved: l2_loss with its gradient, l2_loss + metrics.psnr, and
+metrics.Monitor (loss, PSNR and both moving averages from csrc/loss_psnr.hip).  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -78,6 +80,8 @@ def main():
         return refbench(lib, dev, args)
     if args.workload == "prep":
         return prep_ragged(dev, args) if args.ragged else prep(dev, args)
+    if args.workload == "metrics":
+        return metrics_monitor(dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -462,6 +466,76 @@ def prep_ragged(dev, args):
               f"ragged on the uniform set {mq:8.2f} us ({min(q):8.2f} .. {max(q):8.2f}), / uniform {mq / mu:6.3f}")
     if args.json:
         json.dump(dict(workload="prep --ragged", rows=rows), open(args.json, "w"), indent=1)
+
+
+def metrics_monitor(dev, args):
+    """What monitoring a training step costs at 4 x 1080p (config #4's batch): forward + backward of
+    (a) metrics.l2_loss with its gradient, (b) the same plus metrics.psnr as a torch chain under no_grad -- the reference's
+    train_op fetches both (hdrnet/bin/train.py:95-96) -- and (c) metrics.Monitor: loss, PSNR, the moving averages of both
+    and the unit gradient from the two launches of csrc/loss_psnr.hip.  Interleaved (a round of each in turn) after a
+    pre-roll, over three rotating pairs of tensors (600 MB: nothing is served from the cache); per case the median of
+    the rounds and their spread -- once as eager calls (host work included) and once as hipGraph replays (what a
+    GraphedTrainStep runs: device time alone)."""
+    from hdrnet_amd import metrics
+    B, H, W, rounds, sets = 4, 1080, 1920, 7, 3
+    gen = torch.Generator(device=dev).manual_seed(1)
+    tg = [torch.rand((B, H, W, 3), device=dev, generator=gen) for _ in range(sets)]
+    pr = [torch.rand((B, H, W, 3), device=dev, generator=gen).requires_grad_(True) for _ in range(sets)]
+    assert 2 * sets * tg[0].numel() * 4 > 2 * CACHE_BYTES
+    one = torch.ones((), device=dev)
+    monitor = metrics.Monitor()
+
+    def a(k):
+        torch.autograd.grad(metrics.l2_loss(tg[k % sets], pr[k % sets]), pr[k % sets], one)
+
+    def b(k):
+        torch.autograd.grad(metrics.l2_loss(tg[k % sets], pr[k % sets]), pr[k % sets], one)
+        with torch.no_grad():
+            metrics.psnr(tg[k % sets], pr[k % sets])
+
+    def c(k):
+        torch.autograd.grad(monitor(pr[k % sets], tg[k % sets]), pr[k % sets], one)
+
+    def replayed(fn):
+        """fn over each tensor pair captured into a hipGraph of its own: what a GraphedTrainStep replays, no host work."""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for k in range(sets):
+                fn(k)
+        torch.cuda.current_stream().wait_stream(side)
+        graphs = []
+        for k in range(sets):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn(k)
+            graphs.append(g)
+        return lambda k: graphs[k % sets].replay()
+
+    names = ("l2_loss + gradient", "l2_loss + gradient, metrics.psnr", "Monitor + gradient")
+    nbytes = tg[0].numel() * 4 * 3  # two reads and the gradient's write
+    rows = []
+    print(f"loss of a training step at {B} x {H} x {W} x 3 fp32, forward + backward; {rounds} interleaved rounds of {args.steps}")
+    for mode, fns in (("eager", (a, b, c)), ("hipGraph replay", tuple(replayed(fn) for fn in (a, b, c)))):
+        for k in range(60):  # pre-roll
+            for fn in fns:
+                fn(k)
+        torch.cuda.synchronize()
+        times = {name: [] for name in names}
+        for _ in range(rounds):
+            for name, fn in zip(names, fns):
+                times[name].append(timeit(fn, args.steps, rounds=1)[0])
+        lo, hi = min(times[names[0]]), max(times[names[0]])
+        for name in names:
+            t = times[name]
+            med = statistics.median(t)
+            rows.append(dict(op=name, mode=mode, us=round(med, 2), us_min=round(min(t), 2), us_max=round(max(t), 2),
+                             algorithmic_MB=round(nbytes / 1e6, 1), inside_l2_loss_spread=bool(lo <= med <= hi)))
+            print(f"{mode:16s} {name:34s} {med:8.2f} us ({min(t):8.2f} .. {max(t):8.2f})   {nbytes / med / 1e3:7.1f} GB/s of "
+                  f"the loss's own bytes   / l2_loss {med / statistics.median(times[names[0]]):6.3f}")
+    print("Monitor.read():", monitor.read())
+    if args.json:
+        json.dump(dict(workload="metrics", rows=rows), open(args.json, "w"), indent=1)
 
 
 if __name__ == "__main__":
