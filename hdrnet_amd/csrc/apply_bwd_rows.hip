@@ -142,14 +142,8 @@ __global__ __launch_bounds__(256) void apply_vjp_rows_vec4(
 
 constexpr size_t kMaxLdsBytes = 64 * 1024;
 
-struct VjpShape {
-  const float *grid, *guide, *input, *dout;
-  float *dguide, *dinput;
-  int B, H, W, GH, GW, GD, Cin, Cout, Cj;
-};
-
 template <int CIN, int COUT, bool OFFSET, bool WG, bool WI>
-hipError_t launch_vjp_t(const VjpShape& a, const Plan& pl, hipStream_t s) {
+hipError_t launch_vjp_t(const ApplyGradArgs& a, const Plan& pl, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   const int slab_off = round_up(pl.max_cols * a.GD * C, 4);
   const size_t lds =
@@ -162,7 +156,7 @@ hipError_t launch_vjp_t(const VjpShape& a, const Plan& pl, hipStream_t s) {
 }
 
 template <int CIN, int COUT, bool OFFSET>
-hipError_t launch_vjp_want(const VjpShape& a, const Plan& pl, hipStream_t s) {
+hipError_t launch_vjp_want(const ApplyGradArgs& a, const Plan& pl, hipStream_t s) {
   const bool wg = a.dguide != nullptr, wi = (a.dinput != nullptr) && CIN > 0;
   if (wg && wi) return launch_vjp_t<CIN, COUT, OFFSET, true, (CIN > 0)>(a, pl, s);
   if (wg) return launch_vjp_t<CIN, COUT, OFFSET, true, false>(a, pl, s);
@@ -170,7 +164,7 @@ hipError_t launch_vjp_want(const VjpShape& a, const Plan& pl, hipStream_t s) {
   return hipSuccess;
 }
 
-bool vjp_plan(const VjpShape& a, Plan* pl) {
+bool vjp_plan(const ApplyGradArgs& a, Plan* pl) {
   const bool aligned = (((uintptr_t)a.guide | (uintptr_t)a.input | (uintptr_t)a.dout |
                          (uintptr_t)a.grid | (uintptr_t)a.dguide | (uintptr_t)a.dinput) & 15u) == 0;
   *pl = make_row_plan(a.W, a.GW, aligned);
@@ -184,61 +178,35 @@ bool vjp_plan(const VjpShape& a, Plan* pl) {
 
 }  // namespace
 
-// ---- BilateralSliceApply: dguide / dinput -------------------------------------------------
-bool apply_vjp_rows_supported(const ApplyGradArgs& a) {
-  const bool shape = apply_fast_shape(a.Cin, a.Cout, a.has_offset);
-  if (!shape) return false;
-  VjpShape v{a.grid, a.guide, a.input, a.dout, a.dguide, a.dinput, a.B, a.H, a.W,
-             a.GH, a.GW, a.GD, a.Cin, a.Cout, a.Cj};
+bool vjp_rows_supported(const ApplyGradArgs& a) {
   Plan pl;
-  return vjp_plan(v, &pl);
+  return grad_fast_shape(a) && vjp_plan(a, &pl);
 }
 
-hipError_t launch_apply_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** name) {
+hipError_t launch_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** name) {
 #ifdef HDRNET_TOOLS_BUILD
   const bool round1_kernel = a.variant == 11;  // A/B: the round-1 kernel below
 #else
   const bool round1_kernel = false;
 #endif
-  if (!round1_kernel && apply_vjp_seg_supported(a)) {
+  if (!a.slice && !round1_kernel && apply_vjp_seg_supported(a)) {
     const hipError_t e = launch_apply_vjp_seg(a, s, name);
     if (e != hipErrorNotSupported) return e;
   }
-  VjpShape v{a.grid, a.guide, a.input, a.dout, a.dguide, a.dinput, a.B, a.H, a.W,
-             a.GH, a.GW, a.GD, a.Cin, a.Cout, a.Cj};
   Plan pl;
-  if (!vjp_plan(v, &pl)) return hipErrorInvalidValue;
-  *name = "apply_vjp_rows/vec4";
+  if (!vjp_plan(a, &pl)) return hipErrorInvalidValue;
+  if (!a.slice) {  // BilateralSliceApply: dguide / dinput
+    *name = "apply_vjp_rows/vec4";
 #define HDRNET_CASE(CI, CO, OFF) \
-  if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF) return launch_vjp_want<CI, CO, OFF>(v, pl, s);
-  HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
+  if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF) return launch_vjp_want<CI, CO, OFF>(a, pl, s);
+    HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
 #undef HDRNET_CASE
-  return hipErrorInvalidValue;
-}
-
-// ---- BilateralSlice: dguide (CIN = 0, one "offset" column per channel) ------------------------
-bool slice_vjp_rows_supported(const SliceGradArgs& a) {
-  if (!(a.C == 1 || a.C == 2 || a.C == 4 || a.C == 8 || a.C == 12 || a.C == 16)) return false;
-  VjpShape v{a.grid, a.guide, nullptr, a.dout, a.dguide, nullptr, a.B, a.H, a.W,
-             a.GH, a.GW, a.GD, 0, a.C, 1};
-  Plan pl;
-  return vjp_plan(v, &pl);
-}
-
-hipError_t launch_slice_vjp_rows(const SliceGradArgs& a, hipStream_t s, const char** name) {
-  VjpShape v{a.grid, a.guide, nullptr, a.dout, a.dguide, nullptr, a.B, a.H, a.W,
-             a.GH, a.GW, a.GD, 0, a.C, 1};
-  Plan pl;
-  if (!vjp_plan(v, &pl)) return hipErrorInvalidValue;
-  *name = "slice_vjp_rows/vec4";
+    return hipErrorInvalidValue;
+  }
+  *name = "slice_vjp_rows/vec4";  // BilateralSlice: dguide (CIN = 0, one "offset" column per channel)
 #define HDRNET_CASE(CC) \
-  if (a.C == CC) return launch_vjp_t<0, CC, true, true, false>(v, pl, s)
-  HDRNET_CASE(1);
-  HDRNET_CASE(2);
-  HDRNET_CASE(4);
-  HDRNET_CASE(8);
-  HDRNET_CASE(12);
-  HDRNET_CASE(16);
+  if (a.Cout == CC) return launch_vjp_t<0, CC, true, true, false>(a, pl, s);
+  HDRNET_SLICE_FAST_CHANNELS(HDRNET_CASE)
 #undef HDRNET_CASE
   return hipErrorInvalidValue;
 }

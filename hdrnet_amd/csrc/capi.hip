@@ -44,6 +44,11 @@ void set_kernel(const char* a, const char* b = "", const char* c = "") {
            ((*a || *b) && *c) ? "+" : "", c);
 }
 
+}  // namespace
+
+// The tail of every entry point, here and beside the kernels (declared in launch.hip.h).
+namespace hdrnet_amd {
+
 int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -52,29 +57,41 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-int check_launch(hipError_t e, const char* what) {
+int finish_launch(hipError_t e, const char* what, const char* name) {
   if (e != hipSuccess) {
     // TF: errors::Internal("BilateralSliceApply kernel failed.")
     return fail(HDRNET_RUNTIME_FAILURE, "%s kernel failed: %s", what, hipGetErrorString(e));
   }
   g_error[0] = '\0';
+  if (name) set_kernel(name);
   return HDRNET_OK;
 }
+
+int finish_noop() { return finish_launch(hipSuccess, "", "noop"); }
+
+}  // namespace hdrnet_amd
+
+namespace {
+
+using hdrnet_amd::fail;
+using hdrnet_amd::finish_launch;
+using hdrnet_amd::finish_noop;
 
 bool positive(int v) { return v > 0; }
 
 // A grid gradient on the generic gather kernel (the reference's own design, bilateral_slice_apply.cc:84-138: every grid
 // element loops over its +-1-cell pixel window) is ~100x slower than the contraction pass.  HDRNET_KERNEL_AUTO falls
 // back to it for shapes the pass has no specialisation for (GD > 16, C > 32, an unlisted channel combination) or
-// without a workspace; on a frame-sized call that is a performance cliff worth one line on stderr per process.
+// without a large enough workspace; on a frame-sized call (grad_dispatch asks only above kWarnGenericPixels, and works
+// out the reason only then) that is a performance cliff worth one line on stderr per process and reason.
 constexpr long long kWarnGenericPixels = 65536;
-void warn_generic_grid_grad(const char* op, long long npix, int GD, int C, bool have_workspace) {
-  static std::atomic<bool> said{false};
-  if (npix <= kWarnGenericPixels || said.exchange(true)) return;
+void warn_generic_grid_grad(const char* op, long long npix, int GD, int C, bool no_fast_shape) {
+  static std::atomic<bool> said[2];
+  if (said[no_fast_shape].exchange(true)) return;
   fprintf(stderr, "hdrnet_amd: %s on %lld pixels (GD=%d, C=%d) takes the generic grid-gradient kernel, ~100x slower "
           "than the fast pass (%s)\n", op, npix, GD, C,
-          have_workspace ? "no fast specialisation for this shape: needs GD <= 16, C <= 32 and a listed channel combination"
-                         : "no workspace passed: see hdrnet_bilateral_slice*_grad_workspace_bytes");
+          no_fast_shape ? "no fast specialisation for this shape: needs GD <= 16, C <= 32 and a listed channel combination"
+                        : "no workspace passed: see hdrnet_bilateral_slice*_grad_workspace_bytes");
 }
 
 // Extents >= 0; a zero-sized batch / image is a legal no-op, a zero-sized grid is not.
@@ -114,6 +131,28 @@ int check_guide_prescaled(unsigned flags, int Cin, const float* conv1, const flo
   return HDRNET_OK;
 }
 
+// the wire formats of the ..._io entry points: 0 f32, 1 u8, 2 u16 in; 0 f32, 1 u8 out
+int check_io_format(int input_dtype, float input_white_level, int output_dtype) {
+  if (input_dtype < 0 || input_dtype > 2 || output_dtype < 0 || output_dtype > 1)
+    return fail(HDRNET_INVALID_ARGUMENT, "unknown dtype code (input %d, output %d)", input_dtype, output_dtype);
+  if (!(input_white_level > 0.0f)) return fail(HDRNET_INVALID_ARGUMENT, "input_white_level must be positive");
+  return HDRNET_OK;
+}
+
+// any parameter the coefficient network reads (and, for the gradient, any it writes) missing?
+bool coeff_net_null_param(const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads* grads) {
+  int n_ds = 0;
+  for (int v = net.net_input_size / net.spatial_bin; v > 1; v >>= 1) ++n_ds;
+  const auto scan = [n_ds](const auto& p) {
+    bool null_param = !p.pred_w || !p.pred_b || !p.local_w[0] || !p.local_w[1] || !p.local_b[0];
+    for (int i = 0; i < n_ds; ++i) null_param = null_param || !p.splat_w[i] || !p.splat_b[i];
+    for (int i = 0; i < 2; ++i) null_param = null_param || !p.global_conv_w[i] || !p.global_conv_b[i];
+    for (int i = 0; i < 3; ++i) null_param = null_param || !p.fc_w[i] || !p.fc_b[i];
+    return null_param;
+  };
+  return scan(net) || (grads && scan(*grads));
+}
+
 int check_flags(unsigned flags) {
   if ((flags & 0xffu) > HDRNET_KERNEL_FAST || (flags >> 16) != 0)
     return fail(HDRNET_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
@@ -128,6 +167,62 @@ int check_flags(unsigned flags) {
 unsigned family(unsigned flags) { return flags & 0xffu; }
 int variant(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
 
+// Both gradient entry points, once their own arguments are checked: the legal no-ops, then the ladder -- all gradients
+// from ONE pass over the pixels (fused), else dguide / dinput on the per-pixel fast kernel and dgrid on the MFMA
+// contraction, and what neither took on the op's generic kernel.  `family`: HDRNET_KERNEL_*.
+int grad_dispatch(const hdrnet_amd::ApplyGradArgs& a, unsigned family, hipStream_t s) {
+  using namespace hdrnet_amd;
+  const char* what = a.slice ? "BilateralSliceGrad" : "BilateralSliceApplyGrad";
+  if (!a.dgrid && !a.dguide && !a.dinput) return finish_noop();
+  const long long npix = (long long)a.B * a.H * a.W;
+  if (npix == 0) {
+    // Gradients of an empty image: dgrid is all zeros, the others are empty.
+    if (a.dgrid && a.B > 0) {
+      const hipError_t e =
+          hipMemsetAsync(a.dgrid, 0, sizeof(float) * (size_t)a.B * a.GH * a.GW * a.GD * a.Cout * a.Cj, s);
+      if (e != hipSuccess) return finish_launch(e, what, nullptr);
+    }
+    return finish_noop();
+  }
+  if (!a.guide || !a.dout || (a.Cin > 0 && !a.input) || ((a.dguide || a.dinput) && !a.grid))
+    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  // (tools variant 3: the un-fused kernels)
+  if (family != HDRNET_KERNEL_GENERIC && a.variant != 3 && bwd_fused_supported(a)) {
+    const char* name = "";
+    const hipError_t e = launch_bwd_fused(a, s, &name);
+    return finish_launch(e, what, name);
+  }
+  const bool pix_fast = family != HDRNET_KERNEL_GENERIC && (a.dguide || a.dinput) && vjp_rows_supported(a);
+  if (family == HDRNET_KERNEL_FAST && (a.dguide || a.dinput) && !pix_fast)
+    return fail(HDRNET_INVALID_ARGUMENT, "no fast %s variant for this shape", what);
+  const char *pix_name = "", *gg_name = "", *rest_name = "";
+  ApplyGradArgs rest = a;
+  if (pix_fast) {
+    if (int rc = finish_launch(launch_vjp_rows(a, s, &pix_name), what, nullptr)) return rc;
+    rest.dguide = nullptr;
+    rest.dinput = nullptr;
+  }
+  if (a.dgrid && family != HDRNET_KERNEL_GENERIC) {
+    if (grid_grad_mfma_supported(a)) {
+      if (int rc = finish_launch(launch_grid_grad_mfma(a, s, &gg_name), what, nullptr)) return rc;
+      rest.dgrid = nullptr;
+    } else if (family == HDRNET_KERNEL_FAST) {
+      return fail(HDRNET_INVALID_ARGUMENT,
+                  "no fast grid-gradient variant for this shape (or workspace missing / too small)");
+    }
+  }
+  if (rest.dgrid || rest.dguide || rest.dinput) {
+    if (rest.dgrid && family == HDRNET_KERNEL_AUTO && npix > kWarnGenericPixels)
+      warn_generic_grid_grad(what, npix, a.GD, a.Cout * a.Cj, /*no_fast_shape=*/!grad_fast_shape(a) ||
+                             grid_grad_mfma_workspace(a.B, a.H, a.W, a.GH, a.GW, a.GD, a.Cout * a.Cj) == 0);
+    const hipError_t e = a.slice ? launch_slice_grad_generic(rest, s) : launch_apply_grad_generic(rest, s);
+    if (int rc = finish_launch(e, what, nullptr)) return rc;
+    rest_name = a.slice ? "slice_grad_generic" : "apply_grad_generic";
+  }
+  set_kernel(pix_name, gg_name, rest_name);
+  return HDRNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,7 +236,8 @@ extern "C" {
 // 0.2.6.0: + hdrnet_prepare_batch (include/hdrnet_amd_train.h), hdrnet_lowres_input: sample preparation from u8 / u16 / f32
 // 0.2.7.0: + hdrnet_prepare_batch_ragged (include/hdrnet_amd_train.h): sample preparation from a packed set of images of
 //          mixed extents
-int hdrnet_version(void) { return 280; }
+// 0.2.8.1: the training-loop entry points of include/hdrnet_amd_train.h set / clear hdrnet_last_error() like the rest
+int hdrnet_version(void) { return 281; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -176,11 +272,7 @@ static int apply_fwd_impl(const float* grid, const float* guide, const float* in
                 "grid should have output_channels * (input_channels%s) channels "
                 "(Cin=%d, Cout=%d)", has_offset ? " + 1" : "", Cin, Cout);
   const long long npix = (long long)B * H * W;
-  if (npix == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if (npix == 0) return finish_noop();
   if (!grid || !guide || !out || (Cin > 0 && !input))
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   ApplyArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout,
@@ -196,13 +288,9 @@ static int apply_fwd_impl(const float* grid, const float* guide, const float* in
   if (family(flags) != HDRNET_KERNEL_GENERIC && fast_ok) {
     const char* name = "";
     const hipError_t e = band ? launch_apply_fwd_seg(a, s, &name) : launch_apply_fwd_rows(a, s, &name);
-    const int rc = check_launch(e, "BilateralSliceApply");
-    if (rc == HDRNET_OK) set_kernel(name);
-    return rc;
+    return finish_launch(e, "BilateralSliceApply", name);
   }
-  const int rc = check_launch(launch_apply_fwd_generic(a, s), "BilateralSliceApply");
-  if (rc == HDRNET_OK) set_kernel("apply_fwd_generic");
-  return rc;
+  return finish_launch(launch_apply_fwd_generic(a, s), "BilateralSliceApply", "apply_fwd_generic");
 }
 
 int hdrnet_bilateral_slice_apply_f32_ex(const float* grid, const float* guide,
@@ -255,11 +343,7 @@ int hdrnet_bilateral_slice_apply_nnguide_f32_ex(const float* grid, const float* 
   if (Cin <= 0 || Cout <= 0 || n_feats <= 0 || n_feats > 4096)
     return fail(HDRNET_INVALID_ARGUMENT, "bad channel / feature counts (Cin=%d, Cout=%d, n=%d)", Cin,
                 Cout, n_feats);
-  if ((long long)B * H * W == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !guide_conv1 || !guide_conv2)
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
@@ -272,11 +356,9 @@ int hdrnet_bilateral_slice_apply_nnguide_f32_ex(const float* grid, const float* 
                 "fused guide + slice-apply needs (Cin, Cout) in {(3,3), (1,1)}, W %% 4 == 0 and 16-B "
                 "aligned buffers; run the guide network and hdrnet_bilateral_slice_apply_f32 instead");
   const char* name = "";
-  const int rc = check_launch(launch_apply_fwd_nnguide(a, guide_conv1, guide_conv2, n_feats, guide_out,
-                                                      static_cast<hipStream_t>(stream), &name),
-                              "BilateralSliceApplyNNGuide");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_apply_fwd_nnguide(a, guide_conv1, guide_conv2, n_feats, guide_out,
+                                                static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "BilateralSliceApplyNNGuide", name);
 }
 
 int hdrnet_bilateral_slice_apply_upadd_f32(const float* grid, const float* guide, const float* input,
@@ -303,11 +385,7 @@ int hdrnet_bilateral_slice_apply_upadd_f32_ex(const float* grid, const float* gu
     return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
   if (guide_conv1 && (!guide_conv2 || n_feats <= 0 || n_feats > 4096))
     return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
-  if ((long long)B * H * W == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !coarse) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
   ApplyArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout,
@@ -319,11 +397,9 @@ int hdrnet_bilateral_slice_apply_upadd_f32_ex(const float* grid, const float* gu
                 "slice-apply + up-add needs Cin = Cout = 3 with offset, W %% 4 == 0 and 16-B aligned "
                 "buffers; compose hdrnet_bilateral_slice_apply_f32 and hdrnet_resize_bilinear_f32 instead");
   const char* name = "";
-  const int rc = check_launch(launch_apply_fwd_upadd(a, coarse, Hc, Wc, guide_conv1, guide_conv2, n_feats,
-                                                    static_cast<hipStream_t>(stream), &name),
-                              "BilateralSliceApplyUpAdd");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_apply_fwd_upadd(a, coarse, Hc, Wc, guide_conv1, guide_conv2, n_feats,
+                                              static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "BilateralSliceApplyUpAdd", name);
 }
 
 int hdrnet_resize_bilinear_f32(const float* in, float* out, int B, int Hin, int Win, int Hout, int Wout,
@@ -332,18 +408,12 @@ int hdrnet_resize_bilinear_f32(const float* in, float* out, int B, int Hin, int 
   if (B < 0 || Hin <= 0 || Win <= 0 || Hout < 0 || Wout < 0 || C <= 0)
     return fail(HDRNET_INVALID_ARGUMENT, "bad extents (B=%d, in %dx%d, out %dx%d, C=%d)", B, Hin, Win, Hout,
                 Wout, C);
-  if ((long long)B * Hout * Wout == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if ((long long)B * Hout * Wout == 0) return finish_noop();
   if (!in || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   const char* name = "";
-  const int rc = check_launch(launch_resize_bilinear(in, out, B, Hin, Win, Hout, Wout, C,
-                                                    static_cast<hipStream_t>(stream), &name),
-                              "ResizeBilinear");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_resize_bilinear(in, out, B, Hin, Win, Hout, Wout, C, static_cast<hipStream_t>(stream),
+                                              &name);
+  return finish_launch(e, "ResizeBilinear", name);
 }
 
 size_t hdrnet_pointwise_guide_grad_workspace_bytes(long long npx, int Cin, int n_feats) {
@@ -365,9 +435,7 @@ int hdrnet_pointwise_guide_grad_f32(const float* input, const float* guide, cons
   if (npx == 0) {  // no pixels: zero parameter gradients
     hipError_t e = hipMemsetAsync(dconv1, 0, sizeof(float) * (size_t)n_feats * (Cin + 1), s);
     if (e == hipSuccess) e = hipMemsetAsync(dconv2, 0, sizeof(float) * (size_t)(n_feats + 1), s);
-    const int rc = check_launch(e, "PointwiseGuideGrad");
-    if (rc == HDRNET_OK) set_kernel("noop");
-    return rc;
+    return finish_launch(e, "PointwiseGuideGrad", "noop");
   }
   if (!input || !guide || !dguide) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   GuideGradArgs a{input, guide, dguide, guide_conv1, guide_conv2, dinput, accumulate_dinput != 0,
@@ -377,9 +445,8 @@ int hdrnet_pointwise_guide_grad_f32(const float* input, const float* guide, cons
                 "guide-network gradient needs Cin in {1,3}, n_feats in {4,8,16}, 16-B aligned buffers "
                 "and a workspace of hdrnet_pointwise_guide_grad_workspace_bytes()");
   const char* name = "";
-  const int rc = check_launch(launch_guide_grad(a, s, &name), "PointwiseGuideGrad");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_guide_grad(a, s, &name);
+  return finish_launch(e, "PointwiseGuideGrad", name);
 }
 
 size_t hdrnet_curves_guide_grad_workspace_bytes(long long npx, int Cin, int npts) {
@@ -404,9 +471,7 @@ int hdrnet_curves_guide_grad_f32(const float* input, const float* dguide, const 
     if (e == hipSuccess) e = hipMemsetAsync(dshifts, 0, sizeof(float) * (size_t)npts * Cin, s);
     if (e == hipSuccess) e = hipMemsetAsync(dslopes, 0, sizeof(float) * (size_t)npts * Cin, s);
     if (e == hipSuccess) e = hipMemsetAsync(dmix, 0, sizeof(float) * (size_t)(Cin + 1), s);
-    const int rc = check_launch(e, "CurvesGuideGrad");
-    if (rc == HDRNET_OK) set_kernel("noop");
-    return rc;
+    return finish_launch(e, "CurvesGuideGrad", "noop");
   }
   if (!input || !dguide) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   CurvesGradArgs a{input, dguide, guide_ccm, guide_shifts, guide_slopes, guide_mix, dinput,
@@ -417,9 +482,8 @@ int hdrnet_curves_guide_grad_f32(const float* input, const float* dguide, const 
                 "curves-guide gradient needs Cin = 3, npts = 16 and a workspace of "
                 "hdrnet_curves_guide_grad_workspace_bytes()");
   const char* name = "";
-  const int rc = check_launch(launch_curves_grad(a, s, &name), "CurvesGuideGrad");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_curves_grad(a, s, &name);
+  return finish_launch(e, "CurvesGuideGrad", name);
 }
 
 size_t hdrnet_input_moments_workspace_bytes(long long npx, int Cin) {
@@ -439,19 +503,15 @@ int hdrnet_input_moments_f32(const float* input, long long npx, int Cin, float* 
   if (npx == 0) {
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(float) * Cin, s);
     if (e == hipSuccess) e = hipMemsetAsync(moments, 0, sizeof(float) * Cin * Cin, s);
-    const int rc = check_launch(e, "InputMoments");
-    if (rc == HDRNET_OK) set_kernel("noop");
-    return rc;
+    return finish_launch(e, "InputMoments", "noop");
   }
   const size_t need = input_moments_workspace_bytes(npx, Cin);
   if (!input || ((uintptr_t)input & 15u) || !workspace || workspace_bytes < need)
     return fail(HDRNET_INVALID_ARGUMENT, "input moments need a 16-B aligned input and a workspace of "
                                          "hdrnet_input_moments_workspace_bytes()");
   const char* name = "";
-  const int rc = check_launch(launch_input_moments(input, npx, Cin, sums, moments, workspace, s, &name),
-                              "InputMoments");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_input_moments(input, npx, Cin, sums, moments, workspace, s, &name);
+  return finish_launch(e, "InputMoments", name);
 }
 
 int hdrnet_guide_nn_prescale_f32(const float* guide_conv1, const float* guide_conv2, int n_feats, int Cin, float x_max,
@@ -464,11 +524,9 @@ int hdrnet_guide_nn_prescale_f32(const float* guide_conv1, const float* guide_co
   if (!guide_conv1 || !guide_conv2 || !conv1_out || !conv2_out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (((uintptr_t)conv1_out | (uintptr_t)conv2_out) & 15u)
     return fail(HDRNET_INVALID_ARGUMENT, "guide prescale needs 16-B aligned output arrays");
-  const int rc = check_launch(launch_guide_nn_prescale(guide_conv1, guide_conv2, n_feats, x_max, conv1_out, conv2_out,
-                                                       static_cast<hipStream_t>(stream)),
-                              "GuideNNPrescale");
-  if (rc == HDRNET_OK) set_kernel("guide_nn_prescale");
-  return rc;
+  return finish_launch(launch_guide_nn_prescale(guide_conv1, guide_conv2, n_feats, x_max, conv1_out, conv2_out,
+                                                static_cast<hipStream_t>(stream)), "GuideNNPrescale",
+                       "guide_nn_prescale");
 }
 
 int hdrnet_guide_fold_batch_f32(const float* sums, const float* moments, long long npx, const float* w1,
@@ -482,12 +540,9 @@ int hdrnet_guide_fold_batch_f32(const float* sums, const float* moments, long lo
                 npx, Cin, n_feats);
   if (!sums || !moments || !w1 || !gamma || !beta || !w2 || !b2 || !conv1 || !conv2 || (!running_mean != !running_var))
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  const int rc = check_launch(launch_guide_fold_batch(sums, moments, npx, w1, gamma, beta, w2, b2, eps, momentum, Cin,
-                                                      n_feats, conv1, conv2, running_mean, running_var,
-                                                      num_batches_tracked, static_cast<hipStream_t>(stream)),
-                              "GuideFoldBatch");
-  if (rc == HDRNET_OK) set_kernel("guide_fold_batch");
-  return rc;
+  return finish_launch(launch_guide_fold_batch(sums, moments, npx, w1, gamma, beta, w2, b2, eps, momentum, Cin, n_feats,
+                                               conv1, conv2, running_mean, running_var, num_batches_tracked,
+                                               static_cast<hipStream_t>(stream)), "GuideFoldBatch", "guide_fold_batch");
 }
 
 int hdrnet_guide_fold_batch_grad_f32(const float* sums, const float* moments, long long npx, const float* w1,
@@ -500,12 +555,9 @@ int hdrnet_guide_fold_batch_grad_f32(const float* sums, const float* moments, lo
                 npx, Cin, n_feats);
   if (!sums || !moments || !w1 || !gamma || !beta || !dconv1 || !dconv2 || !dw1 || !dbeta || !dw2 || !db2)
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  const int rc = check_launch(launch_guide_fold_batch_grad(sums, moments, npx, w1, gamma, beta, eps, Cin, n_feats,
-                                                           dconv1, dconv2, dw1, dbeta, dw2, db2,
-                                                           static_cast<hipStream_t>(stream)),
-                              "GuideFoldBatchGrad");
-  if (rc == HDRNET_OK) set_kernel("guide_fold_batch_grad");
-  return rc;
+  return finish_launch(launch_guide_fold_batch_grad(sums, moments, npx, w1, gamma, beta, eps, Cin, n_feats, dconv1,
+                                                    dconv2, dw1, dbeta, dw2, db2, static_cast<hipStream_t>(stream)),
+                       "GuideFoldBatchGrad", "guide_fold_batch_grad");
 }
 
 size_t hdrnet_l2_loss_workspace_bytes(long long n) { return hdrnet_amd::l2_loss_workspace_bytes(n); }
@@ -518,10 +570,8 @@ int hdrnet_l2_loss_f32(const float* prediction, const float* target, long long n
   if ((((uintptr_t)prediction | (uintptr_t)target) & 15u) || !workspace || workspace_bytes < l2_loss_workspace_bytes(n))
     return fail(HDRNET_INVALID_ARGUMENT, "l2 loss needs 16-B aligned tensors and a workspace of "
                                          "hdrnet_l2_loss_workspace_bytes()");
-  const int rc = check_launch(launch_l2_loss(prediction, target, n, loss, workspace, static_cast<hipStream_t>(stream)),
-                              "L2Loss");
-  if (rc == HDRNET_OK) set_kernel("l2_loss");
-  return rc;
+  return finish_launch(launch_l2_loss(prediction, target, n, loss, workspace, static_cast<hipStream_t>(stream)),
+                       "L2Loss", "l2_loss");
 }
 
 int hdrnet_l2_loss_grad_f32(const float* prediction, const float* target, const float* grad_output, long long n,
@@ -531,11 +581,8 @@ int hdrnet_l2_loss_grad_f32(const float* prediction, const float* target, const 
   if (!prediction || !target || !grad_output || !dprediction) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (((uintptr_t)prediction | (uintptr_t)target | (uintptr_t)dprediction) & 15u)
     return fail(HDRNET_INVALID_ARGUMENT, "l2 loss needs 16-B aligned tensors");
-  const int rc = check_launch(launch_l2_loss_grad(prediction, target, grad_output, n, dprediction,
-                                                  static_cast<hipStream_t>(stream)),
-                              "L2LossGrad");
-  if (rc == HDRNET_OK) set_kernel("l2_loss_grad");
-  return rc;
+  return finish_launch(launch_l2_loss_grad(prediction, target, grad_output, n, dprediction,
+                                           static_cast<hipStream_t>(stream)), "L2LossGrad", "l2_loss_grad");
 }
 
 size_t hdrnet_coefficients_workspace_bytes(const hdrnet_coeff_net* net, int B) {
@@ -555,29 +602,16 @@ int hdrnet_coefficients_f32(const float* lowres, const hdrnet_coeff_net* net, fl
                 "channel_multiplier * luma_bins / 4 a power of two",
                 net->net_input_size, net->spatial_bin, net->luma_bins, net->channel_multiplier, net->n_out,
                 net->n_in, net->n_levels);
-  if (B == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
-  int n_ds = 0;
-  for (int v = net->net_input_size / net->spatial_bin; v > 1; v >>= 1) ++n_ds;
-  bool null_param = !net->pred_w || !net->pred_b || !net->local_w[0] || !net->local_w[1] || !net->local_b[0];
-  for (int i = 0; i < n_ds; ++i) null_param = null_param || !net->splat_w[i] || !net->splat_b[i];
-  for (int i = 0; i < 2; ++i) null_param = null_param || !net->global_conv_w[i] || !net->global_conv_b[i];
-  for (int i = 0; i < 3; ++i) null_param = null_param || !net->fc_w[i] || !net->fc_b[i];
-  if (null_param) return fail(HDRNET_INVALID_ARGUMENT, "coefficient network: null parameter");
+  if (B == 0) return finish_noop();
+  if (coeff_net_null_param(*net, nullptr)) return fail(HDRNET_INVALID_ARGUMENT, "coefficient network: null parameter");
   if (!lowres || !coeffs) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   const size_t need = coefficients_workspace_bytes(*net, B);
   if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
     return fail(HDRNET_INVALID_ARGUMENT, "coefficient network needs a 16-B aligned workspace of "
                                          "hdrnet_coefficients_workspace_bytes() = %zu bytes", need);
   const char* name = "";
-  const int rc = check_launch(launch_coefficients(lowres, *net, coeffs, B, workspace,
-                                                  static_cast<hipStream_t>(stream), &name),
-                              "Coefficients");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_coefficients(lowres, *net, coeffs, B, workspace, static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "Coefficients", name);
 }
 
 size_t hdrnet_coefficients_grad_workspace_bytes(const hdrnet_coeff_net* net, int B) {
@@ -595,28 +629,16 @@ int hdrnet_coefficients_grad_f32(const float* lowres, const hdrnet_coeff_net* ne
     return fail(HDRNET_INVALID_ARGUMENT,
                 "coefficient network gradient: unsupported (needs the forward's support, n_levels = 1, fc_layout = 1, "
                 "1 <= B <= 8, 8 * cm * gd <= 256; got B=%d, n_levels=%d, fc_layout=%d)", B, net->n_levels, net->fc_layout);
-  int n_ds = 0;
-  for (int v = net->net_input_size / net->spatial_bin; v > 1; v >>= 1) ++n_ds;
-  bool null_param = !net->pred_w || !net->pred_b || !net->local_w[0] || !net->local_w[1] || !net->local_b[0] ||
-                    !grads->pred_w || !grads->pred_b || !grads->local_w[0] || !grads->local_w[1] || !grads->local_b[0];
-  for (int i = 0; i < n_ds; ++i)
-    null_param = null_param || !net->splat_w[i] || !net->splat_b[i] || !grads->splat_w[i] || !grads->splat_b[i];
-  for (int i = 0; i < 2; ++i)
-    null_param = null_param || !net->global_conv_w[i] || !net->global_conv_b[i] || !grads->global_conv_w[i] ||
-                 !grads->global_conv_b[i];
-  for (int i = 0; i < 3; ++i)
-    null_param = null_param || !net->fc_w[i] || !net->fc_b[i] || !grads->fc_w[i] || !grads->fc_b[i];
-  if (null_param) return fail(HDRNET_INVALID_ARGUMENT, "coefficient network gradient: null parameter");
+  if (coeff_net_null_param(*net, grads))
+    return fail(HDRNET_INVALID_ARGUMENT, "coefficient network gradient: null parameter");
   if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
     return fail(HDRNET_INVALID_ARGUMENT, "coefficient network gradient needs a 16-B aligned workspace of "
                                          "hdrnet_coefficients_grad_workspace_bytes() = %zu bytes", need);
   const char* name = "";
-  const int rc = check_launch(launch_coefficients_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
-                                                       static_cast<hipStream_t>(stream), &name),
-                              "CoefficientsGrad");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_coefficients_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
+                                                static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "CoefficientsGrad", name);
 }
 
 int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,
@@ -640,16 +662,8 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
   if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (input_dtype < 0 || input_dtype > 2 || output_dtype < 0 || output_dtype > 1)
-    return fail(HDRNET_INVALID_ARGUMENT, "unknown dtype code (input %d, output %d)", input_dtype,
-                output_dtype);
-  if (!(input_white_level > 0.0f))
-    return fail(HDRNET_INVALID_ARGUMENT, "input_white_level must be positive");
-  if ((long long)B * H * W == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (!guide && (!guide_conv1 || !guide_conv2 || n_feats <= 0 || n_feats > 4096))
     return fail(HDRNET_INVALID_ARGUMENT, "either a guide map or the guide network must be given");
@@ -664,10 +678,8 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
                 "the wire-format forward supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
                 "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32");
   const char* name = "";
-  const int rc = check_launch(launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name),
-                              "BilateralSliceApplyIO");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "BilateralSliceApplyIO", name);
 }
 
 // Sample preparation (sample_prep.hip).  Everything is checked before any HIP call.  `ragged`: the sources are flat
@@ -707,11 +719,7 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
                 what);
   if ((long long)Hs * Ws * 12 >= (1LL << 31) || (long long)H * W * 12 >= (1LL << 31) || (long long)net_input_size * net_input_size * 12 >= (1LL << 31) || B > 65535)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large", what);
-  if (B == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if (B == 0) return finish_noop();
   if (!src_input) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (the input sources)", what);
   if (ragged && !images) return fail(HDRNET_INVALID_ARGUMENT, "%s: null image table (images)", what);
   if (ragged && !ops)
@@ -733,9 +741,8 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
                          lowres_input, lowres_input ? net_input_size : 0, (flags & HDRNET_SAMPLE_EVEN_TURNS_ONLY) != 0};
   a.images = images;
   a.n_samples = n_samples;
-  const int rc = check_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what);
-  if (rc == HDRNET_OK) set_kernel(ragged ? "sample_prep_ragged" : "sample_prep");
-  return rc;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what,
+                       ragged ? "sample_prep_ragged" : "sample_prep");
 }
 
 int hdrnet_prepare_batch(const void* src_input, int input_dtype, float input_white_level, const void* src_target,
@@ -790,11 +797,10 @@ int hdrnet_curves_guide_prepare_f32(const float* guide_shifts, const float* guid
     return fail(HDRNET_INVALID_ARGUMENT, "curves prepare needs a 16-B aligned buffer of hdrnet_curves_guide_prepared_bytes()");
   if (!usable) return fail(HDRNET_INVALID_ARGUMENT, "curves prepare: `usable` must point to an int");
   *usable = 0;
-  const int rc = check_launch(launch_curves_guide_prepare(guide_shifts, guide_slopes, npts, Cin, static_cast<float*>(prepared),
-                                                          static_cast<hipStream_t>(stream)),
-                              "CurvesGuidePrepare");
+  const int rc = finish_launch(launch_curves_guide_prepare(guide_shifts, guide_slopes, npts, Cin,
+                                                           static_cast<float*>(prepared), static_cast<hipStream_t>(stream)),
+                                "CurvesGuidePrepare", "curves_prepare");
   if (rc != HDRNET_OK) return rc;
-  set_kernel("curves_prepare");
   // a SET-UP call, once per parameter set: the table's `ok` word comes back to the host (this waits for `stream`), because
   // which forward kernel a prepared buffer selects is decided on the host
   float ok = 0.0f;
@@ -817,17 +823,9 @@ int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const voi
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (input_dtype < 0 || input_dtype > 2 || output_dtype < 0 || output_dtype > 1)
-    return fail(HDRNET_INVALID_ARGUMENT, "unknown dtype code (input %d, output %d)", input_dtype,
-                output_dtype);
-  if (!(input_white_level > 0.0f))
-    return fail(HDRNET_INVALID_ARGUMENT, "input_white_level must be positive");
+  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
   if (npts <= 0 || npts > 4096) return fail(HDRNET_INVALID_ARGUMENT, "bad number of curve knots (%d)", npts);
-  if ((long long)B * H * W == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
@@ -844,17 +842,16 @@ int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const voi
                 "the fused curves-guide forward supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
                 "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32");
   const char* name = "";
-  const int rc = check_launch(launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name),
-                              "BilateralSliceApplyIOCurves");
-  if (rc == HDRNET_OK) set_kernel(name);
-  return rc;
+  const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, "BilateralSliceApplyIOCurves", name);
 }
 
 size_t hdrnet_bilateral_slice_apply_grad_workspace_bytes(int B, int H, int W, int GH, int GW,
                                                          int GD, int Cin, int Cout,
                                                          int has_offset) {
   if (B <= 0 || H <= 0 || W <= 0 || GH <= 0 || GW <= 0 || GD <= 0 || Cin < 0 || Cout <= 0) return 0;
-  return hdrnet_amd::apply_grid_grad_mfma_workspace(B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0);
+  if (!hdrnet_amd::apply_fast_shape(Cin, Cout, has_offset != 0)) return 0;
+  return hdrnet_amd::grid_grad_mfma_workspace(B, H, W, GH, GW, GD, Cout * (Cin + (has_offset ? 1 : 0)));
 }
 
 int hdrnet_bilateral_slice_apply_grad_f32_ex(const float* grid, const float* guide,
@@ -864,76 +861,14 @@ int hdrnet_bilateral_slice_apply_grad_f32_ex(const float* grid, const float* gui
                                              int Cout, int has_offset, void* workspace,
                                              size_t workspace_bytes, unsigned flags,
                                              void* stream) {
-  using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_flags(flags)) return rc;
   if (Cin < 0 || Cout <= 0 || Cin + (has_offset ? 1 : 0) <= 0)
     return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts (Cin=%d, Cout=%d)", Cin, Cout);
-  if (!dgrid && !dguide && !dinput) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int Cj = Cin + (has_offset ? 1 : 0);
-  const long long npix = (long long)B * H * W;
-  if (npix == 0) {
-    // Gradients of an empty image: dgrid is all zeros, the others are empty.
-    if (dgrid && B > 0) {
-      const hipError_t e =
-          hipMemsetAsync(dgrid, 0, sizeof(float) * (size_t)B * GH * GW * GD * Cout * Cj, s);
-      if (e != hipSuccess) return check_launch(e, "BilateralSliceApplyGrad");
-    }
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
-  if (!guide || !dout || (Cin > 0 && !input) || ((dguide || dinput) && !grid))
-    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  ApplyGradArgs a{grid, guide, input, dout, dgrid, dguide, dinput, B, H, W, GH, GW, GD,
-                  Cin, Cout, Cj, has_offset != 0, workspace, workspace_bytes, variant(flags)};
-  // All three gradients from ONE pass over the pixels when dgrid and a per-pixel VJP are both
-  // wanted (the training case) and the shape has a fused specialisation.
-  if (family(flags) != HDRNET_KERNEL_GENERIC && a.variant != 3 && apply_bwd_fused_supported(a)) {
-    const char* name = "";
-    const int rc = check_launch(launch_apply_bwd_fused(a, s, &name), "BilateralSliceApplyGrad");
-    if (rc == HDRNET_OK) set_kernel(name);
-    return rc;
-  }
-  // dguide / dinput: one fused LDS-staged pass when a specialisation exists.
-  const bool pix_fast = family(flags) != HDRNET_KERNEL_GENERIC && (dguide || dinput) &&
-                        apply_vjp_rows_supported(a);
-  if (family(flags) == HDRNET_KERNEL_FAST && (dguide || dinput) && !pix_fast)
-    return fail(HDRNET_INVALID_ARGUMENT, "no fast BilateralSliceApplyGrad variant for this shape");
-  const char* pix_name = "";
-  ApplyGradArgs rest = a;
-  if (pix_fast) {
-    const int rc = check_launch(launch_apply_vjp_rows(a, s, &pix_name), "BilateralSliceApplyGrad");
-    if (rc != HDRNET_OK) return rc;
-    rest.dguide = nullptr;
-    rest.dinput = nullptr;
-  }
-  const char* gg_name = "";
-  if (dgrid && family(flags) != HDRNET_KERNEL_GENERIC) {
-    if (apply_grid_grad_mfma_supported(a)) {
-      const int rc = check_launch(launch_apply_grid_grad_mfma(a, s, &gg_name), "BilateralSliceApplyGrad");
-      if (rc != HDRNET_OK) return rc;
-      rest.dgrid = nullptr;
-    } else if (family(flags) == HDRNET_KERNEL_FAST) {
-      return fail(HDRNET_INVALID_ARGUMENT,
-                  "no fast grid-gradient variant for this shape (or workspace missing / too small)");
-    }
-  }
-  const char* rest_name = "";
-  if (rest.dgrid || rest.dguide || rest.dinput) {
-    if (rest.dgrid && family(flags) == HDRNET_KERNEL_AUTO)
-      warn_generic_grid_grad("BilateralSliceApplyGrad", npix, GD, Cout * Cj, workspace != nullptr);
-    const int rc = check_launch(launch_apply_grad_generic(rest, s), "BilateralSliceApplyGrad");
-    if (rc != HDRNET_OK) return rc;
-    rest_name = "apply_grad_generic";
-  }
-  set_kernel(pix_name, gg_name, rest_name);
-  return HDRNET_OK;
+  const hdrnet_amd::ApplyGradArgs a{grid, guide, input, dout, dgrid, dguide, dinput, B, H, W, GH, GW, GD, Cin, Cout,
+                                    Cin + (has_offset ? 1 : 0), has_offset != 0, workspace, workspace_bytes,
+                                    variant(flags)};
+  return grad_dispatch(a, family(flags), static_cast<hipStream_t>(stream));
 }
 
 int hdrnet_bilateral_slice_apply_grad_f32(const float* grid, const float* guide,
@@ -955,11 +890,7 @@ int hdrnet_bilateral_slice_f32_ex(const float* grid, const float* guide, float* 
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_flags(flags)) return rc;
   if (C <= 0) return fail(HDRNET_INVALID_ARGUMENT, "grid_channels must be positive (C=%d)", C);
-  if ((long long)B * H * W == 0) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
+  if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !guide || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   SliceArgs a{grid, guide, out, B, H, W, GH, GW, GD, C};
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -968,13 +899,10 @@ int hdrnet_bilateral_slice_f32_ex(const float* grid, const float* guide, float* 
     return fail(HDRNET_INVALID_ARGUMENT, "no fast BilateralSlice variant for this shape");
   if (family(flags) != HDRNET_KERNEL_GENERIC && fast_ok) {
     const char* name = "";
-    const int rc = check_launch(launch_slice_fwd_rows(a, s, &name), "BilateralSlice");
-    if (rc == HDRNET_OK) set_kernel(name);
-    return rc;
+    const hipError_t e = launch_slice_fwd_rows(a, s, &name);
+    return finish_launch(e, "BilateralSlice", name);
   }
-  const int rc = check_launch(launch_slice_fwd_generic(a, s), "BilateralSlice");
-  if (rc == HDRNET_OK) set_kernel("slice_fwd_generic");
-  return rc;
+  return finish_launch(launch_slice_fwd_generic(a, s), "BilateralSlice", "slice_fwd_generic");
 }
 
 int hdrnet_bilateral_slice_f32(const float* grid, const float* guide, float* out, int B, int H,
@@ -986,73 +914,22 @@ int hdrnet_bilateral_slice_f32(const float* grid, const float* guide, float* out
 size_t hdrnet_bilateral_slice_grad_workspace_bytes(int B, int H, int W, int GH, int GW, int GD,
                                                    int C) {
   if (B <= 0 || H <= 0 || W <= 0 || GH <= 0 || GW <= 0 || GD <= 0 || C <= 0) return 0;
-  return hdrnet_amd::slice_grid_grad_mfma_workspace(B, H, W, GH, GW, GD, C);
+  if (!hdrnet_amd::slice_fast_channels(C)) return 0;
+  return hdrnet_amd::grid_grad_mfma_workspace(B, H, W, GH, GW, GD, C);
 }
 
 int hdrnet_bilateral_slice_grad_f32_ex(const float* grid, const float* guide, const float* dout,
                                        float* dgrid, float* dguide, int B, int H, int W, int GH,
                                        int GW, int GD, int C, void* workspace,
                                        size_t workspace_bytes, unsigned flags, void* stream) {
-  using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_flags(flags)) return rc;
   if (C <= 0) return fail(HDRNET_INVALID_ARGUMENT, "grid_channels must be positive (C=%d)", C);
-  if (!dgrid && !dguide) {
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((long long)B * H * W == 0) {
-    if (dgrid && B > 0) {
-      const hipError_t e = hipMemsetAsync(dgrid, 0, sizeof(float) * (size_t)B * GH * GW * GD * C, s);
-      if (e != hipSuccess) return check_launch(e, "BilateralSliceGrad");
-    }
-    set_kernel("noop");
-    g_error[0] = '\0';
-    return HDRNET_OK;
-  }
-  if (!guide || !dout || (dguide && !grid)) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  SliceGradArgs a{grid, guide, dout, dgrid, dguide, B, H, W, GH, GW, GD, C, workspace,
-                  workspace_bytes, variant(flags)};
-  if (family(flags) != HDRNET_KERNEL_GENERIC && a.variant != 3 && slice_bwd_fused_supported(a)) {
-    const char* name = "";
-    const int rc = check_launch(launch_slice_bwd_fused(a, s, &name), "BilateralSliceGrad");
-    if (rc == HDRNET_OK) set_kernel(name);
-    return rc;
-  }
-  const bool pix_fast =
-      family(flags) != HDRNET_KERNEL_GENERIC && dguide && slice_vjp_rows_supported(a);
-  if (family(flags) == HDRNET_KERNEL_FAST && dguide && !pix_fast)
-    return fail(HDRNET_INVALID_ARGUMENT, "no fast BilateralSliceGrad variant for this shape");
-  const char* pix_name = "";
-  SliceGradArgs rest = a;
-  if (pix_fast) {
-    const int rc = check_launch(launch_slice_vjp_rows(a, s, &pix_name), "BilateralSliceGrad");
-    if (rc != HDRNET_OK) return rc;
-    rest.dguide = nullptr;
-  }
-  const char* gg_name = "";
-  if (dgrid && family(flags) != HDRNET_KERNEL_GENERIC) {
-    if (slice_grid_grad_mfma_supported(a)) {
-      const int rc = check_launch(launch_slice_grid_grad_mfma(a, s, &gg_name), "BilateralSliceGrad");
-      if (rc != HDRNET_OK) return rc;
-      rest.dgrid = nullptr;
-    } else if (family(flags) == HDRNET_KERNEL_FAST) {
-      return fail(HDRNET_INVALID_ARGUMENT,
-                  "no fast grid-gradient variant for this shape (or workspace missing / too small)");
-    }
-  }
-  const char* rest_name = "";
-  if (rest.dgrid || rest.dguide) {
-    if (rest.dgrid && family(flags) == HDRNET_KERNEL_AUTO)
-      warn_generic_grid_grad("BilateralSliceGrad", (long long)B * H * W, GD, C, workspace != nullptr);
-    const int rc = check_launch(launch_slice_grad_generic(rest, s), "BilateralSliceGrad");
-    if (rc != HDRNET_OK) return rc;
-    rest_name = "slice_grad_generic";
-  }
-  set_kernel(pix_name, gg_name, rest_name);
-  return HDRNET_OK;
+  // BilateralSlice is the apply op without an input: one "offset" column per channel
+  hdrnet_amd::ApplyGradArgs a{grid, guide, nullptr, dout, dgrid, dguide, nullptr, B, H, W, GH, GW, GD, 0, C, 1, true,
+                              workspace, workspace_bytes, variant(flags)};
+  a.slice = true;
+  return grad_dispatch(a, family(flags), static_cast<hipStream_t>(stream));
 }
 
 int hdrnet_bilateral_slice_grad_f32(const float* grid, const float* guide, const float* dout,

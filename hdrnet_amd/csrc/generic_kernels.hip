@@ -291,17 +291,18 @@ hipError_t launch_slice_fwd_generic(const SliceArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_slice_grad_generic(const SliceGradArgs& a, hipStream_t s) {
+hipError_t launch_slice_grad_generic(const ApplyGradArgs& a, hipStream_t s) {
   const long long npix = (long long)a.B * a.H * a.W;
+  const int C = a.Cout;  // a.slice: Cin = 0, Cj = 1
   if (a.dgrid) {
-    const long long nelem = (long long)a.B * a.GH * a.GW * a.GD * a.C;
+    const long long nelem = (long long)a.B * a.GH * a.GW * a.GD * C;
     grid_grad_gather_generic<false><<<blocks_for(nelem), kThreads, 0, s>>>(
-        a.guide, nullptr, a.dout, a.dgrid, nelem, a.H, a.W, a.GH, a.GW, a.GD, 0, a.C, 1,
+        a.guide, nullptr, a.dout, a.dgrid, nelem, a.H, a.W, a.GH, a.GW, a.GD, 0, C, 1,
         (float)a.W / a.GW, (float)a.H / a.GH);
   }
   if (a.dguide) {
     slice_guide_grad_generic<<<blocks_for(npix), kThreads, 0, s>>>(
-        a.grid, a.guide, a.dout, a.dguide, npix, a.H, a.W, a.GH, a.GW, a.GD, a.C,
+        a.grid, a.guide, a.dout, a.dguide, npix, a.H, a.W, a.GH, a.GW, a.GD, C,
         (float)a.GW / a.W, (float)a.GH / a.H);
   }
   return hipGetLastError();

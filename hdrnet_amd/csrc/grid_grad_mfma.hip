@@ -1165,42 +1165,32 @@ hipError_t gg_launch_windows(const GGPtrs& q, int B, int H, int W, int GH, int G
   return hipSuccess;
 }
 
-// the shared fast-shape table (launch.hip.h) restricted to what the contraction pass covers: one 16-column tile, or two
-// channel windows for dgrid alone
-bool apply_shape_ok(int Cin, int Cout, bool off) {
-  return apply_fast_shape(Cin, Cout, off) && Cout * (Cin + (off ? 1 : 0)) <= 32;
-}
-
-bool slice_c_ok(int C) { return C == 1 || C == 2 || C == 4 || C == 8 || C == 12 || C == 16; }
-
 }  // namespace
 
 #ifdef HDRNET_TOOLS_BUILD
 void grid_grad_set_trace(long long* device_buf) { g_gg_trace = device_buf; }
 #endif
 
-size_t apply_grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout,
-                                      bool has_offset) {
+size_t grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C) {
   size_t bytes = 0;
-  if (!apply_shape_ok(Cin, Cout, has_offset)) return 0;
-  if (!gg_ws_bound(B, H, W, GH, GW, GD, Cout * (Cin + (has_offset ? 1 : 0)), &bytes)) return 0;
-  return bytes;
+  return gg_ws_bound(B, H, W, GH, GW, GD, C, &bytes) ? bytes : 0;
 }
 
-bool apply_grid_grad_mfma_supported(const ApplyGradArgs& a) {
+// One 16-column tile, or two channel windows for dgrid alone (C <= 32: gg_plan), of the op's fast shapes.
+bool grid_grad_mfma_supported(const ApplyGradArgs& a) {
   size_t bytes = 0;
-  if (!apply_shape_ok(a.Cin, a.Cout, a.has_offset) || !gg_ws_bound(a.B, a.H, a.W, a.GH, a.GW, a.GD, a.Cout * a.Cj, &bytes))
-    return false;
+  if (!grad_fast_shape(a) || !gg_ws_bound(a.B, a.H, a.W, a.GH, a.GW, a.GD, a.Cout * a.Cj, &bytes)) return false;
   if (a.workspace != nullptr && a.workspace_bytes >= bytes) return true;
   warn_small_workspace(a.workspace ? a.workspace_bytes : 0, bytes);
   return false;
 }
 
-// variant (tools A/B): 2 = bf16-split contraction.  fused: also write a.dguide / a.dinput.
-static hipError_t apply_gg(const ApplyGradArgs& a, bool fused, hipStream_t s) {
+// variant (tools A/B): 2 = bf16-split contraction, 10 = f16 hi-lo' split.  fused: also write a.dguide / a.dinput.
+static hipError_t gg_dispatch(const ApplyGradArgs& a, bool fused, hipStream_t s) {
   const GGPtrs q{a.guide, a.input, a.dout, a.grid, a.dgrid, fused ? a.dguide : nullptr,
                  fused ? a.dinput : nullptr};
-  const int split = a.variant == 2 ? 1 : a.variant == 10 ? 2 : 0;  // tools: bf16 split / f16 hi-lo' split
+  const int split = a.variant == 2 ? 1 : a.variant == 10 ? 2 : 0;
+  if (!a.slice) {
 #define HDRNET_CASE(CI, CO, OFF)                                                                  \
   if constexpr (CO * (CI + (OFF ? 1 : 0)) <= 16) {                                                \
     if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF)                                       \
@@ -1212,73 +1202,35 @@ static hipError_t apply_gg(const ApplyGradArgs& a, bool fused, hipStream_t s) {
       return gg_launch_windows<CI, CO, OFF>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s); \
     }                                                                                             \
   }
-  HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
+    HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
 #undef HDRNET_CASE
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_apply_grid_grad_mfma(const ApplyGradArgs& a, hipStream_t s, const char** name) {
-  *name = a.variant == 2 ? "grid_grad_mfma/bf16x2" : a.variant == 10 ? "grid_grad_mfma/f16hilo" : "grid_grad_mfma";
-  return apply_gg(a, false, s);
-}
-
-// Fused backward: dgrid AND dguide / dinput in one pass over the pixels (C % 4 == 0 shapes).
-bool apply_bwd_fused_supported(const ApplyGradArgs& a) {
-  if (!a.dgrid || !(a.dguide || a.dinput) || !a.grid) return false;
-  if ((a.Cout * a.Cj) % 4 != 0 || a.Cout * a.Cj > 16 || a.Cj != 4 || ((uintptr_t)a.grid & 15u)) return false;
-  if (a.dinput && a.Cin == 0) return false;
-  return apply_grid_grad_mfma_supported(a);
-}
-
-hipError_t launch_apply_bwd_fused(const ApplyGradArgs& a, hipStream_t s, const char** name) {
-  *name = a.variant == 2 ? "apply_bwd_fused/mfma-bf16x2" : a.variant == 10 ? "apply_bwd_fused/mfma-f16hilo" : "apply_bwd_fused/mfma";
-  return apply_gg(a, true, s);
-}
-
-size_t slice_grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C) {
-  size_t bytes = 0;
-  if (!slice_c_ok(C) || !gg_ws_bound(B, H, W, GH, GW, GD, C, &bytes)) return 0;
-  return bytes;
-}
-
-bool slice_grid_grad_mfma_supported(const SliceGradArgs& a) {
-  size_t bytes = 0;
-  if (!slice_c_ok(a.C) || !gg_ws_bound(a.B, a.H, a.W, a.GH, a.GW, a.GD, a.C, &bytes)) return false;
-  if (a.workspace != nullptr && a.workspace_bytes >= bytes) return true;
-  warn_small_workspace(a.workspace ? a.workspace_bytes : 0, bytes);
-  return false;
-}
-
-static hipError_t slice_gg(const SliceGradArgs& a, bool fused, hipStream_t s) {
-  const GGPtrs q{a.guide, nullptr, a.dout, a.grid, a.dgrid, fused ? a.dguide : nullptr, nullptr};
-  const int split = a.variant == 2 ? 1 : a.variant == 10 ? 2 : 0;
+    return hipErrorInvalidValue;
+  }
 #define HDRNET_CASE(CC)                                                                            \
-  if (a.C == CC)                                                                                   \
-  return gg_launch<0, CC, false, false>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s, split)
-  HDRNET_CASE(1);
-  HDRNET_CASE(2);
-  HDRNET_CASE(4);
-  HDRNET_CASE(8);
-  HDRNET_CASE(12);
-  HDRNET_CASE(16);
+  if (a.Cout == CC)                                                                                \
+    return gg_launch<0, CC, false, false>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s, split);
+  HDRNET_SLICE_FAST_CHANNELS(HDRNET_CASE)
 #undef HDRNET_CASE
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_slice_grid_grad_mfma(const SliceGradArgs& a, hipStream_t s, const char** name) {
-  *name = a.variant == 2 ? "grid_grad_mfma/bf16x2" : "grid_grad_mfma";
-  return slice_gg(a, false, s);
+hipError_t launch_grid_grad_mfma(const ApplyGradArgs& a, hipStream_t s, const char** name) {
+  *name = a.variant == 2 ? "grid_grad_mfma/bf16x2" : (a.variant == 10 && !a.slice) ? "grid_grad_mfma/f16hilo" : "grid_grad_mfma";
+  return gg_dispatch(a, false, s);
 }
 
-bool slice_bwd_fused_supported(const SliceGradArgs& a) {
-  if (!a.dgrid || !a.dguide || !a.grid) return false;
-  if (a.C % 4 != 0 || ((uintptr_t)a.grid & 15u)) return false;
-  return slice_grid_grad_mfma_supported(a);
+// Fused backward: dgrid AND dguide / dinput in one pass over the pixels (C % 4 == 0 shapes of one tile; apply: Cj = 4).
+bool bwd_fused_supported(const ApplyGradArgs& a) {
+  if (!a.dgrid || !(a.dguide || a.dinput) || !a.grid) return false;
+  if ((a.Cout * a.Cj) % 4 != 0 || a.Cout * a.Cj > 16 || (!a.slice && a.Cj != 4) || ((uintptr_t)a.grid & 15u)) return false;
+  if (a.dinput && a.Cin == 0) return false;
+  return grid_grad_mfma_supported(a);
 }
 
-hipError_t launch_slice_bwd_fused(const SliceGradArgs& a, hipStream_t s, const char** name) {
-  *name = "slice_bwd_fused/mfma";
-  return slice_gg(a, true, s);
+hipError_t launch_bwd_fused(const ApplyGradArgs& a, hipStream_t s, const char** name) {
+  *name = a.slice ? "slice_bwd_fused/mfma"
+                  : a.variant == 2 ? "apply_bwd_fused/mfma-bf16x2" : a.variant == 10 ? "apply_bwd_fused/mfma-f16hilo" : "apply_bwd_fused/mfma";
+  return gg_dispatch(a, true, s);
 }
 
 }  // namespace hdrnet_amd

@@ -51,6 +51,9 @@ struct ApplyIoArgs {
   const float* guide_prepared = nullptr;  // curves guide: the cell tables of hdrnet_curves_guide_prepare_f32, or null
 };
 
+// Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
+// input = dinput = null, Cin = 0, Cout = C, Cj = 1.  The tag, not the channel counts, says which op it is: the apply
+// entry point itself takes Cin = 0 with offset, and the two ops differ in fast shapes, generic kernel and kernel names.
 struct ApplyGradArgs {
   const float* grid;
   const float* guide;
@@ -64,6 +67,7 @@ struct ApplyGradArgs {
   void* workspace;
   size_t workspace_bytes;
   int variant = 0;  // tools build A/B: 2 = bf16-split dgrid contraction, 3 = separate (un-fused) kernels
+  bool slice = false;
 };
 
 // Training side of the point-wise guide network (guide_grad.hip).
@@ -104,18 +108,6 @@ struct SliceArgs {
   int B, H, W, GH, GW, GD, C;
 };
 
-struct SliceGradArgs {
-  const float* grid;
-  const float* guide;
-  const float* dout;
-  float* dgrid;   // may be null
-  float* dguide;  // may be null
-  int B, H, W, GH, GW, GD, C;
-  void* workspace;
-  size_t workspace_bytes;
-  int variant = 0;  // as ApplyGradArgs
-};
-
 // The (Cin, Cout, has_offset) shapes every fast BilateralSliceApply path specialises -- ONE table for the
 // forward (apply_fwd_seg / apply_fwd_rows), the per-pixel VJPs (apply_vjp_seg / apply_vjp_rows) and the
 // grid VJP (grid_grad_mfma: one 16-column MFMA tile for C = Cout * Cj <= 16, fused with the per-pixel VJPs where Cj = 4;
@@ -130,11 +122,25 @@ inline bool apply_fast_shape(int Cin, int Cout, bool has_offset) {
   return false;
 }
 
+// The grid channel counts the fast BilateralSlice gradients specialise (apply_bwd_rows / grid_grad_mfma).  X(C).
+#define HDRNET_SLICE_FAST_CHANNELS(X) X(1) X(2) X(4) X(8) X(12) X(16)
+
+inline bool slice_fast_channels(int C) {
+#define HDRNET_CHANNELS_EQ(CC) if (C == CC) return true;
+  HDRNET_SLICE_FAST_CHANNELS(HDRNET_CHANNELS_EQ)
+#undef HDRNET_CHANNELS_EQ
+  return false;
+}
+
+inline bool grad_fast_shape(const ApplyGradArgs& a) {
+  return a.slice ? slice_fast_channels(a.Cout) : apply_fast_shape(a.Cin, a.Cout, a.has_offset);
+}
+
 // generic_kernels.hip -- any shape, bit-exact vs the reference CPU op.
 hipError_t launch_apply_fwd_generic(const ApplyArgs& a, hipStream_t s);
 hipError_t launch_apply_grad_generic(const ApplyGradArgs& a, hipStream_t s);
 hipError_t launch_slice_fwd_generic(const SliceArgs& a, hipStream_t s);
-hipError_t launch_slice_grad_generic(const SliceGradArgs& a, hipStream_t s);
+hipError_t launch_slice_grad_generic(const ApplyGradArgs& a, hipStream_t s);  // a.slice
 
 // apply_fwd_rows.hip -- LDS-staged row-segment forward.  `*_supported` says whether a
 // specialisation exists for the shape; `name` receives a static string naming
@@ -212,13 +218,11 @@ hipError_t launch_curves_guide_prepare(const float* shifts, const float* slopes,
 
 // apply_bwd_rows.hip -- LDS-staged per-pixel VJPs: dguide and dinput in one pass
 // (BilateralSliceApply), dguide (BilateralSlice).  dgrid is not their business.
-bool apply_vjp_rows_supported(const ApplyGradArgs& a);
-hipError_t launch_apply_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** name);
-// the same on the product forward's core (apply_vjp_seg.hip); launch_apply_vjp_rows routes here when it applies
+bool vjp_rows_supported(const ApplyGradArgs& a);
+hipError_t launch_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** name);
+// BilateralSliceApply's on the product forward's core (apply_vjp_seg.hip); launch_vjp_rows routes here when it applies
 bool apply_vjp_seg_supported(const ApplyGradArgs& a);
 hipError_t launch_apply_vjp_seg(const ApplyGradArgs& a, hipStream_t s, const char** name);
-bool slice_vjp_rows_supported(const SliceGradArgs& a);
-hipError_t launch_slice_vjp_rows(const SliceGradArgs& a, hipStream_t s, const char** name);
 
 // slice_fwd_rows.hip -- LDS-staged BilateralSlice forward with lane-contiguous stores.
 bool slice_fwd_rows_supported(const SliceArgs& a);
@@ -226,18 +230,14 @@ hipError_t launch_slice_fwd_rows(const SliceArgs& a, hipStream_t s, const char**
 
 // grid_grad_mfma.hip -- deterministic two-stage dgrid: per-row-run fp32 MFMA contraction over
 // the pixels + fixed-order reduction of partial tiles held in the caller's workspace.
-size_t apply_grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout,
-                                      bool has_offset);
-bool apply_grid_grad_mfma_supported(const ApplyGradArgs& a);  // shape AND workspace large enough
-hipError_t launch_apply_grid_grad_mfma(const ApplyGradArgs& a, hipStream_t s, const char** name);
+// The workspace bound of a grid with C channels, whichever op (0: GD > 16, C > 32 or extents out of range); whether
+// the op has a fast kernel for its channel counts is grad_fast_shape's business.
+size_t grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C);
+bool grid_grad_mfma_supported(const ApplyGradArgs& a);  // shape AND workspace large enough
+hipError_t launch_grid_grad_mfma(const ApplyGradArgs& a, hipStream_t s, const char** name);
 // The same pass also producing dguide / dinput (fused backward: pixels read once for all gradients).
-bool apply_bwd_fused_supported(const ApplyGradArgs& a);
-hipError_t launch_apply_bwd_fused(const ApplyGradArgs& a, hipStream_t s, const char** name);
-size_t slice_grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C);
-bool slice_grid_grad_mfma_supported(const SliceGradArgs& a);
-hipError_t launch_slice_grid_grad_mfma(const SliceGradArgs& a, hipStream_t s, const char** name);
-bool slice_bwd_fused_supported(const SliceGradArgs& a);
-hipError_t launch_slice_bwd_fused(const SliceGradArgs& a, hipStream_t s, const char** name);
+bool bwd_fused_supported(const ApplyGradArgs& a);
+hipError_t launch_bwd_fused(const ApplyGradArgs& a, hipStream_t s, const char** name);
 
 // guide_grad.hip -- VJP of the folded point-wise guide network; input moments for batch norm.
 size_t guide_grad_workspace_bytes(long long npx, int Cin, int n);
@@ -279,5 +279,13 @@ size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B);  /
 hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
                                     const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s,
                                     const char** name);
+
+// capi.hip -- the tail of every C-ABI entry point, for those defined beside their kernels too.  The error text
+// (hdrnet_last_error) is thread-local and the kernel name (hdrnet_last_kernel) optional bookkeeping; both live there.
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // sets the text, returns `code`
+// e != hipSuccess: HDRNET_RUNTIME_FAILURE and "<what> kernel failed: <HIP's text>"; else clears the text, records
+// `name` as the kernel launched (null: leaves the recorded name alone) and returns HDRNET_OK
+int finish_launch(hipError_t e, const char* what, const char* name);
+int finish_noop();  // the legal no-op: HDRNET_OK, no text, kernel name "noop"
 
 }  // namespace hdrnet_amd

@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "../../include/hdrnet_amd_train.h"
+#include "launch.hip.h"
 
 namespace hdrnet_amd {
 namespace {
@@ -175,13 +176,22 @@ extern "C" int hdrnet_loss_psnr_f32(const float* prediction, const float* target
                                     float* psnr, float* image_mse, float* dprediction_unit, float* ema, float decay,
                                     double* totals, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace hdrnet_amd;
-  if (n <= 0 || batch <= 0 || n % batch != 0) return 1;
-  if (!prediction || !target || !loss || !psnr || !workspace) return 1;
-  if (workspace_bytes < hdrnet_loss_psnr_workspace_bytes(n, batch)) return 1;
-  if (((uintptr_t)prediction | (uintptr_t)target | (uintptr_t)dprediction_unit | (uintptr_t)workspace) & 15u) return 1;
-  if (((uintptr_t)loss | (uintptr_t)psnr | (uintptr_t)image_mse | (uintptr_t)ema) & 3u) return 1;
-  if ((uintptr_t)totals & 7u) return 1;
-  if (ema && !(decay >= 0.0f && decay < 1.0f)) return 1;
+  const char* what = "hdrnet_loss_psnr_f32";
+  if (n <= 0 || batch <= 0 || n % batch != 0)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs n > 0, batch > 0 and n a multiple of batch (n=%lld, batch=%d)", what, n,
+                batch);
+  if (!prediction || !target || !loss || !psnr || !workspace)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", what);
+  if (workspace_bytes < hdrnet_loss_psnr_workspace_bytes(n, batch))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a workspace of hdrnet_loss_psnr_workspace_bytes() = %zu bytes", what,
+                hdrnet_loss_psnr_workspace_bytes(n, batch));
+  if (((uintptr_t)prediction | (uintptr_t)target | (uintptr_t)dprediction_unit | (uintptr_t)workspace) & 15u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: prediction, target, dprediction_unit and workspace must be 16-B aligned", what);
+  if (((uintptr_t)loss | (uintptr_t)psnr | (uintptr_t)image_mse | (uintptr_t)ema) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: loss, psnr, image_mse and ema must be 4-B aligned", what);
+  if ((uintptr_t)totals & 7u) return fail(HDRNET_INVALID_ARGUMENT, "%s: totals must be 8-B aligned", what);
+  if (ema && !(decay >= 0.0f && decay < 1.0f))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: decay must lie in [0, 1) (decay=%g)", what, (double)decay);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long m = n / batch;
   const int share = share_of(batch), grid = grid_of(batch);
@@ -193,5 +203,5 @@ extern "C" int hdrnet_loss_psnr_f32(const float* prediction, const float* target
   else
     loss_psnr_partial<false><<<grid, kThreads, 0, s>>>(prediction, target, m, batch, share, k, partial, nullptr);
   loss_psnr_final<<<1, kThreads, 0, s>>>(partial, batch, share, m, loss, psnr, image_mse, ema, decay, totals, per_image);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return finish_launch(hipGetLastError(), what, nullptr);
 }

@@ -169,41 +169,50 @@ extern "C" int hdrnet_l2_loss_with_grad_f32(const float* prediction, const float
                                             float* dprediction_unit, void* workspace, size_t workspace_bytes,
                                             void* stream) {
   using namespace hdrnet_amd;
-  if (n <= 0 || !prediction || !target || !loss || !dprediction_unit || !workspace) return 1;
-  if (workspace_bytes < l2_loss_workspace_bytes(n)) return 1;
-  if (((uintptr_t)prediction | (uintptr_t)target | (uintptr_t)dprediction_unit) & 15u) return 1;
-  return launch_l2_loss_with_grad(prediction, target, n, loss, dprediction_unit, workspace,
-                                  static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : 2;
+  const char* what = "hdrnet_l2_loss_with_grad_f32";
+  if (n <= 0 || !prediction || !target || !loss || !dprediction_unit || !workspace)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: empty tensor or null buffer (n=%lld)", what, n);
+  if (workspace_bytes < l2_loss_workspace_bytes(n))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a workspace of hdrnet_l2_loss_workspace_bytes() = %zu bytes", what,
+                l2_loss_workspace_bytes(n));
+  if (((uintptr_t)prediction | (uintptr_t)target | (uintptr_t)dprediction_unit) & 15u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: tensors must be 16-B aligned", what);
+  return finish_launch(launch_l2_loss_with_grad(prediction, target, n, loss, dprediction_unit, workspace,
+                                                static_cast<hipStream_t>(stream)), what, nullptr);
 }
 
 extern "C" int hdrnet_l2_loss_grad_scale_f32(float* dprediction, const float* grad_output, long long n, void* stream) {
   using namespace hdrnet_amd;
-  if (n <= 0 || !dprediction || !grad_output || ((uintptr_t)dprediction & 15u)) return 1;
+  if (n <= 0 || !dprediction || !grad_output || ((uintptr_t)dprediction & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "hdrnet_l2_loss_grad_scale_f32: empty tensor, null buffer or dprediction not 16-B aligned (n=%lld)", n);
   l2_loss_grad_scale<<<kLossBlocks, 256, 0, static_cast<hipStream_t>(stream)>>>(dprediction, grad_output, n);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return finish_launch(hipGetLastError(), "hdrnet_l2_loss_grad_scale_f32", nullptr);
 }
 
 namespace {
-int adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float* step, float lr,
+int adam_step(const char* what, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float* step, float lr,
               float beta1, float beta2, float eps, int eps_hat, void* stream) {
   using namespace hdrnet_amd;
-  if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return 1;
-  if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u) return 1;
+  if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: empty tensor or null buffer (n=%lld)", what, n);
+  if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: param, grad, exp_avg and exp_avg_sq must be 16-B aligned", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long want = ((n >> 2) + 255) / 256;
   const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
   adam_flat<<<blocks, 256, 0, s>>>(param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, eps_hat);
   adam_count<<<1, 1, 0, s>>>(step);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return finish_launch(hipGetLastError(), what, nullptr);
 }
 }  // namespace
 
 extern "C" int hdrnet_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                                     float* step, float lr, float beta1, float beta2, float eps, void* stream) {
-  return adam_step(param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, 0, stream);
+  return adam_step("hdrnet_adam_step_f32", param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, 0, stream);
 }
 
 extern "C" int hdrnet_adam_step_tf_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                                        float* step, float lr, float beta1, float beta2, float eps, void* stream) {
-  return adam_step(param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, 1, stream);
+  return adam_step("hdrnet_adam_step_tf_f32", param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, 1, stream);
 }

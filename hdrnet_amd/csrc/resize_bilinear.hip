@@ -187,12 +187,14 @@ hipError_t launch_resize_bilinear(const float* in, float* out, int B, int Hin, i
 extern "C" int hdrnet_resize_add_f32(const float* coarse, const float* fine, float* output, int batch, int in_height,
                                      int in_width, int out_height, int out_width, int channels, void* stream) {
   using namespace hdrnet_amd;
+  const char* what = "hdrnet_resize_add_f32";
   if (!coarse || !fine || !output || batch <= 0 || in_height <= 0 || in_width <= 0 || out_height <= 0 || out_width <= 0 ||
       channels <= 0)
-    return 1;
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer or non-positive extent (B=%d, in %dx%d, out %dx%d, C=%d)", what,
+                batch, in_height, in_width, out_height, out_width, channels);
   const long long npx = (long long)batch * out_height * out_width;
   const long long nblocks = (npx + 255) / 256;
-  if (nblocks > 0x7fffffffLL) return 1;
+  if (nblocks > 0x7fffffffLL) return fail(HDRNET_INVALID_ARGUMENT, "%s: output too large (%lld pixels)", what, npx);
   const float sh = out_height > 1 ? (float)(in_height - 1) / (float)(out_height - 1) : (float)in_height / (float)out_height;
   const float sw = out_width > 1 ? (float)(in_width - 1) / (float)(out_width - 1) : (float)in_width / (float)out_width;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -202,18 +204,20 @@ extern "C" int hdrnet_resize_add_f32(const float* coarse, const float* fine, flo
   else
     resize_add_ac<0><<<(unsigned)nblocks, 256, 0, s>>>(coarse, fine, output, in_height, in_width, out_height, out_width,
                                                        channels, sh, sw, npx);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return finish_launch(hipGetLastError(), what, nullptr);
 }
 
 extern "C" int hdrnet_resize_bilinear_grad_f32(const float* doutput, float* dinput, int batch, int in_height, int in_width,
                                                int out_height, int out_width, int channels, void* stream) {
   using namespace hdrnet_amd;
+  const char* what = "hdrnet_resize_bilinear_grad_f32";
   if (!doutput || !dinput || batch <= 0 || in_height <= 0 || in_width <= 0 || out_height <= 0 || out_width <= 0 ||
       channels <= 0)
-    return 1;
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer or non-positive extent (B=%d, in %dx%d, out %dx%d, C=%d)", what,
+                batch, in_height, in_width, out_height, out_width, channels);
   const long long npx = (long long)batch * in_height * in_width;
   const long long nblocks = (npx + 255) / 256;
-  if (nblocks > 0x7fffffffLL) return 1;
+  if (nblocks > 0x7fffffffLL) return fail(HDRNET_INVALID_ARGUMENT, "%s: input too large (%lld pixels)", what, npx);
   const float sh = out_height > 1 ? (float)(in_height - 1) / (float)(out_height - 1) : (float)in_height / (float)out_height;
   const float sw = out_width > 1 ? (float)(in_width - 1) / (float)(out_width - 1) : (float)in_width / (float)out_width;
   // a source index k is touched by destination indices within (k - 1, k + 1) / scale; scale 0 (one source row): all of them
@@ -225,5 +229,5 @@ extern "C" int hdrnet_resize_bilinear_grad_f32(const float* doutput, float* dinp
   else
     resize_bilinear_grad_ac<0><<<(unsigned)nblocks, 256, 0, s>>>(doutput, dinput, in_height, in_width, out_height, out_width,
                                                                  channels, sh, sw, inv_sh, inv_sw, npx);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
+  return finish_launch(hipGetLastError(), what, nullptr);
 }

@@ -852,7 +852,7 @@ class _UpsampleAdd(torch.autograd.Function):
             rc = _lib.load().hdrnet_resize_add_f32(c.data_ptr(), f.data_ptr(), out.data_ptr(), B, IH, IW, OH, OW, C,
                                                    _stream(f.device))
         if rc != 0:
-            raise RuntimeError(f"hdrnet_resize_add_f32 failed (rc={rc})")
+            raise RuntimeError(f"hdrnet_resize_add_f32 failed (rc={rc}): {_lib.last_error()}")
         ctx.dims = (B, IH, IW, OH, OW, C)
         return out
 
@@ -868,7 +868,7 @@ class _UpsampleAdd(torch.autograd.Function):
                 rc = _lib.load().hdrnet_resize_bilinear_grad_f32(g.data_ptr(), dcoarse.data_ptr(), B, IH, IW, OH, OW, C,
                                                                  _stream(g.device))
             if rc != 0:
-                raise RuntimeError(f"hdrnet_resize_bilinear_grad_f32 failed (rc={rc})")
+                raise RuntimeError(f"hdrnet_resize_bilinear_grad_f32 failed (rc={rc}): {_lib.last_error()}")
         return dcoarse, (g if ctx.needs_input_grad[1] else None)
 
 

@@ -46,7 +46,7 @@ class _L2Loss(torch.autograd.Function):
                 rc = lib.hdrnet_l2_loss_with_grad_f32(p.data_ptr(), t.data_ptr(), n, loss.data_ptr(), ctx.unit.data_ptr(),
                                                       ws.data_ptr(), wbytes, stream)
                 if rc != 0:
-                    raise RuntimeError(f"hdrnet_l2_loss_with_grad_f32 failed (rc={rc})")
+                    raise RuntimeError(f"hdrnet_l2_loss_with_grad_f32 failed (rc={rc}): {_lib.last_error()}")
             else:
                 _lib.check(lib.hdrnet_l2_loss_f32(p.data_ptr(), t.data_ptr(), n, loss.data_ptr(), ws.data_ptr(), wbytes,
                                                   stream), "L2Loss")
@@ -66,7 +66,7 @@ class _L2Loss(torch.autograd.Function):
                 rc = lib.hdrnet_l2_loss_grad_scale_f32(dpred.data_ptr(), g.data_ptr(), p.numel(),
                                                        torch.cuda.current_stream(dev).cuda_stream)
             if rc != 0:
-                raise RuntimeError(f"hdrnet_l2_loss_grad_scale_f32 failed (rc={rc})")
+                raise RuntimeError(f"hdrnet_l2_loss_grad_scale_f32 failed (rc={rc}): {_lib.last_error()}")
             return dpred, None
         dpred = torch.empty_like(p)
         with torch.cuda.device(dev):
@@ -120,7 +120,7 @@ def _loss_psnr_call(p: torch.Tensor, t: torch.Tensor, loss_ptr: int, psnr_ptr: i
                                       None if totals is None else totals.data_ptr(), ws.data_ptr(), wbytes,
                                       torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise RuntimeError(f"hdrnet_loss_psnr_f32 failed (rc={rc})")
+        raise RuntimeError(f"hdrnet_loss_psnr_f32 failed (rc={rc}): {_lib.last_error()}")
 
 
 class _LossPsnr(torch.autograd.Function):

@@ -98,7 +98,7 @@ class FlatAdam:
                         self.exp_avg_sq.data_ptr(), self.flat.numel(), self.steps.data_ptr(),
                         self.lr, b1, b2, self.eps, _stream(self.flat.device))
             if rc != 0:
-                raise RuntimeError(f"hdrnet_adam_step{'_tf' if self.epsilon_hat else ''}_f32 failed (rc={rc})")
+                raise RuntimeError(f"hdrnet_adam_step{'_tf' if self.epsilon_hat else ''}_f32 failed (rc={rc}): {_lib.last_error()}")
             return
         # CPU (the gloo tests): the same formula with torch ops
         self.steps += 1

@@ -89,7 +89,10 @@ extern "C" {
  *   260  + hdrnet_lowres_input, and hdrnet_prepare_batch in hdrnet_amd_train.h (sample preparation from u8 / u16 / f32).
  *   270  + hdrnet_prepare_batch_ragged in hdrnet_amd_train.h (the same from a packed set of images of mixed extents).
  *   280  + hdrnet_loss_psnr_f32 / hdrnet_loss_psnr_workspace_bytes in hdrnet_amd_train.h (loss, per-image PSNR and their
- *        running averages in the loss's own pass). */
+ *        running averages in the loss's own pass).
+ *   281  the loss / resize / Adam helpers of hdrnet_amd_train.h set hdrnet_last_error() when they refuse a call or a
+ *        launch fails, and clear it on success, like every other entry point (return codes unchanged).  The stderr
+ *        line of 250 is printed once per process and REASON (no fast kernel for the shape / no workspace). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

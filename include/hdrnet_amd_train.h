@@ -15,7 +15,8 @@
  * i.e. the formula above with eps / sqrt(1 - b2^t) in place of eps.  The two agree to rounding once sqrt(v) >> eps.
  * `step` is a DEVICE float holding the number of updates done so far; the call increments it (a second, one-thread
  * launch), so a captured hipGraph replays correctly.  Returns 0, or 1 for a bad argument (null / misaligned buffer,
- * n <= 0); no host synchronisation. */
+ * n <= 0), 2 when a launch fails -- with the reason in hdrnet_last_error(), as for every helper of this header; no host
+ * synchronisation. */
 #ifndef HDRNET_AMD_TRAIN_H_
 #define HDRNET_AMD_TRAIN_H_
 

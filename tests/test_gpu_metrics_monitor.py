@@ -100,10 +100,16 @@ def raw(lib, p, t, grad=None, image_mse=None, ema=None, decay=0.99, totals=None,
     if ws is None:
         ws = torch.empty((wbytes,), dtype=torch.uint8, device=p.device)
     out = torch.zeros((2,), device=p.device)
+    from hdrnet_amd import _lib
+    # a refused call (n = 0) leaves its text, which names the entry point; the successful call below clears it
+    assert lib.hdrnet_loss_psnr_f32(p.data_ptr(), t.data_ptr(), 0, B, out.data_ptr(), out.data_ptr() + 4, None, None,
+                                    None, decay, None, ws.data_ptr(), wbytes, None) == 1
+    assert _lib.last_error().startswith("hdrnet_loss_psnr_f32: "), _lib.last_error()
     rc = lib.hdrnet_loss_psnr_f32(p.data_ptr(), t.data_ptr(), n, B, out.data_ptr(), out.data_ptr() + 4, ptr(image_mse),
                                   ptr(grad), ptr(ema), decay, ptr(totals), ws.data_ptr(), wbytes,
                                   torch.cuda.current_stream(p.device).cuda_stream)
     assert rc == 0, rc
+    assert _lib.last_error() == ""
     return out
 
 

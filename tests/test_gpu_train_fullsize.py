@@ -348,15 +348,22 @@ class RawAdam:
         self.v[:n] = 0.0
         self.g = torch.full((n + self.PAD,), 1.0, device=dev)
         self.steps = torch.zeros((1,), device=dev)
+        # a refused call (n = 0) leaves its text, which names the entry point; the first successful step clears it
+        fn = self.lib.hdrnet_adam_step_tf_f32 if self.eh else self.lib.hdrnet_adam_step_f32
+        assert fn(self.p.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), ctypes.c_longlong(0),
+                  self.steps.data_ptr(), HYPER["lr"], HYPER["b1"], HYPER["b2"], HYPER["eps"], None) == 1
+        assert _lib.last_error().startswith(fn.__name__ + ": "), _lib.last_error()
 
     def step(self, g):
         self.g[:self.n] = g
         fn = self.lib.hdrnet_adam_step_tf_f32 if self.eh else self.lib.hdrnet_adam_step_f32
+        from hdrnet_amd import _lib
         with torch.cuda.device(self.dev):
             rc = fn(self.p.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), ctypes.c_longlong(self.n),
                     self.steps.data_ptr(), HYPER["lr"], HYPER["b1"], HYPER["b2"], HYPER["eps"],
                     torch.cuda.current_stream(self.dev).cuda_stream)
         assert rc == 0, rc
+        assert _lib.last_error() == ""
         torch.cuda.synchronize()
 
     def poison_intact(self):
