@@ -237,7 +237,9 @@ extern "C" {
 // 0.2.7.0: + hdrnet_prepare_batch_ragged (include/hdrnet_amd_train.h): sample preparation from a packed set of images of
 //          mixed extents
 // 0.2.8.1: the training-loop entry points of include/hdrnet_amd_train.h set / clear hdrnet_last_error() like the rest
-int hdrnet_version(void) { return 281; }
+// 0.2.8.2: the coefficient network's entry points refuse widths their kernels cannot run (workspace queries return 0
+//          where 281 returned a size: include/hdrnet_amd.h)
+int hdrnet_version(void) { return 282; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -595,6 +597,10 @@ int hdrnet_coefficients_f32(const float* lowres, const hdrnet_coeff_net* net, fl
   using namespace hdrnet_amd;
   if (!net) return fail(HDRNET_INVALID_ARGUMENT, "null network description");
   if (B < 0 || B > 65535) return fail(HDRNET_INVALID_ARGUMENT, "batch out of range (B=%d, at most 65535 per call)", B);
+  if (const char* limit = coefficients_limit(*net))
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "coefficient network: %s (net_input_size=%d, spatial_bin=%d, luma_bins=%d, channel_multiplier=%d)", limit,
+                net->net_input_size, net->spatial_bin, net->luma_bins, net->channel_multiplier);
   if (!coefficients_supported(*net))
     return fail(HDRNET_INVALID_ARGUMENT,
                 "coefficient network: unsupported hyper-parameters (net_input_size=%d, spatial_bin=%d, luma_bins=%d, "
@@ -625,6 +631,10 @@ int hdrnet_coefficients_grad_f32(const float* lowres, const hdrnet_coeff_net* ne
   using namespace hdrnet_amd;
   if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "null network description");
   const size_t need = B > 0 ? coefficients_grad_workspace_bytes(*net, B) : 0;
+  if (const char* limit = B > 0 ? coefficients_grad_limit(*net, B) : nullptr)
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "coefficient network gradient: %s (spatial_bin=%d, luma_bins=%d, n_out=%d, n_in=%d); the forward has no "
+                "such limit", limit, net->spatial_bin, net->luma_bins, net->n_out, net->n_in);
   if (need == 0)
     return fail(HDRNET_INVALID_ARGUMENT,
                 "coefficient network gradient: unsupported (needs the forward's support, n_levels = 1, fc_layout = 1, "

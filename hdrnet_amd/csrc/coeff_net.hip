@@ -62,8 +62,9 @@ struct ConvGeom {  // one convolution layer; read in ONE batch of wide scalar lo
   int stride, pad_top, pad_left, relu;
   int tiles_x, tiles;   // tiles of this problem (tiles_x per row)
   int oc_groups;        // workgroups along the output channels
-  unsigned ti_mul;      // ceil(2^32 / input tile edge):  pix / TI  == umulhi(pix, ti_mul)   (pix < 2^16)
-  unsigned tx_mul;      // ceil(2^32 / tiles_x):          tile / tiles_x == umulhi(tile, tx_mul)
+  unsigned ti_mul;      // ceil(2^32 / input tile edge):  pix / TI  == umulhi(pix, ti_mul); pix < 256 * kMaxU <= 1536
+  unsigned tx_mul;      // ceil(2^32 / tiles_x):          tile / tiles_x == umulhi(tile, tx_mul); tiles_x is a power of
+                        // two (net_dims), so the product is exact for any tile; tiles_x == 1 gives 0 == tile
   int c4shift, nchunks; // coeff_conv_mfma: float4 per staged pixel = 1 << c4shift; 64-channel chunks
   int pad_;
 };
@@ -237,7 +238,8 @@ __global__ __launch_bounds__(256) void coeff_conv_mfma(const ConvBatch batch) {
   const int npix = TI * TI;
   const float* in_b = p_in + (size_t)b * Hin * Win * Cin;
   float* gl = lds + npix * PS;          // the transform's g[Cin] behind the tile
-  float* red = gl + ((Cin + 3) & ~3);   // [4 waves][4][64] partial tiles behind that (the transform: its scratch)
+  float* red = gl + ((Cin + 3) & ~3);   // [4 waves][4][64] partial tiles behind that; before them the transform's
+                                        // xg[gK] (+ 256 floats of scratch at 512 while gK <= 256): max(1024, gK) floats
   const int q = lane >> 4, j = lane & 15;
   const int n0 = blockIdx.y * 16;
   const bool qvalid = 4 * q < cch;      // chunks narrower than 16 channels: the upper k rows are zero
@@ -479,7 +481,8 @@ inline int same_pad_before(int in, int out, int k, int s) {  // tf padding='SAME
   return total > 0 ? total / 2 : 0;
 }
 
-unsigned magic32(int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }  // umulhi(x, .) == x / d, x < 2^16
+// umulhi(x, magic32(d)) == x / d for x, d < 2^16, and for any x when d is a power of two (d == 1: 0, right for x == 0 only)
+unsigned magic32(int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
 // tile: output pixels per workgroup edge; oc_per_wg: output channels per workgroup
 ConvGeom conv_geom(const float* in, const float* w, const float* bias, float* out, int Hin, int Win, int Cin,
@@ -520,7 +523,7 @@ void fill_steps(ConvBatch* cb, int i, int ks) {
       const int tap = s / g16, grp = s - tap * g16;
       const int ky = tap / ks, kx = tap - ky * ks;
       const unsigned lds_off = (unsigned)((ky * ti + kx) * ps + 16 * grp);
-      const unsigned w_off = (unsigned)(tap * p.Cin + 16 * grp);
+      const unsigned w_off = (unsigned)(tap * p.Cin + 16 * grp);  // < 2^16: Cin <= 4096 (net_dims)
       cb->steps[i][wv][s - s0] = lds_off | (w_off << 16);
     }
     cb->steps[i][wv][9] = (unsigned)(s1 - s0);
@@ -536,10 +539,13 @@ long long* next_trace() { return g_coeff_trace ? g_coeff_trace + kTraceStride * 
 long long* next_trace() { return nullptr; }
 #endif
 
-size_t mfma_lds(int ks, int stride, int Cin) {
+// gK: the prediction layer's fc3 input, staged where the partial tiles go later (0: no such layer).  At most
+// 81 * 68 + 4096 + 1024 floats (3 x 3, stride 2, Cin = 4096) = 42 KB; the prediction layer 16 * 68 + 1024 + 2048 = 16 KB.
+size_t mfma_lds(int ks, int stride, int Cin, int gK) {
   const int ti = (kMTile - 1) * stride + ks;
   const int cch = Cin < kChunkCh ? Cin : kChunkCh;
-  return ((size_t)ti * ti * (cch + 4) + ((Cin + 3) & ~3) + 4 * 4 * 64) * sizeof(float);  // tile, g, partial tiles
+  const int red = gK > 4 * 4 * 64 ? gK : 4 * 4 * 64;
+  return ((size_t)ti * ti * (cch + 4) + ((Cin + 3) & ~3) + red) * sizeof(float);  // tile, g, partial tiles / xg
 }
 
 template <int KS, bool PRED>
@@ -550,7 +556,7 @@ hipError_t launch_conv_mfma(const ConvBatch& cb_in, int B, hipStream_t s) {
   unsigned tiles = 0, groups = 0;
   for (int i = 0; i < cb.n; ++i) {
     fill_steps(&cb, i, KS);
-    const size_t l = mfma_lds(KS, cb.g[i].stride, cb.g[i].Cin);
+    const size_t l = mfma_lds(KS, cb.g[i].stride, cb.g[i].Cin, PRED ? cb.x.gK : 0);
     lds = l > lds ? l : lds;
     tiles += (unsigned)cb.g[i].tiles;
     groups = (unsigned)cb.g[i].oc_groups > groups ? (unsigned)cb.g[i].oc_groups : groups;
@@ -574,6 +580,13 @@ size_t coefficients_workspace_bytes(const hdrnet_coeff_net& net, int B) {
 bool coefficients_supported(const hdrnet_coeff_net& net) {
   NetDims d;
   return net_dims(net, &d);
+}
+
+const char* coefficients_limit(const hdrnet_coeff_net& net) {
+  NetDims d;
+  const char* limit = nullptr;
+  net_dims(net, &d, &limit);
+  return limit;
 }
 
 hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,

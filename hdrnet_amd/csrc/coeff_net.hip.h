@@ -18,11 +18,29 @@ struct NetDims {
   int gside;                                // side of the global path's last conv
 };
 
-bool net_dims(const hdrnet_coeff_net& n, NetDims* d) {
+// The kernels' own limits inside the shape rules (`limit` names the one that refuses a configuration, for the error text):
+//   feat <= 4096  coeff_conv_mfma's step table packs the filter offset tap * Cin + 16 * group of a step into 16 bits:
+//                 8 * Cin + 48 < 65536.  Cin is feat (local1, global conv1) or gl.
+//   gl <= 1024    a choice of what is tested, not a limit of the kernels: the prediction layer keeps g[gl] and fc3's input
+//                 xg[2 * gl] in LDS beside its tile (4 * (3 * gl + 1088) bytes, sized from gl by mfma_lds) and is right
+//                 for any power-of-two gl by reading; 1024 is the widest layer the suite runs
+//                 (tests/test_gpu_coeff_net_edges.py: wide1024), and nothing wider is promised.
+//   pred <= 16 * 65535   the prediction layer's 16-channel groups are the launch grid's y extent.
+constexpr int kMaxFeat = 4096;
+constexpr int kMaxGl = 1024;
+
+bool net_dims(const hdrnet_coeff_net& n, NetDims* d, const char** limit = nullptr) {
+  if (limit) *limit = nullptr;
   if (n.net_input_size <= 0 || n.spatial_bin <= 0 || n.luma_bins <= 0 || n.channel_multiplier <= 0) return false;
   if (n.n_out <= 0 || n.n_in <= 0 || n.n_levels <= 0 || n.n_out % n.n_levels != 0) return false;
   if (!pow2(n.net_input_size) || !pow2(n.spatial_bin) || n.spatial_bin > n.net_input_size) return false;
-  if (n.net_input_size > 4096) return false;  // tile counts stay below 2^16 (umulhi divisions), grids below 2^31
+  // every side, and with it every tile count per row, is a power of two: the umulhi divisions by tile counts are exact
+  // for any dividend; N <= 4096 keeps a layer's tiles at 2^16 and the launch grids below 2^31
+  if (n.net_input_size > 4096) return false;
+  if ((long long)n.luma_bins * n.channel_multiplier > (1 << 20)) {  // (the products below stay in an int)
+    if (limit) *limit = "8 * cm * gd exceeds 1024";
+    return false;
+  }
   d->N = n.net_input_size; d->sb = n.spatial_bin; d->gd = n.luma_bins; d->cm = n.channel_multiplier;
   d->n_ds = 0;
   for (int v = d->N / d->sb; v > 1; v >>= 1) ++d->n_ds;
@@ -33,7 +51,20 @@ bool net_dims(const hdrnet_coeff_net& n, NetDims* d) {
   if (base % 4 != 0 || !pow2(base / 4)) return false;
   d->feat = base << (d->n_ds - 1);
   d->gl = 8 * base;
-  d->pred = d->gd * n.n_out * n.n_in;
+  if (d->feat > kMaxFeat) {
+    if (limit) *limit = "the last splat layer's channels, cm * gd * N / (2 * sb), exceed 4096";
+    return false;
+  }
+  if (d->gl > kMaxGl) {
+    if (limit) *limit = "8 * cm * gd exceeds 1024";
+    return false;
+  }
+  const long long pred = (long long)d->gd * n.n_out * n.n_in;
+  if (pred > 16 * 65535) {
+    if (limit) *limit = "gd * n_out * n_in exceeds 1048560 (16 * 65535)";
+    return false;
+  }
+  d->pred = (int)pred;
   d->gside = (((d->sb + 1) / 2) + 1) / 2;
   if ((long long)d->gside * d->gside * d->gl > (1 << 24)) return false;
   return true;

@@ -43,7 +43,10 @@ constexpr int kT = 4;          // pixel tile edge (16 pixels = the 16 rows / 4 K
 constexpr int kChunkCh = 64;   // coeff_conv_dx: gradient channels staged at a time
 constexpr int kMaxB = 8;       // coeff_fc_bwd keeps one accumulator per image in registers
 
-// x / d == umulhi(x, magic32(d)) for x < 2^16 and d >= 2; d == 1 has no 32-bit magic number (udiv handles it)
+// x / d == umulhi(x, magic32(d)) for x < 2^16 and 2 <= d < 2^16, and for ANY x when d is a power of two (the magic number
+// is 2^32 / d exactly); d == 1 has no 32-bit magic number (udiv handles it).  Every image, grid and tile side of the
+// network is a power of two (net_dims), so the divisions by tile counts below are of the second kind; the others state
+// their dividend's bound where they are made.
 unsigned magic32(int d) { return d > 1 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; }
 __device__ __forceinline__ int udiv(int x, unsigned mul, int d) { return d == 1 ? x : (int)__umulhi((unsigned)x, mul); }
 
@@ -58,7 +61,7 @@ struct DwParams {
   float* db_part;      // [nchunks][Cout] or null
   int Hin, Win, Cin, Hout, Wout, Cout, stride, pad_top, pad_left;
   int tiles_x, tiles_per_image, tiles_total, tiles_per_chunk;
-  unsigned tx_mul, tpi_mul;
+  unsigned tx_mul, tpi_mul;  // tiles_x and tiles_per_image = tiles_x^2 are powers of two: exact for any tile index
   int ic_blocks;
 };
 
@@ -196,7 +199,7 @@ struct DwFirstParams {
   float* db_part;      // [nchunks][Cout]
   int Hin, Win, Hout, Wout, Cout, pad_top, pad_left;
   int tiles_x, tiles_per_image, tiles_total, tiles_per_chunk;
-  unsigned tx_mul, tpi_mul, cout_mul;
+  unsigned tx_mul, tpi_mul, cout_mul;  // powers of two as in DwParams; cout_mul divides i < 3 * 256 by Cout <= 9
 };
 
 __global__ __launch_bounds__(256) void coeff_conv_dw_first(const DwFirstParams p) {
@@ -361,7 +364,7 @@ struct DxParams {
   int tiles_x, tiles, oc_groups;
   int tpb, tile_blocks;  // a workgroup's run of consecutive tiles (one is a chain of round trips: the next tile's loads fly
                          // under this tile's products); tile_blocks = ceil(tiles / tpb)
-  unsigned ti_mul, tx_mul;
+  unsigned ti_mul, tx_mul;  // ti_mul divides pix < 256 * kMaxU <= 1536 by the tile edge (4 or 6); tiles_x: a power of two
   int c4shift, nchunks;
   unsigned lds_off[4][12];  // per wave: LDS float offset of each (tap, 16-channel group) step | group << 24; [9] = count
   unsigned w_off[4][12];    // per wave: filter float offset of the step: (16 g * KK + flipped tap) * Cx
@@ -547,7 +550,11 @@ struct BwdPair {
   DxParams dx;
   int dw_chunks, dw_blocks;   // dw grid: dw_chunks x pairs, flattened
   int dx_tiles, dx_groups;    // dx grid: tiles x groups x B, flattened
-  unsigned chunk_mul, tile_mul, tg_mul;  // magic numbers of dw_chunks, dx_tiles, dx_tiles * dx_groups
+  // magic numbers of dw_chunks, dx_tiles, dx_tiles * dx_groups.  dw_chunks is any number, but it divides a block index
+  // below dw_blocks = dw_chunks * pairs, which part_plan keeps <= 256 unless dw_chunks == 1 (udiv: no division).
+  // dx_tiles = tiles / tpb and dx_groups = ceil(Cx / 16) are powers of two (Cx is 4, 8 or a power of two >= 16): exact
+  // for any block index.
+  unsigned chunk_mul, tile_mul, tg_mul;
 };
 
 template <int KS, bool MULTI>
@@ -678,7 +685,9 @@ struct RecomputeParams {
   float* x1; float* x2; float* g; float* fusion;  // [B][K2], [B][K3], [B][O3], [B][P][O3]
   float* dyp;                   // [B][P][gd * n_out * n_in] in the prediction layer's channel order
   int K2, K3, O3, P, gd, n_out, n_in;
-  unsigned C_mul, gd_mul, nout_mul;  // magic numbers of gd * n_out * n_in, gd, n_out
+  // magic numbers of C = gd * n_out * n_in, gd, n_out: any numbers below 2^16 (recompute_slabs), dividing an index below
+  // a slab's cells * C < 2^16, a channel < C and a channel / gd < C
+  unsigned C_mul, gd_mul, nout_mul;
 };
 
 // One workgroup per image (grid.x) and slab of cells (grid.y < slabs); every slab re-derives the (tiny) global features.
@@ -773,7 +782,7 @@ __global__ __launch_bounds__(256) void coeff_recompute(const RecomputeParams p) 
   const int C = p.gd * p.n_out * p.n_in;
   {
     const size_t base = ((size_t)b * p.P + px0) * C;
-    const int n = max(px1 - px0, 0) * C;  // < 2^16 (the magic divisions): <= 32 cells x 288 channels per slab
+    const int n = max(px1 - px0, 0) * C;  // < 2^16 (the magic divisions): the host sizes the slabs so, recompute_slabs
     for (int i0 = 0; i0 < n; i0 += 4 * 256) {
       float t[4];
 #pragma unroll
@@ -1100,14 +1109,41 @@ BwdSpace bwd_space(const NetDims& d, const hdrnet_coeff_net& net, int B) {
   return w;
 }
 
-bool train_supported(const hdrnet_coeff_net& net, int B, NetDims* d) {
+// The slabs coeff_recompute splits an image's P cells into: its gradient permutation divides indices below a slab's
+// cells * C (C = gd * n_out * n_in) by magic numbers that are exact for dividends and divisors below 2^16, so there are as
+// many slabs as keep ceil(P / slabs) * C below that -- more than kRecomputeSlabs from P * C = 2^21 on (a 32 x 32 grid of
+// 8 x 16 x 16 coefficients).  0: C itself is too large, or the slabs (+ 1) exceed the launch grid's y extent.
+int recompute_slabs(int P, int C) {
+  if (C >= 65536) return 0;
+  long long slabs = kRecomputeSlabs;
+  while ((((long long)P + slabs - 1) / slabs) * C >= 65536) slabs *= 2;
+  return slabs <= 32768 ? (int)slabs : 0;
+}
+
+bool train_supported(const hdrnet_coeff_net& net, int B, NetDims* d, const char** limit = nullptr) {
+  if (limit) *limit = nullptr;
   if (!net_dims(net, d)) return false;
   if (B < 1 || B > kMaxB || net.n_levels != 1 || net.fc_layout != 1) return false;
   if (d->gl > 256) return false;  // coeff_recompute's shared arrays
+  if (d->pred % 4 != 0) {  // coeff_conv_dx reads the prediction layer's gradient, [..][pred], four channels a load
+    if (limit) *limit = "gd * n_out * n_in must be a multiple of 4";
+    return false;
+  }
+  if (recompute_slabs(d->sb * d->sb, d->pred) == 0) {
+    if (limit) *limit = "gd * n_out * n_in must be below 65536 and sb^2 * gd * n_out * n_in below 2^31";
+    return false;
+  }
   return true;
 }
 
 }  // namespace
+
+const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B) {
+  NetDims d;
+  const char* limit = nullptr;
+  train_supported(net, B, &d, &limit);
+  return limit;
+}
 
 size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B) {
   NetDims d;
@@ -1146,8 +1182,7 @@ hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net&
                       dcoeffs, buf(bs.x1), buf(bs.x2), buf(bs.g), buf(bs.fusion), buf(bs.dyp),
                       4 * d.gl, 2 * d.gl, d.gl, P, d.gd, net.n_out, net.n_in,
                       magic32(d.gd * net.n_out * net.n_in), magic32(d.gd), magic32(net.n_out)};
-    int slabs = kRecomputeSlabs;
-    while (slabs > 1 && ((P + slabs - 1) / slabs) * (d.gd * net.n_out * net.n_in) >= 65536) slabs *= 2;  // (never: see the kernel)
+    const int slabs = recompute_slabs(P, d.pred);  // > 0: train_supported
     coeff_recompute<<<dim3((unsigned)B, (unsigned)slabs + 1), 256, 0, s>>>(p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }

@@ -271,6 +271,9 @@ hipError_t launch_l2_loss_grad(const float* pred, const float* target, const flo
 
 // coeff_net.hip -- the low-resolution coefficient network (hdrnet/models.py:62-142) as inference kernels.
 bool coefficients_supported(const hdrnet_coeff_net& net);
+// unsupported because of a limit of the kernels rather than the shape rules: the limit in words; else null
+const char* coefficients_limit(const hdrnet_coeff_net& net);
+const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B);
 size_t coefficients_workspace_bytes(const hdrnet_coeff_net& net, int B);  // 0: unsupported hyper-parameters
 hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,
                                hipStream_t s, const char** name);

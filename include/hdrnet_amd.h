@@ -92,7 +92,11 @@ extern "C" {
  *        running averages in the loss's own pass).
  *   281  the loss / resize / Adam helpers of hdrnet_amd_train.h set hdrnet_last_error() when they refuse a call or a
  *        launch fails, and clear it on success, like every other entry point (return codes unchanged).  The stderr
- *        line of 250 is printed once per process and REASON (no fast kernel for the shape / no workspace). */
+ *        line of 250 is printed once per process and REASON (no fast kernel for the shape / no workspace).
+ *   282  the coefficient network refuses what its kernels cannot run: hdrnet_coefficients_workspace_bytes returns 0 (281:
+ *        a size) for a last splat layer wider than 4096 channels, 8 * cm * gd > 1024, gd * n_out * n_in > 1048560;
+ *        hdrnet_coefficients_grad_workspace_bytes also for gd * n_out * n_in no multiple of 4 or >= 65536 (281 read out
+ *        of bounds or divided wrongly there).  The entry points name the limit in hdrnet_last_error(). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */
@@ -434,8 +438,11 @@ int hdrnet_guide_fold_batch_grad_f32(const float* sums, const float* moments, lo
  * n_levels > 1 (HDRNetGaussianPyrNN: n_out = 9, n_levels = 3) writes the output level-major,
  * [n_levels][B][sb][sb][gd][n_out / n_levels][n_in] -- each level's grid contiguous, as the per-level
  * slice-applies of models.py:277-289 (coeffs[:, :, :, :, 3*l : 3*l + 3, :]) need it.
- * Supported: N <= 4096 and sb powers of two, N / sb in [2, 256], cm * gd a multiple of 4 with cm * gd / 4 a power of two,
- * B <= 65535; hdrnet_coefficients_workspace_bytes returns 0 otherwise (run the framework's own graph instead).  The
+ * Supported: N <= 4096 and sb powers of two (sb = 1 and 2 included), N / sb in [2, 256], cm * gd a multiple of 4 with
+ * cm * gd / 4 a power of two, the last splat layer's channels cm * gd * N / (2 * sb) <= 4096, 8 * cm * gd <= 1024, any
+ * n_out and n_in with gd * n_out * n_in <= 1048560 (the output is stored element by element: no multiple of 4 needed),
+ * B <= 65535; hdrnet_coefficients_workspace_bytes returns 0 otherwise (run the framework's own graph instead) and
+ * hdrnet_coefficients_f32 returns 1, naming the limit in hdrnet_last_error() where one of the three widths is it.  The
  * parameter arrays are read by the launches: keep them alive and unchanged until those have run. */
 typedef struct hdrnet_coeff_net {
   int net_input_size;     /* N */
@@ -466,7 +473,10 @@ size_t hdrnet_coefficients_workspace_bytes(const hdrnet_coeff_net* net, int B);
  * workspace: `forward_workspace` here is that buffer, untouched since.  `dcoeffs` is [B][sb][sb][gd][n_out][n_in];
  * gradients are written (not accumulated) in the parameters' own layouts; local_b[1] is ignored (no such bias).
  * 15 launches on `stream`, deterministic.  Supported: what the forward supports, n_levels = 1, fc_layout = 1,
- * B <= 8, 8 * cm * gd <= 256; hdrnet_coefficients_grad_workspace_bytes returns 0 otherwise. */
+ * B <= 8, 8 * cm * gd <= 256, and -- limits of this entry point alone, the forward has neither -- gd * n_out * n_in a
+ * multiple of 4 (the prediction layer's gradient is read four channels at a time) and below 65536, with
+ * sb^2 * gd * n_out * n_in below 2^31; hdrnet_coefficients_grad_workspace_bytes returns 0 otherwise and
+ * hdrnet_coefficients_grad_f32 returns 1 with the reason in hdrnet_last_error(). */
 typedef struct hdrnet_coeff_net_grads {
   float* splat_w[8];
   float* splat_b[8];

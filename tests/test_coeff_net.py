@@ -11,8 +11,8 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+import coeff_reference
 from hdrnet_amd import models
 
 
@@ -33,44 +33,12 @@ def randomize(module, seed=0):
 
 def evaluate_exported(w, low):
     """The network evaluated from the EXPORTED arrays with plain torch ops -- the layout contract of
-    include/hdrnet_amd.h (hdrnet_coeff_net) spelled out."""
-    keep = iter(w._keep)
-
-    def take(has_bias=True):
-        wt = next(keep)
-        return wt, (next(keep) if has_bias else None)
-
-    def conv(x, wt, b, stride, relu):
-        k = wt.shape[1]
-        x = models.tf_same_pad(x, k, stride)
-        y = F.conv2d(x, wt.permute(0, 3, 1, 2), b, stride=stride)  # [Cout][kh][kw][Cin] -> OIHW
-        return F.relu(y) if relu else y
-
-    x = low.permute(0, 3, 1, 2)
-    for _ in range(w.n_splat):
-        wt, b = take()
-        x = conv(x, wt, b, 2, True)
-    g = x
-    for _ in range(2):
-        wt, b = take()
-        g = conv(g, wt, b, 2, True)
-    g = g.permute(0, 2, 3, 1).reshape(g.shape[0], -1)
-    for i in range(3):
-        wt, b = take()
-        g = g @ wt + b  # [in][out]
-        if i < 2:
-            g = F.relu(g)
-    wt, b = take()
-    loc = conv(x, wt, b, 1, True)
-    wt, b = take(has_bias=False)
-    loc = conv(loc, wt, None, 1, False)
-    fusion = F.relu(loc + g[:, :, None, None])
-    wt, b = take()
-    pred = conv(fusion, wt, b, 1, False)
-    B, _, GH, GW = pred.shape
-    gd = w.params["luma_bins"]
-    pred = pred.reshape(B, w.n_in, w.n_out, gd, GH, GW)
-    return pred.permute(0, 4, 5, 3, 2, 1).contiguous()
+    include/hdrnet_amd.h (hdrnet_coeff_net) spelled out, for any hyper-parameters, in tests/coeff_reference.py."""
+    p = w.params
+    shape = coeff_reference.Shape(p["net_input_size"], p["spatial_bin"], p["luma_bins"], p["channel_multiplier"],
+                                  w.n_out, w.n_in)
+    assert coeff_reference.dims(shape)["n_ds"] == w.n_splat
+    return coeff_reference.evaluate(list(w._keep), low, shape)
 
 
 @pytest.mark.parametrize("bn", [False, True])
