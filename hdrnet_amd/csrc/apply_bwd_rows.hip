@@ -127,61 +127,44 @@ __global__ __launch_bounds__(256) void apply_vjp_rows_vec4(
 #pragma unroll
       for (int q = 0; q < CIN; ++q) slab[lane * CIN + q] = div[q];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int wave_x0 = xs + kPxPerThread * (int)(threadIdx.x & ~63u);
-    const int nvalid = (min(xe, wave_x0 + 64 * kPxPerThread) - wave_x0) * CIN / 4;
+    const int wave_px = min(xe, wave_x0 + 64 * kPxPerThread) - wave_x0;
     // nontemporal buffer stores on a descriptor over exactly this wave's run (rows_common.hip.h)
-    const __amdgpu_buffer_rsrc_t orsrc =
-        make_rsrc_uniform(dinput + ((size_t)row * W + wave_x0) * CIN, nvalid > 0 ? (unsigned)nvalid * 16u : 0u);
-#pragma unroll
-    for (int k = 0; k < CIN; ++k) buf_store16<kAuxStream>(slab[lane + 64 * k], orsrc, (unsigned)(lane + 64 * k) * 16u);
+    store_slab_run<CIN>(slab, dinput + ((size_t)row * W + wave_x0) * CIN, wave_px, lane);
   }
 }
 
-constexpr size_t kMaxLdsBytes = 64 * 1024;
-
+// WI: the dinput slab of the geometry exists (vjp_geom: a.dinput wanted and CIN > 0).
 template <int CIN, int COUT, bool OFFSET, bool WG, bool WI>
-hipError_t launch_vjp_t(const ApplyGradArgs& a, const Plan& pl, hipStream_t s) {
-  constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
-  const int slab_off = round_up(pl.max_cols * a.GD * C, 4);
-  const size_t lds =
-      ((size_t)slab_off + (WI ? (size_t)(pl.threads / 64) * 64 * kPxPerThread * CIN : 0)) * sizeof(float);
-  const long long nblocks = (long long)a.B * a.H * pl.nseg;
-  apply_vjp_rows_vec4<CIN, COUT, OFFSET, WG, WI><<<(unsigned)nblocks, pl.threads, lds, s>>>(
-      a.grid, a.guide, a.input, a.dout, a.dguide, a.dinput, a.H, a.W, a.GH, a.GW, a.GD, pl.nseg,
-      pl.seg, slab_off, (float)a.GW / a.W, (float)a.GH / a.H);
+hipError_t launch_vjp_t(const ApplyGradArgs& a, const RowGeom& g, hipStream_t s) {
+  const long long nblocks = (long long)a.B * a.H * g.pl.nseg;
+  apply_vjp_rows_vec4<CIN, COUT, OFFSET, WG, WI><<<(unsigned)nblocks, g.pl.threads, g.lds, s>>>(
+      a.grid, a.guide, a.input, a.dout, a.dguide, a.dinput, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg,
+      g.pl.seg, g.slab_off, (float)a.GW / a.W, (float)a.GH / a.H);
   return hipGetLastError();
 }
 
+bool want_dinput(const ApplyGradArgs& a) { return a.dinput != nullptr && a.Cin > 0; }
+
 template <int CIN, int COUT, bool OFFSET>
-hipError_t launch_vjp_want(const ApplyGradArgs& a, const Plan& pl, hipStream_t s) {
-  const bool wg = a.dguide != nullptr, wi = (a.dinput != nullptr) && CIN > 0;
-  if (wg && wi) return launch_vjp_t<CIN, COUT, OFFSET, true, (CIN > 0)>(a, pl, s);
-  if (wg) return launch_vjp_t<CIN, COUT, OFFSET, true, false>(a, pl, s);
-  if (wi) return launch_vjp_t<CIN, COUT, OFFSET, false, (CIN > 0)>(a, pl, s);
+hipError_t launch_vjp_want(const ApplyGradArgs& a, const RowGeom& g, hipStream_t s) {
+  const bool wg = a.dguide != nullptr, wi = want_dinput(a);
+  if (wg && wi) return launch_vjp_t<CIN, COUT, OFFSET, true, (CIN > 0)>(a, g, s);
+  if (wg) return launch_vjp_t<CIN, COUT, OFFSET, true, false>(a, g, s);
+  if (wi) return launch_vjp_t<CIN, COUT, OFFSET, false, (CIN > 0)>(a, g, s);
   return hipSuccess;
 }
 
-bool vjp_plan(const ApplyGradArgs& a, Plan* pl) {
-  const bool aligned = (((uintptr_t)a.guide | (uintptr_t)a.input | (uintptr_t)a.dout |
-                         (uintptr_t)a.grid | (uintptr_t)a.dguide | (uintptr_t)a.dinput) & 15u) == 0;
-  *pl = make_row_plan(a.W, a.GW, aligned);
-  if (!pl->vec4) return false;
-  if ((long long)a.B * a.H * pl->nseg > 0x7fffffffLL) return false;
-  const size_t lds = ((size_t)pl->max_cols * a.GD * a.Cout * a.Cj + 4 +
-                      (size_t)(pl->threads / 64) * 64 * kPxPerThread * (a.Cin > 0 ? a.Cin : 1)) *
-                     sizeof(float);
-  return lds <= kMaxLdsBytes;
+// Launch geometry (row_geom.h).
+RowGeom vjp_geom(const ApplyGradArgs& a) {
+  return vjp_rows_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cin, a.Cout, a.Cj, want_dinput(a),
+                       ptr_bits(a.guide, a.input, a.dout, a.grid, a.dguide, a.dinput));
 }
 
 }  // namespace
 
-bool vjp_rows_supported(const ApplyGradArgs& a) {
-  Plan pl;
-  return grad_fast_shape(a) && vjp_plan(a, &pl);
-}
+bool vjp_rows_supported(const ApplyGradArgs& a) { return grad_fast_shape(a) && vjp_geom(a).ok; }
 
 hipError_t launch_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** name) {
 #ifdef HDRNET_TOOLS_BUILD
@@ -193,19 +176,19 @@ hipError_t launch_vjp_rows(const ApplyGradArgs& a, hipStream_t s, const char** n
     const hipError_t e = launch_apply_vjp_seg(a, s, name);
     if (e != hipErrorNotSupported) return e;
   }
-  Plan pl;
-  if (!vjp_plan(a, &pl)) return hipErrorInvalidValue;
+  const RowGeom g = vjp_geom(a);
+  if (!g.ok) return hipErrorInvalidValue;
   if (!a.slice) {  // BilateralSliceApply: dguide / dinput
     *name = "apply_vjp_rows/vec4";
 #define HDRNET_CASE(CI, CO, OFF) \
-  if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF) return launch_vjp_want<CI, CO, OFF>(a, pl, s);
+  if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF) return launch_vjp_want<CI, CO, OFF>(a, g, s);
     HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
 #undef HDRNET_CASE
     return hipErrorInvalidValue;
   }
   *name = "slice_vjp_rows/vec4";  // BilateralSlice: dguide (CIN = 0, one "offset" column per channel)
 #define HDRNET_CASE(CC) \
-  if (a.Cout == CC) return launch_vjp_t<0, CC, true, true, false>(a, pl, s);
+  if (a.Cout == CC) return launch_vjp_t<0, CC, true, true, false>(a, g, s);
   HDRNET_SLICE_FAST_CHANNELS(HDRNET_CASE)
 #undef HDRNET_CASE
   return hipErrorInvalidValue;

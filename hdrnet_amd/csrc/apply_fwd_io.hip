@@ -152,9 +152,7 @@ __device__ __forceinline__ void curves_build_tables(float* __restrict__ tab, con
     tab[T::kRawS + lane] = s;
     tab[T::kRawL + lane] = sl;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   if (mine) {
     int rank = 0;
 #pragma unroll
@@ -165,9 +163,7 @@ __device__ __forceinline__ void curves_build_tables(float* __restrict__ tab, con
     tab[T::kSortS + c * 16 + rank] = s;
     tab[T::kSortL + c * 16 + rank] = sl;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   if (mine) {
     const int i = k;
     const float si = tab[T::kSortS + c * 16 + i];
@@ -468,9 +464,7 @@ __device__ __forceinline__ void nn_build_tables(unsigned* __restrict__ tab, floa
     }
     lin[j] = (float)acc;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   if (lane == 0) {
     const float w[4] = {lin[0], lin[1], lin[2], lin[3]};
     nn_store_row(tab, 4, 0, w);
@@ -631,7 +625,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   const float* grid_b = p.grid + (size_t)b * (unsigned)p.grid_image;
   const int x = xs + kPxPerThread * tid;
   const bool active = x < xe;
-  const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (plan_io)
+  const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (kLimBH, row_geom.h)
   const size_t px = row * p.W + x;
   const TI* input = static_cast<const TI*>(p.input);
 
@@ -732,37 +726,31 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
       for (int q = 0; q < COUT; ++q)
         slab[lane * COUT + q] = make_float4(of[4 * q], of[4 * q + 1], of[4 * q + 2], of[4 * q + 3]);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const unsigned wpx = kPxPerThread * 64u * (unsigned)wave;
     float* oseg = static_cast<float*>(p.out) + (row * p.W + xs) * COUT;
-    const __amdgpu_buffer_rsrc_t orsrc = make_rsrc_uniform(oseg, (unsigned)(xe - xs) * COUT * 4u);
-#pragma unroll
-    for (int k = 0; k < COUT; ++k)
-      buf_store16<kAuxStream>(slab[lane + 64 * k], orsrc, (wpx * COUT + 4u * (unsigned)(lane + 64 * k)) * 4u);
+    store_slab_seg<COUT>(slab, oseg, (unsigned)(xe - xs), wpx, lane);
   }
 }
 
-struct IoGeom {
-  Plan pl;
-  int slab_off;
-  size_t lds;
-};
+// The curves instantiations keep their lookup tables in STATIC LDS: no launch passes those bytes, but the workgroup
+// occupies them, so the geometry's `ok` budgets the largest static table of any instantiation.
+constexpr int kStaticTabFloats = CurveTab<3>::kFloats > 3 * kCurveCells * 4 ? CurveTab<3>::kFloats : 3 * kCurveCells * 4;
+static_assert(kStaticTabFloats == 768, "tests/test_row_geom.py and io_fits of tests/row_plan.py budget 768 floats of static tables");
 
-IoGeom io_geom(int W, int GW, int GD, int C, int Cout, int tab_floats = 0) {
-  IoGeom g;
-  g.pl = make_row_plan(W, GW, true);
-  const int max_cols = (int)(((long long)(g.pl.seg - 1) * GW) / W + 4);
-  g.slab_off = round_up(max_cols * (GD + 2) * C, 4);
-  g.lds = ((size_t)tab_floats + (size_t)g.slab_off + (size_t)(g.pl.threads / 64) * 64 * kPxPerThread * Cout) * sizeof(float);
-  return g;
+// Launch geometry (row_geom.h).  `tab_floats`: dynamic LDS in front of the image -- the tables of the tools build's
+// matrix-core guide network, known to its instantiation alone (launch_io), so the predicate passes 0.
+RowGeom io_geom(const ApplyIoArgs& a, int tab_floats) {
+  return io_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cout * (a.Cin + (a.has_offset ? 1 : 0)), a.Cout, tab_floats,
+                     kStaticTabFloats,
+                     ptr_bits(a.grid, a.guide, a.guide_out, a.output_dtype == 0 ? a.out : nullptr,
+                              a.input_dtype == 0 ? a.input : nullptr));
 }
 
 template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO>
-hipError_t launch_io(const ApplyIoArgs& a, const Plan&, hipStream_t s) {
+hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
-  const IoGeom g = io_geom(a.W, a.GW, a.GD, C, COUT, (kToolsBuild && GUIDE == kGuideNN) ? NnTab::kWords : 0);
+  const RowGeom g = io_geom(a, (kToolsBuild && GUIDE == kGuideNN) ? NnTab::kWords : 0);
   IoParams p;
   p.grid = a.grid;
   p.guide = a.guide;
@@ -790,43 +778,29 @@ hipError_t launch_io(const ApplyIoArgs& a, const Plan&, hipStream_t s) {
 }
 
 template <int GUIDE, typename TI, typename TO>
-hipError_t dispatch_shape(const ApplyIoArgs& a, const Plan& pl, hipStream_t s) {
-  if (a.Cin == 3 && a.Cout == 3 && a.has_offset) return launch_io<3, 3, true, GUIDE, TI, TO>(a, pl, s);
+hipError_t dispatch_shape(const ApplyIoArgs& a, hipStream_t s) {
+  if (a.Cin == 3 && a.Cout == 3 && a.has_offset) return launch_io<3, 3, true, GUIDE, TI, TO>(a, s);
   return hipErrorInvalidValue;
 }
 
 template <int GUIDE>
-hipError_t dispatch_types(const ApplyIoArgs& a, const Plan& pl, hipStream_t s) {
+hipError_t dispatch_types(const ApplyIoArgs& a, hipStream_t s) {
   const int in = a.input_dtype, out = a.output_dtype;
-  if (in == 1 && out == 1) return dispatch_shape<GUIDE, uint8_t, uint8_t>(a, pl, s);
-  if (in == 1 && out == 0) return dispatch_shape<GUIDE, uint8_t, float>(a, pl, s);
-  if (in == 2 && out == 1) return dispatch_shape<GUIDE, uint16_t, uint8_t>(a, pl, s);
-  if (in == 2 && out == 0) return dispatch_shape<GUIDE, uint16_t, float>(a, pl, s);
-  if (in == 0 && out == 1) return dispatch_shape<GUIDE, float, uint8_t>(a, pl, s);
-  if (in == 0 && out == 0) return dispatch_shape<GUIDE, float, float>(a, pl, s);
+  if (in == 1 && out == 1) return dispatch_shape<GUIDE, uint8_t, uint8_t>(a, s);
+  if (in == 1 && out == 0) return dispatch_shape<GUIDE, uint8_t, float>(a, s);
+  if (in == 2 && out == 1) return dispatch_shape<GUIDE, uint16_t, uint8_t>(a, s);
+  if (in == 2 && out == 0) return dispatch_shape<GUIDE, uint16_t, float>(a, s);
+  if (in == 0 && out == 1) return dispatch_shape<GUIDE, float, uint8_t>(a, s);
+  if (in == 0 && out == 0) return dispatch_shape<GUIDE, float, float>(a, s);
   return hipErrorInvalidValue;
-}
-
-bool plan_io(const ApplyIoArgs& a, Plan* pl) {
-  if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
-  if (a.W % 4 != 0) return false;
-  const uintptr_t bits = (uintptr_t)a.grid | (uintptr_t)a.guide | (uintptr_t)a.guide_out |
-                         (a.output_dtype == 0 ? (uintptr_t)a.out : 0) |
-                         (a.input_dtype == 0 ? (uintptr_t)a.input : 0);
-  if (bits & 15u) return false;
-  if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;
-  const IoGeom g = io_geom(a.W, a.GW, a.GD, 12, 3, CurveTab<3>::kFloats > 3 * kCurveCells * 4 ? CurveTab<3>::kFloats : 3 * kCurveCells * 4);  // + the curves kernel's static tables: the largest of the kernels
-  *pl = g.pl;
-  if (a.B > 65535 || a.H > 65535 || (long long)a.W * a.Cout * 4 >= (1LL << 31)) return false;
-  if ((long long)(g.slab_off) >= (1 << 20)) return false;
-  return g.lds <= 64 * 1024;
 }
 
 }  // namespace
 
 bool apply_fwd_io_supported(const ApplyIoArgs& a) {
-  Plan pl;
-  return plan_io(a, &pl);
+  if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
+  if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;  // quantised pixels: whole dwords per lane
+  return io_geom(a, 0).ok;
 }
 
 size_t curves_guide_prepared_bytes(int Cin) { return Cin == 3 ? CurveCells<3>::kFloats * sizeof(float) : 0; }
@@ -841,8 +815,7 @@ hipError_t launch_curves_guide_prepare(const float* shifts, const float* slopes,
 }
 
 hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char** name) {
-  Plan pl;
-  if (!plan_io(a, &pl)) return hipErrorInvalidValue;
+  if (!apply_fwd_io_supported(a)) return hipErrorInvalidValue;
   static const char* const io[3][2] = {{"f32->f32", "f32->u8"}, {"u8->f32", "u8->u8"}, {"u16->f32", "u16->u8"}};
   static const char* const suffix[3] = {"", "+nnguide", "+curvesguide"};
   static thread_local char label[64];
@@ -853,10 +826,10 @@ hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char**
            cells ? "/cells" : scan ? "/scan" : "");
   *name = label;
   if (kind == kGuideCurves) {
-    if (a.n_feats > kCurveMaxKnots) return dispatch_types<kGuideCurvesScan>(a, pl, s);
-    return cells ? dispatch_types<kGuideCurvesCells>(a, pl, s) : dispatch_types<kGuideCurves>(a, pl, s);
+    if (a.n_feats > kCurveMaxKnots) return dispatch_types<kGuideCurvesScan>(a, s);
+    return cells ? dispatch_types<kGuideCurvesCells>(a, s) : dispatch_types<kGuideCurves>(a, s);
   }
-  return kind == kGuideNN ? dispatch_types<kGuideNN>(a, pl, s) : dispatch_types<kGuideMap>(a, pl, s);
+  return kind == kGuideNN ? dispatch_types<kGuideNN>(a, s) : dispatch_types<kGuideMap>(a, s);
 }
 
 }  // namespace hdrnet_amd

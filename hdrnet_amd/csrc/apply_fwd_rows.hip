@@ -110,9 +110,7 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
       const int e = lane + 64 * k;
       if (e < wave_px * CIN / 4) slab[e] = iv[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (active) {
 #pragma unroll
       for (int q = 0; q < CIN; ++q) iv[q] = slab[lane * CIN + q];
@@ -139,30 +137,7 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
 #pragma unroll
       for (int i = 0; i < COUT; ++i) of[k * COUT + i] = o[i];
     }
-    if constexpr (UPADD) {
-      // row terms are workgroup-uniform; the 2 x 2 x COUT gathers hit the (small, cache-resident)
-      // coarse level
-      const float sy = mul_rn((float)y, up.sh);
-      const float fy = floorf(sy);
-      const float ly = sy - fy;
-      const int y0 = (int)fy, y1 = min((int)ceilf(sy), up.Hc - 1);
-      const float* r0 = up.coarse + ((size_t)b * up.Hc + y0) * up.Wc * COUT;
-      const float* r1 = up.coarse + ((size_t)b * up.Hc + y1) * up.Wc * COUT;
-#pragma unroll
-      for (int k = 0; k < kPxPerThread; ++k) {
-        const float sxf = mul_rn((float)(x + k), up.sw);
-        const float fx = floorf(sxf);
-        const float lx = sxf - fx;
-        const int x0 = (int)fx * COUT, x1 = min((int)ceilf(sxf), up.Wc - 1) * COUT;
-#pragma unroll
-        for (int i = 0; i < COUT; ++i) {
-          const float tl = r0[x0 + i], tr = r0[x1 + i], bl = r1[x0 + i], br = r1[x1 + i];
-          const float top = tl + (tr - tl) * lx;
-          const float bot = bl + (br - bl) * lx;
-          of[k * COUT + i] += top + (bot - top) * ly;
-        }
-      }
-    }
+    if constexpr (UPADD) upadd_quad<COUT>(up, b, y, x, of);
   }
   if constexpr (!LDS_STORES) {
     if (!active) return;
@@ -181,15 +156,9 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
 #pragma unroll
     for (int q = 0; q < COUT; ++q) slab[lane * COUT + q] = ov[q];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   // nontemporal buffer stores on a descriptor over exactly this wave's run (rows_common.hip.h)
-  const int nvalid = wave_px * COUT / 4;  // float4s
-  const __amdgpu_buffer_rsrc_t orsrc =
-      make_rsrc_uniform(out + ((size_t)row * W + wave_x0) * COUT, nvalid > 0 ? (unsigned)nvalid * 16u : 0u);
-#pragma unroll
-  for (int k = 0; k < COUT; ++k) buf_store16<kAuxStream>(slab[lane + 64 * k], orsrc, (unsigned)(lane + 64 * k) * 16u);
+  store_slab_run<COUT>(slab, out + ((size_t)row * W + wave_x0) * COUT, wave_px, lane);
 }
 
 // ---- scalar variant: any W / alignment; thread t takes pixels xs + t + k*blockDim ------
@@ -236,67 +205,49 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_scalar(
   }
 }
 
-struct LaunchGeom {
-  Plan pl;
-  int slab_off;
-  size_t lds;
-  long long nblocks;
-};
+// Launch geometry (row_geom.h).  A fused guide network reads no guide buffer: its callers pass a.guide = a.input.
+RowGeom geom_for(const ApplyArgs& a) {
+  return rows_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cin, a.Cout, a.Cj, ptr_bits(a.guide, a.input, a.out, a.grid));
+}
 
-template <int C, int COUT>
-LaunchGeom geom_for(const ApplyArgs& a) {
-  const int slab_ch = a.Cin > COUT ? a.Cin : COUT;  // the slab transposes the input run, then the output
-  LaunchGeom g;
-  const bool aligned = (((uintptr_t)a.guide | (uintptr_t)a.input | (uintptr_t)a.out |
-                         (uintptr_t)a.grid) & 15u) == 0;
-  g.pl = make_row_plan(a.W, a.GW, aligned);
-  // dynamic LDS: [colY image][one 64 x 4*COUT-float output slab per wave (vec4 kernel)]
-  g.slab_off = round_up(g.pl.max_cols * a.GD * C, 4);
-  g.lds = ((size_t)g.slab_off + (size_t)(g.pl.threads / 64) * 64 * kPxPerThread * slab_ch) * sizeof(float);
-  g.nblocks = (long long)a.B * a.H * g.pl.nseg;
-  return g;
+unsigned nblocks_of(const ApplyArgs& a, const RowGeom& g) { return (unsigned)((long long)a.B * a.H * g.pl.nseg); }
+
+// One launch of the vec4 kernel, whichever FLAVOUR (GUIDE_NN, LDS_STORES, UPADD, NT_LOADS): the kernel's argument list.
+template <int CIN, int COUT, bool OFFSET, bool... FLAVOUR>
+hipError_t launch_vec4(const ApplyArgs& a, const RowGeom& g, const float* guide, hipStream_t s,
+                       const GuideNN& gn = GuideNN{nullptr, nullptr, nullptr, 0},
+                       const UpAdd& up = UpAdd{nullptr, 0, 0, 0.f, 0.f}) {
+  apply_fwd_rows_vec4<CIN, COUT, OFFSET, FLAVOUR...><<<nblocks_of(a, g), g.pl.threads, g.lds, s>>>(
+      a.grid, guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
+      (float)a.GW / a.W, (float)a.GH / a.H, gn, up);
+  return hipGetLastError();
 }
 
 template <int CIN, int COUT, bool OFFSET>
 hipError_t launch_t(const ApplyArgs& a, hipStream_t s, const char** name) {
-  constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
-  const LaunchGeom g = geom_for<C, COUT>(a);
-  const float sx = (float)a.GW / a.W, sy = (float)a.GH / a.H;
-  if (g.pl.vec4) {
-    apply_fwd_rows_vec4<CIN, COUT, OFFSET><<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-        a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
-        sx, sy);
-    *name = "apply_fwd_rows/vec4";
-  } else {
-    apply_fwd_rows_scalar<CIN, COUT, OFFSET><<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-        a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, sx, sy);
-    *name = "apply_fwd_rows/scalar";
-  }
-  return hipGetLastError();
-}
-
-constexpr size_t kMaxLdsBytes = 64 * 1024;  // keep >= 2 workgroups per CU
-
-template <int CIN, int COUT, bool OFFSET>
-hipError_t launch_nnguide_t(const ApplyArgs& a, const GuideNN& gn, hipStream_t s) {
-  constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
-  const LaunchGeom g = geom_for<C, COUT>(a);
-  apply_fwd_rows_vec4<CIN, COUT, OFFSET, true><<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-      a.grid, nullptr, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
-      (float)a.GW / a.W, (float)a.GH / a.H, gn);
+  const RowGeom g = geom_for(a);
+  *name = g.pl.vec4 ? "apply_fwd_rows/vec4" : "apply_fwd_rows/scalar";
+  if (g.pl.vec4) return launch_vec4<CIN, COUT, OFFSET>(a, g, a.guide, s);
+  apply_fwd_rows_scalar<CIN, COUT, OFFSET><<<nblocks_of(a, g), g.pl.threads, g.lds, s>>>(
+      a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, (float)a.GW / a.W,
+      (float)a.GH / a.H);
   return hipGetLastError();
 }
 
 template <bool GUIDE_NN>
 hipError_t launch_upadd_t(const ApplyArgs& a, const GuideNN& gn, const float* coarse, int Hc, int Wc,
                           hipStream_t s) {
-  const LaunchGeom g = geom_for<12, 3>(a);
   const UpAdd up{coarse, Hc, Wc, resize_scale(Hc, a.H), resize_scale(Wc, a.W)};
-  apply_fwd_rows_vec4<3, 3, true, GUIDE_NN, true, true>
-      <<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-          a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
-          (float)a.GW / a.W, (float)a.GH / a.H, gn, up);
-  return hipGetLastError();
+  return launch_vec4<3, 3, true, GUIDE_NN, true, true>(a, geom_for(a), a.guide, s, gn, up);
+}
+
+// A fast shape whose geometry fits; `vec4`: ... and that the vec4 kernel serves (the fused forwards have no scalar twin).
+bool rows_supported(const ApplyArgs& a, bool vec4) {
+  if (!apply_fast_shape(a.Cin, a.Cout, a.has_offset)) return false;
+  // stage_row reads the grid as float4 when C % 4 == 0.
+  if ((a.Cout * a.Cj) % 4 == 0 && ((uintptr_t)a.grid & 15u)) return false;
+  const RowGeom g = geom_for(a);
+  return g.ok && (g.pl.vec4 || !vec4);
 }
 
 }  // namespace
@@ -307,8 +258,7 @@ bool apply_fwd_nnguide_supported(const ApplyArgs& a, const float* guide_out) {
   ApplyArgs t = a;
   t.guide = a.input;  // alignment check stand-in: no guide buffer is read
   if ((uintptr_t)guide_out & 15u) return false;
-  if (!apply_fwd_rows_supported(t)) return false;
-  return make_row_plan(t.W, t.GW, (((uintptr_t)t.input | (uintptr_t)t.out | (uintptr_t)t.grid) & 15u) == 0).vec4;
+  return rows_supported(t, true);
 }
 
 hipError_t launch_apply_fwd_nnguide(const ApplyArgs& a, const float* conv1, const float* conv2,
@@ -322,10 +272,11 @@ hipError_t launch_apply_fwd_nnguide(const ApplyArgs& a, const float* conv1, cons
   ApplyArgs t = a;
   t.guide = a.input;
   *name = "apply_fwd_rows/vec4+nnguide";
-  if (a.Cin == 3 && a.Cout == 3 && a.has_offset) return launch_nnguide_t<3, 3, true>(t, gn, s);
-  if (a.Cin == 3 && a.Cout == 3 && !a.has_offset) return launch_nnguide_t<3, 3, false>(t, gn, s);
-  if (a.Cin == 1 && a.Cout == 1 && a.has_offset) return launch_nnguide_t<1, 1, true>(t, gn, s);
-  if (a.Cin == 1 && a.Cout == 1 && !a.has_offset) return launch_nnguide_t<1, 1, false>(t, gn, s);
+  const RowGeom g = geom_for(t);
+  if (a.Cin == 3 && a.Cout == 3 && a.has_offset) return launch_vec4<3, 3, true, true>(t, g, nullptr, s, gn);
+  if (a.Cin == 3 && a.Cout == 3 && !a.has_offset) return launch_vec4<3, 3, false, true>(t, g, nullptr, s, gn);
+  if (a.Cin == 1 && a.Cout == 1 && a.has_offset) return launch_vec4<1, 1, true, true>(t, g, nullptr, s, gn);
+  if (a.Cin == 1 && a.Cout == 1 && !a.has_offset) return launch_vec4<1, 1, false, true>(t, g, nullptr, s, gn);
   return hipErrorInvalidValue;
 }
 
@@ -335,9 +286,7 @@ bool apply_fwd_upadd_supported(const ApplyArgs& a, const float* coarse, bool gui
   if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset) || ((uintptr_t)coarse & 3u)) return false;
   ApplyArgs t = a;
   if (guide_nn) t.guide = a.input;
-  if (!apply_fwd_rows_supported(t)) return false;
-  const bool aligned = (((uintptr_t)t.guide | (uintptr_t)t.input | (uintptr_t)t.out | (uintptr_t)t.grid) & 15u) == 0;
-  return make_row_plan(t.W, t.GW, aligned).vec4;
+  return rows_supported(t, true);
 }
 
 hipError_t launch_apply_fwd_upadd(const ApplyArgs& a, const float* coarse, int Hc, int Wc,
@@ -358,18 +307,7 @@ hipError_t launch_apply_fwd_upadd(const ApplyArgs& a, const float* coarse, int H
   return launch_upadd_t<false>(a, GuideNN{nullptr, nullptr, nullptr, 0}, coarse, Hc, Wc, s);
 }
 
-bool apply_fwd_rows_supported(const ApplyArgs& a) {
-  const bool shape = apply_fast_shape(a.Cin, a.Cout, a.has_offset);
-  if (!shape) return false;
-  // stage_row reads the grid as float4 when C % 4 == 0.
-  if ((a.Cout * a.Cj) % 4 == 0 && ((uintptr_t)a.grid & 15u)) return false;
-  if ((long long)a.B * a.H * ((a.W + 511) / 512) > 0x7fffffffLL) return false;
-  const Plan pl = make_row_plan(a.W, a.GW, true);
-  const size_t lds = ((size_t)pl.max_cols * a.GD * a.Cout * a.Cj + 4 +
-                      (size_t)(pl.threads / 64) * 64 * kPxPerThread * (a.Cin > a.Cout ? a.Cin : a.Cout)) *
-                     sizeof(float);
-  return lds <= kMaxLdsBytes;
-}
+bool apply_fwd_rows_supported(const ApplyArgs& a) { return rows_supported(a, false); }
 
 hipError_t launch_apply_fwd_rows(const ApplyArgs& a, hipStream_t s, const char** name) {
 #ifdef HDRNET_TOOLS_BUILD
@@ -396,18 +334,11 @@ hipError_t launch_apply_fwd_rows(const ApplyArgs& a, hipStream_t s, const char**
 // routes here): which = 0 per-lane stores, 1 = nontemporal lane-contiguous input loads.
 hipError_t launch_apply_fwd_rows_direct_stores(const ApplyArgs& a, hipStream_t s, const char** name, int which) {
   if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return hipErrorInvalidValue;
-  const LaunchGeom g = geom_for<12, 3>(a);
+  const RowGeom g = geom_for(a);
   if (!g.pl.vec4) return hipErrorInvalidValue;
-  if (which == 0)
-    apply_fwd_rows_vec4<3, 3, true, false, false><<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-        a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
-        (float)a.GW / a.W, (float)a.GH / a.H);
-  else
-    apply_fwd_rows_vec4<3, 3, true, false, true, false, true><<<(unsigned)g.nblocks, g.pl.threads, g.lds, s>>>(
-        a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
-        (float)a.GW / a.W, (float)a.GH / a.H);
   *name = which == 0 ? "apply_fwd_rows/vec4-direct-stores" : "apply_fwd_rows/vec4-nt-loads";
-  return hipGetLastError();
+  if (which == 0) return launch_vec4<3, 3, true, false, false>(a, g, a.guide, s);
+  return launch_vec4<3, 3, true, false, true, false, true>(a, g, a.guide, s);
 }
 
 #endif  // HDRNET_TOOLS_BUILD

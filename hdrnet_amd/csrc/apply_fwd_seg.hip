@@ -191,9 +191,7 @@ __device__ __forceinline__ void seg_task(const SegParams& p, float* __restrict__
   // CIN == COUT: a lane reads and writes only ITS slab entries -- in place, no cross-lane hazard;
   // otherwise the input reads of all lanes must precede the output writes below.
   if constexpr (LOADS != kLoadsLane && CIN != COUT) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   }
 
   float gs[4] = {g4.x, g4.y, g4.z, g4.w};
@@ -219,9 +217,7 @@ __device__ __forceinline__ void seg_task(const SegParams& p, float* __restrict__
 #pragma unroll
     for (int q = 0; q < COUT; ++q) slab[lane * COUT + q] = ov[q];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 
   // Store phase: lane l stores float4 number l + 64 k of the wave's output run -- every store
   // instruction covers one dense 1 KiB (per-lane 16-B stores at a 16*COUT-byte stride cost 6.5 us
@@ -244,29 +240,10 @@ __global__ __launch_bounds__(256) void apply_fwd_seg(const SegParams p) {
   seg_task<CIN, COUT, OFFSET, LOADS, STORES, GUIDE_NN, UPADD, PIX>(p, lds, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
-struct SegGeom {
-  Plan pl;
-  int max_cols, slab_off;
-  size_t lds;
-  bool ok;
-};
-
-constexpr size_t kMaxLdsBytes = 64 * 1024;  // keep >= 2 workgroups per CU
-
-SegGeom seg_geom(const ApplyArgs& a, bool dma, bool guide_map = true) {
-  const int C = a.Cout * a.Cj;
-  SegGeom g{};
-  const bool aligned = (((guide_map ? (uintptr_t)a.guide : 0) | (uintptr_t)a.input | (uintptr_t)a.out |
-                         (uintptr_t)a.grid) & 15u) == 0;
-  g.pl = make_row_plan(a.W, a.GW, aligned);
-  g.max_cols = (int)(((long long)(g.pl.seg - 1) * a.GW) / a.W + 4);
-  g.slab_off = round_up(g.max_cols * (a.GD + 2) * C, 4);
-  const int slabw = 64 * kPxPerThread * (a.Cin > a.Cout ? a.Cin : a.Cout) + ((dma && guide_map) ? 64 * kPxPerThread : 0);
-  g.lds = ((size_t)g.slab_off + (size_t)(g.pl.threads / 64) * slabw) * sizeof(float);
-  const long long nstage = (long long)g.max_cols * a.GD * C;
-  g.ok = g.pl.vec4 && g.lds <= kMaxLdsBytes && nstage < (1 << 20) && a.B <= 65535 && a.H <= 65535 &&
-         (long long)a.W * a.Cout * 4 < (1LL << 31);
-  return g;
+// Launch geometry (row_geom.h); without a guide map no guide buffer is read, so none has to be aligned.
+RowGeom seg_geom(const ApplyArgs& a, bool dma, bool guide_map = true) {
+  return seg_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cin, a.Cout, a.Cj, dma, guide_map,
+                      ptr_bits(guide_map ? a.guide : nullptr, a.input, a.out, a.grid));
 }
 
 // RESIDENT-WAVE CAP (round 4).  The kernel needs only ~40 KB of loads in flight per CU to saturate its share of the HBM
@@ -297,7 +274,7 @@ hipError_t launch_seg_t(const ApplyArgs& a, hipStream_t s, const GuideNN& gn = G
                         const UpAdd& up = UpAdd{nullptr, 0, 0, 0.f, 0.f}) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   constexpr int VEC = (C % 4 == 0) ? 4 : 1;
-  SegGeom g = seg_geom(a, LOADS == kLoadsBufDmaNt, !GUIDE_NN);
+  RowGeom g = seg_geom(a, LOADS == kLoadsBufDmaNt, !GUIDE_NN);
   if (!g.ok) return hipErrorNotSupported;
   // (not for the per-lane-load flavour, which serves grids of about ONE round of workgroups -- a single 1080p frame:
   //  there every resident slot counts, 11.7 us uncapped / 12.0 at 7 workgroups per CU / 13.1 at 6;
@@ -350,7 +327,7 @@ bool apply_fwd_seg_supported(const ApplyArgs& a) {
 // The per-launch flavour choice for one shape (PIX: the pixel phase, DMAL: the DMA form).
 template <int CI, int CO, bool OFF, int PIX, int DMAL>
 hipError_t launch_seg_pick(const ApplyArgs& a, hipStream_t s) {
-  const SegGeom g = seg_geom(a, true);
+  const RowGeom g = seg_geom(a, true);
   const long long nblocks = (long long)g.pl.nseg * a.H * a.B;
   const long long one_round = (long long)num_cus() * (32 / (g.pl.threads / 64));  // workgroups resident at once
   const bool small = 4 * nblocks <= 5 * one_round;

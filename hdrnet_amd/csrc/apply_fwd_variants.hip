@@ -231,7 +231,7 @@ hipError_t launch_multiquad(const ApplyArgs& a, hipStream_t s, const char** name
   const int max_cols = max_cols_for(seg, a.GW, a.W);
   const int slab_off = round_up(max_cols * a.GD * 12, 4);
   const size_t lds = ((size_t)slab_off + (size_t)(threads / 64) * 64 * kPxPerThread * 3) * sizeof(float);
-  if (lds > 64 * 1024) return hipErrorNotSupported;
+  if (!lds_fits(lds)) return hipErrorNotSupported;
   const long long nblocks = (long long)a.B * a.H * best_nseg;
   apply_fwd_rows_multiquad<3, 3, true, Q><<<(unsigned)nblocks, threads, lds, s>>>(
       a.grid, a.guide, a.input, a.out, a.H, a.W, a.GH, a.GW, a.GD, best_nseg, seg, slab_off,
@@ -520,8 +520,7 @@ hipError_t launch_variant_t(const ApplyArgs& a, const Plan& pl, hipStream_t s, c
     // One wavefront per tile of <= 256 pixels, balanced over the row.
     const int tiles_per_row = (a.W + 64 * kPxPerThread - 1) / (64 * kPxPerThread);
     const int tile_w = round_up((a.W + tiles_per_row - 1) / tiles_per_row, 4);
-    const long long ncol = ((long long)(tile_w - 1) * a.GW) / a.W + 4;
-    const int cols = (int)(ncol < a.GW ? ncol : a.GW);
+    const int cols = max_cols_for(tile_w, a.GW, a.W);
     const int lds_floats = round_up(cols * a.GD * C, 4);
     const long long ntiles = (long long)a.B * a.H * tiles_per_row;
     const int waves = 4;
@@ -587,8 +586,7 @@ hipError_t launch_variant_t(const ApplyArgs& a, const Plan& pl, hipStream_t s, c
       }
       case 107: {
         // LDS per workgroup as the product kernel's: padded image + one (guide + in / out) slab per wave
-        const size_t lds = ((size_t)round_up(((pl.seg - 1) * a.GW / a.W + 4) * (a.GD + 2) * C, 4) +
-                            (size_t)(pl.threads / 64) * 64 * kPxPerThread * 4) * sizeof(float);
+        const size_t lds = seg_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, CIN, COUT, CIN + 1, true, true, 0).lds;
         apply_fwd_empty<<<nblocks, pl.threads, lds, s>>>(a.out);
         *name = "ABLATION/empty launch, product geometry";
         return hipGetLastError();

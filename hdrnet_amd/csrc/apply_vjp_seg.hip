@@ -271,9 +271,7 @@ __global__ __launch_bounds__(256) void apply_vjp_seg(const VjpSegParams p) {
     }
   }
   if constexpr (WANT_INPUT) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const __amdgpu_buffer_rsrc_t orsrc = make_rsrc_uniform(p.dinput + (row * p.W + xs) * CIN, (unsigned)(xe - xs) * CIN * 4u);
 #pragma unroll
     for (int k = 0; k < CIN; ++k)
@@ -281,31 +279,14 @@ __global__ __launch_bounds__(256) void apply_vjp_seg(const VjpSegParams p) {
   }
 }
 
-constexpr size_t kMaxLdsBytes = 64 * 1024;
-
-struct VjpGeom {
-  Plan pl;
-  int slab_off;
-  size_t lds;
-  bool ok;
-};
-
-VjpGeom vjp_geom(const ApplyGradArgs& a) {
-  const int C = a.Cout * a.Cj;
-  VjpGeom g{};
-  const bool aligned = (((uintptr_t)a.guide | (uintptr_t)a.input | (uintptr_t)a.dout | (uintptr_t)a.grid |
-                         (uintptr_t)a.dguide | (uintptr_t)a.dinput) & 15u) == 0;
-  g.pl = make_row_plan(a.W, a.GW, aligned);
-  const int max_cols = (int)(((long long)(g.pl.seg - 1) * a.GW) / a.W + 4);
-  g.slab_off = round_up(max_cols * (a.GD + 2) * C, 4);
-  g.lds = ((size_t)g.slab_off + (size_t)(g.pl.threads / 64) * 64 * kPxPerThread * (1 + a.Cin + a.Cout)) * sizeof(float);
-  g.ok = g.pl.vec4 && g.lds <= kMaxLdsBytes && (long long)max_cols * a.GD * C < (1 << 20) && a.B <= 65535 &&
-         a.H <= 65535 && (long long)a.W * (a.Cin > a.Cout ? a.Cin : a.Cout) * 4 < (1LL << 31);
-  return g;
+// Launch geometry (row_geom.h).
+RowGeom vjp_geom(const ApplyGradArgs& a) {
+  return vjp_seg_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cin, a.Cout, a.Cj,
+                      ptr_bits(a.guide, a.input, a.dout, a.grid, a.dguide, a.dinput));
 }
 
 template <int CIN, int COUT, bool OFFSET, bool WG, bool WI>
-hipError_t launch_t(const ApplyGradArgs& a, const VjpGeom& g, hipStream_t s) {
+hipError_t launch_t(const ApplyGradArgs& a, const RowGeom& g, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   constexpr int VEC = (C % 4 == 0) ? 4 : 1;
   VjpSegParams p{a.grid, a.guide, a.input, a.dout, a.dguide, a.dinput, a.H, a.W, a.GH, a.GW, a.GD,
@@ -316,7 +297,7 @@ hipError_t launch_t(const ApplyGradArgs& a, const VjpGeom& g, hipStream_t s) {
 }
 
 template <int CIN, int COUT, bool OFFSET>
-hipError_t launch_want(const ApplyGradArgs& a, const VjpGeom& g, hipStream_t s) {
+hipError_t launch_want(const ApplyGradArgs& a, const RowGeom& g, hipStream_t s) {
   const bool wg = a.dguide != nullptr, wi = a.dinput != nullptr;
   if (wg && wi) return launch_t<CIN, COUT, OFFSET, true, true>(a, g, s);
   if (wg) return launch_t<CIN, COUT, OFFSET, true, false>(a, g, s);
@@ -334,7 +315,7 @@ bool apply_vjp_seg_supported(const ApplyGradArgs& a) {
 }
 
 hipError_t launch_apply_vjp_seg(const ApplyGradArgs& a, hipStream_t s, const char** name) {
-  const VjpGeom g = vjp_geom(a);
+  const RowGeom g = vjp_geom(a);
   if (!g.ok) return hipErrorNotSupported;
   *name = "apply_vjp_seg/vec4";
 #define HDRNET_CASE(CI, CO, OFF) \

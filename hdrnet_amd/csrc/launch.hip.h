@@ -122,7 +122,8 @@ inline bool apply_fast_shape(int Cin, int Cout, bool has_offset) {
   return false;
 }
 
-// The grid channel counts the fast BilateralSlice gradients specialise (apply_bwd_rows / grid_grad_mfma).  X(C).
+// The grid channel counts the fast BilateralSlice paths specialise -- ONE table for the forward (slice_fwd_rows) and the
+// gradients (apply_bwd_rows / grid_grad_mfma).  X(C).
 #define HDRNET_SLICE_FAST_CHANNELS(X) X(1) X(2) X(4) X(8) X(12) X(16)
 
 inline bool slice_fast_channels(int C) {
@@ -142,6 +143,10 @@ hipError_t launch_apply_grad_generic(const ApplyGradArgs& a, hipStream_t s);
 hipError_t launch_slice_fwd_generic(const SliceArgs& a, hipStream_t s);
 hipError_t launch_slice_grad_generic(const ApplyGradArgs& a, hipStream_t s);  // a.slice
 
+// The row-segment families below (apply_fwd_rows / _seg / _io, apply_bwd_rows, apply_vjp_seg, slice_fwd_rows) take their
+// launch geometry -- row plan, LDS layout and bytes, limits -- from row_geom.h: a `*_supported` predicate and its
+// launcher read the same result.
+//
 // apply_fwd_rows.hip -- LDS-staged row-segment forward.  `*_supported` says whether a
 // specialisation exists for the shape; `name` receives a static string naming
 // the variant launched.

@@ -220,7 +220,7 @@ extern "C" int hdrnet_tools_pyramid_onepass_f32(const float* const grids[3], con
   p.inv_col = 1.0f / (float)(GD * (kC / 4));
   p.grid_image = GH * GW * GD * kC;
   const size_t lds_bytes = sizeof(float) * ((size_t)kLvRows * p.img_floats + (size_t)kLvRows * 3 * (p.pitch1 + p.pitch2));
-  if (lds_bytes > 64 * 1024) return HDRNET_INVALID_ARGUMENT;
+  if (!rows::lds_fits(lds_bytes)) return HDRNET_INVALID_ARGUMENT;
   const dim3 nblocks((unsigned)((W + seg - 1) / seg), (unsigned)(H / kR), (unsigned)B);
   hipLaunchKernelGGL(pyramid_onepass_kernel, nblocks, dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), p);
   return hipGetLastError() == hipSuccess ? HDRNET_OK : HDRNET_RUNTIME_FAILURE;

@@ -7,11 +7,10 @@
 #include <hip/hip_runtime.h>
 
 #include "numerics.hip.h"
+#include "row_geom.h"
 
 namespace hdrnet_amd {
 namespace rows {
-
-constexpr int kPxPerThread = 4;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -50,6 +49,14 @@ __device__ __forceinline__ void accum_vec(CoefVec<C>& coef, const float* __restr
     for (int q = 0; q < C; ++q)
       coef.v[q >> 1][q & 1] = FIRST ? w * p[q] : fmaf(w, p[q], coef.v[q >> 1][q & 1]);
   }
+}
+
+// Hand LDS data over between the lanes of ONE wavefront: what a lane wrote before is visible to every lane after.
+// No s_barrier: waves never wait for each other.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct RowCtx {
@@ -103,9 +110,7 @@ __device__ __forceinline__ RowCtx stage_row(float* __restrict__ colY,
     for (int e = e0; e < n; e += estep) colY[e] = wy0 * r0[e] + wy1 * r1[e];
   }
   if constexpr (WAVE) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
   } else {
     __syncthreads();
   }
@@ -340,14 +345,24 @@ __device__ __forceinline__ float4 load_stream4(const float* __restrict__ p) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// Upper bound of grid columns `npx` consecutive pixels can touch: floor differences of gx0
-// over npx-1 pixels (<= floor(d)+1), +1 for the upper neighbour, +1 for the count, +1
-// slack for float rounding of the coordinates; never more than GW.
-inline int max_cols_for(int npx, int GW, int W) {
-  const long long cols = ((long long)(npx - 1) * GW) / W + 4;
-  return (int)(cols < GW ? cols : GW);
+// The store epilogue of a wave that has transposed its CH-float-per-pixel run through its LDS slab: lane l stores float4
+// number l + 64 k of the run, so that every store instruction covers one dense 1 KiB.  Two forms of the descriptor:
+// over exactly the wave's run of `run_px` pixels at `run` (<= 0: an idle wave) ...
+template <int CH, int AUX = kAuxStream>
+__device__ __forceinline__ void store_slab_run(float4* slab, float* run, int run_px, int lane) {
+  const int nvalid = run_px * CH / 4;  // float4s
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc_uniform(run, nvalid > 0 ? (unsigned)nvalid * 16u : 0u);
+#pragma unroll
+  for (int k = 0; k < CH; ++k) buf_store16<AUX>(slab[lane + 64 * k], rs, (unsigned)(lane + 64 * k) * 16u);
+}
+// ... or over the row segment of `seg_px` pixels at `seg`, the wave's run starting at pixel `wpx` of it.  (apply_fwd_seg.hip
+// and apply_vjp_seg.hip keep this loop written out: through the helper the compiler schedules those two differently.)
+template <int CH, int AUX = kAuxStream>
+__device__ __forceinline__ void store_slab_seg(float4* slab, float* seg, unsigned seg_px, unsigned wpx, int lane) {
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc_uniform(seg, seg_px * CH * 4u);
+#pragma unroll
+  for (int k = 0; k < CH; ++k)
+    buf_store16<AUX>(slab[lane + 64 * k], rs, (wpx * CH + 4u * (unsigned)(lane + 64 * k)) * 4u);
 }
 
 // ---- fused guide network / pyramid up-add (shared by apply_fwd_seg.hip and apply_fwd_rows.hip) ----
@@ -515,39 +530,6 @@ __device__ __forceinline__ void upadd_quad(const UpAdd& up, int b, int y, int x,
   }
 }
 
-
-// How a row is cut into workgroup segments: `threads` lanes x 4 pixels per segment, the
-// segment width balanced over the row (e.g. W = 3840 -> 5 segments of 768 px / 192 threads;
-// W = 1920 -> 2 x 960 px / 256 threads with 16 idle lanes).
-struct Plan {
-  int threads, nseg, seg, max_cols;
-  bool vec4;  // 16-B accesses usable: W % 4 == 0 and 16-B aligned buffers
-};
-
-inline Plan make_row_plan(int W, int GW, bool aligned16) {
-  Plan best{};
-  long long best_waste = -1;
-  const int cands[3] = {256, 192, 128};
-  for (int T : cands) {
-    const int span = T * kPxPerThread;
-    const int nseg = (W + span - 1) / span;
-    const long long waste = (long long)nseg * span - W;
-    if (best_waste < 0 || waste < best_waste) {
-      best_waste = waste;
-      best.threads = T;
-      best.nseg = nseg;
-    }
-  }
-  best.vec4 = aligned16 && (W % 4 == 0);
-  best.seg = round_up((W + best.nseg - 1) / best.nseg, 4);
-  // (Round 4: rounding the segments to 32-px multiples -- W = 4000 as 1024 / 1024 / 1024 / 928 instead of 4 x 1000,
-  // so that every output run is whole 128-B lines and the forward may store write-through -- measured 61.3 vs
-  // 60.7 us at 4000 x 3000, interleaved, the memory skeleton at 61.0: no gain, not kept.  profiles/r04/fwd_launch_shape.md)
-  best.threads = round_up((best.seg + kPxPerThread - 1) / kPxPerThread, 64);
-  if (best.threads > 256) best.threads = 256;
-  best.max_cols = max_cols_for(best.seg, GW, W);
-  return best;
-}
 
 // Compute units of the current device (cached per device ordinal; benign race).
 inline int num_cus() {

@@ -75,9 +75,7 @@ __global__ __launch_bounds__(256) void slice_fwd_rows(
         for (int c = 0; c < C; ++c) sf[lane * C + c] = coef.get(c);
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // nontemporal buffer stores on a descriptor over exactly this run (rows_common.hip.h)
     // (the descriptor ends at the run's last float: the bounds check is per dword, so a final
     //  partial float4 -- possible for C < 4 -- is written up to the run's end and no further)
@@ -94,52 +92,32 @@ __global__ __launch_bounds__(256) void slice_fwd_rows(
   }
 }
 
-constexpr size_t kMaxLdsBytes = 64 * 1024;
-
-bool plan_for(const SliceArgs& a, Plan* pl, size_t* lds, int* slab_off) {
-  const bool aligned = (((uintptr_t)a.grid | (uintptr_t)a.out) & 15u) == 0;
-  if (!aligned) return false;
-  *pl = make_row_plan(a.W, a.GW, true);
-  pl->vec4 = true;  // guide is read per pixel; only grid / out need 16-B alignment
-  if ((long long)a.B * a.H * pl->nseg > 0x7fffffffLL) return false;
-  *slab_off = round_up(pl->max_cols * a.GD * a.C, 4);
-  *lds = ((size_t)*slab_off + (size_t)(pl->threads / 64) * 64 * a.C) * sizeof(float);
-  return *lds <= kMaxLdsBytes;
+// Launch geometry (row_geom.h): the guide is read per pixel; only grid / out need 16-B alignment.
+RowGeom plan_for(const SliceArgs& a) {
+  return slice_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.C, ptr_bits(a.grid, a.out));
 }
 
 template <int C>
-hipError_t launch_c(const SliceArgs& a, const Plan& pl, size_t lds, int slab_off, hipStream_t s) {
-  const long long nblocks = (long long)a.B * a.H * pl.nseg;
-  slice_fwd_rows<C><<<(unsigned)nblocks, pl.threads, lds, s>>>(
-      a.grid, a.guide, a.out, a.H, a.W, a.GH, a.GW, a.GD, pl.nseg, pl.seg, slab_off,
+hipError_t launch_c(const SliceArgs& a, const RowGeom& g, hipStream_t s) {
+  const long long nblocks = (long long)a.B * a.H * g.pl.nseg;
+  slice_fwd_rows<C><<<(unsigned)nblocks, g.pl.threads, g.lds, s>>>(
+      a.grid, a.guide, a.out, a.H, a.W, a.GH, a.GW, a.GD, g.pl.nseg, g.pl.seg, g.slab_off,
       (float)a.GW / a.W, (float)a.GH / a.H);
   return hipGetLastError();
 }
 
 }  // namespace
 
-bool slice_fwd_rows_supported(const SliceArgs& a) {
-  if (!(a.C == 1 || a.C == 2 || a.C == 4 || a.C == 8 || a.C == 12 || a.C == 16)) return false;
-  Plan pl;
-  size_t lds;
-  int so;
-  return plan_for(a, &pl, &lds, &so);
-}
+bool slice_fwd_rows_supported(const SliceArgs& a) { return slice_fast_channels(a.C) && plan_for(a).ok; }
 
 hipError_t launch_slice_fwd_rows(const SliceArgs& a, hipStream_t s, const char** name) {
-  Plan pl;
-  size_t lds;
-  int so;
-  if (!plan_for(a, &pl, &lds, &so)) return hipErrorInvalidValue;
+  const RowGeom g = plan_for(a);
+  if (!g.ok) return hipErrorInvalidValue;
   *name = "slice_fwd_rows";
-  switch (a.C) {
-    case 1: return launch_c<1>(a, pl, lds, so, s);
-    case 2: return launch_c<2>(a, pl, lds, so, s);
-    case 4: return launch_c<4>(a, pl, lds, so, s);
-    case 8: return launch_c<8>(a, pl, lds, so, s);
-    case 12: return launch_c<12>(a, pl, lds, so, s);
-    case 16: return launch_c<16>(a, pl, lds, so, s);
-  }
+#define HDRNET_CASE(CC) \
+  if (a.C == CC) return launch_c<CC>(a, g, s);
+  HDRNET_SLICE_FAST_CHANNELS(HDRNET_CASE)
+#undef HDRNET_CASE
   return hipErrorInvalidValue;
 }
 

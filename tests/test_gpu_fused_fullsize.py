@@ -2,7 +2,7 @@
 size and at the edges of the row plan (tests/test_gpu_parity.py checks them at toy sizes only).
 
 * Frame size, 1 x 2160 x 3840 and 1 x 1080 x 1920, grid 16 x 16 x 8 x 12: rows of five / two workgroup segments
-  (rows_common.hip.h: make_row_plan), so every segment's column window, the u8 stores beside idle lanes and the
+  (row_geom.h: make_row_plan), so every segment's column window, the u8 stores beside idle lanes and the
   descriptor-bounded f32 stores are compared with something.  Each family is also called once through its C-ABI entry
   point with a POISONED output (NaN for f32; 0x00 and 0xFF for u8, which must give the same bytes): the Python
   wrappers allocate with torch.empty, so an element the kernel never writes would otherwise go unseen.
@@ -24,6 +24,7 @@ torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402
 from conftest import check_dgrid, check_pixel_grad  # noqa: E402
+from row_plan import io_fits, row_plan, rows_fits, seg_fits  # noqa: E402
 
 FWD_TOL = 1e-5
 NN_GUIDE_TOL = 1e-6
@@ -120,46 +121,6 @@ def u8_close(name, got, want_f, clip_ends=True, count=True):
     assert frac < 5e-4 or not count, name
     if clip_ends:
         assert got.min() == 0 and got.max() == 255, name  # the clip is exercised on both sides
-
-
-# ---- the row plan, restated (rows_common.hip.h: make_row_plan; apply_fwd_seg.hip: seg_geom; apply_fwd_rows.hip:
-# apply_fwd_rows_supported; apply_fwd_io.hip: plan_io) for Cin = Cout = 3 with offset (C = 12) ----------------------
-def _rup(v, m):
-    return (v + m - 1) // m * m
-
-
-def row_plan(W):
-    best = None
-    for threads in (256, 192, 128):
-        nseg = -(-W // (4 * threads))
-        waste = nseg * 4 * threads - W
-        if best is None or waste < best[0]:
-            best = (waste, nseg)
-    nseg = best[1]
-    seg = _rup(-(-W // nseg), 4)
-    return min(_rup(-(-seg // 4), 64), 256), nseg, seg
-
-
-def seg_fits(W, GW, GD, guide_map):
-    """seg_geom(dma = true, guide_map).ok: (GD + 2) planes of the window's columns + the per-wave slabs in 64 KiB."""
-    threads, _, seg = row_plan(W)
-    cols = (seg - 1) * GW // W + 4
-    slabw = 256 * 3 + (256 if guide_map else 0)
-    return (_rup(cols * (GD + 2) * 12, 4) + threads // 64 * slabw) * 4 <= 65536
-
-
-def rows_fits(W, GW, GD):
-    """apply_fwd_rows_supported: GD planes of at most GW columns + the per-wave slabs in 64 KiB."""
-    threads, _, seg = row_plan(W)
-    cols = min((seg - 1) * GW // W + 4, GW)
-    return (cols * GD * 12 + 4 + threads // 64 * 256 * 3) * 4 <= 65536
-
-
-def io_fits(W, GW, GD):
-    """plan_io: the curves kernel's static tables (768 floats) + (GD + 2) planes + the per-wave slabs in 64 KiB."""
-    threads, _, seg = row_plan(W)
-    cols = (seg - 1) * GW // W + 4
-    return (768 + _rup(cols * (GD + 2) * 12, 4) + threads // 64 * 256 * 3) * 4 <= 65536
 
 
 # ---- the C-ABI entry points, called with caller-owned (poisoned) outputs -------------------------------------------
