@@ -100,6 +100,25 @@ class CoeffNetGrads(ctypes.Structure):
                 ("pred_w", _VP), ("pred_b", _VP)]
 
 
+class CoeffNetBn(ctypes.Structure):
+    """``hdrnet_coeff_net_bn`` of include/hdrnet_amd_coeff_bn.h: the network description (its ``net`` member, spelled out:
+    the same memory) and, per normalised layer, beta and the running statistics."""
+
+    _fields_ = CoeffNet._fields_ + [
+        ("splat_beta", _VP * 8), ("splat_running_mean", _VP * 8), ("splat_running_var", _VP * 8),
+        ("global_conv_beta", _VP * 2), ("global_conv_running_mean", _VP * 2), ("global_conv_running_var", _VP * 2),
+        ("fc_beta", _VP * 2), ("fc_running_mean", _VP * 2), ("fc_running_var", _VP * 2),
+        ("local_beta", _VP), ("local_running_mean", _VP), ("local_running_var", _VP),
+        ("eps", ctypes.c_float), ("momentum", ctypes.c_float)]
+
+
+class CoeffNetBnGrads(ctypes.Structure):
+    """``hdrnet_coeff_net_bn_grads``: ``hdrnet_coeff_net_grads`` (spelled out) and where the gradients of beta go."""
+
+    _fields_ = CoeffNetGrads._fields_ + [("splat_beta", _VP * 8), ("global_conv_beta", _VP * 2), ("fc_beta", _VP * 2),
+                                         ("local_beta", _VP)]
+
+
 class HdrnetLibraryError(RuntimeError):
     """libhdrnet_amd.so is missing, failed to build, or failed to load."""
 
@@ -125,6 +144,14 @@ TRAIN_SIGNATURES = {
     "hdrnet_prepare_batch": (_I, [_FP, _I, ctypes.c_float] * 2 + [_I] * 3 + [_FP, _I, _FP, _FP, _I, _I, _FP, _I, _U, _VP]),
     "hdrnet_prepare_batch_ragged": (_I, [_FP, _I, ctypes.c_float] * 2 + [ctypes.c_longlong, _FP, _I] +
                                     [_FP, _I, _FP, _FP, _I, _I, _FP, _I, _U, _VP]),
+}
+
+# include/hdrnet_amd_coeff_bn.h (included by hdrnet_amd_train.h): the coefficient network trained with batch norm.
+COEFF_BN_SIGNATURES = {
+    "hdrnet_coefficients_bn_workspace_bytes": (_SZ, [_VP, _I]),
+    "hdrnet_coefficients_bn_train_f32": (_I, [_FP, _VP, _FP, _I, _VP, _SZ, _VP]),
+    "hdrnet_coefficients_bn_grad_workspace_bytes": (_SZ, [_VP, _I]),
+    "hdrnet_coefficients_bn_grad_f32": (_I, [_FP, _VP, _VP, _FP, _VP, _I, _VP, _SZ, _VP]),
 }
 
 _lock = threading.Lock()
@@ -177,6 +204,7 @@ def _open(tools: bool) -> ctypes.CDLL:
         raise HdrnetLibraryError(f"cannot load {path}: {e}") from e
     table = dict(SIGNATURES)
     table.update(TRAIN_SIGNATURES)
+    table.update(COEFF_BN_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

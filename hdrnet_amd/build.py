@@ -46,6 +46,7 @@ SOURCES = [
     ("resize_bilinear.hip", []),
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
+    ("coeff_net_bn.hip", []),
     ("metrics.hip", []),
     ("loss_psnr.hip", []),
     ("sample_prep.hip", []),
@@ -98,7 +99,8 @@ def _usable_flags(cc: str, extra: List[str]) -> List[str]:
 
 
 def _deps() -> List[str]:
-    out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"), os.path.abspath(__file__)]
+    out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):
             out.append(os.path.join(CSRC, f))

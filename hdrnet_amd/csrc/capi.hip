@@ -153,6 +153,38 @@ bool coeff_net_null_param(const hdrnet_coeff_net& net, const hdrnet_coeff_net_gr
   return scan(net) || (grads && scan(*grads));
 }
 
+// the batch-norm description: why a call cannot run (null: it can).  `grads`: also check where the gradients go.
+const char* coeff_net_bn_refusal(const hdrnet_coeff_net_bn& bn, const hdrnet_coeff_net_bn_grads* grads, int B) {
+  using namespace hdrnet_amd;
+  const hdrnet_coeff_net& net = bn.net;
+  if (coefficients_bn_workspace_bytes(net, B) == 0 || coefficients_bn_grad_workspace_bytes(net, B) == 0)
+    return "unsupported (needs what hdrnet_coefficients_grad_f32 supports, 2 <= B <= 8, n_levels = 1, fc_layout = 1)";
+  int n_ds = 0;
+  for (int v = net.net_input_size / net.spatial_bin; v > 1; v >>= 1) ++n_ds;
+  bool null_param = !net.pred_w || !net.pred_b || !net.local_w[0] || !net.local_w[1] || !net.splat_b[0] || !net.fc_b[2];
+  for (int i = 0; i < n_ds; ++i) null_param = null_param || !net.splat_w[i];
+  for (int i = 0; i < 2; ++i) null_param = null_param || !net.global_conv_w[i];
+  for (int i = 0; i < 3; ++i) null_param = null_param || !net.fc_w[i];
+  if (null_param) return "null parameter";
+  bool null_bn = !bn.local_beta || !bn.local_running_mean || !bn.local_running_var;
+  for (int i = 1; i < n_ds; ++i)
+    null_bn = null_bn || !bn.splat_beta[i] || !bn.splat_running_mean[i] || !bn.splat_running_var[i];
+  for (int i = 0; i < 2; ++i)
+    null_bn = null_bn || !bn.global_conv_beta[i] || !bn.global_conv_running_mean[i] || !bn.global_conv_running_var[i] ||
+              !bn.fc_beta[i] || !bn.fc_running_mean[i] || !bn.fc_running_var[i];
+  if (null_bn) return "null beta, running_mean or running_var of a normalised layer";
+  if (!(bn.eps > 0.0f) || !(bn.momentum >= 0.0f && bn.momentum <= 1.0f)) return "eps must be positive and momentum in [0, 1]";
+  if (grads) {
+    const hdrnet_coeff_net_grads& g = grads->net;
+    bool null_grad = !g.pred_w || !g.pred_b || !g.local_w[0] || !g.local_w[1] || !g.splat_b[0] || !g.fc_b[2] || !grads->local_beta;
+    for (int i = 0; i < n_ds; ++i) null_grad = null_grad || !g.splat_w[i] || (i > 0 && !grads->splat_beta[i]);
+    for (int i = 0; i < 2; ++i) null_grad = null_grad || !g.global_conv_w[i] || !grads->global_conv_beta[i] || !grads->fc_beta[i];
+    for (int i = 0; i < 3; ++i) null_grad = null_grad || !g.fc_w[i];
+    if (null_grad) return "null gradient";
+  }
+  return nullptr;
+}
+
 int check_flags(unsigned flags) {
   if ((flags & 0xffu) > HDRNET_KERNEL_FAST || (flags >> 16) != 0)
     return fail(HDRNET_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
@@ -239,7 +271,7 @@ extern "C" {
 // 0.2.8.1: the training-loop entry points of include/hdrnet_amd_train.h set / clear hdrnet_last_error() like the rest
 // 0.2.8.2: the coefficient network's entry points refuse widths their kernels cannot run (workspace queries return 0
 //          where 281 returned a size: include/hdrnet_amd.h)
-int hdrnet_version(void) { return 282; }
+int hdrnet_version(void) { return 283; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -649,6 +681,52 @@ int hdrnet_coefficients_grad_f32(const float* lowres, const hdrnet_coeff_net* ne
   const hipError_t e = launch_coefficients_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
                                                 static_cast<hipStream_t>(stream), &name);
   return finish_launch(e, "CoefficientsGrad", name);
+}
+
+size_t hdrnet_coefficients_bn_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
+  if (!net || B <= 0) return 0;
+  return hdrnet_amd::coefficients_bn_workspace_bytes(net->net, B);
+}
+
+int hdrnet_coefficients_bn_train_f32(const float* lowres, const hdrnet_coeff_net_bn* net, float* coeffs, int B,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace hdrnet_amd;
+  constexpr const char* kFn = "hdrnet_coefficients_bn_train_f32";
+  if (!net) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
+  if (const char* why = coeff_net_bn_refusal(*net, nullptr, B))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
+                net->net.fc_layout);
+  if (!lowres || !coeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
+  const size_t need = coefficients_bn_workspace_bytes(net->net, B);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of hdrnet_coefficients_bn_workspace_bytes() = "
+                                         "%zu bytes", kFn, need);
+  // (no kernel name recorded: the training-loop helpers leave hdrnet_last_kernel() alone)
+  return finish_launch(launch_coefficients_bn(lowres, *net, coeffs, B, workspace, static_cast<hipStream_t>(stream)), kFn,
+                       nullptr);
+}
+
+size_t hdrnet_coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
+  if (!net || B <= 0) return 0;
+  return hdrnet_amd::coefficients_bn_grad_workspace_bytes(net->net, B);
+}
+
+int hdrnet_coefficients_bn_grad_f32(const float* lowres, const hdrnet_coeff_net_bn* net, const void* forward_workspace,
+                                    const float* dcoeffs, const hdrnet_coeff_net_bn_grads* grads, int B, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  using namespace hdrnet_amd;
+  constexpr const char* kFn = "hdrnet_coefficients_bn_grad_f32";
+  if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
+  if (const char* why = coeff_net_bn_refusal(*net, grads, B))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
+                net->net.fc_layout);
+  if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
+  const size_t need = coefficients_bn_grad_workspace_bytes(net->net, B);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of "
+                                         "hdrnet_coefficients_bn_grad_workspace_bytes() = %zu bytes", kFn, need);
+  return finish_launch(launch_coefficients_bn_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
+                                                   static_cast<hipStream_t>(stream)), kFn, nullptr);
 }
 
 int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,

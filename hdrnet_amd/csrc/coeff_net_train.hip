@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coeff_net.hip.h"
+#include "coeff_net_bn.hip.h"
 #include "launch.hip.h"
 
 namespace hdrnet_amd {
@@ -1258,6 +1259,155 @@ hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net&
     }
   }
   // ---- the chunks' partial sums of every weight / bias gradient
+  coeff_reduce_parts<<<dim3((unsigned)tab.first[tab.count]), 256, 0, s>>>(tab);
+  return hipGetLastError();
+}
+
+// ---- with batch norm (coeff_net_bn.hip): every normalised layer's gradient of y becomes the gradient of its raw output
+// z, in place, before the layer's own backward launches read it -- those then run without ReLU mask and without a bias
+// gradient (dy = dz, ymask = NULL), and coeff_recompute reads fc1 / fc2's materialised outputs as one partial sum each.
+
+namespace {
+
+struct BnBwdSpace {  // float offsets behind bwd_space's
+  size_t db_scratch, part, total;
+};
+
+BnBwdSpace bn_bwd_space(const NetDims& d, const BwdSpace& bs) {
+  BnBwdSpace w{};
+  size_t off = bs.total;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
+  w.db_scratch = take((size_t)4 * d.gl);  // where coeff_fc_bwd leaves the "bias gradient" of a layer without bias
+  w.part = take(2 * bn_part_doubles(bn_max_channels(d)));
+  w.total = off;
+  return w;
+}
+
+}  // namespace
+
+size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B) {
+  NetDims d;
+  if (B < 2 || !train_supported(net, B, &d)) return 0;
+  return bn_bwd_space(d, bwd_space(d, net, B)).total * sizeof(float);
+}
+
+hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_net_bn& bn,
+                                       const hdrnet_coeff_net_bn_grads& grads, const float* dcoeffs, int B,
+                                       const void* fwd_ws, void* workspace, hipStream_t s) {
+  const hdrnet_coeff_net& net = bn.net;
+  const hdrnet_coeff_net_grads& gr = grads.net;
+  NetDims d;
+  if (B < 2 || !train_supported(net, B, &d)) return hipErrorInvalidValue;
+  const NetWorkspace fw = net_workspace(d);
+  const BnWorkspace bw = bn_workspace(d, B);
+  const float* fbase = static_cast<const float*>(fwd_ws);
+  auto fbuf = [&](size_t off) { return fbase + off * (size_t)B; };
+  auto fext = [&](size_t off) { return fbase + off; };
+  const BwdSpace bs = bwd_space(d, net, B);
+  const BnBwdSpace xs = bn_bwd_space(d, bs);
+  float* base = static_cast<float*>(workspace);
+  auto buf = [&](size_t off) { return base + off; };
+  double* bnpart = reinterpret_cast<double*>(buf(xs.part));
+  const int P = d.sb * d.sb, g1side = (d.sb + 1) / 2;
+  const int K1 = d.gside * d.gside * d.gl;
+  hipError_t e;
+
+  // the forward's activated outputs (the plain workspace's slots)
+  const float* S[8];
+  for (int i = 0; i < d.n_ds; ++i) S[i] = fbuf(fw.splat[i]);
+  const float* L1 = fbuf(fw.local1);
+  const float* L2 = fbuf(fw.local2);
+  const float* G1 = fbuf(fw.g1);
+  const float* G2 = fbuf(fw.g2);
+  const float* zeros = fext(bw.zeros);
+
+  {
+    RecomputeParams p{fext(bw.y1), 1, fext(bw.y2), 1, zeros, zeros, net.fc_w[2], net.fc_b[2], L2,
+                      dcoeffs, buf(bs.x1), buf(bs.x2), buf(bs.g), buf(bs.fusion), buf(bs.dyp),
+                      4 * d.gl, 2 * d.gl, d.gl, P, d.gd, net.n_out, net.n_in,
+                      magic32(d.gd * net.n_out * net.n_in), magic32(d.gd), magic32(net.n_out)};
+    const int slabs = recompute_slabs(P, d.pred);  // > 0: train_supported
+    coeff_recompute<<<dim3((unsigned)B, (unsigned)slabs + 1), 256, 0, s>>>(p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  ReduceTab tab{};
+  tab.count = 0;
+  tab.first[0] = 0;
+  float* parts = buf(bs.parts);
+  // ---- prediction layer and the fusion's column sums: as without batch norm
+  const Layer pr{buf(bs.fusion), nullptr, net.pred_w, gr.pred_w, gr.pred_b, d.sb, d.gl, d.sb, d.pred, 1, 1};
+  const int ntile = ((d.sb + kT - 1) / kT) * ((d.sb + kT - 1) / kT);
+  e = launch_pair(pr, B, buf(bs.dyp), nullptr, false, buf(bs.df), parts, &tab, s, buf(bs.fusion), buf(bs.dgp));
+  parts += dw_part_floats(B, pr);
+  if (e != hipSuccess) return e;
+  coeff_slab_sum<<<dim3((unsigned)B), 256, 0, s>>>(buf(bs.dgp), buf(bs.dg), ntile, d.gl);
+  // ---- fully connected layers: coeff_fc_bwd's mask_x applies the ReLU of the layer below, whose batch norm follows
+  {
+    FcBwdParams f3{buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1};
+    coeff_fc_bwd<<<dim3((unsigned)((2 * d.gl + 15) / 16)), 256, 0, s>>>(f3);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = launch_bn_fc_backward(buf(bs.dx2), fext(bw.xh2), fext(bw.inv2), buf(bs.dx2), grads.fc_beta[1], B, 2 * d.gl, s);
+    if (e != hipSuccess) return e;
+    FcBwdParams f2{buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], buf(xs.db_scratch), buf(bs.dx1), B, 4 * d.gl, 2 * d.gl, 1};
+    coeff_fc_bwd<<<dim3((unsigned)((4 * d.gl + 15) / 16)), 256, 0, s>>>(f2);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = launch_bn_fc_backward(buf(bs.dx1), fext(bw.xh1), fext(bw.inv1), buf(bs.dx1), grads.fc_beta[0], B, 4 * d.gl, s);
+    if (e != hipSuccess) return e;
+    FcBwdParams f1{G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], buf(xs.db_scratch), buf(bs.dg2), B, K1, 4 * d.gl, 0};
+    coeff_fc_bwd<<<dim3((unsigned)((K1 + 15) / 16)), 256, 0, s>>>(f1);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  auto norm_bwd = [&](float* dy, const float* dy2, const float* y, size_t z, size_t save, float* dbeta, int M, int C) {
+    return launch_bn_backward(dy, dy2, y, fext(z), fext(save), dy, dbeta, M, C, bnpart, s);
+  };
+  // ---- local2 (the fusion's mask) with global conv2, then local1 with global conv1
+  const float* feat = S[d.n_ds - 1];
+  {
+    e = norm_bwd(buf(bs.dg2), nullptr, G2, bw.zg2, bw.sg2, grads.global_conv_beta[1], B * d.gside * d.gside, d.gl);
+    if (e != hipSuccess) return e;
+    const Layer l2{L1, buf(bs.fusion), net.local_w[1], gr.local_w[1], nullptr, d.sb, d.gl, d.sb, d.gl, 3, 1};
+    const Layer c2{G1, G2, net.global_conv_w[1], gr.global_conv_w[1], nullptr, g1side, d.gl, d.gside, d.gl, 3, 2};
+    const PairSetup a = make_pair(l2, B, buf(bs.df), nullptr, true, buf(bs.dl1), parts, &tab);
+    parts += dw_part_floats(B, l2);
+    const PairSetup b = make_pair(c2, B, buf(bs.dg2), nullptr, false, buf(bs.dg1), parts, &tab);
+    parts += dw_part_floats(B, c2);
+    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
+  }
+  {
+    e = norm_bwd(buf(bs.dl1), nullptr, L1, bw.zlocal1, bw.slocal1, grads.local_beta, B * P, d.gl);
+    if (e != hipSuccess) return e;
+    e = norm_bwd(buf(bs.dg1), nullptr, G1, bw.zg1, bw.sg1, grads.global_conv_beta[0], B * g1side * g1side, d.gl);
+    if (e != hipSuccess) return e;
+    const Layer l1{feat, L1, net.local_w[0], gr.local_w[0], nullptr, d.sb, d.feat, d.sb, d.gl, 3, 1};
+    const Layer c1{feat, G1, net.global_conv_w[0], gr.global_conv_w[0], nullptr, d.sb, d.feat, g1side, d.gl, 3, 2};
+    const PairSetup a = make_pair(l1, B, buf(bs.dl1), nullptr, false, buf(bs.ds4a), parts, &tab);
+    parts += dw_part_floats(B, l1);
+    const PairSetup b = make_pair(c1, B, buf(bs.dg1), nullptr, false, buf(bs.ds4b), parts, &tab);
+    parts += dw_part_floats(B, c1);
+    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
+  }
+  // ---- splat, last to first; the last layer's gradient is the sum of the two paths', added by its batch norm's backward
+  float* dy = buf(bs.ds4a);
+  const float* dy2 = buf(bs.ds4b);
+  for (int i = d.n_ds - 1; i >= 0; --i) {
+    const int cout = (d.cm * d.gd) << i, cin = i > 0 ? (d.cm * d.gd) << (i - 1) : 3;
+    const int hin = d.N >> i;
+    if (i > 0) {
+      e = norm_bwd(dy, dy2, S[i], bw.zsplat[i], bw.ssplat[i], grads.splat_beta[i], B * (hin / 2) * (hin / 2), cout);
+      if (e != hipSuccess) return e;
+      const Layer L{S[i - 1], S[i], net.splat_w[i], gr.splat_w[i], nullptr, hin, cin, hin / 2, cout, 3, 2};
+      e = launch_pair(L, B, dy, nullptr, false, buf(bs.ds[i - 1]), parts, &tab, s);
+      parts += dw_part_floats(B, L);
+      if (e != hipSuccess) return e;
+      dy = buf(bs.ds[i - 1]);
+      dy2 = nullptr;
+    } else {
+      const Layer L{lowres, S[0], net.splat_w[0], gr.splat_w[0], gr.splat_b[0], hin, cin, hin / 2, cout, 3, 2};
+      e = launch_dw(L, B, dy, dy2, true, parts, &tab, s);
+      parts += dw_part_floats(B, L);
+      if (e != hipSuccess) return e;
+    }
+  }
   coeff_reduce_parts<<<dim3((unsigned)tab.first[tab.count]), 256, 0, s>>>(tab);
   return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 #include <stddef.h>
 
 #include "../../include/hdrnet_amd.h"
+#include "../../include/hdrnet_amd_train.h"
 
 namespace hdrnet_amd {
 
@@ -287,6 +288,15 @@ size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B);  /
 hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
                                     const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s,
                                     const char** name);
+// The same network trained WITH batch norm (coeff_net_bn.hip's kernels between the launches of the two files above);
+// the workspace queries return 0 outside 2 <= B <= 8 or what the gradient above supports.
+size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B);
+hipError_t launch_coefficients_bn(const float* lowres, const hdrnet_coeff_net_bn& bn, float* coeffs, int B,
+                                  void* workspace, hipStream_t s);
+size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B);
+hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_net_bn& bn,
+                                       const hdrnet_coeff_net_bn_grads& grads, const float* dcoeffs, int B,
+                                       const void* fwd_ws, void* workspace, hipStream_t s);
 
 // capi.hip -- the tail of every C-ABI entry point, for those defined beside their kernels too.  The error text
 // (hdrnet_last_error) is thread-local and the kernel name (hdrnet_last_kernel) optional bookkeeping; both live there.

@@ -819,6 +819,127 @@ def coefficients_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: int,
     return _CoefficientsTrain.apply(lowres_input, hyper, n_out, n_in, n_splat, *params)
 
 
+def _live_net_bn(hyper, n_out: int, n_in: int, params, n_splat: int, stats, eps: float, momentum: float):
+    """``hdrnet_coeff_net_bn`` over the module's LIVE parameters and buffers.  ``params`` in ``_live_net``'s order with
+    beta where a normalised layer (splat 1.., both global convs, fc1, fc2, local1) would have its bias; ``stats``:
+    ``(running_mean, running_var)`` of those layers in the same order."""
+    net = _lib.CoeffNetBn()
+    net.net_input_size, net.spatial_bin = int(hyper["net_input_size"]), int(hyper["spatial_bin"])
+    net.luma_bins, net.channel_multiplier = int(hyper["luma_bins"]), int(hyper["channel_multiplier"])
+    net.n_out, net.n_in, net.n_levels, net.fc_layout = int(n_out), int(n_in), 1, 1
+    net.eps, net.momentum = float(eps), float(momentum)
+    it, st = iter(params), iter(stats)
+    for i in range(n_splat):
+        net.splat_w[i] = next(it).data_ptr()
+        if i == 0:
+            net.splat_b[0] = next(it).data_ptr()
+        else:
+            net.splat_beta[i] = next(it).data_ptr()
+            net.splat_running_mean[i], net.splat_running_var[i] = (t.data_ptr() for t in next(st))
+    for i in range(2):
+        net.global_conv_w[i], net.global_conv_beta[i] = next(it).data_ptr(), next(it).data_ptr()
+        net.global_conv_running_mean[i], net.global_conv_running_var[i] = (t.data_ptr() for t in next(st))
+    for i in range(2):
+        net.fc_w[i], net.fc_beta[i] = next(it).data_ptr(), next(it).data_ptr()
+        net.fc_running_mean[i], net.fc_running_var[i] = (t.data_ptr() for t in next(st))
+    net.fc_w[2], net.fc_b[2] = next(it).data_ptr(), next(it).data_ptr()
+    net.local_w[0], net.local_beta = next(it).data_ptr(), next(it).data_ptr()
+    net.local_running_mean, net.local_running_var = (t.data_ptr() for t in next(st))
+    net.local_w[1] = next(it).data_ptr()
+    net.pred_w, net.pred_b = next(it).data_ptr(), next(it).data_ptr()
+    return net
+
+
+def coefficients_bn_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, stats, batch: int) -> bool:
+    """True if ``coefficients_bn_train`` can run this network: parameters and running statistics fp32 on the GPU in
+    torch's own layouts, hyper-parameters within the kernels' reach, 2 <= batch <= 8."""
+    import ctypes
+    params, stats = list(params), [tuple(st) for st in stats]
+    if len(params) != 2 * n_splat + 4 + 6 + 2 + 1 + 2 or len(stats) != n_splat + 4 or not _params_ok(params):
+        return False
+    if not _params_ok([t for st in stats for t in st]):
+        return False
+    net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, 1e-3, 1e-3)
+    lib = _lib.load()
+    return (lib.hdrnet_coefficients_bn_workspace_bytes(ctypes.byref(net), int(batch)) > 0
+            and lib.hdrnet_coefficients_bn_grad_workspace_bytes(ctypes.byref(net), int(batch)) > 0)
+
+
+class _CoefficientsBnTrain(torch.autograd.Function):
+    """``hdrnet_coefficients_bn_train_f32`` / ``hdrnet_coefficients_bn_grad_f32`` (csrc/coeff_net_bn.hip between the
+    launches of coeff_net.hip / coeff_net_train.hip): the coefficient network with batch norm in training mode."""
+
+    @staticmethod
+    def forward(ctx, lowres, hyper, n_out, n_in, n_splat, stats, eps, momentum, *params):
+        import ctypes
+        low = lowres.detach().contiguous()
+        B, dev = low.shape[0], low.device
+        net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, eps, momentum)
+        sb, gd = int(hyper["spatial_bin"]), int(hyper["luma_bins"])
+        out = torch.empty((B, sb, sb, gd, n_out, n_in), dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            wbytes = lib.hdrnet_coefficients_bn_workspace_bytes(ctypes.byref(net), B)
+            ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+            rc = lib.hdrnet_coefficients_bn_train_f32(low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(),
+                                                      wbytes, _stream(dev))
+        _lib.check(rc, "CoefficientsBnTrain")
+        for st in stats:
+            for t in st:  # written through a raw pointer: tell autograd / the fold caches keyed on ._version
+                torch.autograd.graph.increment_version(t)
+        ctx.save_for_backward(low, ws, *params)
+        ctx.stats = stats  # (the backward reads none of them: the struct wants their addresses)
+        ctx.meta = (dict(hyper), int(n_out), int(n_in), int(n_splat), float(eps), float(momentum))
+        return out
+
+    @staticmethod
+    def backward(ctx, dcoeffs):
+        import ctypes
+        low, ws = ctx.saved_tensors[:2]
+        params = ctx.saved_tensors[2:]
+        hyper, n_out, n_in, n_splat, eps, momentum = ctx.meta
+        B, dev = low.shape[0], low.device
+        net = _live_net_bn(hyper, n_out, n_in, params, n_splat, ctx.stats, eps, momentum)
+        grads = [_grad_out(p) for p in params]
+        gr = _lib.CoeffNetBnGrads()
+        it = iter(grads)
+        for i in range(n_splat):
+            gr.splat_w[i] = next(it).data_ptr()
+            if i == 0:
+                gr.splat_b[0] = next(it).data_ptr()
+            else:
+                gr.splat_beta[i] = next(it).data_ptr()
+        for i in range(2):
+            gr.global_conv_w[i], gr.global_conv_beta[i] = next(it).data_ptr(), next(it).data_ptr()
+        for i in range(2):
+            gr.fc_w[i], gr.fc_beta[i] = next(it).data_ptr(), next(it).data_ptr()
+        gr.fc_w[2], gr.fc_b[2] = next(it).data_ptr(), next(it).data_ptr()
+        gr.local_w[0], gr.local_beta = next(it).data_ptr(), next(it).data_ptr()
+        gr.local_w[1] = next(it).data_ptr()
+        gr.pred_w, gr.pred_b = next(it).data_ptr(), next(it).data_ptr()
+        dc = dcoeffs.contiguous()
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            wbytes = lib.hdrnet_coefficients_bn_grad_workspace_bytes(ctypes.byref(net), B)
+            ws2 = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+            rc = lib.hdrnet_coefficients_bn_grad_f32(low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(),
+                                                     ctypes.byref(gr), B, ws2.data_ptr(), wbytes, _stream(dev))
+        _lib.check(rc, "CoefficientsBnGrad")
+        return (None, None, None, None, None, None, None, None, *grads)
+
+
+def coefficients_bn_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: int, params, n_splat: int, stats,
+                          eps: float = 1e-3, momentum: float = 1e-3) -> torch.Tensor:
+    """``HDRNetCurves._coefficients`` (hdrnet/models.py:62-142) WITH batch norm in training mode (``--batch_norm``,
+    hdrnet/layers.py:30-54), differentiable in its weights, biases and betas, on the HIP kernels; moves the running
+    statistics of ``stats`` in place.  ``params`` / ``stats`` as ``_live_net_bn`` takes them.  ``lowres_input [B, N, N, 3]``
+    (no gradient, 2 <= B <= 8) -> ``[B, sb, sb, gd, n_out, n_in]``."""
+    _require_f32("lowres_input", lowres_input)
+    _require_gpu("lowres_input", lowres_input)
+    stats = tuple(tuple(st) for st in stats)
+    return _CoefficientsBnTrain.apply(lowres_input, hyper, n_out, n_in, n_splat, stats, eps, momentum, *params)
+
+
 def resize_bilinear(input: torch.Tensor, height: int, width: int) -> torch.Tensor:  # noqa: A002
     """NHWC ``tf.image.resize_images(input, (height, width), BILINEAR, align_corners=True)`` --
     the resize that builds HDRNetGaussianPyrNN's multi-scale input (hdrnet/models.py:253-266).

@@ -217,8 +217,8 @@ class _Coefficients(nn.Module):
 
     # Training (and any differentiable evaluation) of the network WITHOUT batch norm -- the reference's own training
     # configuration for the guide-network model (scripts/ll/train_nn_guide.sh) -- on the HIP kernels as well: forward
-    # + backward in ~35 launches instead of ~130 stock-op launches.  With batch norm, or when the input itself needs a
-    # gradient, the torch ops below run.  ``native_training = False`` forces them.
+    # + backward in ~35 launches instead of ~130 stock-op launches.  With batch norm ``_use_native_bn_training`` below
+    # decides; when the input itself needs a gradient the torch ops run.  ``native_training = False`` forces them for both.
     native_training = True
 
     def _train_params(self):
@@ -249,6 +249,68 @@ class _Coefficients(nn.Module):
         return hdrnet_ops.coefficients_train_supported(self.hyper, self.n_out, self.n_in, ps, len(self.splat),
                                                        int(lowres_nhwc.shape[0]))
 
+    # The same WITH batch norm in training mode (the reference's --batch_norm): the statistics, the normalisation and
+    # their backward as kernels of csrc/coeff_net_bn.hip between the same convolution launches.  Inference, a batch of one
+    # (torch refuses to train on it), an input that needs a gradient or a gamma that is not the constant 1 run the torch ops.
+    def _bn_layers(self):
+        return list(self.splat)[1:] + list(self.global_conv) + [self.fc1, self.fc2, self.local1]
+
+    def _train_params_bn(self):
+        """(parameters, running statistics) in ``hdrnet_ops.coefficients_bn_train``'s order: beta where a normalised layer
+        would have its bias."""
+        def second(layer, lin):
+            return layer.bn.bn.bias if layer.bn is not None else lin.bias
+        ps = []
+        for layer in list(self.splat) + list(self.global_conv):
+            ps += [layer.conv.weight, second(layer, layer.conv)]
+        for layer in (self.fc1, self.fc2, self.fc3):
+            ps += [layer.fc.weight, second(layer, layer.fc)]
+        ps += [self.local1.conv.weight, second(self.local1, self.local1.conv), self.local2.conv.weight,
+               self.pred.conv.weight, self.pred.conv.bias]
+        stats = [(layer.bn.bn.running_mean, layer.bn.bn.running_var) for layer in self._bn_layers()]
+        return ps, stats
+
+    def _gamma_is_one(self, bns) -> bool:
+        """Every gamma the constant 1 (the kernels have no scale).  Reading the values waits for the device, so the answer
+        is kept per state of the gammas; while a stream capture runs only a kept answer counts."""
+        gammas = [m.weight for m in bns]
+        key = _param_key(gammas)
+        cached = getattr(self, "_gamma_one", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if not _cacheable():
+            return False
+        ok = all(bool((g == 1).all()) for g in gammas)
+        self._gamma_one = (key, ok)
+        return ok
+
+    def _use_native_bn_training(self, lowres_nhwc: torch.Tensor) -> bool:
+        if not (self.native and self.native_training and self.training and lowres_nhwc.is_cuda
+                and lowres_nhwc.dtype == torch.float32):
+            return False
+        if not torch.is_grad_enabled() or lowres_nhwc.requires_grad:
+            return False
+        normalised = self._bn_layers()
+        plain = [self.splat[0], self.fc3, self.local2, self.pred]
+        if any(m.bn is None for m in normalised) or any(m.bn is not None for m in plain):
+            return False
+        N = self.hyper["net_input_size"]
+        if lowres_nhwc.dim() != 4 or tuple(lowres_nhwc.shape[1:]) != (N, N, 3):
+            return False
+        bns = [m.bn.bn for m in normalised]
+        if any(m.weight is None or m.bias is None or m.running_mean is None or m.running_var is None
+               or m.weight.requires_grad or not m.bias.requires_grad or m.momentum is None
+               or m.eps != bns[0].eps or m.momentum != bns[0].momentum for m in bns):
+            return False
+        ps, stats = self._train_params_bn()
+        if any(p is None for p in ps):
+            return False
+        from . import hdrnet_ops
+        if not hdrnet_ops.coefficients_bn_train_supported(self.hyper, self.n_out, self.n_in, ps, len(self.splat), stats,
+                                                          int(lowres_nhwc.shape[0])):
+            return False
+        return self._gamma_is_one(bns)
+
     def levels(self, lowres_nhwc: torch.Tensor) -> List[torch.Tensor]:
         """Per pyramid level the 5-D grid ``[B, GH, GW, gd, (n_out / n_levels) * n_in]`` of
         ``coeffs[:, :, :, :, l*k:(l+1)*k, :]`` (hdrnet/models.py:279), each contiguous."""
@@ -267,6 +329,12 @@ class _Coefficients(nn.Module):
             from . import hdrnet_ops
             return hdrnet_ops.coefficients_train(lowres_nhwc, self.hyper, self.n_out, self.n_in, self._train_params(),
                                                  len(self.splat))
+        if self._use_native_bn_training(lowres_nhwc):
+            from . import hdrnet_ops
+            ps, stats = self._train_params_bn()
+            bn = self.fc1.bn.bn
+            return hdrnet_ops.coefficients_bn_train(lowres_nhwc, self.hyper, self.n_out, self.n_in, ps, len(self.splat),
+                                                    stats, bn.eps, bn.momentum)
         if self._use_native(lowres_nhwc):
             from . import hdrnet_ops
             out = hdrnet_ops.coefficients(lowres_nhwc, self.exported())

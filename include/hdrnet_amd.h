@@ -96,7 +96,9 @@ extern "C" {
  *   282  the coefficient network refuses what its kernels cannot run: hdrnet_coefficients_workspace_bytes returns 0 (281:
  *        a size) for a last splat layer wider than 4096 channels, 8 * cm * gd > 1024, gd * n_out * n_in > 1048560;
  *        hdrnet_coefficients_grad_workspace_bytes also for gd * n_out * n_in no multiple of 4 or >= 65536 (281 read out
- *        of bounds or divided wrongly there).  The entry points name the limit in hdrnet_last_error(). */
+ *        of bounds or divided wrongly there).  The entry points name the limit in hdrnet_last_error().
+ *   283  + hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 and their workspace queries in
+ *        hdrnet_amd_coeff_bn.h, which hdrnet_amd_train.h includes (the coefficient network trained WITH batch norm). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */
@@ -467,7 +469,8 @@ typedef struct hdrnet_coeff_net {
 size_t hdrnet_coefficients_workspace_bytes(const hdrnet_coeff_net* net, int B);
 
 /* Training side: the VJP of the coefficient network with respect to every weight and bias, for the model WITHOUT batch
- * norm (how the reference's script trains the guide-network model: scripts/ll/train_nn_guide.sh, --nobatch_norm).
+ * norm (how the reference's script trains the guide-network model: scripts/ll/train_nn_guide.sh, --nobatch_norm; with
+ * batch norm: hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 of hdrnet_amd_coeff_bn.h).
  * Forward = hdrnet_coefficients_f32 with the parameters AS TORCH HOLDS THEM -- Conv2d weights in channels_last memory
  * order ([Cout][kh][kw][Cin], the same layout as above) and fc_layout = 1 (Linear weights [out][in]) -- keeping its
  * workspace: `forward_workspace` here is that buffer, untouched since.  `dcoeffs` is [B][sb][sb][gd][n_out][n_in];

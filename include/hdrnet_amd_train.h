@@ -22,6 +22,9 @@
 
 #include <stddef.h>
 
+/* the coefficient network trained with batch norm: hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 */
+#include "hdrnet_amd_coeff_bn.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif

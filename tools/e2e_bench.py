@@ -195,7 +195,7 @@ def main():
     # the whole step (fwd + loss + bwd + Adam) as one hipGraph
     from hdrnet_amd.runtime import GraphedTrainStep
     t_graph = {}
-    for bn, native in ((True, True), (False, False), (False, True)):
+    for bn, native in ((True, True), (True, False), (False, False), (False, True)):
         mg = models.HDRNetPointwiseNNGuide(dict(batch_norm=bn)).to(dev).train()
         mg.coefficients.native_training = native
         optg = optim.FlatAdam([p for p in mg.parameters() if p.requires_grad], lr=1e-4, epsilon_hat=True)
@@ -204,7 +204,8 @@ def main():
     t = t_graph[(False, True)]
     print(f"config #4  the whole step as one hipGraph, no batch norm (the reference's scripts), coefficient network's "
           f"forward + backward on the HIP kernels: {t * 1e3:.3f} ms/step = {B * 1080 * 1920 / 1e6 / t:.0f} MP/s per GPU;  "
-          f"on stock ops: {t_graph[(False, False)] * 1e3:.3f};  with batch norm (stock ops): {t_graph[(True, True)] * 1e3:.3f}")
+          f"on stock ops: {t_graph[(False, False)] * 1e3:.3f};  with batch norm (stock ops): {t_graph[(True, False)] * 1e3:.3f};  "
+          f"with batch norm, coefficient network on the HIP kernels: {t_graph[(True, True)] * 1e3:.3f}")
 
     # the reference's DEFAULT model class (hdrnet/bin/train.py:225: models.__all__[0] = HDRNetCurves) and the pyramid model,
     # the same graph-captured step without batch norm
