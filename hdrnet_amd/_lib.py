@@ -154,6 +154,16 @@ COEFF_BN_SIGNATURES = {
     "hdrnet_coefficients_bn_grad_f32": (_I, [_FP, _VP, _VP, _FP, _VP, _I, _VP, _SZ, _VP]),
 }
 
+# include/hdrnet_amd_coeff_wide.h (included by hdrnet_amd_train.h): the same training entry points for batches up to 32.
+COEFF_WIDE_SIGNATURES = {
+    "hdrnet_coefficients_grad_wide_workspace_bytes": (_SZ, [_VP, _I]),
+    "hdrnet_coefficients_grad_wide_f32": (_I, [_FP, _VP, _VP, _FP, _VP, _I, _VP, _SZ, _VP]),
+    "hdrnet_coefficients_bn_wide_workspace_bytes": (_SZ, [_VP, _I]),
+    "hdrnet_coefficients_bn_train_wide_f32": (_I, [_FP, _VP, _FP, _I, _VP, _SZ, _VP]),
+    "hdrnet_coefficients_bn_grad_wide_workspace_bytes": (_SZ, [_VP, _I]),
+    "hdrnet_coefficients_bn_grad_wide_f32": (_I, [_FP, _VP, _VP, _FP, _VP, _I, _VP, _SZ, _VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -205,6 +215,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table = dict(SIGNATURES)
     table.update(TRAIN_SIGNATURES)
     table.update(COEFF_BN_SIGNATURES)
+    table.update(COEFF_WIDE_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

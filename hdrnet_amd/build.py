@@ -47,6 +47,7 @@ SOURCES = [
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
     ("coeff_net_bn.hip", []),
+    ("coeff_fc_wide.hip", []),
     ("metrics.hip", []),
     ("loss_psnr.hip", []),
     ("sample_prep.hip", []),
@@ -100,7 +101,8 @@ def _usable_flags(cc: str, extra: List[str]) -> List[str]:
 
 def _deps() -> List[str]:
     out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"),
-           os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.abspath(__file__)]
+           os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.join(INCLUDE, "hdrnet_amd_coeff_wide.h"),
+           os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):
             out.append(os.path.join(CSRC, f))

@@ -154,11 +154,14 @@ bool coeff_net_null_param(const hdrnet_coeff_net& net, const hdrnet_coeff_net_gr
 }
 
 // the batch-norm description: why a call cannot run (null: it can).  `grads`: also check where the gradients go.
-const char* coeff_net_bn_refusal(const hdrnet_coeff_net_bn& bn, const hdrnet_coeff_net_bn_grads* grads, int B) {
+// `max_b`: the entry point's largest batch (8, or 32 for the ..._wide ones).
+const char* coeff_net_bn_refusal(const hdrnet_coeff_net_bn& bn, const hdrnet_coeff_net_bn_grads* grads, int B, int max_b) {
   using namespace hdrnet_amd;
   const hdrnet_coeff_net& net = bn.net;
-  if (coefficients_bn_workspace_bytes(net, B) == 0 || coefficients_bn_grad_workspace_bytes(net, B) == 0)
-    return "unsupported (needs what hdrnet_coefficients_grad_f32 supports, 2 <= B <= 8, n_levels = 1, fc_layout = 1)";
+  if (coefficients_bn_workspace_bytes(net, B, max_b) == 0 || coefficients_bn_grad_workspace_bytes(net, B, max_b) == 0)
+    return max_b > kCoeffNarrowMaxB
+               ? "unsupported (needs what hdrnet_coefficients_grad_wide_f32 supports, 2 <= B <= 32, n_levels = 1, fc_layout = 1)"
+               : "unsupported (needs what hdrnet_coefficients_grad_f32 supports, 2 <= B <= 8, n_levels = 1, fc_layout = 1)";
   int n_ds = 0;
   for (int v = net.net_input_size / net.spatial_bin; v > 1; v >>= 1) ++n_ds;
   bool null_param = !net.pred_w || !net.pred_b || !net.local_w[0] || !net.local_w[1] || !net.splat_b[0] || !net.fc_b[2];
@@ -271,7 +274,7 @@ extern "C" {
 // 0.2.8.1: the training-loop entry points of include/hdrnet_amd_train.h set / clear hdrnet_last_error() like the rest
 // 0.2.8.2: the coefficient network's entry points refuse widths their kernels cannot run (workspace queries return 0
 //          where 281 returned a size: include/hdrnet_amd.h)
-int hdrnet_version(void) { return 283; }
+int hdrnet_version(void) { return 284; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -652,6 +655,78 @@ int hdrnet_coefficients_f32(const float* lowres, const hdrnet_coeff_net* net, fl
   return finish_launch(e, "Coefficients", name);
 }
 
+// The training entry points of the coefficient network exist twice: the first ones for batches up to 8 and their ..._wide
+// twins (include/hdrnet_amd_coeff_wide.h) up to 32.  One body each: `prefix` goes in front of every refusal ("" for
+// hdrnet_coefficients_grad_f32, which predates the convention), `query` names the workspace query in the text.
+namespace {
+
+int coefficients_grad_entry(const char* prefix, const char* query, int max_b, const float* lowres,
+                            const hdrnet_coeff_net* net, const void* forward_workspace, const float* dcoeffs,
+                            const hdrnet_coeff_net_grads* grads, int B, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  using namespace hdrnet_amd;
+  if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "%snull network description", prefix);
+  const size_t need = B > 0 ? coefficients_grad_workspace_bytes(*net, B, max_b) : 0;
+  if (const char* limit = B > 0 ? coefficients_grad_limit(*net, B, max_b) : nullptr) {
+    char batch[24] = "";  // the wide entry point's refusals all carry the batch; the first one's text stays as it was
+    if (prefix[0]) snprintf(batch, sizeof batch, "; B=%d", B);
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "%scoefficient network gradient: %s (spatial_bin=%d, luma_bins=%d, n_out=%d, n_in=%d); the forward has no "
+                "such limit%s", prefix, limit, net->spatial_bin, net->luma_bins, net->n_out, net->n_in, batch);
+  }
+  if (need == 0)
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "%scoefficient network gradient: unsupported (needs the forward's support, n_levels = 1, fc_layout = 1, "
+                "1 <= B <= %d, 8 * cm * gd <= 256; got B=%d, n_levels=%d, fc_layout=%d)", prefix, max_b, B, net->n_levels,
+                net->fc_layout);
+  if (coeff_net_null_param(*net, grads))
+    return fail(HDRNET_INVALID_ARGUMENT, "%scoefficient network gradient: null parameter", prefix);
+  if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "%snull buffer", prefix);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%scoefficient network gradient needs a 16-B aligned workspace of "
+                                         "%s() = %zu bytes", prefix, query, need);
+  const char* name = "";
+  const hipError_t e = launch_coefficients_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
+                                                static_cast<hipStream_t>(stream), &name, max_b);
+  return finish_launch(e, "CoefficientsGrad", name);
+}
+
+int coefficients_bn_train_entry(const char* kFn, const char* query, int max_b, const float* lowres,
+                                const hdrnet_coeff_net_bn* net, float* coeffs, int B, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  using namespace hdrnet_amd;
+  if (!net) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
+  if (const char* why = coeff_net_bn_refusal(*net, nullptr, B, max_b))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
+                net->net.fc_layout);
+  if (!lowres || !coeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
+  const size_t need = coefficients_bn_workspace_bytes(net->net, B, max_b);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of %s() = %zu bytes", kFn, query, need);
+  // (no kernel name recorded: the training-loop helpers leave hdrnet_last_kernel() alone)
+  return finish_launch(launch_coefficients_bn(lowres, *net, coeffs, B, workspace, static_cast<hipStream_t>(stream), max_b),
+                       kFn, nullptr);
+}
+
+int coefficients_bn_grad_entry(const char* kFn, const char* query, int max_b, const float* lowres,
+                               const hdrnet_coeff_net_bn* net, const void* forward_workspace, const float* dcoeffs,
+                               const hdrnet_coeff_net_bn_grads* grads, int B, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  using namespace hdrnet_amd;
+  if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
+  if (const char* why = coeff_net_bn_refusal(*net, grads, B, max_b))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
+                net->net.fc_layout);
+  if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
+  const size_t need = coefficients_bn_grad_workspace_bytes(net->net, B, max_b);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of %s() = %zu bytes", kFn, query, need);
+  return finish_launch(launch_coefficients_bn_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
+                                                   static_cast<hipStream_t>(stream), max_b), kFn, nullptr);
+}
+
+}  // namespace
+
 size_t hdrnet_coefficients_grad_workspace_bytes(const hdrnet_coeff_net* net, int B) {
   if (!net || B <= 0) return 0;
   return hdrnet_amd::coefficients_grad_workspace_bytes(*net, B);
@@ -660,27 +735,8 @@ size_t hdrnet_coefficients_grad_workspace_bytes(const hdrnet_coeff_net* net, int
 int hdrnet_coefficients_grad_f32(const float* lowres, const hdrnet_coeff_net* net, const void* forward_workspace,
                                  const float* dcoeffs, const hdrnet_coeff_net_grads* grads, int B, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  using namespace hdrnet_amd;
-  if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "null network description");
-  const size_t need = B > 0 ? coefficients_grad_workspace_bytes(*net, B) : 0;
-  if (const char* limit = B > 0 ? coefficients_grad_limit(*net, B) : nullptr)
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "coefficient network gradient: %s (spatial_bin=%d, luma_bins=%d, n_out=%d, n_in=%d); the forward has no "
-                "such limit", limit, net->spatial_bin, net->luma_bins, net->n_out, net->n_in);
-  if (need == 0)
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "coefficient network gradient: unsupported (needs the forward's support, n_levels = 1, fc_layout = 1, "
-                "1 <= B <= 8, 8 * cm * gd <= 256; got B=%d, n_levels=%d, fc_layout=%d)", B, net->n_levels, net->fc_layout);
-  if (coeff_net_null_param(*net, grads))
-    return fail(HDRNET_INVALID_ARGUMENT, "coefficient network gradient: null parameter");
-  if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
-    return fail(HDRNET_INVALID_ARGUMENT, "coefficient network gradient needs a 16-B aligned workspace of "
-                                         "hdrnet_coefficients_grad_workspace_bytes() = %zu bytes", need);
-  const char* name = "";
-  const hipError_t e = launch_coefficients_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
-                                                static_cast<hipStream_t>(stream), &name);
-  return finish_launch(e, "CoefficientsGrad", name);
+  return coefficients_grad_entry("", "hdrnet_coefficients_grad_workspace_bytes", hdrnet_amd::kCoeffNarrowMaxB, lowres, net,
+                                 forward_workspace, dcoeffs, grads, B, workspace, workspace_bytes, stream);
 }
 
 size_t hdrnet_coefficients_bn_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
@@ -690,20 +746,8 @@ size_t hdrnet_coefficients_bn_workspace_bytes(const hdrnet_coeff_net_bn* net, in
 
 int hdrnet_coefficients_bn_train_f32(const float* lowres, const hdrnet_coeff_net_bn* net, float* coeffs, int B,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  using namespace hdrnet_amd;
-  constexpr const char* kFn = "hdrnet_coefficients_bn_train_f32";
-  if (!net) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
-  if (const char* why = coeff_net_bn_refusal(*net, nullptr, B))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
-                net->net.fc_layout);
-  if (!lowres || !coeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
-  const size_t need = coefficients_bn_workspace_bytes(net->net, B);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of hdrnet_coefficients_bn_workspace_bytes() = "
-                                         "%zu bytes", kFn, need);
-  // (no kernel name recorded: the training-loop helpers leave hdrnet_last_kernel() alone)
-  return finish_launch(launch_coefficients_bn(lowres, *net, coeffs, B, workspace, static_cast<hipStream_t>(stream)), kFn,
-                       nullptr);
+  return coefficients_bn_train_entry("hdrnet_coefficients_bn_train_f32", "hdrnet_coefficients_bn_workspace_bytes",
+                                     hdrnet_amd::kCoeffNarrowMaxB, lowres, net, coeffs, B, workspace, workspace_bytes, stream);
 }
 
 size_t hdrnet_coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
@@ -714,19 +758,48 @@ size_t hdrnet_coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net_bn* ne
 int hdrnet_coefficients_bn_grad_f32(const float* lowres, const hdrnet_coeff_net_bn* net, const void* forward_workspace,
                                     const float* dcoeffs, const hdrnet_coeff_net_bn_grads* grads, int B, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  using namespace hdrnet_amd;
-  constexpr const char* kFn = "hdrnet_coefficients_bn_grad_f32";
-  if (!net || !grads) return fail(HDRNET_INVALID_ARGUMENT, "%s: null network description", kFn);
-  if (const char* why = coeff_net_bn_refusal(*net, grads, B))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s (B=%d, n_levels=%d, fc_layout=%d)", kFn, why, B, net->net.n_levels,
-                net->net.fc_layout);
-  if (!lowres || !forward_workspace || !dcoeffs) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", kFn);
-  const size_t need = coefficients_bn_grad_workspace_bytes(net->net, B);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15u))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: needs a 16-B aligned workspace of "
-                                         "hdrnet_coefficients_bn_grad_workspace_bytes() = %zu bytes", kFn, need);
-  return finish_launch(launch_coefficients_bn_grad(lowres, *net, *grads, dcoeffs, B, forward_workspace, workspace,
-                                                   static_cast<hipStream_t>(stream)), kFn, nullptr);
+  return coefficients_bn_grad_entry("hdrnet_coefficients_bn_grad_f32", "hdrnet_coefficients_bn_grad_workspace_bytes",
+                                    hdrnet_amd::kCoeffNarrowMaxB, lowres, net, forward_workspace, dcoeffs, grads, B,
+                                    workspace, workspace_bytes, stream);
+}
+
+// ---- the same for batches up to 32 (include/hdrnet_amd_coeff_wide.h)
+
+size_t hdrnet_coefficients_grad_wide_workspace_bytes(const hdrnet_coeff_net* net, int B) {
+  if (!net || B <= 0) return 0;
+  return hdrnet_amd::coefficients_grad_workspace_bytes(*net, B, hdrnet_amd::kCoeffWideMaxB);
+}
+
+int hdrnet_coefficients_grad_wide_f32(const float* lowres, const hdrnet_coeff_net* net, const void* forward_workspace,
+                                      const float* dcoeffs, const hdrnet_coeff_net_grads* grads, int B, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return coefficients_grad_entry("hdrnet_coefficients_grad_wide_f32: ", "hdrnet_coefficients_grad_wide_workspace_bytes",
+                                 hdrnet_amd::kCoeffWideMaxB, lowres, net, forward_workspace, dcoeffs, grads, B, workspace,
+                                 workspace_bytes, stream);
+}
+
+size_t hdrnet_coefficients_bn_wide_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
+  if (!net || B <= 0) return 0;
+  return hdrnet_amd::coefficients_bn_workspace_bytes(net->net, B, hdrnet_amd::kCoeffWideMaxB);
+}
+
+int hdrnet_coefficients_bn_train_wide_f32(const float* lowres, const hdrnet_coeff_net_bn* net, float* coeffs, int B,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  return coefficients_bn_train_entry("hdrnet_coefficients_bn_train_wide_f32", "hdrnet_coefficients_bn_wide_workspace_bytes",
+                                     hdrnet_amd::kCoeffWideMaxB, lowres, net, coeffs, B, workspace, workspace_bytes, stream);
+}
+
+size_t hdrnet_coefficients_bn_grad_wide_workspace_bytes(const hdrnet_coeff_net_bn* net, int B) {
+  if (!net || B <= 0) return 0;
+  return hdrnet_amd::coefficients_bn_grad_workspace_bytes(net->net, B, hdrnet_amd::kCoeffWideMaxB);
+}
+
+int hdrnet_coefficients_bn_grad_wide_f32(const float* lowres, const hdrnet_coeff_net_bn* net, const void* forward_workspace,
+                                         const float* dcoeffs, const hdrnet_coeff_net_bn_grads* grads, int B,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return coefficients_bn_grad_entry("hdrnet_coefficients_bn_grad_wide_f32", "hdrnet_coefficients_bn_grad_wide_workspace_bytes",
+                                    hdrnet_amd::kCoeffWideMaxB, lowres, net, forward_workspace, dcoeffs, grads, B,
+                                    workspace, workspace_bytes, stream);
 }
 
 int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,

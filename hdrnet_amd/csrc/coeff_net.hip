@@ -694,17 +694,17 @@ hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net,
 // y = relu(bn(z)); fc1 / fc2 materialise their activated outputs, which their consumers read as an input of one partial
 // sum (xS = 1) without bias.
 
-size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B) {
+size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
-  if (B < 2 || coefficients_grad_workspace_bytes(net, B) == 0 || !net_dims(net, &d)) return 0;
+  if (B < 2 || coefficients_grad_workspace_bytes(net, B, max_b) == 0 || !net_dims(net, &d)) return 0;
   return bn_workspace(d, B).total * sizeof(float);
 }
 
 hipError_t launch_coefficients_bn(const float* lowres, const hdrnet_coeff_net_bn& bn, float* coeffs, int B,
-                                  void* workspace, hipStream_t s) {
+                                  void* workspace, hipStream_t s, int max_b) {
   const hdrnet_coeff_net& net = bn.net;
   NetDims d;
-  if (coefficients_bn_workspace_bytes(net, B) == 0 || !net_dims(net, &d)) return hipErrorInvalidValue;
+  if (coefficients_bn_workspace_bytes(net, B, max_b) == 0 || !net_dims(net, &d)) return hipErrorInvalidValue;
   const NetWorkspace ws = net_workspace(d);
   const BnWorkspace bw = bn_workspace(d, B);
   float* base = static_cast<float*>(workspace);

@@ -14,7 +14,8 @@
 //                        (in place over dy if asked to); chunk 0 writes dbeta
 //
 // z stays where the convolution wrote it: xhat is recomputed from it, for every element (the backward formula needs
-// it also where y = 0).  The fully connected layers (M = B <= 8 rows) are one launch each way, a thread per channel.
+// it also where y = 0).  The fully connected layers (M = B <= 8 rows) are one launch each way, a thread per channel; 9 to 32 rows
+// go to their twins in coeff_fc_wide.hip.
 //
 // Sums run in float64 from the first addend on: E[z^2] - mean^2 then loses nothing that matters (the operands are
 // exact to 2^-53, the cancellation costs mean^2 / var of that), and the order of the additions is fixed -- per thread
@@ -23,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coeff_net_bn.hip.h"
+#include "coeff_fc_wide.hip.h"
 
 namespace hdrnet_amd {
 namespace {
@@ -355,7 +357,10 @@ hipError_t launch_bn_backward(const float* dy, const float* dy2, const float* y,
 hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
                                 float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
                                 float momentum, hipStream_t s) {
-  if (B < 2 || B > kMaxB || S < 1 || O < 1) return hipErrorInvalidValue;
+  if (B > kMaxB)  // 9 .. 32 images: coeff_fc_wide.hip
+    return launch_bn_fc_forward_wide(zpart, S, B, O, beta, running_mean, running_var, xhat, y, inv_std, zeros, eps,
+                                     momentum, s);
+  if (B < 2 || S < 1 || O < 1) return hipErrorInvalidValue;
   BnFcParams p{};
   p.zpart = zpart; p.S = S; p.B = B; p.O = O; p.beta = beta; p.running_mean = running_mean; p.running_var = running_var;
   p.xhat = xhat; p.y = y; p.inv_std = inv_std; p.zeros = zeros; p.eps = eps; p.momentum = momentum;
@@ -365,7 +370,8 @@ hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const f
 
 hipError_t launch_bn_fc_backward(const float* g, const float* xhat, const float* inv_std, float* dz, float* dbeta, int B,
                                  int O, hipStream_t s) {
-  if (B < 2 || B > kMaxB || O < 1) return hipErrorInvalidValue;
+  if (B > kMaxB) return launch_bn_fc_backward_wide(g, xhat, inv_std, dz, dbeta, B, O, s);  // 9 .. 32 images
+  if (B < 2 || O < 1) return hipErrorInvalidValue;
   BnFcParams p{};
   p.g = g; p.xhat = const_cast<float*>(xhat); p.inv_std = const_cast<float*>(inv_std); p.dz = dz; p.dbeta = dbeta;
   p.B = B; p.O = O;

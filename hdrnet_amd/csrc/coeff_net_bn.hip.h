@@ -48,7 +48,8 @@ hipError_t launch_bn_forward(const float* z, float* y, int M, int C, const float
 hipError_t launch_bn_backward(const float* dy, const float* dy2, const float* y, const float* z, const float* save,
                               float* dz, float* dbeta, int M, int C, double* part, hipStream_t s);
 // A fully connected layer: z[b][o] = sum_s zpart[b][s][o]; xhat and y = relu(xhat + beta) are [B][O], inv_std [O];
-// `zeros` (optional): O floats set to 0 (the bias the consumers of y read).  2 <= B <= 8.
+// `zeros` (optional): O floats set to 0 (the bias the consumers of y read).  2 <= B <= 32 (above 8:
+// coeff_fc_wide.hip's kernels).
 hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
                                 float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
                                 float momentum, hipStream_t s);

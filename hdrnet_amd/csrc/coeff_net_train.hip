@@ -24,7 +24,8 @@
 //                     flipped filter -- the forward's 4 x 4 x 16 MFMA kernel with the upsampling and the mask folded
 //                     into the LDS staging and the filter read in place ([Cout][kh][kw][Cin]: four 4-byte loads per
 //                     16-channel group instead of one float4; no transposed copy of the weights per step).
-//   coeff_fc_bwd      a fully connected layer: dW, db and dx in one launch.
+//   coeff_fc_bwd      a fully connected layer: dW, db and dx in one launch (batches of 9 to 32 images: its twin
+//                     coeff_fc_bwd_wide, coeff_fc_wide.hip).
 //
 // Weights are read and gradients written in the layouts torch holds them in (Conv2d weights in channels_last memory
 // order = [Cout][kh][kw][Cin]; Linear weights [out][in]): the training step moves no parameter data.
@@ -32,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coeff_net.hip.h"
+#include "coeff_fc_wide.hip.h"
 #include "coeff_net_bn.hip.h"
 #include "launch.hip.h"
 
@@ -675,6 +677,13 @@ __global__ __launch_bounds__(256) void coeff_fc_bwd(const FcBwdParams p) {
   }
 }
 
+// One workgroup per 16 inputs; more than kMaxB images: the wide kernel.
+hipError_t launch_fc_bwd(const FcBwdParams& p, hipStream_t s) {
+  if (p.B > kMaxB) return launch_fc_bwd_wide(p.x, p.dy, p.w, p.dw, p.db, p.dx, p.B, p.K, p.O, p.mask_x, s);
+  coeff_fc_bwd<<<dim3((unsigned)((p.K + 15) / 16)), 256, 0, s>>>(p);
+  return hipGetLastError();
+}
+
 // ----------------------------------------------------------------------- what the forward did not keep; permutes
 
 struct RecomputeParams {
@@ -1121,10 +1130,13 @@ int recompute_slabs(int P, int C) {
   return slabs <= 32768 ? (int)slabs : 0;
 }
 
-bool train_supported(const hdrnet_coeff_net& net, int B, NetDims* d, const char** limit = nullptr) {
+// `max_b`: the caller's largest batch, kCoeffNarrowMaxB (= kMaxB) or kCoeffWideMaxB (coeff_fc_wide.hip.h); everything but
+// the fully connected layers' kernels takes any batch.
+bool train_supported(const hdrnet_coeff_net& net, int B, int max_b, NetDims* d, const char** limit = nullptr) {
+  static_assert(kMaxB == kCoeffNarrowMaxB, "coeff_fc_bwd's batch is where coeff_fc_bwd_wide's begins");
   if (limit) *limit = nullptr;
   if (!net_dims(net, d)) return false;
-  if (B < 1 || B > kMaxB || net.n_levels != 1 || net.fc_layout != 1) return false;
+  if (B < 1 || B > max_b || max_b > kCoeffWideMaxB || net.n_levels != 1 || net.fc_layout != 1) return false;
   if (d->gl > 256) return false;  // coeff_recompute's shared arrays
   if (d->pred % 4 != 0) {  // coeff_conv_dx reads the prediction layer's gradient, [..][pred], four channels a load
     if (limit) *limit = "gd * n_out * n_in must be a multiple of 4";
@@ -1139,25 +1151,25 @@ bool train_supported(const hdrnet_coeff_net& net, int B, NetDims* d, const char*
 
 }  // namespace
 
-const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B) {
+const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
   const char* limit = nullptr;
-  train_supported(net, B, &d, &limit);
+  train_supported(net, B, max_b, &d, &limit);
   return limit;
 }
 
-size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B) {
+size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
-  if (!train_supported(net, B, &d)) return 0;
+  if (!train_supported(net, B, max_b, &d)) return 0;
   return bwd_space(d, net, B).total * sizeof(float);
 }
 
 // `fwd_ws`: the workspace a forward launch_coefficients() call with the same net and B left behind.
 hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
                                     const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s,
-                                    const char** name) {
+                                    const char** name, int max_b) {
   NetDims d;
-  if (!train_supported(net, B, &d)) return hipErrorInvalidValue;
+  if (!train_supported(net, B, max_b, &d)) return hipErrorInvalidValue;
   *name = "coeff_net_grad";
   const NetWorkspace fw = net_workspace(d);
   const float* fbase = static_cast<const float*>(fwd_ws);
@@ -1215,12 +1227,11 @@ hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net&
   // ---- fully connected layers
   {
     FcBwdParams f3{buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1};
-    coeff_fc_bwd<<<dim3((unsigned)((2 * d.gl + 15) / 16)), 256, 0, s>>>(f3);
+    if ((e = launch_fc_bwd(f3, s)) != hipSuccess) return e;
     FcBwdParams f2{buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], gr.fc_b[1], buf(bs.dx1), B, 4 * d.gl, 2 * d.gl, 1};
-    coeff_fc_bwd<<<dim3((unsigned)((4 * d.gl + 15) / 16)), 256, 0, s>>>(f2);
+    if ((e = launch_fc_bwd(f2, s)) != hipSuccess) return e;
     FcBwdParams f1{G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], gr.fc_b[0], buf(bs.dg2), B, K1, 4 * d.gl, 0};
-    coeff_fc_bwd<<<dim3((unsigned)((K1 + 15) / 16)), 256, 0, s>>>(f1);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_fc_bwd(f1, s)) != hipSuccess) return e;
   }
   // ---- the local path (local2: no bias, no ReLU on its own output -- the fusion's mask --, local1) and the global path's
   // convolutions (conv2, conv1) do not depend on each other: local2 + conv2 in one launch, then local1 + conv1
@@ -1285,19 +1296,19 @@ BnBwdSpace bn_bwd_space(const NetDims& d, const BwdSpace& bs) {
 
 }  // namespace
 
-size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B) {
+size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
-  if (B < 2 || !train_supported(net, B, &d)) return 0;
+  if (B < 2 || !train_supported(net, B, max_b, &d)) return 0;
   return bn_bwd_space(d, bwd_space(d, net, B)).total * sizeof(float);
 }
 
 hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_net_bn& bn,
                                        const hdrnet_coeff_net_bn_grads& grads, const float* dcoeffs, int B,
-                                       const void* fwd_ws, void* workspace, hipStream_t s) {
+                                       const void* fwd_ws, void* workspace, hipStream_t s, int max_b) {
   const hdrnet_coeff_net& net = bn.net;
   const hdrnet_coeff_net_grads& gr = grads.net;
   NetDims d;
-  if (B < 2 || !train_supported(net, B, &d)) return hipErrorInvalidValue;
+  if (B < 2 || !train_supported(net, B, max_b, &d)) return hipErrorInvalidValue;
   const NetWorkspace fw = net_workspace(d);
   const BnWorkspace bw = bn_workspace(d, B);
   const float* fbase = static_cast<const float*>(fwd_ws);
@@ -1344,18 +1355,15 @@ hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_n
   // ---- fully connected layers: coeff_fc_bwd's mask_x applies the ReLU of the layer below, whose batch norm follows
   {
     FcBwdParams f3{buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1};
-    coeff_fc_bwd<<<dim3((unsigned)((2 * d.gl + 15) / 16)), 256, 0, s>>>(f3);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_fc_bwd(f3, s)) != hipSuccess) return e;
     e = launch_bn_fc_backward(buf(bs.dx2), fext(bw.xh2), fext(bw.inv2), buf(bs.dx2), grads.fc_beta[1], B, 2 * d.gl, s);
     if (e != hipSuccess) return e;
     FcBwdParams f2{buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], buf(xs.db_scratch), buf(bs.dx1), B, 4 * d.gl, 2 * d.gl, 1};
-    coeff_fc_bwd<<<dim3((unsigned)((4 * d.gl + 15) / 16)), 256, 0, s>>>(f2);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_fc_bwd(f2, s)) != hipSuccess) return e;
     e = launch_bn_fc_backward(buf(bs.dx1), fext(bw.xh1), fext(bw.inv1), buf(bs.dx1), grads.fc_beta[0], B, 4 * d.gl, s);
     if (e != hipSuccess) return e;
     FcBwdParams f1{G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], buf(xs.db_scratch), buf(bs.dg2), B, K1, 4 * d.gl, 0};
-    coeff_fc_bwd<<<dim3((unsigned)((K1 + 15) / 16)), 256, 0, s>>>(f1);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_fc_bwd(f1, s)) != hipSuccess) return e;
   }
   auto norm_bwd = [&](float* dy, const float* dy2, const float* y, size_t z, size_t save, float* dbeta, int M, int C) {
     return launch_bn_backward(dy, dy2, y, fext(z), fext(save), dy, dbeta, M, C, bnpart, s);

@@ -9,6 +9,7 @@
 
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_train.h"
+#include "coeff_fc_wide.hip.h"
 
 namespace hdrnet_amd {
 
@@ -279,24 +280,26 @@ hipError_t launch_l2_loss_grad(const float* pred, const float* target, const flo
 bool coefficients_supported(const hdrnet_coeff_net& net);
 // unsupported because of a limit of the kernels rather than the shape rules: the limit in words; else null
 const char* coefficients_limit(const hdrnet_coeff_net& net);
-const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B);
+const char* coefficients_grad_limit(const hdrnet_coeff_net& net, int B, int max_b = kCoeffNarrowMaxB);
 size_t coefficients_workspace_bytes(const hdrnet_coeff_net& net, int B);  // 0: unsupported hyper-parameters
 hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,
                                hipStream_t s, const char** name);
 // coeff_net_train.hip -- its VJP with respect to the parameters (no batch norm); fwd_ws = the forward's workspace.
-size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B);  // 0: not supported
+// `max_b`: the largest batch the caller admits, 8 (the C-ABI's first entry points) or 32 (their ..._wide twins, whose
+// fully connected layers run on coeff_fc_wide.hip's kernels above 8 images); the launches for B <= 8 are the same.
+size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b = kCoeffNarrowMaxB);  // 0: not supported
 hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
                                     const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s,
-                                    const char** name);
+                                    const char** name, int max_b = kCoeffNarrowMaxB);
 // The same network trained WITH batch norm (coeff_net_bn.hip's kernels between the launches of the two files above);
-// the workspace queries return 0 outside 2 <= B <= 8 or what the gradient above supports.
-size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B);
+// the workspace queries return 0 outside 2 <= B <= max_b or what the gradient above supports.
+size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b = kCoeffNarrowMaxB);
 hipError_t launch_coefficients_bn(const float* lowres, const hdrnet_coeff_net_bn& bn, float* coeffs, int B,
-                                  void* workspace, hipStream_t s);
-size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B);
+                                  void* workspace, hipStream_t s, int max_b = kCoeffNarrowMaxB);
+size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b = kCoeffNarrowMaxB);
 hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_net_bn& bn,
                                        const hdrnet_coeff_net_bn_grads& grads, const float* dcoeffs, int B,
-                                       const void* fwd_ws, void* workspace, hipStream_t s);
+                                       const void* fwd_ws, void* workspace, hipStream_t s, int max_b = kCoeffNarrowMaxB);
 
 // capi.hip -- the tail of every C-ABI entry point, for those defined beside their kernels too.  The error text
 // (hdrnet_last_error) is thread-local and the kernel name (hdrnet_last_kernel) optional bookkeeping; both live there.

@@ -724,15 +724,34 @@ def _params_ok(params) -> bool:
     return True
 
 
+# The coefficient network's training entry points take batches up to 8; their ``..._wide`` twins
+# (include/hdrnet_amd_coeff_wide.h) up to 32, with the same arguments and, up to 8, the same launches.
+_COEFF_NARROW_BATCH = 8
+_COEFF_WIDE = {
+    "hdrnet_coefficients_grad_workspace_bytes": "hdrnet_coefficients_grad_wide_workspace_bytes",
+    "hdrnet_coefficients_grad_f32": "hdrnet_coefficients_grad_wide_f32",
+    "hdrnet_coefficients_bn_workspace_bytes": "hdrnet_coefficients_bn_wide_workspace_bytes",
+    "hdrnet_coefficients_bn_train_f32": "hdrnet_coefficients_bn_train_wide_f32",
+    "hdrnet_coefficients_bn_grad_workspace_bytes": "hdrnet_coefficients_bn_grad_wide_workspace_bytes",
+    "hdrnet_coefficients_bn_grad_f32": "hdrnet_coefficients_bn_grad_wide_f32",
+}
+
+
+def _coeff_entry(lib, name: str, batch: int):
+    """The training entry point ``name`` for this batch: itself up to 8 images, its wide twin above."""
+    return getattr(lib, name if int(batch) <= _COEFF_NARROW_BATCH else _COEFF_WIDE[name])
+
+
 def coefficients_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, batch: int) -> bool:
     """True if ``coefficients_train`` can run this network (no batch norm is the caller's business): parameters fp32 on
-    the GPU in torch's own layouts, hyper-parameters and batch within the kernels' reach."""
+    the GPU in torch's own layouts, hyper-parameters within the kernels' reach, 1 <= batch <= 32."""
     import ctypes
     params = list(params)
     if len(params) != 2 * n_splat + 4 + 6 + 2 + 1 + 2 or not _params_ok(params):
         return False
     net = _live_net(hyper, n_out, n_in, params, n_splat)
-    return _lib.load().hdrnet_coefficients_grad_workspace_bytes(ctypes.byref(net), int(batch)) > 0
+    query = _coeff_entry(_lib.load(), "hdrnet_coefficients_grad_workspace_bytes", batch)
+    return query(ctypes.byref(net), int(batch)) > 0
 
 
 def _grad_out(p: torch.Tensor) -> torch.Tensor:
@@ -757,7 +776,7 @@ def _grad_out(p: torch.Tensor) -> torch.Tensor:
 
 class _CoefficientsTrain(torch.autograd.Function):
     """Forward = the inference launch sequence on the live parameters, its workspace kept; backward =
-    ``hdrnet_coefficients_grad_f32`` (csrc/coeff_net_train.hip)."""
+    ``hdrnet_coefficients_grad_f32`` (csrc/coeff_net_train.hip), above 8 images ``hdrnet_coefficients_grad_wide_f32``."""
 
     @staticmethod
     def forward(ctx, lowres, hyper, n_out, n_in, n_splat, *params):
@@ -801,10 +820,11 @@ class _CoefficientsTrain(torch.autograd.Function):
         dc = dcoeffs.contiguous()
         lib = _lib.load()
         with torch.cuda.device(dev):
-            wbytes = lib.hdrnet_coefficients_grad_workspace_bytes(ctypes.byref(net), B)
+            wbytes = _coeff_entry(lib, "hdrnet_coefficients_grad_workspace_bytes", B)(ctypes.byref(net), B)
             ws2 = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = lib.hdrnet_coefficients_grad_f32(low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(),
-                                                  ctypes.byref(gr), B, ws2.data_ptr(), wbytes, _stream(dev))
+            rc = _coeff_entry(lib, "hdrnet_coefficients_grad_f32", B)(
+                low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(), ctypes.byref(gr), B, ws2.data_ptr(), wbytes,
+                _stream(dev))
         _lib.check(rc, "CoefficientsGrad")
         return (None, None, None, None, None, *grads)
 
@@ -852,7 +872,7 @@ def _live_net_bn(hyper, n_out: int, n_in: int, params, n_splat: int, stats, eps:
 
 def coefficients_bn_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, stats, batch: int) -> bool:
     """True if ``coefficients_bn_train`` can run this network: parameters and running statistics fp32 on the GPU in
-    torch's own layouts, hyper-parameters within the kernels' reach, 2 <= batch <= 8."""
+    torch's own layouts, hyper-parameters within the kernels' reach, 2 <= batch <= 32."""
     import ctypes
     params, stats = list(params), [tuple(st) for st in stats]
     if len(params) != 2 * n_splat + 4 + 6 + 2 + 1 + 2 or len(stats) != n_splat + 4 or not _params_ok(params):
@@ -861,13 +881,14 @@ def coefficients_bn_train_supported(hyper, n_out: int, n_in: int, params, n_spla
         return False
     net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, 1e-3, 1e-3)
     lib = _lib.load()
-    return (lib.hdrnet_coefficients_bn_workspace_bytes(ctypes.byref(net), int(batch)) > 0
-            and lib.hdrnet_coefficients_bn_grad_workspace_bytes(ctypes.byref(net), int(batch)) > 0)
+    return (_coeff_entry(lib, "hdrnet_coefficients_bn_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0
+            and _coeff_entry(lib, "hdrnet_coefficients_bn_grad_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0)
 
 
 class _CoefficientsBnTrain(torch.autograd.Function):
     """``hdrnet_coefficients_bn_train_f32`` / ``hdrnet_coefficients_bn_grad_f32`` (csrc/coeff_net_bn.hip between the
-    launches of coeff_net.hip / coeff_net_train.hip): the coefficient network with batch norm in training mode."""
+    launches of coeff_net.hip / coeff_net_train.hip): the coefficient network with batch norm in training mode.  Above 8
+    images their ``..._wide`` twins."""
 
     @staticmethod
     def forward(ctx, lowres, hyper, n_out, n_in, n_splat, stats, eps, momentum, *params):
@@ -879,10 +900,10 @@ class _CoefficientsBnTrain(torch.autograd.Function):
         out = torch.empty((B, sb, sb, gd, n_out, n_in), dtype=torch.float32, device=dev)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            wbytes = lib.hdrnet_coefficients_bn_workspace_bytes(ctypes.byref(net), B)
+            wbytes = _coeff_entry(lib, "hdrnet_coefficients_bn_workspace_bytes", B)(ctypes.byref(net), B)
             ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = lib.hdrnet_coefficients_bn_train_f32(low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(),
-                                                      wbytes, _stream(dev))
+            rc = _coeff_entry(lib, "hdrnet_coefficients_bn_train_f32", B)(
+                low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(), wbytes, _stream(dev))
         _lib.check(rc, "CoefficientsBnTrain")
         for st in stats:
             for t in st:  # written through a raw pointer: tell autograd / the fold caches keyed on ._version
@@ -920,10 +941,11 @@ class _CoefficientsBnTrain(torch.autograd.Function):
         dc = dcoeffs.contiguous()
         lib = _lib.load()
         with torch.cuda.device(dev):
-            wbytes = lib.hdrnet_coefficients_bn_grad_workspace_bytes(ctypes.byref(net), B)
+            wbytes = _coeff_entry(lib, "hdrnet_coefficients_bn_grad_workspace_bytes", B)(ctypes.byref(net), B)
             ws2 = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = lib.hdrnet_coefficients_bn_grad_f32(low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(),
-                                                     ctypes.byref(gr), B, ws2.data_ptr(), wbytes, _stream(dev))
+            rc = _coeff_entry(lib, "hdrnet_coefficients_bn_grad_f32", B)(
+                low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(), ctypes.byref(gr), B, ws2.data_ptr(), wbytes,
+                _stream(dev))
         _lib.check(rc, "CoefficientsBnGrad")
         return (None, None, None, None, None, None, None, None, *grads)
 
@@ -933,7 +955,7 @@ def coefficients_bn_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: i
     """``HDRNetCurves._coefficients`` (hdrnet/models.py:62-142) WITH batch norm in training mode (``--batch_norm``,
     hdrnet/layers.py:30-54), differentiable in its weights, biases and betas, on the HIP kernels; moves the running
     statistics of ``stats`` in place.  ``params`` / ``stats`` as ``_live_net_bn`` takes them.  ``lowres_input [B, N, N, 3]``
-    (no gradient, 2 <= B <= 8) -> ``[B, sb, sb, gd, n_out, n_in]``."""
+    (no gradient, 2 <= B <= 32) -> ``[B, sb, sb, gd, n_out, n_in]``."""
     _require_f32("lowres_input", lowres_input)
     _require_gpu("lowres_input", lowres_input)
     stats = tuple(tuple(st) for st in stats)

@@ -218,7 +218,8 @@ class _Coefficients(nn.Module):
     # Training (and any differentiable evaluation) of the network WITHOUT batch norm -- the reference's own training
     # configuration for the guide-network model (scripts/ll/train_nn_guide.sh) -- on the HIP kernels as well: forward
     # + backward in ~35 launches instead of ~130 stock-op launches.  With batch norm ``_use_native_bn_training`` below
-    # decides; when the input itself needs a gradient the torch ops run.  ``native_training = False`` forces them for both.
+    # decides; when the input itself needs a gradient, or the batch exceeds the kernels' 32 images, the torch ops run.
+    # ``native_training = False`` forces them for both.
     native_training = True
 
     def _train_params(self):

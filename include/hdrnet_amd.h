@@ -98,7 +98,9 @@ extern "C" {
  *        hdrnet_coefficients_grad_workspace_bytes also for gd * n_out * n_in no multiple of 4 or >= 65536 (281 read out
  *        of bounds or divided wrongly there).  The entry points name the limit in hdrnet_last_error().
  *   283  + hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 and their workspace queries in
- *        hdrnet_amd_coeff_bn.h, which hdrnet_amd_train.h includes (the coefficient network trained WITH batch norm). */
+ *        hdrnet_amd_coeff_bn.h, which hdrnet_amd_train.h includes (the coefficient network trained WITH batch norm).
+ *   284  + the ..._wide twins of the coefficient network's three training entry points and their workspace queries in
+ *        hdrnet_amd_coeff_wide.h, which hdrnet_amd_train.h includes: batches up to 32 (the first ones stay at 8). */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

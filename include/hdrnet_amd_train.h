@@ -24,6 +24,8 @@
 
 /* the coefficient network trained with batch norm: hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 */
 #include "hdrnet_amd_coeff_bn.h"
+/* the same training entry points, with and without batch norm, for batches up to 32 */
+#include "hdrnet_amd_coeff_wide.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -2,7 +2,7 @@
 """End-to-end timings of the reference's model graphs with the HIP hot path inside
 (BASELINE.json configs #3 and #4 on ONE MI355X; the 8-GPU runs are the driver's).
 
-    python tools/e2e_bench.py [--steps 20] [--feed]
+    python tools/e2e_bench.py [--steps 20] [--feed] [--train-batch B] [--train-crop H W]
 
 config #3: HDRNetPointwiseNNGuide inference, 3840x2160, batch 1 (coefficient net + guide in
            PyTorch-ROCm ops, slice-apply in the HIP kernel).
@@ -10,6 +10,9 @@ config #4: training step (fwd + bwd + Adam) at 1920x1080, 4 images per GPU (= 32
 --feed:    only config #4's graph-captured step, fed three ways, interleaved: from its own static buffers (no feed), by
            pre-made f32 tensors through the staging copy, and by data.DeviceDataset.feed (u8 pairs on the device, drawn
            and prepared into the static buffers each step).
+--train-batch / --train-crop: only the graph-captured training step of HDRNetPointwiseNNGuide at B images of H x W (config
+           #4's step at another batch and crop, e.g. the reference's own --batch_size 16 on 256 x 256 or 512 x 512 crops),
+           with and without batch norm, the coefficient network on the HIP kernels and on stock ops.
 """
 import argparse
 import os
@@ -67,15 +70,55 @@ def feed_bench(dev, steps):
         print(f"config #4  step fed by {k:42s}: {t * 1e3:.3f} ms/step (min {min(v) * 1e3:.3f}) = {B * H * W / 1e6 / t:.0f} MP/s")
 
 
+def train_step_bench(dev, steps, B, H, W):
+    """The whole step (fwd + loss + bwd + Adam) as one hipGraph at B x H x W: five windows of `steps` replays per variant,
+    the variants interleaved; median and extremes."""
+    import statistics
+
+    from hdrnet_amd.runtime import GraphedTrainStep
+    low = torch.rand(B, 256, 256, 3, device=dev)
+    full = torch.rand(B, H, W, 3, device=dev)
+    target = torch.rand(B, H, W, 3, device=dev)
+    steps_of, native_of = {}, {}
+    for bn in (False, True):
+        for native in (True, False):
+            mg = models.HDRNetPointwiseNNGuide(dict(batch_norm=bn)).to(dev).train()
+            mg.coefficients.native_training = native
+            net = mg.coefficients
+            native_of[(bn, native)] = bool(net._use_native_bn_training(low) if bn else net._use_native_training(low))
+            optg = optim.FlatAdam([p for p in mg.parameters() if p.requires_grad], lr=1e-4, epsilon_hat=True)
+            gstep = GraphedTrainStep(mg, lambda out, tgt: metrics.l2_loss(tgt, out), optg, [low, full], [target])
+            steps_of[(bn, native)] = lambda g=gstep: g([low, full], [target])
+    for fn in steps_of.values():  # pre-roll
+        for _ in range(50):
+            fn()
+    res = {k: [] for k in steps_of}
+    for _ in range(5):
+        for k, fn in steps_of.items():
+            res[k].append(timeit(fn, steps))
+    for (bn, native), v in res.items():
+        t = statistics.median(v)
+        print(f"train step {B} x {H} x {W}, {'batch norm' if bn else 'no batch norm'}, coefficient network "
+              f"{'on the HIP kernels' if native_of[(bn, native)] else 'on stock ops'}"
+              f"{'' if native == native_of[(bn, native)] else ' (the HIP kernels do not take this batch)'}: "
+              f"{t * 1e3:.3f} ms/step (min {min(v) * 1e3:.3f}, max {max(v) * 1e3:.3f}) = {B * H * W / 1e6 / t:.0f} MP/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--feed", action="store_true", help="only config #4's step, fed three ways (see the module text)")
+    ap.add_argument("--train-batch", type=int, default=None, help="only the graph-captured training step, at this batch")
+    ap.add_argument("--train-crop", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="only the graph-captured training step, at this crop size (default 1080 1920)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     if args.feed:
         return feed_bench(dev, args.steps)
+    if args.train_batch is not None or args.train_crop is not None:
+        H, W = args.train_crop or (1080, 1920)
+        return train_step_bench(dev, args.steps, args.train_batch or 4, H, W)
 
     m = models.HDRNetPointwiseNNGuide().to(dev).eval()
     low = torch.rand(1, 256, 256, 3, device=dev)
