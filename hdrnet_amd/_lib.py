@@ -164,6 +164,14 @@ COEFF_WIDE_SIGNATURES = {
     "hdrnet_coefficients_bn_grad_wide_f32": (_I, [_FP, _VP, _VP, _FP, _VP, _I, _VP, _SZ, _VP]),
 }
 
+# include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats (the resize that reads u8 / u16, the finest level's
+# slice-apply + up-add with both conversions in registers).
+PYRAMID_IO_SIGNATURES = {
+    "hdrnet_resize_bilinear_io": (_I, [_FP, _I, ctypes.c_float, _FP] + [_I] * 6 + [_VP]),
+    "hdrnet_bilateral_slice_apply_upadd_io_ex": (_I, [_FP] * 4 + [_I, _I, _FP] + [_I] * 9 + [_I, ctypes.c_float, _I] +
+                                                 [_FP, _FP, _I, _U, _VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -216,6 +224,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(TRAIN_SIGNATURES)
     table.update(COEFF_BN_SIGNATURES)
     table.update(COEFF_WIDE_SIGNATURES)
+    table.update(PYRAMID_IO_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

@@ -534,37 +534,7 @@ __device__ __forceinline__ void guide_nn_quad_mfma_u8(const unsigned* __restrict
   }
 }
 
-// div_white / WhiteLevel / io_white_level (tf.to_float(im) / white_level in three instructions): white_level.hip.h
-
-// Load 4 pixels x CIN channels of TI starting at element index e0, as floats / white level.
-// UNSCALED: the samples as they are, (float)v -- the white level then sits in the coefficient image (stage_image IN_SCALE).
-template <typename TI, int N, bool UNSCALED = false>
-__device__ __forceinline__ void load_pixels(const TI* __restrict__ src, size_t e0, const WhiteLevel& wl,
-                                            float (&dst)[N], uint32_t* raw = nullptr) {
-  if constexpr (sizeof(TI) == 4) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) dst[q] = reinterpret_cast<const float*>(src)[e0 + q];
-  } else {
-    static_assert((N * sizeof(TI)) % 4 == 0, "whole dwords per thread");
-    constexpr int ND = N * sizeof(TI) / 4;
-    uint32_t w[ND];
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(src + e0);
-#pragma unroll
-    for (int q = 0; q < ND; ++q) w[q] = p[q];
-    if (raw) {
-#pragma unroll
-      for (int q = 0; q < ND; ++q) raw[q] = w[q];
-    }
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      uint32_t v;
-      if constexpr (sizeof(TI) == 1) v = (w[q >> 2] >> (8 * (q & 3))) & 0xffu;
-      else v = (w[q >> 1] >> (16 * (q & 1))) & 0xffffu;
-      if constexpr (UNSCALED) dst[q] = (float)v;
-      else dst[q] = div_white((float)v, wl);  // tf.to_float(im) / white_level, rounded as TF's IEEE division
-    }
-  }
-}
+// div_white / WhiteLevel / io_white_level (tf.to_float(im) / white_level in three instructions) and load_pixels: white_level.hip.h
 
 struct IoParams {
   const float* grid;
@@ -802,6 +772,8 @@ bool apply_fwd_io_supported(const ApplyIoArgs& a) {
   if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;  // quantised pixels: whole dwords per lane
   return io_geom(a, 0).ok;
 }
+
+rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a) { return io_geom(a, 0); }
 
 size_t curves_guide_prepared_bytes(int Cin) { return Cin == 3 ? CurveCells<3>::kFloats * sizeof(float) : 0; }
 size_t curves_guide_prepared_ok_offset(int Cin) { return Cin == 3 ? (size_t)CurveCells<3>::kOk : 0; }

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "../../include/hdrnet_amd.h"
+#include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
 
@@ -274,7 +275,9 @@ extern "C" {
 // 0.2.8.1: the training-loop entry points of include/hdrnet_amd_train.h set / clear hdrnet_last_error() like the rest
 // 0.2.8.2: the coefficient network's entry points refuse widths their kernels cannot run (workspace queries return 0
 //          where 281 returned a size: include/hdrnet_amd.h)
-int hdrnet_version(void) { return 284; }
+// 0.2.8.5: + include/hdrnet_amd_pyramid_io.h: hdrnet_resize_bilinear_io, hdrnet_bilateral_slice_apply_upadd_io_ex (the
+//          pyramid model's wire formats)
+int hdrnet_version(void) { return 285; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -841,6 +844,69 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
   const char* name = "";
   const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
   return finish_launch(e, "BilateralSliceApplyIO", name);
+}
+
+// ---- include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats ---------------------------------------------
+int hdrnet_resize_bilinear_io(const void* input, int input_dtype, float white_level, float* out, int B, int Hin, int Win,
+                              int Hout, int Wout, int C, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_resize_bilinear_io";
+  if (B < 0 || Hin <= 0 || Win <= 0 || Hout < 0 || Wout < 0)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: bad extents (B=%d, in %dx%d, out %dx%d)", what, B, Hin, Win, Hout, Wout);
+  if (C != 3) return fail(HDRNET_INVALID_ARGUMENT, "%s: C must be 3 (RGB frames), got C=%d", what, C);
+  if (input_dtype < 0 || input_dtype > 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", what, input_dtype);
+  if (!(white_level > 0.0f) || !(white_level <= 3.4028234e38f))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: white_level must be positive and finite", what);
+  if ((long long)B * Hin * Win * 12 >= (1LL << 40))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: input too large", what);
+  if ((long long)B * Hout * Wout == 0) return finish_noop();
+  if (!input || !out) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer", what);
+  if (((uintptr_t)input | (uintptr_t)out) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: input and out must be 4-B aligned (rows are read as aligned dwords)", what);
+  const char* name = "";
+  const hipError_t e = launch_resize_bilinear_io(input, input_dtype, white_level, out, B, Hin, Win, Hout, Wout,
+                                                 static_cast<hipStream_t>(stream), &name);
+  if (e == hipErrorInvalidValue) return fail(HDRNET_INVALID_ARGUMENT, "%s: output too large", what);
+  return finish_launch(e, what, name);
+}
+
+int hdrnet_bilateral_slice_apply_upadd_io_ex(const float* grid, const float* guide, const void* input,
+                                             const float* coarse, int Hc, int Wc, void* out, int B, int H, int W, int GH,
+                                             int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype,
+                                             float white_level, int output_dtype, const float* guide_conv1,
+                                             const float* guide_conv2, int n_feats, unsigned flags, void* stream) {
+  using namespace hdrnet_amd;
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_guide_flags(flags)) return rc;
+  if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
+  if (int rc = check_io_format(input_dtype, white_level, output_dtype)) return rc;
+  if (Hc <= 0 || Wc <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad coarse extents (%d x %d)", Hc, Wc);
+  if ((guide != nullptr) == (guide_conv1 != nullptr))
+    return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
+  if (guide_conv1 && (!guide_conv2 || n_feats <= 0 || n_feats > 4096))
+    return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (!grid || !input || !out || !coarse) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* name = "";
+  if (input_dtype == 0 && output_dtype == 0) {
+    // float32 both ways: the float op itself (its kernel, its bits)
+    return hdrnet_bilateral_slice_apply_upadd_f32_ex(grid, guide, static_cast<const float*>(input), coarse, Hc, Wc,
+                                                     static_cast<float*>(out), B, H, W, GH, GW, GD, Cin, Cout, has_offset,
+                                                     guide_conv1, guide_conv2, n_feats, flags, stream);
+  }
+  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
+                input_dtype, output_dtype, white_level, guide_conv1, guide_conv2, n_feats, nullptr};
+  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
+  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
+  if (!apply_fwd_io_upadd_supported(a, coarse))
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
+                "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32");
+  const hipError_t e = launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name);
+  return finish_launch(e, "BilateralSliceApplyUpAddIO", name);
 }
 
 // Sample preparation (sample_prep.hip).  Everything is checked before any HIP call.  `ragged`: the sources are flat

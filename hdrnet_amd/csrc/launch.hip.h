@@ -10,6 +10,7 @@
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "coeff_fc_wide.hip.h"
+#include "row_geom.h"
 
 namespace hdrnet_amd {
 
@@ -193,6 +194,10 @@ hipError_t launch_apply_fwd_upadd(const ApplyArgs& a, const float* coarse, int H
 // resize_bilinear.hip -- NHWC bilinear resize, align_corners = true (TF legacy semantics).
 hipError_t launch_resize_bilinear(const float* in, float* out, int B, int Hin, int Win, int Hout,
                                   int Wout, int C, hipStream_t s, const char** name);
+// ... of a wire-format frame: in / white_level, input_dtype 0 f32 (the launch above) / 1 u8 / 2 u16; three channels,
+// a 4-byte aligned base (include/hdrnet_amd_pyramid_io.h)
+hipError_t launch_resize_bilinear_io(const void* in, int input_dtype, float white_level, float* out, int B, int Hin, int Win,
+                                     int Hout, int Wout, hipStream_t s, const char** name);
 
 // Sample preparation (sample_prep.hip): wire-format sources -> the fp32 NHWC tensors of a batch, one launch.
 struct SamplePrepArgs {
@@ -217,6 +222,12 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 
 bool apply_fwd_io_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char** name);
+rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a);  // the launch geometry both of them, and the sibling below, read
+// apply_fwd_io_upadd.hip -- the same forward + the up-add of the coarser pyramid level (guide map or guide network; every
+// dtype pair but f32 -> f32, which is launch_apply_fwd_upadd's)
+bool apply_fwd_io_upadd_supported(const ApplyIoArgs& a, const float* coarse);
+hipError_t launch_apply_fwd_io_upadd(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
+                                     const char** name);
 // the curves guide's uniform cell tables (apply_fwd_io.hip: CurveCells), prepared once per parameter set
 size_t curves_guide_prepared_bytes(int Cin);  // 0: no cell tables for this channel count
 size_t curves_guide_prepared_ok_offset(int Cin);  // float index of the buffer's `ok` word

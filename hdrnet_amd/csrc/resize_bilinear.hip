@@ -19,9 +19,12 @@
 // gradient is bit-reproducible.  Entry points in include/hdrnet_amd_train.h.
 #include <hip/hip_runtime.h>
 
+#include <stdint.h>
+
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
 #include "numerics.hip.h"
+#include "white_level.hip.h"
 
 namespace hdrnet_amd {
 namespace {
@@ -163,6 +166,117 @@ __global__ __launch_bounds__(256) void resize_bilinear_grad_ac(const float* __re
   }
 }
 
+// ---- the forward resize reading the WIRE FORMAT (hdrnet_resize_bilinear_io, include/hdrnet_amd_pyramid_io.h) ----------
+// out = resize_bilinear_ac(in / white_level) for uint8 / uint16 RGB: level 1 of the pyramid model built from the frame as it
+// arrives (a 2:1 reduction of a uint8 4K frame reads 25 MB where the float32 frame is 100 MB).  Taps, scales and lerp are
+// resize_bilinear_ac's, expression for expression; value / white_level is div_white (white_level.hip.h).
+// A pixel's two taps of a source row are ADJACENT pixels (x1 = min(ceil(sx), Win - 1) <= floor(sx) + 1): 6 bytes of uint8
+// or 12 of uint16 that start at any byte / even byte (a uint8 row is 3 * Win bytes), i.e. inside 3 / 4 aligned dwords.
+// Those come with ONE load per source row and are realigned in registers (v_alignbyte, as sample_prep.hip does) -- two
+// loads per output pixel instead of twelve single-byte ones.  A thread owns kIoRun consecutive output pixels: 2 * kIoRun
+// independent loads in flight (the kernel is a gather bound by load latency) and 48 contiguous output bytes.  (At the
+// pyramid's 2:1 the taps of neighbouring output pixels are disjoint source pixels, so a run shares no bytes; lanes next to
+// each other read next to each other.)  Every load is of aligned dwords that hold at least one byte of the frame: where
+// the span would pass the frame's last dword the lane loads dword by dword with each index clamped to it, and what a
+// clamped dword returns is only ever the unused right tap of the frame's last pixel.
+constexpr int kIoRun = 4;
+
+struct u32x3a { uint32_t x, y, z; };  // 12 bytes exactly, 4-byte aligned
+typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+
+// l = pixel at sample index e (3 samples), r = the pixel after it, as floats / white level.  `last`: index of the frame
+// buffer's last dword.
+template <typename T>
+__device__ __forceinline__ void load_tap_pair(const uint32_t* __restrict__ base, long long e, long long last,
+                                              const WhiteLevel& wl, float (&l)[3], float (&r)[3]) {
+  constexpr int ND = sizeof(T) == 1 ? 3 : 4;
+  const long long o = e * (long long)sizeof(T);  // byte offset
+  const long long d = o >> 2;
+  const uint32_t shift = (uint32_t)o & 3u;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (d + ND - 1 <= last) {
+    if constexpr (sizeof(T) == 1) {
+      const u32x3a a = *reinterpret_cast<const u32x3a*>(base + d);
+      w[0] = a.x; w[1] = a.y; w[2] = a.z;
+    } else {
+      const u32x4a a = *reinterpret_cast<const u32x4a*>(base + d);
+      w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) w[k] = base[d + k < last ? d + k : last];
+  }
+  uint32_t v[6];
+  if constexpr (sizeof(T) == 1) {
+    const uint32_t a = __builtin_amdgcn_alignbyte(w[1], w[0], shift), b = __builtin_amdgcn_alignbyte(w[2], w[1], shift);
+    v[0] = a & 0xffu; v[1] = (a >> 8) & 0xffu; v[2] = (a >> 16) & 0xffu; v[3] = a >> 24; v[4] = b & 0xffu; v[5] = (b >> 8) & 0xffu;
+  } else {
+    const uint32_t a = __builtin_amdgcn_alignbyte(w[1], w[0], shift), b = __builtin_amdgcn_alignbyte(w[2], w[1], shift),
+                   c = __builtin_amdgcn_alignbyte(w[3], w[2], shift);
+    v[0] = a & 0xffffu; v[1] = a >> 16; v[2] = b & 0xffffu; v[3] = b >> 16; v[4] = c & 0xffffu; v[5] = c >> 16;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    l[c] = div_white((float)v[c], wl);
+    r[c] = div_white((float)v[3 + c], wl);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void resize_bilinear_io_ac(const uint32_t* __restrict__ in, float* __restrict__ out,
+                                                             const WhiteLevel wl, int Hin, int Win, int Hout, int Wout,
+                                                             int nrun, float sh, float sw, long long nruns,
+                                                             long long last, int vec) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= nruns) return;
+  const int x = (int)(p % nrun) * kIoRun;
+  const int y = (int)((p / nrun) % Hout);
+  const long long b = p / ((long long)nrun * Hout);
+  const float sy = mul_rn((float)y, sh);
+  const float fy = floorf(sy);
+  const float ly = sy - fy;
+  const int y0 = min((int)fy, Hin - 1), y1 = min((int)ceilf(sy), Hin - 1);
+  const long long r0 = (b * Hin + y0) * Win, r1 = (b * Hin + y1) * Win;  // first pixel of the two source rows
+  float tl[kIoRun][3], tr[kIoRun][3], bl[kIoRun][3], br[kIoRun][3], lx[kIoRun];
+  bool same[kIoRun];
+#pragma unroll
+  for (int k = 0; k < kIoRun; ++k) {
+    const int xk = min(x + k, Wout - 1);  // a run's pixels past the row repeat its last one and are not stored
+    const float sx = mul_rn((float)xk, sw);
+    const float fx = floorf(sx);
+    lx[k] = sx - fx;
+    const int x0 = min((int)fx, Win - 1), x1 = min((int)ceilf(sx), Win - 1);
+    same[k] = x1 <= x0;
+    load_tap_pair<T>(in, (r0 + x0) * 3, last, wl, tl[k], tr[k]);
+    load_tap_pair<T>(in, (r1 + x0) * 3, last, wl, bl[k], br[k]);
+  }
+  float o[kIoRun * 3];
+#pragma unroll
+  for (int k = 0; k < kIoRun; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float l0 = tl[k][c], l1 = bl[k][c];
+      const float t1 = same[k] ? l0 : tr[k][c], b1 = same[k] ? l1 : br[k][c];
+      const float top = l0 + (t1 - l0) * lx[k];
+      const float bot = l1 + (b1 - l1) * lx[k];
+      o[k * 3 + c] = top + (bot - top) * ly;
+    }
+  }
+  float* op = out + ((b * Hout + y) * Wout + x) * 3;
+  if (vec) {  // uniform: Wout % kIoRun == 0 and a 16-byte aligned output
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(op)[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kIoRun; ++k) {
+      if (x + k < Wout) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) op[k * 3 + c] = o[k * 3 + c];
+      }
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t launch_resize_bilinear(const float* in, float* out, int B, int Hin, int Win, int Hout,
@@ -179,6 +293,38 @@ hipError_t launch_resize_bilinear(const float* in, float* out, int B, int Hin, i
     resize_bilinear_ac<1><<<(unsigned)nblocks, 256, 0, s>>>(in, out, Hin, Win, Hout, Wout, C, sh, sw, npx);
   else
     resize_bilinear_ac<0><<<(unsigned)nblocks, 256, 0, s>>>(in, out, Hin, Win, Hout, Wout, C, sh, sw, npx);
+  return hipGetLastError();
+}
+
+// input_dtype 1 uint8 / 2 uint16 (0 float32 forwards to launch_resize_bilinear: float32 is never scaled); three channels.
+hipError_t launch_resize_bilinear_io(const void* in, int input_dtype, float white_level, float* out, int B, int Hin, int Win,
+                                     int Hout, int Wout, hipStream_t s, const char** name) {
+  if (input_dtype == 0) {
+    const hipError_t e = launch_resize_bilinear(static_cast<const float*>(in), out, B, Hin, Win, Hout, Wout, 3, s, name);
+    *name = "resize_bilinear_io/f32";
+    return e;
+  }
+  if (input_dtype != 1 && input_dtype != 2) return hipErrorInvalidValue;
+  const int nrun = (Wout + kIoRun - 1) / kIoRun;
+  const long long nruns = (long long)B * Hout * nrun;
+  const long long nblocks = (nruns + 255) / 256;
+  if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  const float sh = Hout > 1 ? (float)(Hin - 1) / (float)(Hout - 1) : (float)Hin / (float)Hout;
+  const float sw = Wout > 1 ? (float)(Win - 1) / (float)(Wout - 1) : (float)Win / (float)Wout;
+  const long long bytes = (long long)B * Hin * Win * 3 * (input_dtype == 1 ? 1 : 2);
+  const long long last = (bytes - 1) >> 2;
+  const int vec = (Wout % kIoRun == 0 && ((uintptr_t)out & 15u) == 0) ? 1 : 0;
+  const WhiteLevel wl = io_white_level(white_level);
+  const uint32_t* src = static_cast<const uint32_t*>(in);
+  if (input_dtype == 1) {
+    *name = "resize_bilinear_io/u8";
+    resize_bilinear_io_ac<uint8_t><<<(unsigned)nblocks, 256, 0, s>>>(src, out, wl, Hin, Win, Hout, Wout, nrun, sh, sw, nruns,
+                                                                    last, vec);
+  } else {
+    *name = "resize_bilinear_io/u16";
+    resize_bilinear_io_ac<uint16_t><<<(unsigned)nblocks, 256, 0, s>>>(src, out, wl, Hin, Win, Hout, Wout, nrun, sh, sw,
+                                                                     nruns, last, vec);
+  }
   return hipGetLastError();
 }
 

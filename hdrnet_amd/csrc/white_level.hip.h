@@ -1,8 +1,10 @@
-// tf.to_float(im) / white_level for integer samples, shared by the wire-format forward (apply_fwd_io.hip) and the
-// sample preparation (sample_prep.hip).
+// tf.to_float(im) / white_level for integer samples, shared by the wire-format forwards (apply_fwd_io.hip,
+// apply_fwd_io_upadd.hip), the wire-format resize (resize_bilinear.hip) and the sample preparation (sample_prep.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <stdint.h>
 
 #include <cstring>
 
@@ -37,6 +39,36 @@ inline WhiteLevel io_white_level(float wl) {
   const bool in_range = wl >= 0x1p-40f && wl <= 0x1p40f;
   volatile float r = 1.0f / wl;  // IEEE, correctly rounded
   return WhiteLevel{wl, (all_ones || !in_range) ? 0.0f : (float)r, (float)r};
+}
+
+// Load 4 pixels x CIN channels of TI starting at element index e0, as floats / white level.
+// UNSCALED: the samples as they are, (float)v -- the white level then sits in the coefficient image (stage_image IN_SCALE).
+template <typename TI, int N, bool UNSCALED = false>
+__device__ __forceinline__ void load_pixels(const TI* __restrict__ src, size_t e0, const WhiteLevel& wl,
+                                            float (&dst)[N], uint32_t* raw = nullptr) {
+  if constexpr (sizeof(TI) == 4) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) dst[q] = reinterpret_cast<const float*>(src)[e0 + q];
+  } else {
+    static_assert((N * sizeof(TI)) % 4 == 0, "whole dwords per thread");
+    constexpr int ND = N * sizeof(TI) / 4;
+    uint32_t w[ND];
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(src + e0);
+#pragma unroll
+    for (int q = 0; q < ND; ++q) w[q] = p[q];
+    if (raw) {
+#pragma unroll
+      for (int q = 0; q < ND; ++q) raw[q] = w[q];
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      uint32_t v;
+      if constexpr (sizeof(TI) == 1) v = (w[q >> 2] >> (8 * (q & 3))) & 0xffu;
+      else v = (w[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+      if constexpr (UNSCALED) dst[q] = (float)v;
+      else dst[q] = div_white((float)v, wl);  // tf.to_float(im) / white_level, rounded as TF's IEEE division
+    }
+  }
 }
 
 }  // namespace hdrnet_amd

@@ -37,6 +37,7 @@ from . import _lib
 
 __all__ = ["bilateral_slice", "bilateral_slice_apply", "bilateral_slice_apply_rows", "bilateral_slice_apply_nnguide",
            "bilateral_slice_apply_io", "bilateral_slice_apply_curves", "bilateral_slice_apply_upadd", "resize_bilinear", "input_moments",
+           "resize_bilinear_io", "bilateral_slice_apply_upadd_io",
            "CoefficientWeights", "coefficients", "coefficients_train", "coefficients_train_supported", "guide_fold_batch", "guide_nn_prescale", "curves_guide_prepare",
            "kernel_override", "last_kernel"]
 
@@ -1231,3 +1232,101 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
             n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIO")
     return (out, gout) if return_guide else out
+
+
+_DEFAULT_WHITE = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}
+
+
+def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002
+                       white_level: Optional[float] = None) -> torch.Tensor:
+    """``resize_bilinear(input / white_level, height, width)`` of a wire-format RGB frame in one pass: ``input``
+    ``[B, Hin, Win, 3]`` uint8 / uint16 / float32 (``white_level`` 255 / 65535 / 1 by default; float32 is never scaled),
+    float32 ``[B, height, width, 3]`` out -- level 1 of ``HDRNetGaussianPyrNN``'s input pyramid without a float32 copy of
+    the frame (``hdrnet_resize_bilinear_io``, include/hdrnet_amd_pyramid_io.h).  Same taps and lerp as
+    ``resize_bilinear``; the division is the wire-format forward's IEEE-rounded one.  No autograd."""
+    if not isinstance(input, torch.Tensor) or input.dim() != 4:
+        raise ValueError("input should be 4D (batch, height, width, channels)")
+    if input.dtype not in _DTYPE_CODE:
+        raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
+    if input.shape[3] != 3:
+        raise ValueError(f"resize_bilinear_io takes RGB frames (C = 3), got C = {input.shape[3]}")
+    if min(input.shape[1], input.shape[2]) < 1 or int(height) < 0 or int(width) < 0:
+        raise ValueError(f"bad extents: in {tuple(input.shape)}, out {height} x {width}")
+    _require_gpu("input", input)
+    if white_level is None:
+        white_level = _DEFAULT_WHITE[input.dtype]
+    inp = input.detach().contiguous()
+    B, Hin, Win, C = inp.shape
+    out = torch.empty((B, int(height), int(width), C), dtype=torch.float32, device=inp.device)
+    lib = _lib.load()
+    with torch.cuda.device(inp.device):
+        rc = lib.hdrnet_resize_bilinear_io(inp.data_ptr(), _DTYPE_CODE[input.dtype], float(white_level), out.data_ptr(), B,
+                                           Hin, Win, int(height), int(width), C, _stream(inp.device))
+    _lib.check(rc, "ResizeBilinearIO")
+    return out
+
+
+def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coarse: torch.Tensor,  # noqa: A002
+                                   guide: Optional[torch.Tensor] = None,
+                                   guide_conv1: Optional[torch.Tensor] = None,
+                                   guide_conv2: Optional[torch.Tensor] = None,
+                                   input_white_level: Optional[float] = None,
+                                   out_dtype: torch.dtype = torch.float32,
+                                   has_offset: bool = True, fast_sigmoid: bool = False, prescaled: bool = False,
+                                   guide_curves=None) -> torch.Tensor:
+    """The finest level of ``HDRNetGaussianPyrNN._output`` with the wire formats of ``bilateral_slice_apply_io``:
+    ``wire_out(bilateral_slice_apply(grid, guide, input / input_white_level) + resize_bilinear(coarse -> H x W))`` in one
+    pass.  ``input`` uint8 / uint16 / float32 ``[B, H, W, 3]``, ``coarse`` float32 ``[B, Hc, Wc, 3]``; ``out_dtype``
+    float32, or uint8 ``= (uint8)(255 * clip(., 0, 1))`` with the clip after the up-add.  The guide is a ``guide`` map or
+    the folded guide network (``guide_conv1``, ``guide_conv2``; ``fast_sigmoid`` / ``prescaled`` as in
+    ``bilateral_slice_apply_io``); the curves guide belongs to the single-level models and is refused.  Cin = Cout = 3 with
+    offset.  float32 in with float32 out is ``bilateral_slice_apply_upadd`` itself.  No autograd."""
+    if input.dim() != 4:
+        raise ValueError(f"Input image should be 4D (batch_size, height, width, input_channels), got {tuple(input.shape)}")
+    if input.dtype not in _DTYPE_CODE:
+        raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+    if guide_curves is not None:
+        raise ValueError("bilateral_slice_apply_upadd_io takes a guide map or the guide network: the curves guide has no "
+                         "up-add form")
+    if (guide is None) == (guide_conv1 is None or guide_conv2 is None):
+        raise ValueError("give either a guide map or both guide_conv1 and guide_conv2")
+    if input_white_level is None:
+        input_white_level = _DEFAULT_WHITE[input.dtype]
+    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
+    if (Cin, Cout) != (3, 3) or not has_offset:
+        raise ValueError(f"bilateral_slice_apply_upadd_io supports Cin = Cout = 3 with offset, got Cin = {Cin}, "
+                         f"Cout = {Cout}, has_offset = {bool(has_offset)}")
+    _require_f32("coarse", coarse)
+    if coarse.dim() != 4 or coarse.shape[0] != B or coarse.shape[3] != Cout or min(coarse.shape[1], coarse.shape[2]) < 1:
+        raise ValueError(f"coarse should be [B, Hc, Wc, Cout] = [{B}, >= 1, >= 1, {Cout}], got {tuple(coarse.shape)}")
+    n = 0
+    if guide is not None:
+        _require_f32("guide", guide)
+        if tuple(guide.shape) != (B, H, W):
+            raise ValueError("Input and guide size should match.")
+        _require_gpu("guide", guide)
+        guide = guide.detach().contiguous()
+    else:
+        _require_f32("guide_conv1", guide_conv1)
+        _require_f32("guide_conv2", guide_conv2)
+        n = guide_conv1.shape[0]
+        if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
+            raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
+        guide_conv1, guide_conv2 = guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous()
+    for nm, t in (("grid", grid), ("input", input), ("coarse", coarse)):
+        _require_gpu(nm, t)
+    grid, inp, coarse = grid.detach().contiguous(), input.detach().contiguous(), coarse.detach().contiguous()
+    dev = inp.device
+    out = torch.empty((B, H, W, Cout), dtype=out_dtype, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.hdrnet_bilateral_slice_apply_upadd_io_ex(
+            grid.data_ptr(), _ptr(guide), inp.data_ptr(), coarse.data_ptr(), coarse.shape[1], coarse.shape[2],
+            out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, int(bool(has_offset)), _DTYPE_CODE[input.dtype],
+            float(input_white_level), _DTYPE_CODE[out_dtype], _ptr(guide_conv1) if guide is None else None,
+            _ptr(guide_conv2) if guide is None else None, n,
+            _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyUpAddIO")
+    return out

@@ -707,7 +707,8 @@ class HDRNetGaussianPyrNN(HDRNetPointwiseNNGuide):
     n_scales = 3
     n_out, n_in = 9, 4
 
-    # process(): the pyramid is built from a float32 frame (no wire-format variant of the per-level kernels)
+    # process(): the pyramid is built from a float32 frame; uint8 / uint16 frames and uint8 output go through
+    # process_wire() below
     _process_dtypes = (torch.float32,)
 
     def __init__(self, params: Optional[Dict] = None):
@@ -796,3 +797,42 @@ class HDRNetGaussianPyrNN(HDRNetPointwiseNNGuide):
                                                                  guide_conv2=conv2, has_offset=True,
                                                                  fast_sigmoid=self.fast_sigmoid, prescaled=prescaled)
         return current
+
+    def process_wire(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
+                     white_level: Optional[float] = None) -> torch.Tensor:
+        """Frame in, frame out with the wire formats (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on
+        the device, float32 (default) or uint8 ``= (uint8)(255 * clip(out, 0, 1))`` out.  ``_forward_fused`` step for step,
+        with level 1 resized from the frame as it arrives (``hdrnet_ops.resize_bilinear_io``) and the finest level's
+        conversions in registers (``hdrnet_ops.bilateral_slice_apply_upadd_io``): no float32 copy of the frame exists.
+        ``white_level``: 255 / 65535 / 1 by default.  A float32 frame with float32 out is ``process(frame)``.  The fused
+        path's own condition holds: W % 16 == 0.  (``process`` keeps its float32-only contract.)"""
+        from . import data, hdrnet_ops
+        if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] != 3:
+            raise ValueError("frame should be [B, H, W, 3]")
+        if frame.dtype not in (torch.float32, torch.uint8, torch.uint16):
+            raise TypeError(f"{type(self).__name__}.process_wire takes float32 / uint8 / uint16 frames, got {frame.dtype}")
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+        if self.training:
+            raise RuntimeError("process_wire() is inference: call eval() first")
+        if frame.dtype == torch.float32 and out_dtype == torch.float32:
+            return self.process(frame)
+        if frame.shape[2] % 16 != 0:
+            raise ValueError(f"process_wire runs the fused pyramid kernels, which need W % 16 == 0, got W = {frame.shape[2]}")
+        with torch.no_grad():
+            frame = frame.contiguous()
+            h, w = frame.shape[1:3]
+            low = data.lowres_input(frame, self.params["net_input_size"], white_level)
+            grids = self.coefficients.levels(low)
+            l1 = hdrnet_ops.resize_bilinear_io(frame, h // 2, w // 2, white_level)
+            l2 = hdrnet_ops.resize_bilinear(l1, h // 4, w // 4)
+            gp = [g.inference_params(self.prescale_guide) for g in self.guide]  # guide[0]: the finest level (models.py:278)
+            cur = hdrnet_ops.bilateral_slice_apply_nnguide(grids[0], l2, gp[2][0], gp[2][1], has_offset=True,
+                                                           fast_sigmoid=self.fast_sigmoid, prescaled=gp[2][2])
+            cur = hdrnet_ops.bilateral_slice_apply_upadd(grids[1], l1, cur, guide_conv1=gp[1][0], guide_conv2=gp[1][1],
+                                                         has_offset=True, fast_sigmoid=self.fast_sigmoid,
+                                                         prescaled=gp[1][2])
+            return hdrnet_ops.bilateral_slice_apply_upadd_io(
+                grids[2], frame, cur, guide_conv1=gp[0][0], guide_conv2=gp[0][1], input_white_level=white_level,
+                out_dtype=out_dtype, has_offset=True, fast_sigmoid=self.fast_sigmoid, prescaled=gp[0][2])

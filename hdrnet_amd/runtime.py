@@ -84,6 +84,9 @@ class _Process(torch.nn.Module):
         self.model, self.out_dtype, self.white_level = model, out_dtype, white_level
 
     def forward(self, frame: torch.Tensor) -> torch.Tensor:
+        # a model whose process() is float32-only offers its wire formats as process_wire() (HDRNetGaussianPyrNN)
+        if hasattr(self.model, "process_wire") and (frame.dtype != torch.float32 or self.out_dtype == torch.uint8):
+            return self.model.process_wire(frame, self.out_dtype, self.white_level)
         return self.model.process(frame, self.out_dtype, self.white_level)
 
 

@@ -100,7 +100,9 @@ extern "C" {
  *   283  + hdrnet_coefficients_bn_train_f32 / hdrnet_coefficients_bn_grad_f32 and their workspace queries in
  *        hdrnet_amd_coeff_bn.h, which hdrnet_amd_train.h includes (the coefficient network trained WITH batch norm).
  *   284  + the ..._wide twins of the coefficient network's three training entry points and their workspace queries in
- *        hdrnet_amd_coeff_wide.h, which hdrnet_amd_train.h includes: batches up to 32 (the first ones stay at 8). */
+ *        hdrnet_amd_coeff_wide.h, which hdrnet_amd_train.h includes: batches up to 32 (the first ones stay at 8).
+ *   285  + hdrnet_resize_bilinear_io / hdrnet_bilateral_slice_apply_upadd_io_ex in hdrnet_amd_pyramid_io.h (a header of
+ *        its own, beside this one): the pyramid model's uint8 / uint16 wire formats. */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -11,7 +11,9 @@ u16 / 32767 + u8, hdrnet_lowres_input of a 4K u8 frame), each interleaved round 
 index -> flip -> rot90 -> crop -> .float() / wl -> nearest resize; `prep --ragged` instead times the same u8 batch from a
 packed set of images of mixed extents (hdrnet_prepare_batch_ragged) against the uniform call, interleaved; `metrics` =
 the training step's loss at 4 x 1080p three ways, interleaved: l2_loss with its gradient, l2_loss + metrics.psnr, and
-metrics.Monitor (loss, PSNR and both moving averages from csrc/loss_psnr.hip).  --tools loads the tools build and adds the round-1
+metrics.Monitor (loss, PSNR and both moving averages from csrc/loss_psnr.hip); `pyramid_io` = the pyramid model frame in,
+frame out at 4K and 1080p, u8 -> u8 and u16 / 32767 -> f32: FrameInference over process_wire against the chain a caller had
+before it (frame.float() / wl -> FrameInference over process -> quantise), alternating in one process.  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -82,6 +84,8 @@ def main():
         return prep_ragged(dev, args) if args.ragged else prep(dev, args)
     if args.workload == "metrics":
         return metrics_monitor(dev, args)
+    if args.workload == "pyramid_io":
+        return pyramid_io(dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -466,6 +470,55 @@ def prep_ragged(dev, args):
               f"ragged on the uniform set {mq:8.2f} us ({min(q):8.2f} .. {max(q):8.2f}), / uniform {mq / mu:6.3f}")
     if args.json:
         json.dump(dict(workload="prep --ragged", rows=rows), open(args.json, "w"), indent=1)
+
+
+def pyramid_io(dev, args):
+    """HDRNetGaussianPyrNN frame in, frame out with the wire formats: FrameInference over process_wire (the resize reads the
+    wire format, the finest level converts in registers) against the chain a caller had until now -- frame.float() / wl ->
+    FrameInference over process -> (255 * out.clamp(0, 1)).to(uint8) for uint8 out -- built from stock ops and the float32
+    kernels only.  Per case both are warmed, then run ALTERNATING three times each in one process (baseline, new, baseline,
+    ...); reported: the mean of the three and their spread.  The new path counts as faster where its mean is below the
+    baseline's by more than the baseline's own spread."""
+    from hdrnet_amd import models
+    from hdrnet_amd.runtime import FrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetGaussianPyrNN(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    rows = []
+    for H, W in ((2160, 3840), (1080, 1920)):
+        for in_dtype, wl, out_dtype in ((torch.uint8, 255.0, torch.uint8), (torch.uint16, 32767.0, torch.float32)):
+            hi = 256 if in_dtype == torch.uint8 else 32768
+            frames = [torch.randint(0, hi, (1, H, W, 3), device=dev, dtype=torch.int32, generator=gen).to(in_dtype)
+                      for _ in range(3)]
+            new = FrameInference(m, frames[0], out_dtype=out_dtype, white_level=wl)
+            base = FrameInference(m, frames[0].float() / wl)
+
+            def run_new(k):
+                return new(frames[k % 3])
+
+            def run_base(k):
+                out = base(frames[k % 3].float() / wl)
+                return (255 * out.clamp(0, 1)).to(torch.uint8) if out_dtype == torch.uint8 else out
+
+            for k in range(30):  # both warmed with their shapes
+                run_base(k)
+                run_new(k)
+            torch.cuda.synchronize()
+            b, n = [], []
+            for _ in range(3):
+                b.append(timeit(run_base, args.steps, rounds=1)[0])
+                n.append(timeit(run_new, args.steps, rounds=1)[0])
+            mb, mn = statistics.mean(b), statistics.mean(n)
+            spread = max(b) - min(b)
+            name = f"{H}x{W} {str(in_dtype)[6:]}/{wl:g} -> {str(out_dtype)[6:]}"
+            rows.append(dict(op=name, us_baseline=round(mb, 2), us_baseline_min=round(min(b), 2), us_baseline_max=round(max(b), 2),
+                             us_wire=round(mn, 2), us_wire_min=round(min(n), 2), us_wire_max=round(max(n), 2),
+                             faster_beyond_baseline_spread=bool(mb - mn > spread)))
+            print(f"{name:36s} baseline chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_wire {mn:8.2f} us "
+                  f"({min(n):8.2f} .. {max(n):8.2f})   wire / baseline {mn / mb:6.3f}   "
+                  f"faster by more than the baseline's spread: {mb - mn > spread}")
+    if args.json:
+        json.dump(dict(workload="pyramid_io", rows=rows), open(args.json, "w"), indent=1)
 
 
 def metrics_monitor(dev, args):
