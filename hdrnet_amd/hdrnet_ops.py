@@ -28,6 +28,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import threading
 from typing import Optional, Tuple
 
@@ -145,6 +146,13 @@ def _stream(device: torch.device) -> int:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _workspace(query, *args, device):
+    """``(workspace, bytes)`` for the size ``query(*args)`` answers on the current device: at least 16 bytes, so that its
+    address is never null."""
+    wbytes = query(*args)
+    return torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=device), wbytes
 
 
 # ---- raw forward / backward launches (no autograd) ------------------------------------
@@ -377,8 +385,7 @@ def _guide_backward(inp, guide, dguide, c1, c2, dinput, accumulate: bool):
     dc1, dc2 = torch.empty_like(c1), torch.empty_like(c2)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        wbytes = lib.hdrnet_pointwise_guide_grad_workspace_bytes(npx, Cin, n)
-        ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+        ws, wbytes = _workspace(lib.hdrnet_pointwise_guide_grad_workspace_bytes, npx, Cin, n, device=dev)
         rc = lib.hdrnet_pointwise_guide_grad_f32(
             inp.data_ptr(), guide.data_ptr(), dguide.data_ptr(), c1.data_ptr(), c2.data_ptr(),
             _ptr(dinput), int(bool(accumulate)), dc1.data_ptr(), dc2.data_ptr(), npx, Cin, n,
@@ -492,8 +499,7 @@ class _BilateralSliceApplyCurves(torch.autograd.Function):
             npx, npts = dguide.numel(), shifts.shape[0]
             lib = _lib.load()
             with torch.cuda.device(inp.device):
-                wbytes = lib.hdrnet_curves_guide_grad_workspace_bytes(npx, 3, npts)
-                ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=inp.device)
+                ws, wbytes = _workspace(lib.hdrnet_curves_guide_grad_workspace_bytes, npx, 3, npts, device=inp.device)
                 rc = lib.hdrnet_curves_guide_grad_f32(
                     inp_c.data_ptr(), dguide.data_ptr(), *[t.data_ptr() for t in params], _ptr(dinput), 1,
                     *[t.data_ptr() for t in outs], npx, 3, npts, ws.data_ptr(), wbytes, _stream(inp.device))
@@ -534,8 +540,7 @@ def input_moments(input: torch.Tensor):  # noqa: A002
     mom = torch.empty((Cin, Cin), dtype=torch.float32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        wbytes = lib.hdrnet_input_moments_workspace_bytes(npx, Cin)
-        ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+        ws, wbytes = _workspace(lib.hdrnet_input_moments_workspace_bytes, npx, Cin, device=dev)
         rc = lib.hdrnet_input_moments_f32(inp.data_ptr(), npx, Cin, sums.data_ptr(), mom.data_ptr(),
                                           ws.data_ptr(), wbytes, _stream(dev))
     _lib.check(rc, "InputMoments")
@@ -608,23 +613,82 @@ def guide_fold_batch(w1: torch.Tensor, beta: torch.Tensor, w2: torch.Tensor, b2:
                                  num_batches_tracked, npx, eps, momentum)
 
 
+# ---- the coefficient network's tensors: their order, stated once ----------------------------------------------------
+# The network's tensors travel between ``models._Coefficients``, the four ctypes structs of ``_lib`` and the C ABI as ONE
+# flat list, in the order of ``_coeff_slots``: layer by layer (splat x n_splat, global conv x 2, fc x 3, local1, local2,
+# prediction) the weight, then the layer's second tensor -- its bias or, where batch norm normalises the layer, beta (such
+# a layer has no bias).  local2 has a weight only.  The normalised layers are splat 1 and up, both global convs, fc1, fc2
+# and local1: ``models._Coefficients._bn_layers()`` names the same layers in the same order, which is also the order of
+# the running statistics.  ``models._Coefficients._train_params_bn()`` builds the list from the module; everything below
+# reads it through ``_coeff_fill``, and the network without batch norm is the one in which no layer is normalised.
+@functools.lru_cache(maxsize=None)
+def _coeff_slots(n_splat: int, bn: bool = False):
+    """``(group, index, field)`` of every tensor of the list, ``field`` one of ``w``, ``b``, ``beta``."""
+    layers = ([("splat", i, i > 0) for i in range(n_splat)] + [("global_conv", i, True) for i in range(2)]
+              + [("fc", i, i < 2) for i in range(3)] + [("local", 0, True), ("local", 1, None), ("pred", 0, False)])
+    slots = []
+    for group, i, normalised in layers:
+        slots.append((group, i, "w"))
+        if normalised is not None:  # (None: local2, the reference's use_bias=False)
+            slots.append((group, i, "beta" if bn and normalised else "b"))
+    return tuple(slots)
+
+
+@functools.lru_cache(maxsize=None)
+def _coeff_members(n_splat: int, bn: bool, with_stats: bool):
+    """Where the four structs of ``_lib`` keep each tensor of the list: ``(member, element)``, ``element`` None where the
+    member is no array -- ``pred_w``, ``pred_b``, ``local_beta``, ``local_running_mean``, ``local_running_var``.
+    ``with_stats``: followed by the same for running_mean and running_var of each normalised layer."""
+    def member(group, i, field):
+        return f"{group}_{field}", None if group == "pred" or (group == "local" and field not in ("w", "b")) else i
+
+    slots = _coeff_slots(n_splat, bn)
+    stats = [(group, i, what) for group, i, field in slots if field == "beta" for what in ("running_mean", "running_var")]
+    return tuple(member(*slot) for slot in list(slots) + (stats if with_stats else []))
+
+
+def _coeff_fill(struct, n_splat: int, tensors, bn: bool = False, stats=None):
+    """Write the addresses of ``tensors``, a list in ``_coeff_slots``' order, into ``struct`` -- a ``_lib.CoeffNet``,
+    ``CoeffNetBn``, ``CoeffNetGrads`` or ``CoeffNetBnGrads`` -- and, for a ``CoeffNetBn``, those of ``stats``:
+    ``(running_mean, running_var)`` per normalised layer.  What the network does not use stays null."""
+    if stats is not None:
+        tensors = [*tensors, *(t for st in stats for t in st)]
+    for (member, element), t in zip(_coeff_members(n_splat, bn, stats is not None), tensors):
+        address = None if t is None else t.data_ptr()
+        if element is None:
+            setattr(struct, member, address)
+        else:
+            getattr(struct, member)[element] = address
+    return struct
+
+
+def _coeff_struct(cls, hyper, n_out: int, n_in: int, n_levels: int, fc_layout: int):
+    net = cls()
+    net.net_input_size, net.spatial_bin = int(hyper["net_input_size"]), int(hyper["spatial_bin"])
+    net.luma_bins, net.channel_multiplier = int(hyper["luma_bins"]), int(hyper["channel_multiplier"])
+    net.n_out, net.n_in, net.n_levels, net.fc_layout = int(n_out), int(n_in), int(n_levels), int(fc_layout)
+    return net
+
+
 class CoefficientWeights:
     """The coefficient network's parameters in the layout ``hdrnet_coefficients_f32`` reads
     (include/hdrnet_amd.h): convolutions ``[Cout][kh][kw][Cin]``, fully connected layers ``[in][out]``,
     batch norm folded, fp32, contiguous, on one device.  Holds the tensors alive next to the C struct.
 
     ``params``: net_input_size, spatial_bin, luma_bins, channel_multiplier (hdrnet/bin/train.py:227-236);
-    ``splat`` / ``global_conv`` / ``fc`` / ``local``: lists of ``(weight, bias)`` (bias ``None`` only for the second
+    ``splat`` / ``global_conv`` / ``fc`` / ``local``: lists of ``(weight, bias)`` (bias ``None`` for the second
     local conv, the reference's ``use_bias=False``); ``pred``: ``(weight, bias)``.
     """
 
     def __init__(self, params, n_out: int, n_in: int, n_levels: int, splat, global_conv, fc, local, pred):
         self.params = dict(params)
         self.n_out, self.n_in, self.n_levels = int(n_out), int(n_in), int(n_levels)
-        groups = dict(splat=list(splat), global_conv=list(global_conv), fc=list(fc), local=list(local), pred=[pred])
-        if len(groups["global_conv"]) != 2 or len(groups["fc"]) != 3 or len(groups["local"]) != 2 or not 1 <= len(groups["splat"]) <= 8:
+        splat, global_conv, fc, local = list(splat), list(global_conv), list(fc), list(local)
+        if len(global_conv) != 2 or len(fc) != 3 or len(local) != 2 or not 1 <= len(splat) <= 8:
             raise ValueError("coefficient network: 1-8 splat layers, 2 global convs, 3 fc layers, 2 local convs")
-        self.device = groups["pred"][0][0].device
+        if local[1][1] is not None:
+            raise ValueError("coefficient network: the second local conv has no bias")
+        self.device = pred[0].device
         self._keep = []
 
         def prep(t):
@@ -636,29 +700,15 @@ class CoefficientWeights:
                 raise ValueError("coefficient network parameters must live on one device")
             t = t.detach().contiguous()
             self._keep.append(t)
-            return t.data_ptr()
+            return t
 
-        net = _lib.CoeffNet()
-        net.net_input_size = int(self.params["net_input_size"])
-        net.spatial_bin = int(self.params["spatial_bin"])
-        net.luma_bins = int(self.params["luma_bins"])
-        net.channel_multiplier = int(self.params["channel_multiplier"])
-        net.n_out, net.n_in, net.n_levels = self.n_out, self.n_in, self.n_levels
-        for i, (w, b) in enumerate(groups["splat"]):
-            net.splat_w[i], net.splat_b[i] = prep(w), prep(b)
-        for i, (w, b) in enumerate(groups["global_conv"]):
-            net.global_conv_w[i], net.global_conv_b[i] = prep(w), prep(b)
-        for i, (w, b) in enumerate(groups["fc"]):
-            net.fc_w[i], net.fc_b[i] = prep(w), prep(b)
-        for i, (w, b) in enumerate(groups["local"]):
-            net.local_w[i], net.local_b[i] = prep(w), prep(b)
-        net.pred_w, net.pred_b = prep(pred[0]), prep(pred[1])
-        self.net = net
-        self.n_splat = len(groups["splat"])
+        pairs = splat + global_conv + fc + [local[0], local[1][:1], pred]
+        self.net = _coeff_fill(_coeff_struct(_lib.CoeffNet, self.params, self.n_out, self.n_in, self.n_levels, 0),
+                               len(splat), [prep(t) for pair in pairs for t in pair])
+        self.n_splat = len(splat)
 
     def supported(self, batch: int = 1) -> bool:
         """False: hyper-parameters outside the kernels' reach (run the stock-op graph instead)."""
-        import ctypes
         return _lib.load().hdrnet_coefficients_workspace_bytes(ctypes.byref(self.net), int(batch)) > 0
 
 
@@ -666,7 +716,6 @@ def coefficients(lowres_input: torch.Tensor, weights: CoefficientWeights) -> tor
     """``HDRNetCurves._coefficients`` (hdrnet/models.py:62-142) in inference mode, on the HIP kernels of
     csrc/coeff_net.hip: ``lowres_input [B, N, N, 3]`` -> ``[B, sb, sb, gd, n_out, n_in]`` (``n_levels`` > 1:
     ``[n_levels, B, sb, sb, gd, n_out / n_levels, n_in]``, every level's grid contiguous).  No autograd."""
-    import ctypes
     _require_f32("lowres_input", lowres_input)
     if lowres_input.dim() != 4 or lowres_input.shape[3] != 3:
         raise ValueError(f"lowres_input should be [batch, N, N, 3], got {tuple(lowres_input.shape)}")
@@ -684,33 +733,28 @@ def coefficients(lowres_input: torch.Tensor, weights: CoefficientWeights) -> tor
     out = torch.empty((L,) + shape if L > 1 else shape, dtype=torch.float32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        wbytes = lib.hdrnet_coefficients_workspace_bytes(ctypes.byref(weights.net), B)
-        ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+        ws, wbytes = _workspace(lib.hdrnet_coefficients_workspace_bytes, ctypes.byref(weights.net), B, device=dev)
         rc = lib.hdrnet_coefficients_f32(low.data_ptr(), ctypes.byref(weights.net), out.data_ptr(), B,
                                          ws.data_ptr(), wbytes, _stream(dev))
     _lib.check(rc, "Coefficients")
     return out
 
 
+def _live_net_bn(hyper, n_out: int, n_in: int, params, n_splat: int, stats, eps: float, momentum: float):
+    """``hdrnet_coeff_net_bn`` over the module's LIVE parameters and buffers (no copies): Conv2d weights must be in
+    channels_last memory order (= [Cout][kh][kw][Cin]), Linear weights are taken as they are (fc_layout = 1).  ``params``
+    in ``_coeff_slots``' order with batch norm; ``stats``: ``(running_mean, running_var)`` of the normalised layers in the
+    same order.  ``stats = None``: the plain ``hdrnet_coeff_net`` of the network without batch norm."""
+    bn = stats is not None
+    net = _coeff_struct(_lib.CoeffNetBn if bn else _lib.CoeffNet, hyper, n_out, n_in, 1, 1)
+    if bn:
+        net.eps, net.momentum = float(eps), float(momentum)
+    return _coeff_fill(net, n_splat, params, bn, stats)
+
+
 def _live_net(hyper, n_out: int, n_in: int, params, n_splat: int):
-    """``hdrnet_coeff_net`` over the module's LIVE parameters (no copies): Conv2d weights must be in channels_last memory
-    order (= [Cout][kh][kw][Cin]), Linear weights are taken as they are (fc_layout = 1).  ``params`` in the order
-    splat (w, b) x n_splat, global conv (w, b) x 2, fc (w, b) x 3, local1 (w, b), local2 w, prediction (w, b)."""
-    net = _lib.CoeffNet()
-    net.net_input_size, net.spatial_bin = int(hyper["net_input_size"]), int(hyper["spatial_bin"])
-    net.luma_bins, net.channel_multiplier = int(hyper["luma_bins"]), int(hyper["channel_multiplier"])
-    net.n_out, net.n_in, net.n_levels, net.fc_layout = int(n_out), int(n_in), 1, 1
-    it = iter(params)
-    for i in range(n_splat):
-        net.splat_w[i], net.splat_b[i] = next(it).data_ptr(), next(it).data_ptr()
-    for i in range(2):
-        net.global_conv_w[i], net.global_conv_b[i] = next(it).data_ptr(), next(it).data_ptr()
-    for i in range(3):
-        net.fc_w[i], net.fc_b[i] = next(it).data_ptr(), next(it).data_ptr()
-    net.local_w[0], net.local_b[0] = next(it).data_ptr(), next(it).data_ptr()
-    net.local_w[1] = next(it).data_ptr()
-    net.pred_w, net.pred_b = next(it).data_ptr(), next(it).data_ptr()
-    return net
+    """``hdrnet_coeff_net`` over the LIVE parameters of a network without batch norm, ``params`` in ``_coeff_slots``' order."""
+    return _live_net_bn(hyper, n_out, n_in, params, n_splat, None, 0.0, 0.0)
 
 
 def _params_ok(params) -> bool:
@@ -726,7 +770,8 @@ def _params_ok(params) -> bool:
 
 
 # The coefficient network's training entry points take batches up to 8; their ``..._wide`` twins
-# (include/hdrnet_amd_coeff_wide.h) up to 32, with the same arguments and, up to 8, the same launches.
+# (include/hdrnet_amd_coeff_wide.h) up to 32, with the same arguments and, up to 8, the same launches.  The forward
+# without batch norm is the inference one, which has no twin: it takes 32 images as it is.
 _COEFF_NARROW_BATCH = 8
 _COEFF_WIDE = {
     "hdrnet_coefficients_grad_workspace_bytes": "hdrnet_coefficients_grad_wide_workspace_bytes",
@@ -736,19 +781,25 @@ _COEFF_WIDE = {
     "hdrnet_coefficients_bn_grad_workspace_bytes": "hdrnet_coefficients_bn_grad_wide_workspace_bytes",
     "hdrnet_coefficients_bn_grad_f32": "hdrnet_coefficients_bn_grad_wide_f32",
 }
+# batch norm? -> (forward's workspace query, forward, its label; the gradient's workspace query, gradient, its label)
+_COEFF_TRAIN = {
+    False: ("hdrnet_coefficients_workspace_bytes", "hdrnet_coefficients_f32", "Coefficients",
+            "hdrnet_coefficients_grad_workspace_bytes", "hdrnet_coefficients_grad_f32", "CoefficientsGrad"),
+    True: ("hdrnet_coefficients_bn_workspace_bytes", "hdrnet_coefficients_bn_train_f32", "CoefficientsBnTrain",
+           "hdrnet_coefficients_bn_grad_workspace_bytes", "hdrnet_coefficients_bn_grad_f32", "CoefficientsBnGrad"),
+}
 
 
 def _coeff_entry(lib, name: str, batch: int):
-    """The training entry point ``name`` for this batch: itself up to 8 images, its wide twin above."""
-    return getattr(lib, name if int(batch) <= _COEFF_NARROW_BATCH else _COEFF_WIDE[name])
+    """The training entry point ``name`` for this batch: itself up to 8 images, its wide twin (if it has one) above."""
+    return getattr(lib, name if int(batch) <= _COEFF_NARROW_BATCH else _COEFF_WIDE.get(name, name))
 
 
 def coefficients_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, batch: int) -> bool:
     """True if ``coefficients_train`` can run this network (no batch norm is the caller's business): parameters fp32 on
     the GPU in torch's own layouts, hyper-parameters within the kernels' reach, 1 <= batch <= 32."""
-    import ctypes
     params = list(params)
-    if len(params) != 2 * n_splat + 4 + 6 + 2 + 1 + 2 or not _params_ok(params):
+    if len(params) != len(_coeff_slots(n_splat)) or not _params_ok(params):
         return False
     net = _live_net(hyper, n_out, n_in, params, n_splat)
     query = _coeff_entry(_lib.load(), "hdrnet_coefficients_grad_workspace_bytes", batch)
@@ -776,137 +827,27 @@ def _grad_out(p: torch.Tensor) -> torch.Tensor:
 
 
 class _CoefficientsTrain(torch.autograd.Function):
-    """Forward = the inference launch sequence on the live parameters, its workspace kept; backward =
-    ``hdrnet_coefficients_grad_f32`` (csrc/coeff_net_train.hip), above 8 images ``hdrnet_coefficients_grad_wide_f32``."""
-
-    @staticmethod
-    def forward(ctx, lowres, hyper, n_out, n_in, n_splat, *params):
-        import ctypes
-        low = lowres.detach().contiguous()
-        B, dev = low.shape[0], low.device
-        net = _live_net(hyper, n_out, n_in, params, n_splat)
-        sb, gd = int(hyper["spatial_bin"]), int(hyper["luma_bins"])
-        out = torch.empty((B, sb, sb, gd, n_out, n_in), dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            wbytes = lib.hdrnet_coefficients_workspace_bytes(ctypes.byref(net), B)
-            ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = lib.hdrnet_coefficients_f32(low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(), wbytes,
-                                             _stream(dev))
-        _lib.check(rc, "Coefficients")
-        ctx.save_for_backward(low, ws, *params)
-        ctx.meta = (dict(hyper), int(n_out), int(n_in), int(n_splat))
-        return out
-
-    @staticmethod
-    def backward(ctx, dcoeffs):
-        import ctypes
-        low, ws = ctx.saved_tensors[:2]
-        params = ctx.saved_tensors[2:]
-        hyper, n_out, n_in, n_splat = ctx.meta
-        B, dev = low.shape[0], low.device
-        net = _live_net(hyper, n_out, n_in, params, n_splat)
-        grads = [_grad_out(p) for p in params]
-        gr = _lib.CoeffNetGrads()
-        it = iter(grads)
-        for i in range(n_splat):
-            gr.splat_w[i], gr.splat_b[i] = next(it).data_ptr(), next(it).data_ptr()
-        for i in range(2):
-            gr.global_conv_w[i], gr.global_conv_b[i] = next(it).data_ptr(), next(it).data_ptr()
-        for i in range(3):
-            gr.fc_w[i], gr.fc_b[i] = next(it).data_ptr(), next(it).data_ptr()
-        gr.local_w[0], gr.local_b[0] = next(it).data_ptr(), next(it).data_ptr()
-        gr.local_w[1] = next(it).data_ptr()
-        gr.pred_w, gr.pred_b = next(it).data_ptr(), next(it).data_ptr()
-        dc = dcoeffs.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            wbytes = _coeff_entry(lib, "hdrnet_coefficients_grad_workspace_bytes", B)(ctypes.byref(net), B)
-            ws2 = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = _coeff_entry(lib, "hdrnet_coefficients_grad_f32", B)(
-                low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(), ctypes.byref(gr), B, ws2.data_ptr(), wbytes,
-                _stream(dev))
-        _lib.check(rc, "CoefficientsGrad")
-        return (None, None, None, None, None, *grads)
-
-
-def coefficients_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: int, params, n_splat: int) -> torch.Tensor:
-    """``HDRNetCurves._coefficients`` (hdrnet/models.py:62-142) WITHOUT batch norm, differentiable in its parameters:
-    forward and backward on the HIP kernels of csrc/coeff_net.hip / coeff_net_train.hip, reading the parameters and
-    writing their gradients in torch's own layouts.  ``lowres_input [B, N, N, 3]`` (no gradient) ->
-    ``[B, sb, sb, gd, n_out, n_in]``."""
-    _require_f32("lowres_input", lowres_input)
-    _require_gpu("lowres_input", lowres_input)
-    return _CoefficientsTrain.apply(lowres_input, hyper, n_out, n_in, n_splat, *params)
-
-
-def _live_net_bn(hyper, n_out: int, n_in: int, params, n_splat: int, stats, eps: float, momentum: float):
-    """``hdrnet_coeff_net_bn`` over the module's LIVE parameters and buffers.  ``params`` in ``_live_net``'s order with
-    beta where a normalised layer (splat 1.., both global convs, fc1, fc2, local1) would have its bias; ``stats``:
-    ``(running_mean, running_var)`` of those layers in the same order."""
-    net = _lib.CoeffNetBn()
-    net.net_input_size, net.spatial_bin = int(hyper["net_input_size"]), int(hyper["spatial_bin"])
-    net.luma_bins, net.channel_multiplier = int(hyper["luma_bins"]), int(hyper["channel_multiplier"])
-    net.n_out, net.n_in, net.n_levels, net.fc_layout = int(n_out), int(n_in), 1, 1
-    net.eps, net.momentum = float(eps), float(momentum)
-    it, st = iter(params), iter(stats)
-    for i in range(n_splat):
-        net.splat_w[i] = next(it).data_ptr()
-        if i == 0:
-            net.splat_b[0] = next(it).data_ptr()
-        else:
-            net.splat_beta[i] = next(it).data_ptr()
-            net.splat_running_mean[i], net.splat_running_var[i] = (t.data_ptr() for t in next(st))
-    for i in range(2):
-        net.global_conv_w[i], net.global_conv_beta[i] = next(it).data_ptr(), next(it).data_ptr()
-        net.global_conv_running_mean[i], net.global_conv_running_var[i] = (t.data_ptr() for t in next(st))
-    for i in range(2):
-        net.fc_w[i], net.fc_beta[i] = next(it).data_ptr(), next(it).data_ptr()
-        net.fc_running_mean[i], net.fc_running_var[i] = (t.data_ptr() for t in next(st))
-    net.fc_w[2], net.fc_b[2] = next(it).data_ptr(), next(it).data_ptr()
-    net.local_w[0], net.local_beta = next(it).data_ptr(), next(it).data_ptr()
-    net.local_running_mean, net.local_running_var = (t.data_ptr() for t in next(st))
-    net.local_w[1] = next(it).data_ptr()
-    net.pred_w, net.pred_b = next(it).data_ptr(), next(it).data_ptr()
-    return net
-
-
-def coefficients_bn_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, stats, batch: int) -> bool:
-    """True if ``coefficients_bn_train`` can run this network: parameters and running statistics fp32 on the GPU in
-    torch's own layouts, hyper-parameters within the kernels' reach, 2 <= batch <= 32."""
-    import ctypes
-    params, stats = list(params), [tuple(st) for st in stats]
-    if len(params) != 2 * n_splat + 4 + 6 + 2 + 1 + 2 or len(stats) != n_splat + 4 or not _params_ok(params):
-        return False
-    if not _params_ok([t for st in stats for t in st]):
-        return False
-    net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, 1e-3, 1e-3)
-    lib = _lib.load()
-    return (_coeff_entry(lib, "hdrnet_coefficients_bn_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0
-            and _coeff_entry(lib, "hdrnet_coefficients_bn_grad_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0)
-
-
-class _CoefficientsBnTrain(torch.autograd.Function):
-    """``hdrnet_coefficients_bn_train_f32`` / ``hdrnet_coefficients_bn_grad_f32`` (csrc/coeff_net_bn.hip between the
-    launches of coeff_net.hip / coeff_net_train.hip): the coefficient network with batch norm in training mode.  Above 8
-    images their ``..._wide`` twins."""
+    """The coefficient network on its live parameters, for training.  Without batch norm (``stats = None``): forward = the
+    inference launch sequence, its workspace kept; backward = ``hdrnet_coefficients_grad_f32`` (csrc/coeff_net_train.hip).
+    With batch norm in training mode: ``hdrnet_coefficients_bn_train_f32`` / ``hdrnet_coefficients_bn_grad_f32``
+    (csrc/coeff_net_bn.hip between the launches of coeff_net.hip / coeff_net_train.hip), which move the running
+    statistics of ``stats`` in place.  Above 8 images the ``..._wide`` twins (``_coeff_entry``)."""
 
     @staticmethod
     def forward(ctx, lowres, hyper, n_out, n_in, n_splat, stats, eps, momentum, *params):
-        import ctypes
         low = lowres.detach().contiguous()
         B, dev = low.shape[0], low.device
         net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, eps, momentum)
         sb, gd = int(hyper["spatial_bin"]), int(hyper["luma_bins"])
         out = torch.empty((B, sb, sb, gd, n_out, n_in), dtype=torch.float32, device=dev)
+        query, run, label = _COEFF_TRAIN[stats is not None][:3]
         lib = _lib.load()
         with torch.cuda.device(dev):
-            wbytes = _coeff_entry(lib, "hdrnet_coefficients_bn_workspace_bytes", B)(ctypes.byref(net), B)
-            ws = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = _coeff_entry(lib, "hdrnet_coefficients_bn_train_f32", B)(
-                low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(), wbytes, _stream(dev))
-        _lib.check(rc, "CoefficientsBnTrain")
-        for st in stats:
+            ws, wbytes = _workspace(_coeff_entry(lib, query, B), ctypes.byref(net), B, device=dev)
+            rc = _coeff_entry(lib, run, B)(low.data_ptr(), ctypes.byref(net), out.data_ptr(), B, ws.data_ptr(), wbytes,
+                                           _stream(dev))
+        _lib.check(rc, label)
+        for st in stats or ():
             for t in st:  # written through a raw pointer: tell autograd / the fold caches keyed on ._version
                 torch.autograd.graph.increment_version(t)
         ctx.save_for_backward(low, ws, *params)
@@ -916,39 +857,52 @@ class _CoefficientsBnTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dcoeffs):
-        import ctypes
-        low, ws = ctx.saved_tensors[:2]
-        params = ctx.saved_tensors[2:]
+        low, ws, *params = ctx.saved_tensors
         hyper, n_out, n_in, n_splat, eps, momentum = ctx.meta
+        bn = ctx.stats is not None
         B, dev = low.shape[0], low.device
         net = _live_net_bn(hyper, n_out, n_in, params, n_splat, ctx.stats, eps, momentum)
         grads = [_grad_out(p) for p in params]
-        gr = _lib.CoeffNetBnGrads()
-        it = iter(grads)
-        for i in range(n_splat):
-            gr.splat_w[i] = next(it).data_ptr()
-            if i == 0:
-                gr.splat_b[0] = next(it).data_ptr()
-            else:
-                gr.splat_beta[i] = next(it).data_ptr()
-        for i in range(2):
-            gr.global_conv_w[i], gr.global_conv_beta[i] = next(it).data_ptr(), next(it).data_ptr()
-        for i in range(2):
-            gr.fc_w[i], gr.fc_beta[i] = next(it).data_ptr(), next(it).data_ptr()
-        gr.fc_w[2], gr.fc_b[2] = next(it).data_ptr(), next(it).data_ptr()
-        gr.local_w[0], gr.local_beta = next(it).data_ptr(), next(it).data_ptr()
-        gr.local_w[1] = next(it).data_ptr()
-        gr.pred_w, gr.pred_b = next(it).data_ptr(), next(it).data_ptr()
+        gr = _coeff_fill(_lib.CoeffNetBnGrads() if bn else _lib.CoeffNetGrads(), n_splat, grads, bn)
         dc = dcoeffs.contiguous()
+        query, run, label = _COEFF_TRAIN[bn][3:]
         lib = _lib.load()
         with torch.cuda.device(dev):
-            wbytes = _coeff_entry(lib, "hdrnet_coefficients_bn_grad_workspace_bytes", B)(ctypes.byref(net), B)
-            ws2 = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            rc = _coeff_entry(lib, "hdrnet_coefficients_bn_grad_f32", B)(
+            ws2, wbytes = _workspace(_coeff_entry(lib, query, B), ctypes.byref(net), B, device=dev)
+            rc = _coeff_entry(lib, run, B)(
                 low.data_ptr(), ctypes.byref(net), ws.data_ptr(), dc.data_ptr(), ctypes.byref(gr), B, ws2.data_ptr(), wbytes,
                 _stream(dev))
-        _lib.check(rc, "CoefficientsBnGrad")
+        _lib.check(rc, label)
         return (None, None, None, None, None, None, None, None, *grads)
+
+
+class _CoefficientsBnTrain(_CoefficientsTrain):
+    """The same function under a name of its own: the autograd graph then says which of the two paths a step took."""
+
+
+def coefficients_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: int, params, n_splat: int) -> torch.Tensor:
+    """``HDRNetCurves._coefficients`` (hdrnet/models.py:62-142) WITHOUT batch norm, differentiable in its parameters:
+    forward and backward on the HIP kernels of csrc/coeff_net.hip / coeff_net_train.hip, reading the parameters and
+    writing their gradients in torch's own layouts.  ``lowres_input [B, N, N, 3]`` (no gradient) ->
+    ``[B, sb, sb, gd, n_out, n_in]``."""
+    _require_f32("lowres_input", lowres_input)
+    _require_gpu("lowres_input", lowres_input)
+    return _CoefficientsTrain.apply(lowres_input, hyper, n_out, n_in, n_splat, None, 0.0, 0.0, *params)
+
+
+def coefficients_bn_train_supported(hyper, n_out: int, n_in: int, params, n_splat: int, stats, batch: int) -> bool:
+    """True if ``coefficients_bn_train`` can run this network: parameters and running statistics fp32 on the GPU in
+    torch's own layouts, hyper-parameters within the kernels' reach, 2 <= batch <= 32."""
+    params, stats = list(params), [tuple(st) for st in stats]
+    slots = _coeff_slots(n_splat, True)
+    if len(params) != len(slots) or len(stats) != sum(field == "beta" for _, _, field in slots) or not _params_ok(params):
+        return False
+    if not _params_ok([t for st in stats for t in st]):
+        return False
+    net = _live_net_bn(hyper, n_out, n_in, params, n_splat, stats, 1e-3, 1e-3)
+    lib = _lib.load()
+    return (_coeff_entry(lib, "hdrnet_coefficients_bn_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0
+            and _coeff_entry(lib, "hdrnet_coefficients_bn_grad_workspace_bytes", batch)(ctypes.byref(net), int(batch)) > 0)
 
 
 def coefficients_bn_train(lowres_input: torch.Tensor, hyper, n_out: int, n_in: int, params, n_splat: int, stats,
@@ -1068,6 +1022,7 @@ def bilateral_slice_apply_upadd(grid: torch.Tensor, input: torch.Tensor, coarse:
 
 
 _DTYPE_CODE = {torch.float32: 0, torch.uint8: 1, torch.uint16: 2}
+_DEFAULT_WHITE = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}
 
 
 def _check_io(grid, input, has_offset):  # noqa: A002
@@ -1092,6 +1047,23 @@ def _check_io(grid, input, has_offset):  # noqa: A002
             if has_offset else
             "Slicing without affine offset, grid should have output_channels * input_channels channels.")
     return B, H, W, GH, GW, GD, Cin, C // Cj
+
+
+def _io_guide(guide, guide_conv1, guide_conv2, bhw, Cin):
+    """The guide of a wire-format entry point, checked: ``(guide map, None, None, 0)`` or ``(None, guide_conv1,
+    guide_conv2, n)``, detached and contiguous.  The caller has made sure that exactly one of the two is given."""
+    if guide is not None:
+        _require_f32("guide", guide)
+        if tuple(guide.shape) != tuple(bhw):
+            raise ValueError("Input and guide size should match.")
+        _require_gpu("guide", guide)
+        return guide.detach().contiguous(), None, None, 0
+    _require_f32("guide_conv1", guide_conv1)
+    _require_f32("guide_conv2", guide_conv2)
+    n = guide_conv1.shape[0]
+    if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
+        raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
+    return None, guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous(), n
 
 
 def curves_guide_prepare(shifts: torch.Tensor, slopes: torch.Tensor) -> Optional[torch.Tensor]:
@@ -1137,7 +1109,7 @@ def _apply_io_curves(grid, input, curves, input_white_level, out_dtype, has_offs
         if tuple(t.shape) != shape or npts <= 0:
             raise ValueError(f"guide_curves.{nm} should be {list(shape)}, got {list(t.shape)}")
     if input_white_level is None:
-        input_white_level = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}[input.dtype]
+        input_white_level = _DEFAULT_WHITE[input.dtype]
     for nm, t in (("grid", grid), ("input", input), ("guide_curves.ccm", ccm), ("guide_curves.shifts", shifts),
                   ("guide_curves.slopes", slopes), ("guide_curves.mix", mix)):
         _require_gpu(nm, t)
@@ -1201,22 +1173,9 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     if (guide is None) == (guide_conv1 is None or guide_conv2 is None):
         raise ValueError("give either a guide map or both guide_conv1 and guide_conv2")
     if input_white_level is None:
-        input_white_level = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}[input.dtype]
+        input_white_level = _DEFAULT_WHITE[input.dtype]
     B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
-    n = 0
-    if guide is not None:
-        _require_f32("guide", guide)
-        if tuple(guide.shape) != (B, H, W):
-            raise ValueError("Input and guide size should match.")
-        _require_gpu("guide", guide)
-        guide = guide.detach().contiguous()
-    else:
-        _require_f32("guide_conv1", guide_conv1)
-        _require_f32("guide_conv2", guide_conv2)
-        n = guide_conv1.shape[0]
-        if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
-            raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
-        guide_conv1, guide_conv2 = guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous()
+    guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), Cin)
     _require_gpu("grid", grid)
     _require_gpu("input", input)
     grid, inp = grid.detach().contiguous(), input.detach().contiguous()
@@ -1228,13 +1187,9 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
         rc = lib.hdrnet_bilateral_slice_apply_io_ex(
             grid.data_ptr(), _ptr(guide), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
             int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
-            _ptr(guide_conv1) if guide is None else None, _ptr(guide_conv2) if guide is None else None,
-            n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
+            _ptr(c1), _ptr(c2), n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIO")
     return (out, gout) if return_guide else out
-
-
-_DEFAULT_WHITE = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}
 
 
 def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002
@@ -1301,20 +1256,7 @@ def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coar
     _require_f32("coarse", coarse)
     if coarse.dim() != 4 or coarse.shape[0] != B or coarse.shape[3] != Cout or min(coarse.shape[1], coarse.shape[2]) < 1:
         raise ValueError(f"coarse should be [B, Hc, Wc, Cout] = [{B}, >= 1, >= 1, {Cout}], got {tuple(coarse.shape)}")
-    n = 0
-    if guide is not None:
-        _require_f32("guide", guide)
-        if tuple(guide.shape) != (B, H, W):
-            raise ValueError("Input and guide size should match.")
-        _require_gpu("guide", guide)
-        guide = guide.detach().contiguous()
-    else:
-        _require_f32("guide_conv1", guide_conv1)
-        _require_f32("guide_conv2", guide_conv2)
-        n = guide_conv1.shape[0]
-        if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
-            raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
-        guide_conv1, guide_conv2 = guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous()
+    guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), Cin)
     for nm, t in (("grid", grid), ("input", input), ("coarse", coarse)):
         _require_gpu(nm, t)
     grid, inp, coarse = grid.detach().contiguous(), input.detach().contiguous(), coarse.detach().contiguous()
@@ -1325,8 +1267,7 @@ def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coar
         rc = lib.hdrnet_bilateral_slice_apply_upadd_io_ex(
             grid.data_ptr(), _ptr(guide), inp.data_ptr(), coarse.data_ptr(), coarse.shape[1], coarse.shape[2],
             out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, int(bool(has_offset)), _DTYPE_CODE[input.dtype],
-            float(input_white_level), _DTYPE_CODE[out_dtype], _ptr(guide_conv1) if guide is None else None,
-            _ptr(guide_conv2) if guide is None else None, n,
+            float(input_white_level), _DTYPE_CODE[out_dtype], _ptr(c1), _ptr(c2), n,
             _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyUpAddIO")
     return out

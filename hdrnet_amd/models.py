@@ -223,15 +223,7 @@ class _Coefficients(nn.Module):
     native_training = True
 
     def _train_params(self):
-        convs = list(self.splat) + list(self.global_conv)
-        ps = []
-        for layer in convs:
-            ps += [layer.conv.weight, layer.conv.bias]
-        for layer in (self.fc1, self.fc2, self.fc3):
-            ps += [layer.fc.weight, layer.fc.bias]
-        ps += [self.local1.conv.weight, self.local1.conv.bias, self.local2.conv.weight,
-               self.pred.conv.weight, self.pred.conv.bias]
-        return ps
+        return self._train_params_bn()[0]  # (without batch norm every layer's second tensor is its bias)
 
     def _use_native_training(self, lowres_nhwc: torch.Tensor) -> bool:
         if not (self.native and self.native_training and lowres_nhwc.is_cuda and lowres_nhwc.dtype == torch.float32):
@@ -254,21 +246,20 @@ class _Coefficients(nn.Module):
     # their backward as kernels of csrc/coeff_net_bn.hip between the same convolution launches.  Inference, a batch of one
     # (torch refuses to train on it), an input that needs a gradient or a gamma that is not the constant 1 run the torch ops.
     def _bn_layers(self):
+        """The layers batch norm normalises, in the order of ``hdrnet_ops._coeff_slots`` (the order is stated there)."""
         return list(self.splat)[1:] + list(self.global_conv) + [self.fc1, self.fc2, self.local1]
 
     def _train_params_bn(self):
-        """(parameters, running statistics) in ``hdrnet_ops.coefficients_bn_train``'s order: beta where a normalised layer
-        would have its bias."""
-        def second(layer, lin):
-            return layer.bn.bn.bias if layer.bn is not None else lin.bias
-        ps = []
-        for layer in list(self.splat) + list(self.global_conv):
-            ps += [layer.conv.weight, second(layer, layer.conv)]
-        for layer in (self.fc1, self.fc2, self.fc3):
-            ps += [layer.fc.weight, second(layer, layer.fc)]
-        ps += [self.local1.conv.weight, second(self.local1, self.local1.conv), self.local2.conv.weight,
-               self.pred.conv.weight, self.pred.conv.bias]
-        stats = [(layer.bn.bn.running_mean, layer.bn.bn.running_var) for layer in self._bn_layers()]
+        """(parameters, running statistics) in the order of ``hdrnet_ops._coeff_slots``: layer by layer the weight, then
+        beta where the layer is normalised and its bias where it is not; local2 has no second tensor."""
+        ps, stats, local2 = [], [], self.local2
+        for layer in [*self.splat, *self.global_conv, self.fc1, self.fc2, self.fc3, self.local1, local2, self.pred]:
+            lin, bn = layer.fc if isinstance(layer, _FC) else layer.conv, layer.bn
+            ps.append(lin.weight)
+            if layer is not local2:
+                ps.append(lin.bias if bn is None else bn.bn.bias)
+            if bn is not None:
+                stats.append((bn.bn.running_mean, bn.bn.running_var))
         return ps, stats
 
     def _gamma_is_one(self, bns) -> bool:

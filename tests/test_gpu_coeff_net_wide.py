@@ -342,6 +342,28 @@ def test_wide_entry_points_equal_the_narrow_ones_up_to_8_images(case, bn):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bn", [False, True], ids=BN_IDS.get)
+@pytest.mark.parametrize("case", ["tiny_b2", "tiny_b9"])
+def test_autograd_path_returns_the_c_abis_bits(case, bn):
+    """The module's forward and backward on either side of the narrow / wide switch against `raw_step`, which restates the
+    parameter order itself: the output, every parameter gradient and every running statistic, bit for bit (the kernels are
+    deterministic).  Each side starts from its own copy of the module, so the statistics move once on each."""
+    _, low, wts, _, _, _, _ = reference(case, bn)
+    raw = raw_step(case, bn, wide=low.shape[0] > 8)
+    net = device_net(case, bn)
+    out, _ = run(net, low.to(DEV), wts.float().to(DEV))
+    assert is_native(out, bn), type(out.grad_fn).__name__
+    ps, stats = net._train_params_bn() if bn else (net._train_params(), [])
+    got = [out.detach().cpu()]
+    for p in ps:  # raw_step's gradients are flat, in the parameter's memory order
+        g = p.grad
+        assert g is not None and g.stride() == p.stride()
+        got.append((g.permute(0, 2, 3, 1) if g.dim() == 4 else g).contiguous().reshape(-1).cpu())
+    got += [t.cpu() for st in stats for t in st]
+    assert_same_bits(got, raw, "the autograd path and the C ABI")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bn", [False, True], ids=BN_IDS.get)
 def test_graphed_train_step_matches_eager_native_steps(bn):
     """A captured step of the whole model at 16 x 64 x 64, replayed three times, against the same steps run eagerly
     (compared as tests/test_gpu_coeff_net_bn.py compares the pair at a batch of 2)."""
