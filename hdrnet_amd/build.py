@@ -48,7 +48,7 @@ SOURCES = [
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
     ("coeff_net_bn.hip", []),
-    ("coeff_fc_wide.hip", []),
+    ("coeff_fc_train.hip", []),
     ("metrics.hip", []),
     ("loss_psnr.hip", []),
     ("sample_prep.hip", []),

@@ -1,28 +1,29 @@
-// The fully connected layers of the coefficient network's training step for batches of 9 to 32 images: the reference
-// trains with --batch_size 16 (hdrnet/bin/train.py), its data pipeline defaults to 32.  coeff_fc_bwd
-// (coeff_net_train.hip), coeff_bn_fc and coeff_bn_fc_bwd (coeff_net_bn.hip) keep one register and one LDS row per image
-// for at most 8 images; these are the same kernels with the image count as a template parameter, NB = 16 or 32, so that
-// every loop over the images still unrolls into registers:
+// The fully connected layers of the coefficient network's training step: the backward of a layer and, with batch norm
+// (hdrnet/layers.py:30-54 with is_training=True), the normalisation of fc1 / fc2 over the batch and its backward.  A
+// layer has B <= 32 rows (the reference trains with --batch_size 16, hdrnet/bin/train.py; its data pipeline defaults to
+// 32), so every kernel keeps one register per image, and the image count is a template parameter, NB = 8, 16 or 32, so
+// that every loop over the images unrolls into registers.  The launchers take the smallest NB that holds B.
 //
-//   coeff_fc_bwd_wide<NB>     dW, db and dx of a layer in one launch.  Thread = (input k, part of the outputs), every
-//                             (o, k) of dW owned by one thread; all loads of a 256-output chunk -- the thread's 16
-//                             weights, the chunk's dy staged through the LDS -- in flight before the first is used.
-//                             3 NB + 16 live values per thread (x, the dx partial sums, the bias gradient's addends,
-//                             the weights).  The staged dy ([NB][256]) and the dx partial sums ([NB][16][17]) share one
-//                             LDS array: dy is dead when the output loop ends (34 KB at NB = 32 instead of 67.6).
-//   coeff_bn_fc_wide<NB>      reduces a layer's partial sums, then mean and M2 per channel in double over the images in
-//                             index order; thread (channel, r) finishes images r and r + 16.
-//   coeff_bn_fc_bwd_wide<NB>  a thread per channel, sum g and sum g * xhat in double.
+//   coeff_fc_bwd<NB>     dW, db and dx of a layer in one launch.  Thread = (input k, part of the outputs), every
+//                        (o, k) of dW owned by one thread; all loads of a 256-output chunk -- the thread's 16
+//                        weights, the chunk's dy staged through the LDS -- in flight before the first is used.
+//                        3 NB + 16 live values per thread (x, the dx partial sums, the bias gradient's addends,
+//                        the weights).  The staged dy ([NB][256]) and the dx partial sums ([NB][16][17]) share one
+//                        LDS array: dy is dead when the output loop ends (34 KB at NB = 32 instead of 67.6).
+//   coeff_bn_fc<NB>      reduces a layer's partial sums, then mean and M2 per channel in double over the images in
+//                        index order; thread (channel, r) finishes images r and r + 16.
+//   coeff_bn_fc_bwd<NB>  a thread per channel, sum g and sum g * xhat in double.
 //
-// Sums over images run b = 0, 1, ..; sums over outputs in the order of the narrow kernels: deterministic, no atomics.
+// Sums over images run b = 0, 1, .. and sums over outputs in the same order in every instance: a batch gives the same
+// bits whichever instance holds it.  Deterministic, no atomics.
 #include <hip/hip_runtime.h>
 
-#include "coeff_fc_wide.hip.h"
+#include "coeff_fc_train.hip.h"
 
 namespace hdrnet_amd {
 namespace {
 
-struct FcWideParams {
+struct FcBwdParams {
   const float* x;   // [B][K]: the layer's (activated) input
   const float* dy;  // [B][O]
   const float* w;   // [O][K]
@@ -32,9 +33,14 @@ struct FcWideParams {
   int B, K, O, mask_x;  // mask_x: dx passes where x > 0 (the input is a ReLU's output)
 };
 
-// Block = 16 inputs k x 16 parts of the outputs, as coeff_fc_bwd.  B <= NB.
+// Block = 16 inputs k x 16 parts of the outputs; every (o, k) of dW belongs to exactly one thread.  The layers are tiny
+// (<= 1 MB of weights) and the kernel is a chain of memory round trips, so every load of a 256-output chunk is issued before
+// the first is used: the 16 weights of a thread as predicated loads of a fully unrolled loop (a run-time trip count leaves
+// small layers in the compiler's serial remainder loop: one round trip per output), dy staged through the LDS once per
+// workgroup instead of B broadcast loads per output, the bias gradient's loads at the top, spread over the workgroups.
+// B <= NB.
 template <int NB>
-__global__ __launch_bounds__(256) void coeff_fc_bwd_wide(const FcWideParams p) {
+__global__ __launch_bounds__(256) void coeff_fc_bwd(const FcBwdParams p) {
   constexpr int kRedFloats = NB * 16 * 17, kDysFloats = NB * 256;
   __shared__ float lds[kRedFloats > kDysFloats ? kRedFloats : kDysFloats];
   float* dys = lds;  // [NB][256] during the output loop
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(256) void coeff_fc_bwd_wide(const FcWideParams p) {
   }
 }
 
-struct BnFcWideParams {
+struct BnFcParams {
   const float* zpart;  // forward: [B][S][O] partial sums of the layer's output (coeff_fc)
   const float* g;      // backward: [B][O] masked gradient of y
   const float* beta;
@@ -124,9 +130,10 @@ struct BnFcWideParams {
   float eps, momentum;
 };
 
-// Workgroup = 16 channels x 16 reducers of the partial sums, as coeff_bn_fc; then thread (channel, r) = images r, r + 16.
+// Workgroup = 16 channels x 16 reducers of the partial sums (as coeff_fc reduces its input); then thread (channel, r) =
+// images r, r + 16.
 template <int NB>
-__global__ __launch_bounds__(256) void coeff_bn_fc_wide(const BnFcWideParams p) {
+__global__ __launch_bounds__(256) void coeff_bn_fc(const BnFcParams p) {
   __shared__ float red[NB][16][17];
   __shared__ float zs[NB][16];
   const int tid = threadIdx.x, cl = tid & 15, r = tid >> 4;
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(256) void coeff_bn_fc_wide(const BnFcWideParams p) 
 }
 
 template <int NB>
-__global__ __launch_bounds__(256) void coeff_bn_fc_bwd_wide(const BnFcWideParams p) {
+__global__ __launch_bounds__(256) void coeff_bn_fc_bwd(const BnFcParams p) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= p.O) return;
   float g[NB], xh[NB];
@@ -202,42 +209,44 @@ __global__ __launch_bounds__(256) void coeff_bn_fc_bwd_wide(const BnFcWideParams
   p.dbeta[c] = (float)a;
 }
 
-bool wide_batch(int B) { return B > kCoeffNarrowMaxB && B <= kCoeffWideMaxB; }
-
 }  // namespace
 
-hipError_t launch_fc_bwd_wide(const float* x, const float* dy, const float* w, float* dw, float* db, float* dx, int B,
-                              int K, int O, int mask_x, hipStream_t s) {
-  if (!wide_batch(B) || K < 1 || O < 1) return hipErrorInvalidValue;
-  const FcWideParams p{x, dy, w, dw, db, dx, B, K, O, mask_x};
+// One workgroup per 16 inputs.
+hipError_t launch_fc_bwd(const float* x, const float* dy, const float* w, float* dw, float* db, float* dx, int B, int K,
+                         int O, int mask_x, hipStream_t s) {
+  if (B < 1 || B > kCoeffWideMaxB || K < 1 || O < 1) return hipErrorInvalidValue;
+  const FcBwdParams p{x, dy, w, dw, db, dx, B, K, O, mask_x};
   const dim3 grid((unsigned)((K + 15) / 16));
-  if (B <= 16) coeff_fc_bwd_wide<16><<<grid, 256, 0, s>>>(p);
-  else coeff_fc_bwd_wide<32><<<grid, 256, 0, s>>>(p);
+  if (B <= 8) coeff_fc_bwd<8><<<grid, 256, 0, s>>>(p);
+  else if (B <= 16) coeff_fc_bwd<16><<<grid, 256, 0, s>>>(p);
+  else coeff_fc_bwd<32><<<grid, 256, 0, s>>>(p);
   return hipGetLastError();
 }
 
-hipError_t launch_bn_fc_forward_wide(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
-                                     float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
-                                     float momentum, hipStream_t s) {
-  if (!wide_batch(B) || S < 1 || O < 1) return hipErrorInvalidValue;
-  BnFcWideParams p{};
+hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
+                                float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
+                                float momentum, hipStream_t s) {
+  if (B < 2 || B > kCoeffWideMaxB || S < 1 || O < 1) return hipErrorInvalidValue;
+  BnFcParams p{};
   p.zpart = zpart; p.S = S; p.B = B; p.O = O; p.beta = beta; p.running_mean = running_mean; p.running_var = running_var;
   p.xhat = xhat; p.y = y; p.inv_std = inv_std; p.zeros = zeros; p.eps = eps; p.momentum = momentum;
   const dim3 grid((unsigned)((O + 15) / 16));
-  if (B <= 16) coeff_bn_fc_wide<16><<<grid, 256, 0, s>>>(p);
-  else coeff_bn_fc_wide<32><<<grid, 256, 0, s>>>(p);
+  if (B <= 8) coeff_bn_fc<8><<<grid, 256, 0, s>>>(p);
+  else if (B <= 16) coeff_bn_fc<16><<<grid, 256, 0, s>>>(p);
+  else coeff_bn_fc<32><<<grid, 256, 0, s>>>(p);
   return hipGetLastError();
 }
 
-hipError_t launch_bn_fc_backward_wide(const float* g, const float* xhat, const float* inv_std, float* dz, float* dbeta,
-                                      int B, int O, hipStream_t s) {
-  if (!wide_batch(B) || O < 1) return hipErrorInvalidValue;
-  BnFcWideParams p{};
+hipError_t launch_bn_fc_backward(const float* g, const float* xhat, const float* inv_std, float* dz, float* dbeta, int B,
+                                 int O, hipStream_t s) {
+  if (B < 2 || B > kCoeffWideMaxB || O < 1) return hipErrorInvalidValue;
+  BnFcParams p{};
   p.g = g; p.xhat = const_cast<float*>(xhat); p.inv_std = const_cast<float*>(inv_std); p.dz = dz; p.dbeta = dbeta;
   p.B = B; p.O = O;
   const dim3 grid((unsigned)((O + 255) / 256));
-  if (B <= 16) coeff_bn_fc_bwd_wide<16><<<grid, 256, 0, s>>>(p);
-  else coeff_bn_fc_bwd_wide<32><<<grid, 256, 0, s>>>(p);
+  if (B <= 8) coeff_bn_fc_bwd<8><<<grid, 256, 0, s>>>(p);
+  else if (B <= 16) coeff_bn_fc_bwd<16><<<grid, 256, 0, s>>>(p);
+  else coeff_bn_fc_bwd<32><<<grid, 256, 0, s>>>(p);
   return hipGetLastError();
 }
 

@@ -34,11 +34,16 @@
 //                      weights requested before anything else: a launch less.  (fc2 + fc3 in ONE 1024-thread
 //                      workgroup per image measured 9 us: a single CU pulls its 224 KB at ~30 GB/s.)
 //
+// The same launch sequence (coefficients_forward) serves training with batch norm: a normalised layer's convolution
+// leaves its raw output for coeff_net_bn.hip's kernels, a normalised fully connected layer its partial sums for
+// coeff_fc_train.hip's, which follow it.
+//
 // fp32 throughout: the summation order differs from MIOpen's, results agree to ~1e-6 relative
 // (tests/test_coeff_net.py compares both with a float64 evaluation).  Deterministic: no atomics.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hdrnet_amd.h"
+#include "coeff_fc_train.hip.h"
 #include "coeff_net.hip.h"
 #include "coeff_net_bn.hip.h"
 #include "launch.hip.h"
@@ -590,18 +595,37 @@ const char* coefficients_limit(const hdrnet_coeff_net& net) {
   return limit;
 }
 
-hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,
-                               hipStream_t s, const char** name) {
-  NetDims d;
-  if (!net_dims(net, &d)) return hipErrorInvalidValue;
+namespace {
+
+// The network's launches, once.  `bn` null: no layer is normalised and `workspace` is net_workspace(d) floats per image.
+// With training-mode batch norm (coeff_net_bn.hip, coeff_fc_train.hip) `workspace` continues as bn_workspace(d, B)
+// describes: a normalised layer's convolution writes its raw output z (no bias, no ReLU -- as local2 always runs) there,
+// and the slot of the plain workspace receives y = relu(bn(z)); fc1 / fc2 materialise their activated outputs, which their
+// consumers read as an input of one partial sum (xS = 1) without bias.  The first splat layer is never normalised.
+hipError_t coefficients_forward(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_bn* bn,
+                                const NetDims& d, float* coeffs, int B, void* workspace, hipStream_t s) {
   const NetWorkspace ws = net_workspace(d);
+  const BnWorkspace bw = bn ? bn_workspace(d, B) : BnWorkspace{};
+  const hdrnet_coeff_net_bn none{};
+  const hdrnet_coeff_net_bn& q = bn ? *bn : none;  // the betas and running statistics: null where nothing is normalised
   // every activation buffer holds the whole batch, image-major
   float* base = static_cast<float*>(workspace);
-  auto buf = [&](size_t off_floats) { return base + off_floats * (size_t)B; };
-  *name = "coeff_net";
+  auto buf = [&](size_t off_floats) { return base + off_floats * (size_t)B; };  // the plain part: per image
+  auto ext = [&](size_t off_floats) { return base + off_floats; };              // the batch-norm part: whole batch
+  double* part = bn ? reinterpret_cast<double*>(ext(bw.part)) : nullptr;
 #ifdef HDRNET_TOOLS_BUILD
   g_coeff_launch = 0;
 #endif
+  // A 3 x 3 layer with bias and ReLU, or normalised: the convolution to `z`, then norm() from there to `y`
+  auto conv = [&](const float* in, const float* w, const float* bias, float* y, size_t z, int side, int cin, int cout,
+                  int stride) {
+    return bn ? conv_geom(in, w, nullptr, ext(z), side, side, cin, cout, 3, stride, false, kMTile, 16)
+              : conv_geom(in, w, bias, y, side, side, cin, cout, 3, stride, true, kMTile, 16);
+  };
+  auto norm = [&](size_t z, float* y, int M, int C, const float* beta, float* rm, float* rv, size_t save) {
+    if (!bn) return hipSuccess;
+    return launch_bn_forward(ext(z), y, M, C, beta, rm, rv, ext(save), part, q.eps, q.momentum, s);
+  };
   hipError_t e = hipSuccess;
   // ---- splat
   const float* cur = lowres;
@@ -623,8 +647,11 @@ hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net,
       else coeff_conv_first<1><<<grid, 256, lds, s>>>(cb);
       e = hipGetLastError();
     } else {
-      cb.g[0] = conv_geom(cur, net.splat_w[i], net.splat_b[i], out, side, side, cin, cout, 3, 2, true, kMTile, 16);
+      cb.g[0] = conv(cur, net.splat_w[i], net.splat_b[i], out, bw.zsplat[i], side, cin, cout, 2);
       e = launch_conv_mfma<3, false>(cb, B, s);
+      if (e == hipSuccess)
+        e = norm(bw.zsplat[i], out, B * (side / 2) * (side / 2), cout, q.splat_beta[i], q.splat_running_mean[i],
+                 q.splat_running_var[i], bw.ssplat[i]);
     }
     if (e != hipSuccess) return e;
     cur = out;
@@ -634,47 +661,66 @@ hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net,
   // ---- local conv1 (stride 1) and global conv1 (stride 2) read the splat features: one launch
   float* l1 = buf(ws.local1);
   float* g1 = buf(ws.g1);
-  {
-    ConvBatch cb{};
-    cb.g[0] = conv_geom(cur, net.local_w[0], net.local_b[0], l1, d.sb, d.sb, d.feat, d.gl, 3, 1, true, kMTile, 16);
-    cb.g[1] = conv_geom(cur, net.global_conv_w[0], net.global_conv_b[0], g1, d.sb, d.sb, d.feat, d.gl, 3, 2, true, kMTile, 16);
-    cb.n = 2;
-    e = launch_conv_mfma<3, false>(cb, B, s);
-    if (e != hipSuccess) return e;
-  }
-  // ---- local conv2 (no bias, no activation) and global conv2
-  float* l2 = buf(ws.local2);
-  float* g2 = buf(ws.g2);
   const int g1side = (d.sb + 1) / 2;
   {
     ConvBatch cb{};
-    cb.g[0] = conv_geom(l1, net.local_w[1], net.local_b[1], l2, d.sb, d.sb, d.gl, d.gl, 3, 1, false, kMTile, 16);
-    cb.g[1] = conv_geom(g1, net.global_conv_w[1], net.global_conv_b[1], g2, g1side, g1side, d.gl, d.gl, 3, 2, true, kMTile, 16);
+    cb.g[0] = conv(cur, net.local_w[0], net.local_b[0], l1, bw.zlocal1, d.sb, d.feat, d.gl, 1);
+    cb.g[1] = conv(cur, net.global_conv_w[0], net.global_conv_b[0], g1, bw.zg1, d.sb, d.feat, d.gl, 2);
     cb.n = 2;
     e = launch_conv_mfma<3, false>(cb, B, s);
     if (e != hipSuccess) return e;
+    e = norm(bw.zlocal1, l1, B * d.sb * d.sb, d.gl, q.local_beta, q.local_running_mean, q.local_running_var, bw.slocal1);
+    if (e != hipSuccess) return e;
+    e = norm(bw.zg1, g1, B * g1side * g1side, d.gl, q.global_conv_beta[0], q.global_conv_running_mean[0],
+             q.global_conv_running_var[0], bw.sg1);
+    if (e != hipSuccess) return e;
   }
-  // ---- fully connected layers: fc1 and fc2 as K-split launches; fc3 inside the prediction layer's workgroups
+  // ---- local conv2 (no bias, no activation, never normalised) and global conv2
+  float* l2 = buf(ws.local2);
+  float* g2 = buf(ws.g2);
+  {
+    ConvBatch cb{};
+    cb.g[0] = conv_geom(l1, net.local_w[1], bn ? nullptr : net.local_b[1], l2, d.sb, d.sb, d.gl, d.gl, 3, 1, false, kMTile, 16);
+    cb.g[1] = conv(g1, net.global_conv_w[1], net.global_conv_b[1], g2, bw.zg2, g1side, d.gl, d.gl, 2);
+    cb.n = 2;
+    e = launch_conv_mfma<3, false>(cb, B, s);
+    if (e != hipSuccess) return e;
+    e = norm(bw.zg2, g2, B * d.gside * d.gside, d.gl, q.global_conv_beta[1], q.global_conv_running_mean[1],
+             q.global_conv_running_var[1], bw.sg2);
+    if (e != hipSuccess) return e;
+  }
+  // ---- fully connected layers: fc1 and fc2 as K-split launches; fc3 inside the prediction layer's workgroups.  A plain
+  // layer's consumer reduces its partial sums, adds the bias and applies the ReLU; a normalised layer's partial sums are
+  // reduced and normalised over the batch by a launch of their own
   const int K1 = d.gside * d.gside * d.gl;
   float* f1 = buf(ws.fc1);
   float* f2 = buf(ws.fc2);
   {
     auto fc_grid = [&](int chunks, int O) { return dim3((unsigned)chunks, (unsigned)((O + 255) / 256), (unsigned)B); };
-    FcParams p{g2, nullptr, net.fc_w[0], f1, 1, 0, K1, 4 * d.gl, kFcChunk, next_trace(), net.fc_layout};
-    coeff_fc<<<fc_grid(ws.s1, 4 * d.gl), 256, 0, s>>>(p);
-    FcParams q{f1, net.fc_b[0], net.fc_w[1], f2, ws.s1, 1, 4 * d.gl, 2 * d.gl, kFcChunk, next_trace(), net.fc_layout};
-    coeff_fc<<<fc_grid(ws.s2, 2 * d.gl), 256, 0, s>>>(q);
-    e = hipGetLastError();
+    const FcParams p1{g2, nullptr, net.fc_w[0], f1, 1, 0, K1, 4 * d.gl, kFcChunk, next_trace(), net.fc_layout};
+    coeff_fc<<<fc_grid(ws.s1, 4 * d.gl), 256, 0, s>>>(p1);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (bn)
+      e = launch_bn_fc_forward(f1, ws.s1, B, 4 * d.gl, q.fc_beta[0], q.fc_running_mean[0], q.fc_running_var[0],
+                               ext(bw.xh1), ext(bw.y1), ext(bw.inv1), ext(bw.zeros), q.eps, q.momentum, s);
+    if (e != hipSuccess) return e;
+    FcParams p2{f1, net.fc_b[0], net.fc_w[1], f2, ws.s1, 1, 4 * d.gl, 2 * d.gl, kFcChunk, next_trace(), net.fc_layout};
+    if (bn) p2.xpart = ext(bw.y1), p2.xbias = nullptr, p2.xS = 1, p2.xrelu = 0;
+    coeff_fc<<<fc_grid(ws.s2, 2 * d.gl), 256, 0, s>>>(p2);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (bn)
+      e = launch_bn_fc_forward(f2, ws.s2, B, 2 * d.gl, q.fc_beta[1], q.fc_running_mean[1], q.fc_running_var[1],
+                               ext(bw.xh2), ext(bw.y2), ext(bw.inv2), nullptr, q.eps, q.momentum, s);
     if (e != hipSuccess) return e;
   }
-  // ---- fc3 + fusion + prediction + unroll
+  // ---- fc3 + fusion + prediction + unroll (normalised: fc2's activated output as one partial sum, a bias of zeros)
   {
     ConvBatch cb{};
     cb.g[0] = conv_geom(l2, net.pred_w, net.pred_b, coeffs, d.sb, d.sb, d.gl, d.pred, 1, 1, false, kMTile, 16);
     cb.n = 1;
-    cb.x.gx_part = f2;
-    cb.x.gx_bias = net.fc_b[1];
-    cb.x.gxS = ws.s2;
+    cb.x.gx_part = bn ? ext(bw.y2) : f2;
+    cb.x.gx_bias = bn ? ext(bw.zeros) : net.fc_b[1];
+    cb.x.gxS = bn ? 1 : ws.s2;
     cb.x.gK = 2 * d.gl;
     cb.x.gw = net.fc_w[2];
     cb.x.gb = net.fc_b[2];
@@ -689,10 +735,15 @@ hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net,
   return e;
 }
 
-// ---- training-mode batch norm (coeff_net_bn.hip): the same launches with every normalised layer's convolution writing
-// its raw output z (no bias, no ReLU -- as local2 always runs) beside the slot of the plain workspace, which receives
-// y = relu(bn(z)); fc1 / fc2 materialise their activated outputs, which their consumers read as an input of one partial
-// sum (xS = 1) without bias.
+}  // namespace
+
+hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,
+                               hipStream_t s, const char** name) {
+  NetDims d;
+  if (!net_dims(net, &d)) return hipErrorInvalidValue;
+  *name = "coeff_net";
+  return coefficients_forward(lowres, net, nullptr, d, coeffs, B, workspace, s);
+}
 
 size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
@@ -702,123 +753,9 @@ size_t coefficients_bn_workspace_bytes(const hdrnet_coeff_net& net, int B, int m
 
 hipError_t launch_coefficients_bn(const float* lowres, const hdrnet_coeff_net_bn& bn, float* coeffs, int B,
                                   void* workspace, hipStream_t s, int max_b) {
-  const hdrnet_coeff_net& net = bn.net;
   NetDims d;
-  if (coefficients_bn_workspace_bytes(net, B, max_b) == 0 || !net_dims(net, &d)) return hipErrorInvalidValue;
-  const NetWorkspace ws = net_workspace(d);
-  const BnWorkspace bw = bn_workspace(d, B);
-  float* base = static_cast<float*>(workspace);
-  auto buf = [&](size_t off_floats) { return base + off_floats * (size_t)B; };  // the plain part: per image
-  auto ext = [&](size_t off_floats) { return base + off_floats; };              // the batch-norm part: whole batch
-  double* part = reinterpret_cast<double*>(ext(bw.part));
-#ifdef HDRNET_TOOLS_BUILD
-  g_coeff_launch = 0;
-#endif
-  auto norm = [&](const float* z, float* y, int M, int C, const float* beta, float* rm, float* rv, size_t save) {
-    return launch_bn_forward(z, y, M, C, beta, rm, rv, ext(save), part, bn.eps, bn.momentum, s);
-  };
-  hipError_t e = hipSuccess;
-  // ---- splat: the first layer has bias and ReLU, the others batch norm
-  const float* cur = lowres;
-  int side = d.N, cin = 3;
-  for (int i = 0; i < d.n_ds; ++i) {
-    const int cout = (d.cm * d.gd) << i;
-    float* out = buf(ws.splat[i]);
-    ConvBatch cb{};
-    cb.n = 1;
-    if (i == 0) {
-      const long long waves = (long long)((side / 2 + 7) / 8) * ((side / 2 + 7) / 8) * cout * B;
-      const int oct = (cout % 2 == 0 && waves >= 4096) ? 2 : 1;
-      cb.g[0] = conv_geom(cur, net.splat_w[i], net.splat_b[i], out, side, side, cin, cout, 3, 2, true, kTile, 4 * oct);
-      cb.trace = next_trace();
-      const size_t lds = (size_t)17 * 17 * 16;
-      const dim3 grid((unsigned)cb.g[0].tiles, (unsigned)cb.g[0].oc_groups, (unsigned)B);
-      if (oct == 2) coeff_conv_first<2><<<grid, 256, lds, s>>>(cb);
-      else coeff_conv_first<1><<<grid, 256, lds, s>>>(cb);
-      e = hipGetLastError();
-    } else {
-      float* z = ext(bw.zsplat[i]);
-      cb.g[0] = conv_geom(cur, net.splat_w[i], nullptr, z, side, side, cin, cout, 3, 2, false, kMTile, 16);
-      e = launch_conv_mfma<3, false>(cb, B, s);
-      if (e == hipSuccess)
-        e = norm(z, out, B * (side / 2) * (side / 2), cout, bn.splat_beta[i], bn.splat_running_mean[i],
-                 bn.splat_running_var[i], bw.ssplat[i]);
-    }
-    if (e != hipSuccess) return e;
-    cur = out;
-    side /= 2;
-    cin = cout;
-  }
-  // ---- local conv1 and global conv1, both normalised
-  float* l1 = buf(ws.local1);
-  float* g1 = buf(ws.g1);
-  const int g1side = (d.sb + 1) / 2;
-  {
-    ConvBatch cb{};
-    cb.g[0] = conv_geom(cur, net.local_w[0], nullptr, ext(bw.zlocal1), d.sb, d.sb, d.feat, d.gl, 3, 1, false, kMTile, 16);
-    cb.g[1] = conv_geom(cur, net.global_conv_w[0], nullptr, ext(bw.zg1), d.sb, d.sb, d.feat, d.gl, 3, 2, false, kMTile, 16);
-    cb.n = 2;
-    e = launch_conv_mfma<3, false>(cb, B, s);
-    if (e != hipSuccess) return e;
-    e = norm(ext(bw.zlocal1), l1, B * d.sb * d.sb, d.gl, bn.local_beta, bn.local_running_mean, bn.local_running_var, bw.slocal1);
-    if (e != hipSuccess) return e;
-    e = norm(ext(bw.zg1), g1, B * g1side * g1side, d.gl, bn.global_conv_beta[0], bn.global_conv_running_mean[0],
-             bn.global_conv_running_var[0], bw.sg1);
-    if (e != hipSuccess) return e;
-  }
-  // ---- local conv2 (no bias, no activation, no batch norm) and global conv2 (normalised)
-  float* l2 = buf(ws.local2);
-  float* g2 = buf(ws.g2);
-  {
-    ConvBatch cb{};
-    cb.g[0] = conv_geom(l1, net.local_w[1], nullptr, l2, d.sb, d.sb, d.gl, d.gl, 3, 1, false, kMTile, 16);
-    cb.g[1] = conv_geom(g1, net.global_conv_w[1], nullptr, ext(bw.zg2), g1side, g1side, d.gl, d.gl, 3, 2, false, kMTile, 16);
-    cb.n = 2;
-    e = launch_conv_mfma<3, false>(cb, B, s);
-    if (e != hipSuccess) return e;
-    e = norm(ext(bw.zg2), g2, B * d.gside * d.gside, d.gl, bn.global_conv_beta[1], bn.global_conv_running_mean[1],
-             bn.global_conv_running_var[1], bw.sg2);
-    if (e != hipSuccess) return e;
-  }
-  // ---- fc1, fc2: the K-split launches, their partial sums reduced and normalised over the batch
-  const int K1 = d.gside * d.gside * d.gl;
-  float* f1 = buf(ws.fc1);
-  float* f2 = buf(ws.fc2);
-  {
-    auto fc_grid = [&](int chunks, int O) { return dim3((unsigned)chunks, (unsigned)((O + 255) / 256), (unsigned)B); };
-    FcParams p{g2, nullptr, net.fc_w[0], f1, 1, 0, K1, 4 * d.gl, kFcChunk, next_trace(), net.fc_layout};
-    coeff_fc<<<fc_grid(ws.s1, 4 * d.gl), 256, 0, s>>>(p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    e = launch_bn_fc_forward(f1, ws.s1, B, 4 * d.gl, bn.fc_beta[0], bn.fc_running_mean[0], bn.fc_running_var[0],
-                             ext(bw.xh1), ext(bw.y1), ext(bw.inv1), ext(bw.zeros), bn.eps, bn.momentum, s);
-    if (e != hipSuccess) return e;
-    FcParams q{ext(bw.y1), nullptr, net.fc_w[1], f2, 1, 0, 4 * d.gl, 2 * d.gl, kFcChunk, next_trace(), net.fc_layout};
-    coeff_fc<<<fc_grid(ws.s2, 2 * d.gl), 256, 0, s>>>(q);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    e = launch_bn_fc_forward(f2, ws.s2, B, 2 * d.gl, bn.fc_beta[1], bn.fc_running_mean[1], bn.fc_running_var[1],
-                             ext(bw.xh2), ext(bw.y2), ext(bw.inv2), nullptr, bn.eps, bn.momentum, s);
-    if (e != hipSuccess) return e;
-  }
-  // ---- fc3 + fusion + prediction + unroll: fc2's activated output as one partial sum, a bias of zeros
-  {
-    ConvBatch cb{};
-    cb.g[0] = conv_geom(l2, net.pred_w, net.pred_b, coeffs, d.sb, d.sb, d.gl, d.pred, 1, 1, false, kMTile, 16);
-    cb.n = 1;
-    cb.x.gx_part = ext(bw.y2);
-    cb.x.gx_bias = ext(bw.zeros);
-    cb.x.gxS = 1;
-    cb.x.gK = 2 * d.gl;
-    cb.x.gw = net.fc_w[2];
-    cb.x.gb = net.fc_b[2];
-    cb.x.gw_oi = net.fc_layout;
-    cb.x.gd = d.gd;
-    cb.x.n_out = net.n_out;
-    cb.x.n_in = net.n_in;
-    cb.x.n_levels = net.n_levels;
-    cb.x.level_stride = (long long)B * d.sb * d.sb * d.gd * (net.n_out / net.n_levels) * net.n_in;
-    e = launch_conv_mfma<1, true>(cb, B, s);
-  }
-  return e;
+  if (coefficients_bn_workspace_bytes(bn.net, B, max_b) == 0 || !net_dims(bn.net, &d)) return hipErrorInvalidValue;
+  return coefficients_forward(lowres, bn.net, &bn, d, coeffs, B, workspace, s);
 }
 
 }  // namespace hdrnet_amd

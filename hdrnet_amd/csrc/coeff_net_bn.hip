@@ -14,8 +14,8 @@
 //                        (in place over dy if asked to); chunk 0 writes dbeta
 //
 // z stays where the convolution wrote it: xhat is recomputed from it, for every element (the backward formula needs
-// it also where y = 0).  The fully connected layers (M = B <= 8 rows) are one launch each way, a thread per channel; 9 to 32 rows
-// go to their twins in coeff_fc_wide.hip.
+// it also where y = 0).  The fully connected layers (M = B <= 32 rows) are one launch each way, with the images in
+// registers: coeff_bn_fc / coeff_bn_fc_bwd, coeff_fc_train.hip.
 //
 // Sums run in float64 from the first addend on: E[z^2] - mean^2 then loses nothing that matters (the operands are
 // exact to 2^-53, the cancellation costs mean^2 / var of that), and the order of the additions is fixed -- per thread
@@ -24,12 +24,9 @@
 #include <hip/hip_runtime.h>
 
 #include "coeff_net_bn.hip.h"
-#include "coeff_fc_wide.hip.h"
 
 namespace hdrnet_amd {
 namespace {
-
-constexpr int kMaxB = 8;  // coeff_fc_bwd's limit (coeff_net_train.hip)
 
 struct BnParams {
   const float* z;     // [M][C] raw layer output
@@ -229,97 +226,6 @@ __global__ __launch_bounds__(256) void coeff_bn_bwd_apply(const BnParams p) {
   }
 }
 
-// ------------------------------------------------------------------------------------- fully connected layers
-
-struct BnFcParams {
-  const float* zpart;  // forward: [B][S][O] partial sums of the layer's output (coeff_fc)
-  const float* g;      // backward: [B][O] masked gradient of y
-  const float* beta;
-  float* xhat;         // [B][O] (forward writes, backward reads)
-  float* y;            // [B][O]
-  float* inv_std;      // [O]
-  float* zeros;        // [O] or null
-  float* running_mean;
-  float* running_var;
-  float* dz;           // [B][O]
-  float* dbeta;        // [O]
-  int S, B, O;
-  float eps, momentum;
-};
-
-// Workgroup = 16 channels x 16 reducers of the partial sums (as coeff_fc reduces its input); then thread (channel, image).
-__global__ __launch_bounds__(256) void coeff_bn_fc(const BnFcParams p) {
-  __shared__ float red[kMaxB][16][17];
-  __shared__ float zs[kMaxB][16];
-  const int tid = threadIdx.x, cl = tid & 15, r = tid >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  const bool c_ok = c < p.O;
-  float acc[kMaxB];
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) acc[b] = 0.0f;
-  if (c_ok) {
-    for (int s = r; s < p.S; s += 16) {
-#pragma unroll
-      for (int b = 0; b < kMaxB; ++b)
-        if (b < p.B) acc[b] += p.zpart[((size_t)b * p.S + s) * p.O + c];
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) red[b][r][cl] = acc[b];
-  __syncthreads();
-  if (r < p.B) {  // thread (cl, image r)
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v += red[r][k][cl];
-    zs[r][cl] = v;
-  }
-  __syncthreads();
-  if (r >= p.B || !c_ok) return;
-  double sum = 0.0;
-  for (int b = 0; b < p.B; ++b) sum += (double)zs[b][cl];
-  const double mean = sum / p.B;
-  double m2 = 0.0;
-  for (int b = 0; b < p.B; ++b) {
-    const double d = (double)zs[b][cl] - mean;
-    m2 = __builtin_fma(d, d, m2);
-  }
-  const double var = m2 / p.B;
-  const float inv = (float)(1.0 / sqrt(var + (double)p.eps));
-  const float xh = (zs[r][cl] - (float)mean) * inv;
-  p.xhat[(size_t)r * p.O + c] = xh;
-  p.y[(size_t)r * p.O + c] = fmaxf(xh + p.beta[c], 0.0f);
-  if (r == 0) {
-    p.inv_std[c] = inv;
-    if (p.zeros) p.zeros[c] = 0.0f;
-    const double m = p.momentum;
-    p.running_mean[c] = (float)((1.0 - m) * p.running_mean[c] + m * mean);
-    p.running_var[c] = (float)((1.0 - m) * p.running_var[c] + m * (m2 / (p.B - 1)));
-  }
-}
-
-__global__ __launch_bounds__(256) void coeff_bn_fc_bwd(const BnFcParams p) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= p.O) return;
-  float g[kMaxB], xh[kMaxB];
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) {
-    g[b] = b < p.B ? p.g[(size_t)b * p.O + c] : 0.0f;
-    xh[b] = b < p.B ? p.xhat[(size_t)b * p.O + c] : 0.0f;
-  }
-  const float inv = p.inv_std[c];
-  double a = 0.0, q = 0.0;
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) {
-    a += (double)g[b];
-    q = __builtin_fma((double)g[b], (double)xh[b], q);
-  }
-  const float m1 = (float)(a / p.B), m2 = (float)(q / p.B);
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b)
-    if (b < p.B) p.dz[(size_t)b * p.O + c] = inv * (g[b] - m1 - xh[b] * m2);
-  p.dbeta[c] = (float)a;
-}
-
 BnParams bn_params(int M, int C, const BnPlan& pl, double* part) {
   BnParams p{};
   p.M = M; p.C = C; p.cwshift = pl.cwshift; p.rows_per_chunk = pl.rows_per_chunk; p.nchunks = pl.nchunks;
@@ -351,31 +257,6 @@ hipError_t launch_bn_backward(const float* dy, const float* dy2, const float* y,
   const dim3 grid((unsigned)pl.nchunks, (unsigned)pl.groups);
   coeff_bn_bwd_stats<<<grid, 256, 0, s>>>(p);
   coeff_bn_bwd_apply<<<grid, 256, 0, s>>>(p);
-  return hipGetLastError();
-}
-
-hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
-                                float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
-                                float momentum, hipStream_t s) {
-  if (B > kMaxB)  // 9 .. 32 images: coeff_fc_wide.hip
-    return launch_bn_fc_forward_wide(zpart, S, B, O, beta, running_mean, running_var, xhat, y, inv_std, zeros, eps,
-                                     momentum, s);
-  if (B < 2 || S < 1 || O < 1) return hipErrorInvalidValue;
-  BnFcParams p{};
-  p.zpart = zpart; p.S = S; p.B = B; p.O = O; p.beta = beta; p.running_mean = running_mean; p.running_var = running_var;
-  p.xhat = xhat; p.y = y; p.inv_std = inv_std; p.zeros = zeros; p.eps = eps; p.momentum = momentum;
-  coeff_bn_fc<<<dim3((unsigned)((O + 15) / 16)), 256, 0, s>>>(p);
-  return hipGetLastError();
-}
-
-hipError_t launch_bn_fc_backward(const float* g, const float* xhat, const float* inv_std, float* dz, float* dbeta, int B,
-                                 int O, hipStream_t s) {
-  if (B > kMaxB) return launch_bn_fc_backward_wide(g, xhat, inv_std, dz, dbeta, B, O, s);  // 9 .. 32 images
-  if (B < 2 || O < 1) return hipErrorInvalidValue;
-  BnFcParams p{};
-  p.g = g; p.xhat = const_cast<float*>(xhat); p.inv_std = const_cast<float*>(inv_std); p.dz = dz; p.dbeta = dbeta;
-  p.B = B; p.O = O;
-  coeff_bn_fc_bwd<<<dim3((unsigned)((O + 255) / 256)), 256, 0, s>>>(p);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // Training-mode batch norm of the coefficient network (coeff_net_bn.hip): launch plan, the workspace it adds to the
-// forward's, and the launchers the forward (coeff_net.hip) and backward (coeff_net_train.hip) sequences call.
+// forward's, and the launchers the forward (coeff_net.hip) and backward (coeff_net_train.hip) sequences call for the
+// convolutions' outputs; the fully connected layers' are in coeff_fc_train.hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,15 +48,6 @@ hipError_t launch_bn_forward(const float* z, float* y, int M, int C, const float
 // g = (dy [+ dy2]) * [y > 0];  dbeta = sum g;  dz = inv_std * (g - mean(g) - xhat * mean(g * xhat)).  dz may be dy.
 hipError_t launch_bn_backward(const float* dy, const float* dy2, const float* y, const float* z, const float* save,
                               float* dz, float* dbeta, int M, int C, double* part, hipStream_t s);
-// A fully connected layer: z[b][o] = sum_s zpart[b][s][o]; xhat and y = relu(xhat + beta) are [B][O], inv_std [O];
-// `zeros` (optional): O floats set to 0 (the bias the consumers of y read).  2 <= B <= 32 (above 8:
-// coeff_fc_wide.hip's kernels).
-hipError_t launch_bn_fc_forward(const float* zpart, int S, int B, int O, const float* beta, float* running_mean,
-                                float* running_var, float* xhat, float* y, float* inv_std, float* zeros, float eps,
-                                float momentum, hipStream_t s);
-// g = the gradient of y already masked with [y > 0] (coeff_fc_bwd's mask_x); dz may be g.
-hipError_t launch_bn_fc_backward(const float* g, const float* xhat, const float* inv_std, float* dz, float* dbeta, int B,
-                                 int O, hipStream_t s);
 
 namespace {
 

@@ -1,8 +1,10 @@
 // Training side of the coefficient network (csrc/coeff_net.hip is its forward): the VJP of
 // `HDRNetCurves._coefficients` (hdrnet/models.py:62-142) with respect to every weight and bias, for the model
-// WITHOUT batch norm -- how the reference's own script trains the guide-network model
-// (scripts/ll/train_nn_guide.sh: --nobatch_norm).  The forward pass is the inference launch sequence; its workspace
-// (every layer's activation, the fully connected layers' partial sums) is what this file reads back.
+// without batch norm -- how the reference's own script trains the guide-network model
+// (scripts/ll/train_nn_guide.sh: --nobatch_norm) -- and with it: ONE launch sequence (coefficients_backward), in which a
+// normalised layer's backward is preceded by its batch norm's (coeff_net_bn.hip, coeff_fc_train.hip).  The forward pass
+// is the inference launch sequence; its workspace (every layer's activation, the fully connected layers' partial sums)
+// is what this file reads back.
 //
 // On stock ops the backward of this network is ~75 launches of a graph-captured training step (MIOpen backward-data
 // and backward-weights kernels with their companions, ReLU masks, pad slices, bias reductions), ~0.4 ms of launch
@@ -24,16 +26,15 @@
 //                     flipped filter -- the forward's 4 x 4 x 16 MFMA kernel with the upsampling and the mask folded
 //                     into the LDS staging and the filter read in place ([Cout][kh][kw][Cin]: four 4-byte loads per
 //                     16-channel group instead of one float4; no transposed copy of the weights per step).
-//   coeff_fc_bwd      a fully connected layer: dW, db and dx in one launch (batches of 9 to 32 images: its twin
-//                     coeff_fc_bwd_wide, coeff_fc_wide.hip).
+//   coeff_fc_bwd      a fully connected layer: dW, db and dx in one launch (coeff_fc_train.hip).
 //
 // Weights are read and gradients written in the layouts torch holds them in (Conv2d weights in channels_last memory
 // order = [Cout][kh][kw][Cin]; Linear weights [out][in]): the training step moves no parameter data.
 // Deterministic: fixed-order sums, no atomics.
 #include <hip/hip_runtime.h>
 
+#include "coeff_fc_train.hip.h"
 #include "coeff_net.hip.h"
-#include "coeff_fc_wide.hip.h"
 #include "coeff_net_bn.hip.h"
 #include "launch.hip.h"
 
@@ -44,7 +45,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kT = 4;          // pixel tile edge (16 pixels = the 16 rows / 4 K-steps of an MFMA tile)
 constexpr int kChunkCh = 64;   // coeff_conv_dx: gradient channels staged at a time
-constexpr int kMaxB = 8;       // coeff_fc_bwd keeps one accumulator per image in registers
 
 // x / d == umulhi(x, magic32(d)) for x < 2^16 and 2 <= d < 2^16, and for ANY x when d is a power of two (the magic number
 // is 2^32 / d exactly); d == 1 has no 32-bit magic number (udiv handles it).  Every image, grid and tile side of the
@@ -596,94 +596,6 @@ __global__ __launch_bounds__(256) void coeff_conv_bwd2(const BwdTwo two) {
   else bwd_pair_block<KS, MULTI>(two.p[0], lds, (int)blockIdx.x);
 }
 
-// ---------------------------------------------------------------------------------------- fully connected layers
-
-struct FcBwdParams {
-  const float* x;   // [B][K]: the layer's (activated) input
-  const float* dy;  // [B][O]
-  const float* w;   // [O][K]
-  float* dw;        // [O][K]
-  float* db;        // [O]
-  float* dx;        // [B][K] or null
-  int B, K, O, mask_x;  // mask_x: dx passes where x > 0 (the input is a ReLU's output)
-};
-
-// Block = 16 inputs k x 16 parts of the outputs; every (o, k) of dW belongs to exactly one thread.  The layers are tiny
-// (<= 1 MB of weights) and the kernel is a chain of memory round trips, so every load of a 256-output chunk is issued before
-// the first is used: the 16 weights of a thread as predicated loads of a fully unrolled loop (a run-time trip count leaves
-// small layers in the compiler's serial remainder loop: one round trip per output), dy staged through the LDS once per
-// workgroup instead of B broadcast loads per output, the bias gradient's loads at the top, spread over the workgroups.
-__global__ __launch_bounds__(256) void coeff_fc_bwd(const FcBwdParams p) {
-  __shared__ float red[kMaxB][16][17];
-  __shared__ float dys[kMaxB][256];
-  const int tid = threadIdx.x, kl = tid & 15, op = tid >> 4;
-  const int k = blockIdx.x * 16 + kl;
-  const bool k_ok = k < p.K;
-  float xk[kMaxB], dxp[kMaxB], dbv[kMaxB];
-  const int ob = blockIdx.x * 256 + tid;  // this thread's bias gradient (one per thread of the first O / 256 workgroups)
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) {
-    xk[b] = (b < p.B && k_ok) ? p.x[(size_t)b * p.K + k] : 0.0f;
-    dbv[b] = (b < p.B && ob < p.O) ? p.dy[(size_t)b * p.O + ob] : 0.0f;
-    dxp[b] = 0.0f;
-  }
-  for (int o0 = 0; o0 < p.O; o0 += 256) {
-    if (o0 > 0) __syncthreads();
-#pragma unroll
-    for (int b = 0; b < kMaxB; ++b)
-      if (b < p.B) dys[b][tid] = (o0 + tid < p.O) ? p.dy[(size_t)b * p.O + o0 + tid] : 0.0f;
-    float w[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int o = o0 + op + 16 * i;
-      w[i] = (k_ok && o < p.O) ? p.w[(size_t)o * p.K + k] : 0.0f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int o = o0 + op + 16 * i;
-      float dwv = 0.0f;
-#pragma unroll
-      for (int b = 0; b < kMaxB; ++b) {
-        if (b < p.B) {
-          const float g = dys[b][op + 16 * i];
-          dwv = __builtin_fmaf(g, xk[b], dwv);
-          dxp[b] = __builtin_fmaf(g, w[i], dxp[b]);
-        }
-      }
-      if (k_ok && o < p.O) p.dw[(size_t)o * p.K + k] = dwv;
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < kMaxB; ++b) red[b][op][kl] = dxp[b];
-  __syncthreads();
-  if (p.dx && op < p.B && k_ok) {  // thread (kl, op = image)
-    float v = 0.0f;
-#pragma unroll
-    for (int o2 = 0; o2 < 16; ++o2) v += red[op][o2][kl];
-    const float xv = p.x[(size_t)op * p.K + k];
-    p.dx[(size_t)op * p.K + k] = (p.mask_x && !(xv > 0.0f)) ? 0.0f : v;
-  }
-  if (ob < p.O) {
-    float v = 0.0f;
-#pragma unroll
-    for (int b = 0; b < kMaxB; ++b) v += dbv[b];  // images beyond B hold zeros: the order of the sum is b = 0, 1, ...
-    p.db[ob] = v;
-  }
-  for (int o = ob + (int)gridDim.x * 256; o < p.O; o += (int)gridDim.x * 256) {  // (never taken: grid >= O / 256)
-    float v = 0.0f;
-    for (int b = 0; b < p.B; ++b) v += p.dy[(size_t)b * p.O + o];
-    p.db[o] = v;
-  }
-}
-
-// One workgroup per 16 inputs; more than kMaxB images: the wide kernel.
-hipError_t launch_fc_bwd(const FcBwdParams& p, hipStream_t s) {
-  if (p.B > kMaxB) return launch_fc_bwd_wide(p.x, p.dy, p.w, p.dw, p.db, p.dx, p.B, p.K, p.O, p.mask_x, s);
-  coeff_fc_bwd<<<dim3((unsigned)((p.K + 15) / 16)), 256, 0, s>>>(p);
-  return hipGetLastError();
-}
-
 // ----------------------------------------------------------------------- what the forward did not keep; permutes
 
 struct RecomputeParams {
@@ -1130,10 +1042,9 @@ int recompute_slabs(int P, int C) {
   return slabs <= 32768 ? (int)slabs : 0;
 }
 
-// `max_b`: the caller's largest batch, kCoeffNarrowMaxB (= kMaxB) or kCoeffWideMaxB (coeff_fc_wide.hip.h); everything but
-// the fully connected layers' kernels takes any batch.
+// `max_b`: the largest batch the caller admits, kCoeffNarrowMaxB or kCoeffWideMaxB (coeff_fc_train.hip.h); the launches
+// do not depend on it.
 bool train_supported(const hdrnet_coeff_net& net, int B, int max_b, NetDims* d, const char** limit = nullptr) {
-  static_assert(kMaxB == kCoeffNarrowMaxB, "coeff_fc_bwd's batch is where coeff_fc_bwd_wide's begins");
   if (limit) *limit = nullptr;
   if (!net_dims(net, d)) return false;
   if (B < 1 || B > max_b || max_b > kCoeffWideMaxB || net.n_levels != 1 || net.fc_layout != 1) return false;
@@ -1147,6 +1058,157 @@ bool train_supported(const hdrnet_coeff_net& net, int B, int max_b, NetDims* d, 
     return false;
   }
   return true;
+}
+
+struct BnBwdSpace {  // float offsets behind bwd_space's: what the backward needs more with batch norm
+  size_t db_scratch, part, total;
+};
+
+BnBwdSpace bn_bwd_space(const NetDims& d, const BwdSpace& bs) {
+  BnBwdSpace w{};
+  size_t off = bs.total;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
+  w.db_scratch = take((size_t)4 * d.gl);  // where coeff_fc_bwd leaves the "bias gradient" of a layer without bias
+  w.part = take(2 * bn_part_doubles(bn_max_channels(d)));
+  w.total = off;
+  return w;
+}
+
+// The backward's launches, once.  `fwd_ws`: the workspace the forward (coeff_net.hip: coefficients_forward) left behind
+// for the same net, B and `bn`.  `bn` null: no layer is normalised.  With batch norm (`bgr`: where the betas' gradients
+// go) every normalised layer's gradient of y becomes the gradient of its raw output z, in place, before the layer's own
+// backward launches read it -- those then run without ReLU mask and without a bias gradient (dy = dz, ymask = NULL) --
+// and coeff_recompute reads fc1 / fc2's materialised outputs as one partial sum each.
+hipError_t coefficients_backward(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
+                                 const hdrnet_coeff_net_bn* bn, const hdrnet_coeff_net_bn_grads* bgr, const NetDims& d,
+                                 const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s) {
+  const NetWorkspace fw = net_workspace(d);
+  const BnWorkspace bw = bn ? bn_workspace(d, B) : BnWorkspace{};
+  const hdrnet_coeff_net_bn_grads none{};
+  const hdrnet_coeff_net_bn_grads& bg = bn ? *bgr : none;  // the betas' gradients: null where nothing is normalised
+  const float* fbase = static_cast<const float*>(fwd_ws);
+  auto fbuf = [&](size_t off) { return fbase + off * (size_t)B; };  // the forward's plain part: per image
+  auto fext = [&](size_t off) { return fbase + off; };              // its batch-norm part: whole batch
+  const BwdSpace bs = bwd_space(d, net, B);
+  const BnBwdSpace xs = bn_bwd_space(d, bs);
+  float* base = static_cast<float*>(workspace);
+  auto buf = [&](size_t off) { return base + off; };
+  double* bnpart = bn ? reinterpret_cast<double*>(buf(xs.part)) : nullptr;
+  const int P = d.sb * d.sb, g1side = (d.sb + 1) / 2;
+  const int K1 = d.gside * d.gside * d.gl;
+  const bool mask = !bn;  // a plain layer's backward applies its ReLU's mask; a normalised layer's norm_bwd has done so
+  hipError_t e;
+
+  // the forward's activated outputs
+  const float* S[8];
+  for (int i = 0; i < d.n_ds; ++i) S[i] = fbuf(fw.splat[i]);
+  const float* L1 = fbuf(fw.local1);
+  const float* L2 = fbuf(fw.local2);
+  const float* G1 = fbuf(fw.g1);
+  const float* G2 = fbuf(fw.g2);
+
+  // ---- what the forward did not keep + the incoming gradient in the prediction layer's channel order
+  {
+    const float* zeros = fext(bw.zeros);
+    RecomputeParams p{fbuf(fw.fc1), fw.s1, fbuf(fw.fc2), fw.s2, net.fc_b[0], net.fc_b[1], net.fc_w[2], net.fc_b[2], L2,
+                      dcoeffs, buf(bs.x1), buf(bs.x2), buf(bs.g), buf(bs.fusion), buf(bs.dyp),
+                      4 * d.gl, 2 * d.gl, d.gl, P, d.gd, net.n_out, net.n_in,
+                      magic32(d.gd * net.n_out * net.n_in), magic32(d.gd), magic32(net.n_out)};
+    if (bn) p.f1part = fext(bw.y1), p.f2part = fext(bw.y2), p.s1 = p.s2 = 1, p.b1 = p.b2 = zeros;
+    const int slabs = recompute_slabs(P, d.pred);  // > 0: train_supported
+    coeff_recompute<<<dim3((unsigned)B, (unsigned)slabs + 1), 256, 0, s>>>(p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  ReduceTab tab{};
+  tab.count = 0;
+  tab.first[0] = 0;
+  float* parts = buf(bs.parts);
+  // dy -> dz of a normalised layer, in place ([M][C]; y: its activated output; dy2: a second consumer's gradient, added)
+  auto norm_bwd = [&](float* dy, const float* dy2, const float* y, size_t z, size_t save, float* dbeta, int M, int C) {
+    if (!bn) return hipSuccess;
+    return launch_bn_backward(dy, dy2, y, fext(z), fext(save), dy, dbeta, M, C, bnpart, s);
+  };
+  auto fc_norm_bwd = [&](float* dy, size_t xhat, size_t inv_std, float* dbeta, int O) {
+    return bn ? launch_bn_fc_backward(dy, fext(xhat), fext(inv_std), dy, dbeta, B, O, s) : hipSuccess;
+  };
+  // a layer's bias gradient: a normalised layer has no bias (the fully connected kernels write one all the same)
+  auto bias = [&](float* db) { return bn ? nullptr : db; };
+  auto fc_bias = [&](float* db) { return bn ? buf(xs.db_scratch) : db; };
+  auto pair = [&](const Layer& L, const float* dy, bool mask_y, float* dx) {
+    const PairSetup ps = make_pair(L, B, dy, nullptr, mask_y, dx, parts, &tab);
+    parts += dw_part_floats(B, L);
+    return ps;
+  };
+  // ---- prediction layer (1x1 on the fusion; its own output has no ReLU)
+  const Layer pr{buf(bs.fusion), nullptr, net.pred_w, gr.pred_w, gr.pred_b, d.sb, d.gl, d.sb, d.pred, 1, 1};
+  // (its backward-data half also leaves the per-tile column sums of df where the fusion passed it: dg's partial sums)
+  const int ntile = ((d.sb + kT - 1) / kT) * ((d.sb + kT - 1) / kT);
+  e = launch_pair(pr, B, buf(bs.dyp), nullptr, false, buf(bs.df), parts, &tab, s, buf(bs.fusion), buf(bs.dgp));
+  parts += dw_part_floats(B, pr);
+  if (e != hipSuccess) return e;
+  // ---- fusion = relu(local2 + g): d local2 = df masked (applied by the consumers), dg = its sum over the cells
+  // (summed inside fc3's backward instead -- 16 partial sums per element while staging dy -- the launch was 17 us slower:
+  // the extra loads sit on every workgroup's critical path; a launch of its own costs 4.9)
+  coeff_slab_sum<<<dim3((unsigned)B), 256, 0, s>>>(buf(bs.dgp), buf(bs.dg), ntile, d.gl);
+  // ---- fully connected layers: coeff_fc_bwd's mask_x applies the ReLU of the layer below, whose batch norm follows
+  e = launch_fc_bwd(buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1, s);
+  if (e != hipSuccess) return e;
+  if ((e = fc_norm_bwd(buf(bs.dx2), bw.xh2, bw.inv2, bg.fc_beta[1], 2 * d.gl)) != hipSuccess) return e;
+  e = launch_fc_bwd(buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], fc_bias(gr.fc_b[1]), buf(bs.dx1), B, 4 * d.gl,
+                    2 * d.gl, 1, s);
+  if (e != hipSuccess) return e;
+  if ((e = fc_norm_bwd(buf(bs.dx1), bw.xh1, bw.inv1, bg.fc_beta[0], 4 * d.gl)) != hipSuccess) return e;
+  e = launch_fc_bwd(G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], fc_bias(gr.fc_b[0]), buf(bs.dg2), B, K1, 4 * d.gl, 0, s);
+  if (e != hipSuccess) return e;
+  // ---- the local path (local2: no bias, no ReLU on its own output -- the fusion's mask --, local1) and the global path's
+  // convolutions (conv2, conv1) do not depend on each other: local2 + conv2 in one launch, then local1 + conv1
+  const float* feat = S[d.n_ds - 1];
+  {
+    e = norm_bwd(buf(bs.dg2), nullptr, G2, bw.zg2, bw.sg2, bg.global_conv_beta[1], B * d.gside * d.gside, d.gl);
+    if (e != hipSuccess) return e;
+    const Layer l2{L1, buf(bs.fusion), net.local_w[1], gr.local_w[1], nullptr, d.sb, d.gl, d.sb, d.gl, 3, 1};
+    const Layer c2{G1, G2, net.global_conv_w[1], gr.global_conv_w[1], bias(gr.global_conv_b[1]), g1side, d.gl, d.gside, d.gl, 3, 2};
+    const PairSetup a = pair(l2, buf(bs.df), true, buf(bs.dl1));
+    const PairSetup b = pair(c2, buf(bs.dg2), mask, buf(bs.dg1));
+    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
+  }
+  {
+    e = norm_bwd(buf(bs.dl1), nullptr, L1, bw.zlocal1, bw.slocal1, bg.local_beta, B * P, d.gl);
+    if (e != hipSuccess) return e;
+    e = norm_bwd(buf(bs.dg1), nullptr, G1, bw.zg1, bw.sg1, bg.global_conv_beta[0], B * g1side * g1side, d.gl);
+    if (e != hipSuccess) return e;
+    const Layer l1{feat, L1, net.local_w[0], gr.local_w[0], bias(gr.local_b[0]), d.sb, d.feat, d.sb, d.gl, 3, 1};
+    const Layer c1{feat, G1, net.global_conv_w[0], gr.global_conv_w[0], bias(gr.global_conv_b[0]), d.sb, d.feat, g1side, d.gl, 3, 2};
+    const PairSetup a = pair(l1, buf(bs.dl1), mask, buf(bs.ds4a));
+    const PairSetup b = pair(c1, buf(bs.dg1), mask, buf(bs.ds4b));
+    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
+  }
+  // ---- splat, last to first; the last layer's gradient is the sum of the two paths' (added by its batch norm's backward,
+  // if it has one).  The first layer is never normalised.
+  float* dy = buf(bs.ds4a);
+  const float* dy2 = buf(bs.ds4b);
+  for (int i = d.n_ds - 1; i >= 0; --i) {
+    const int cout = (d.cm * d.gd) << i, cin = i > 0 ? (d.cm * d.gd) << (i - 1) : 3;
+    const int hin = d.N >> i;
+    if (i > 0) {
+      e = norm_bwd(dy, dy2, S[i], bw.zsplat[i], bw.ssplat[i], bg.splat_beta[i], B * (hin / 2) * (hin / 2), cout);
+      if (e != hipSuccess) return e;
+      const Layer L{S[i - 1], S[i], net.splat_w[i], gr.splat_w[i], bias(gr.splat_b[i]), hin, cin, hin / 2, cout, 3, 2};
+      e = launch_pair(L, B, dy, bn ? nullptr : dy2, mask, buf(bs.ds[i - 1]), parts, &tab, s);
+      parts += dw_part_floats(B, L);
+      if (e != hipSuccess) return e;
+      dy = buf(bs.ds[i - 1]);
+      dy2 = nullptr;
+    } else {
+      const Layer L{lowres, S[0], net.splat_w[0], gr.splat_w[0], gr.splat_b[0], hin, cin, hin / 2, cout, 3, 2};
+      e = launch_dw(L, B, dy, dy2, true, parts, &tab, s);
+      parts += dw_part_floats(B, L);
+      if (e != hipSuccess) return e;
+    }
+  }
+  // ---- the chunks' partial sums of every weight / bias gradient
+  coeff_reduce_parts<<<dim3((unsigned)tab.first[tab.count]), 256, 0, s>>>(tab);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -1171,130 +1233,8 @@ hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net&
   NetDims d;
   if (!train_supported(net, B, max_b, &d)) return hipErrorInvalidValue;
   *name = "coeff_net_grad";
-  const NetWorkspace fw = net_workspace(d);
-  const float* fbase = static_cast<const float*>(fwd_ws);
-  auto fbuf = [&](size_t off) { return fbase + off * (size_t)B; };
-  const BwdSpace bs = bwd_space(d, net, B);
-  float* base = static_cast<float*>(workspace);
-  auto buf = [&](size_t off) { return base + off; };
-  const int P = d.sb * d.sb, g1side = (d.sb + 1) / 2;
-  const int K1 = d.gside * d.gside * d.gl;
-  hipError_t e;
-
-  // the forward's activations
-  const float* S[8];
-  for (int i = 0; i < d.n_ds; ++i) S[i] = fbuf(fw.splat[i]);
-  const float* L1 = fbuf(fw.local1);
-  const float* L2 = fbuf(fw.local2);
-  const float* G1 = fbuf(fw.g1);
-  const float* G2 = fbuf(fw.g2);
-
-  // ---- what the forward did not keep + the incoming gradient in the prediction layer's channel order
-  {
-    RecomputeParams p{fbuf(fw.fc1), fw.s1, fbuf(fw.fc2), fw.s2, net.fc_b[0], net.fc_b[1], net.fc_w[2], net.fc_b[2], L2,
-                      dcoeffs, buf(bs.x1), buf(bs.x2), buf(bs.g), buf(bs.fusion), buf(bs.dyp),
-                      4 * d.gl, 2 * d.gl, d.gl, P, d.gd, net.n_out, net.n_in,
-                      magic32(d.gd * net.n_out * net.n_in), magic32(d.gd), magic32(net.n_out)};
-    const int slabs = recompute_slabs(P, d.pred);  // > 0: train_supported
-    coeff_recompute<<<dim3((unsigned)B, (unsigned)slabs + 1), 256, 0, s>>>(p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  ReduceTab tab{};
-  tab.count = 0;
-  tab.first[0] = 0;
-  float* parts = buf(bs.parts);
-  auto dw = [&](const Layer& L, const float* dy, const float* dy2, bool mask) -> hipError_t {
-    const hipError_t r = launch_dw(L, B, dy, dy2, mask, parts, &tab, s);
-    parts += dw_part_floats(B, L);
-    return r;
-  };
-  auto pair = [&](const Layer& L, const float* dy, const float* dy2, bool mask, float* dx) -> hipError_t {
-    const hipError_t r = launch_pair(L, B, dy, dy2, mask, dx, parts, &tab, s);
-    parts += dw_part_floats(B, L);
-    return r;
-  };
-  // ---- prediction layer (1x1 on the fusion; its own output has no ReLU)
-  const Layer pr{buf(bs.fusion), nullptr, net.pred_w, gr.pred_w, gr.pred_b, d.sb, d.gl, d.sb, d.pred, 1, 1};
-  // (its backward-data half also leaves the per-tile column sums of df where the fusion passed it: dg's partial sums)
-  const int ntile = ((d.sb + kT - 1) / kT) * ((d.sb + kT - 1) / kT);
-  e = launch_pair(pr, B, buf(bs.dyp), nullptr, false, buf(bs.df), parts, &tab, s, buf(bs.fusion), buf(bs.dgp));
-  parts += dw_part_floats(B, pr);
-  if (e != hipSuccess) return e;
-  // ---- fusion = relu(local2 + g): d local2 = df masked (applied by the consumers), dg = its sum over the cells
-  // (summed inside fc3's backward instead -- 16 partial sums per element while staging dy -- the launch was 17 us slower:
-  // the extra loads sit on every workgroup's critical path; a launch of its own costs 4.9)
-  coeff_slab_sum<<<dim3((unsigned)B), 256, 0, s>>>(buf(bs.dgp), buf(bs.dg), ntile, d.gl);
-  // ---- fully connected layers
-  {
-    FcBwdParams f3{buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1};
-    if ((e = launch_fc_bwd(f3, s)) != hipSuccess) return e;
-    FcBwdParams f2{buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], gr.fc_b[1], buf(bs.dx1), B, 4 * d.gl, 2 * d.gl, 1};
-    if ((e = launch_fc_bwd(f2, s)) != hipSuccess) return e;
-    FcBwdParams f1{G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], gr.fc_b[0], buf(bs.dg2), B, K1, 4 * d.gl, 0};
-    if ((e = launch_fc_bwd(f1, s)) != hipSuccess) return e;
-  }
-  // ---- the local path (local2: no bias, no ReLU on its own output -- the fusion's mask --, local1) and the global path's
-  // convolutions (conv2, conv1) do not depend on each other: local2 + conv2 in one launch, then local1 + conv1
-  const float* feat = S[d.n_ds - 1];
-  {
-    const Layer l2{L1, buf(bs.fusion), net.local_w[1], gr.local_w[1], nullptr, d.sb, d.gl, d.sb, d.gl, 3, 1};
-    const Layer c2{G1, G2, net.global_conv_w[1], gr.global_conv_w[1], gr.global_conv_b[1], g1side, d.gl, d.gside, d.gl, 3, 2};
-    const PairSetup a = make_pair(l2, B, buf(bs.df), nullptr, true, buf(bs.dl1), parts, &tab);
-    parts += dw_part_floats(B, l2);
-    const PairSetup b = make_pair(c2, B, buf(bs.dg2), nullptr, true, buf(bs.dg1), parts, &tab);
-    parts += dw_part_floats(B, c2);
-    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
-  }
-  {
-    const Layer l1{feat, L1, net.local_w[0], gr.local_w[0], gr.local_b[0], d.sb, d.feat, d.sb, d.gl, 3, 1};
-    const Layer c1{feat, G1, net.global_conv_w[0], gr.global_conv_w[0], gr.global_conv_b[0], d.sb, d.feat, g1side, d.gl, 3, 2};
-    const PairSetup a = make_pair(l1, B, buf(bs.dl1), nullptr, true, buf(bs.ds4a), parts, &tab);
-    parts += dw_part_floats(B, l1);
-    const PairSetup b = make_pair(c1, B, buf(bs.dg1), nullptr, true, buf(bs.ds4b), parts, &tab);
-    parts += dw_part_floats(B, c1);
-    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
-  }
-  // ---- splat, last to first; the last layer's gradient is the sum of the two paths'
-  const float* dy = buf(bs.ds4a);
-  const float* dy2 = buf(bs.ds4b);
-  for (int i = d.n_ds - 1; i >= 0; --i) {
-    const int cout = (d.cm * d.gd) << i, cin = i > 0 ? (d.cm * d.gd) << (i - 1) : 3;
-    const int hin = d.N >> i;
-    const Layer L{i > 0 ? S[i - 1] : lowres, S[i], net.splat_w[i], gr.splat_w[i], gr.splat_b[i], hin, cin, hin / 2, cout, 3, 2};
-    if (i > 0) {
-      if ((e = pair(L, dy, dy2, true, buf(bs.ds[i - 1]))) != hipSuccess) return e;
-      dy = buf(bs.ds[i - 1]);
-      dy2 = nullptr;
-    } else if ((e = dw(L, dy, dy2, true)) != hipSuccess) {
-      return e;
-    }
-  }
-  // ---- the chunks' partial sums of every weight / bias gradient
-  coeff_reduce_parts<<<dim3((unsigned)tab.first[tab.count]), 256, 0, s>>>(tab);
-  return hipGetLastError();
+  return coefficients_backward(lowres, net, gr, nullptr, nullptr, d, dcoeffs, B, fwd_ws, workspace, s);
 }
-
-// ---- with batch norm (coeff_net_bn.hip): every normalised layer's gradient of y becomes the gradient of its raw output
-// z, in place, before the layer's own backward launches read it -- those then run without ReLU mask and without a bias
-// gradient (dy = dz, ymask = NULL), and coeff_recompute reads fc1 / fc2's materialised outputs as one partial sum each.
-
-namespace {
-
-struct BnBwdSpace {  // float offsets behind bwd_space's
-  size_t db_scratch, part, total;
-};
-
-BnBwdSpace bn_bwd_space(const NetDims& d, const BwdSpace& bs) {
-  BnBwdSpace w{};
-  size_t off = bs.total;
-  auto take = [&](size_t n) { const size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
-  w.db_scratch = take((size_t)4 * d.gl);  // where coeff_fc_bwd leaves the "bias gradient" of a layer without bias
-  w.part = take(2 * bn_part_doubles(bn_max_channels(d)));
-  w.total = off;
-  return w;
-}
-
-}  // namespace
 
 size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b) {
   NetDims d;
@@ -1302,122 +1242,13 @@ size_t coefficients_bn_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, 
   return bn_bwd_space(d, bwd_space(d, net, B)).total * sizeof(float);
 }
 
+// `fwd_ws`: what launch_coefficients_bn() left behind.
 hipError_t launch_coefficients_bn_grad(const float* lowres, const hdrnet_coeff_net_bn& bn,
                                        const hdrnet_coeff_net_bn_grads& grads, const float* dcoeffs, int B,
                                        const void* fwd_ws, void* workspace, hipStream_t s, int max_b) {
-  const hdrnet_coeff_net& net = bn.net;
-  const hdrnet_coeff_net_grads& gr = grads.net;
   NetDims d;
-  if (B < 2 || !train_supported(net, B, max_b, &d)) return hipErrorInvalidValue;
-  const NetWorkspace fw = net_workspace(d);
-  const BnWorkspace bw = bn_workspace(d, B);
-  const float* fbase = static_cast<const float*>(fwd_ws);
-  auto fbuf = [&](size_t off) { return fbase + off * (size_t)B; };
-  auto fext = [&](size_t off) { return fbase + off; };
-  const BwdSpace bs = bwd_space(d, net, B);
-  const BnBwdSpace xs = bn_bwd_space(d, bs);
-  float* base = static_cast<float*>(workspace);
-  auto buf = [&](size_t off) { return base + off; };
-  double* bnpart = reinterpret_cast<double*>(buf(xs.part));
-  const int P = d.sb * d.sb, g1side = (d.sb + 1) / 2;
-  const int K1 = d.gside * d.gside * d.gl;
-  hipError_t e;
-
-  // the forward's activated outputs (the plain workspace's slots)
-  const float* S[8];
-  for (int i = 0; i < d.n_ds; ++i) S[i] = fbuf(fw.splat[i]);
-  const float* L1 = fbuf(fw.local1);
-  const float* L2 = fbuf(fw.local2);
-  const float* G1 = fbuf(fw.g1);
-  const float* G2 = fbuf(fw.g2);
-  const float* zeros = fext(bw.zeros);
-
-  {
-    RecomputeParams p{fext(bw.y1), 1, fext(bw.y2), 1, zeros, zeros, net.fc_w[2], net.fc_b[2], L2,
-                      dcoeffs, buf(bs.x1), buf(bs.x2), buf(bs.g), buf(bs.fusion), buf(bs.dyp),
-                      4 * d.gl, 2 * d.gl, d.gl, P, d.gd, net.n_out, net.n_in,
-                      magic32(d.gd * net.n_out * net.n_in), magic32(d.gd), magic32(net.n_out)};
-    const int slabs = recompute_slabs(P, d.pred);  // > 0: train_supported
-    coeff_recompute<<<dim3((unsigned)B, (unsigned)slabs + 1), 256, 0, s>>>(p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  ReduceTab tab{};
-  tab.count = 0;
-  tab.first[0] = 0;
-  float* parts = buf(bs.parts);
-  // ---- prediction layer and the fusion's column sums: as without batch norm
-  const Layer pr{buf(bs.fusion), nullptr, net.pred_w, gr.pred_w, gr.pred_b, d.sb, d.gl, d.sb, d.pred, 1, 1};
-  const int ntile = ((d.sb + kT - 1) / kT) * ((d.sb + kT - 1) / kT);
-  e = launch_pair(pr, B, buf(bs.dyp), nullptr, false, buf(bs.df), parts, &tab, s, buf(bs.fusion), buf(bs.dgp));
-  parts += dw_part_floats(B, pr);
-  if (e != hipSuccess) return e;
-  coeff_slab_sum<<<dim3((unsigned)B), 256, 0, s>>>(buf(bs.dgp), buf(bs.dg), ntile, d.gl);
-  // ---- fully connected layers: coeff_fc_bwd's mask_x applies the ReLU of the layer below, whose batch norm follows
-  {
-    FcBwdParams f3{buf(bs.x2), buf(bs.dg), net.fc_w[2], gr.fc_w[2], gr.fc_b[2], buf(bs.dx2), B, 2 * d.gl, d.gl, 1};
-    if ((e = launch_fc_bwd(f3, s)) != hipSuccess) return e;
-    e = launch_bn_fc_backward(buf(bs.dx2), fext(bw.xh2), fext(bw.inv2), buf(bs.dx2), grads.fc_beta[1], B, 2 * d.gl, s);
-    if (e != hipSuccess) return e;
-    FcBwdParams f2{buf(bs.x1), buf(bs.dx2), net.fc_w[1], gr.fc_w[1], buf(xs.db_scratch), buf(bs.dx1), B, 4 * d.gl, 2 * d.gl, 1};
-    if ((e = launch_fc_bwd(f2, s)) != hipSuccess) return e;
-    e = launch_bn_fc_backward(buf(bs.dx1), fext(bw.xh1), fext(bw.inv1), buf(bs.dx1), grads.fc_beta[0], B, 4 * d.gl, s);
-    if (e != hipSuccess) return e;
-    FcBwdParams f1{G2, buf(bs.dx1), net.fc_w[0], gr.fc_w[0], buf(xs.db_scratch), buf(bs.dg2), B, K1, 4 * d.gl, 0};
-    if ((e = launch_fc_bwd(f1, s)) != hipSuccess) return e;
-  }
-  auto norm_bwd = [&](float* dy, const float* dy2, const float* y, size_t z, size_t save, float* dbeta, int M, int C) {
-    return launch_bn_backward(dy, dy2, y, fext(z), fext(save), dy, dbeta, M, C, bnpart, s);
-  };
-  // ---- local2 (the fusion's mask) with global conv2, then local1 with global conv1
-  const float* feat = S[d.n_ds - 1];
-  {
-    e = norm_bwd(buf(bs.dg2), nullptr, G2, bw.zg2, bw.sg2, grads.global_conv_beta[1], B * d.gside * d.gside, d.gl);
-    if (e != hipSuccess) return e;
-    const Layer l2{L1, buf(bs.fusion), net.local_w[1], gr.local_w[1], nullptr, d.sb, d.gl, d.sb, d.gl, 3, 1};
-    const Layer c2{G1, G2, net.global_conv_w[1], gr.global_conv_w[1], nullptr, g1side, d.gl, d.gside, d.gl, 3, 2};
-    const PairSetup a = make_pair(l2, B, buf(bs.df), nullptr, true, buf(bs.dl1), parts, &tab);
-    parts += dw_part_floats(B, l2);
-    const PairSetup b = make_pair(c2, B, buf(bs.dg2), nullptr, false, buf(bs.dg1), parts, &tab);
-    parts += dw_part_floats(B, c2);
-    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
-  }
-  {
-    e = norm_bwd(buf(bs.dl1), nullptr, L1, bw.zlocal1, bw.slocal1, grads.local_beta, B * P, d.gl);
-    if (e != hipSuccess) return e;
-    e = norm_bwd(buf(bs.dg1), nullptr, G1, bw.zg1, bw.sg1, grads.global_conv_beta[0], B * g1side * g1side, d.gl);
-    if (e != hipSuccess) return e;
-    const Layer l1{feat, L1, net.local_w[0], gr.local_w[0], nullptr, d.sb, d.feat, d.sb, d.gl, 3, 1};
-    const Layer c1{feat, G1, net.global_conv_w[0], gr.global_conv_w[0], nullptr, d.sb, d.feat, g1side, d.gl, 3, 2};
-    const PairSetup a = make_pair(l1, B, buf(bs.dl1), nullptr, false, buf(bs.ds4a), parts, &tab);
-    parts += dw_part_floats(B, l1);
-    const PairSetup b = make_pair(c1, B, buf(bs.dg1), nullptr, false, buf(bs.ds4b), parts, &tab);
-    parts += dw_part_floats(B, c1);
-    if ((e = launch_two(a, b, s)) != hipSuccess) return e;
-  }
-  // ---- splat, last to first; the last layer's gradient is the sum of the two paths', added by its batch norm's backward
-  float* dy = buf(bs.ds4a);
-  const float* dy2 = buf(bs.ds4b);
-  for (int i = d.n_ds - 1; i >= 0; --i) {
-    const int cout = (d.cm * d.gd) << i, cin = i > 0 ? (d.cm * d.gd) << (i - 1) : 3;
-    const int hin = d.N >> i;
-    if (i > 0) {
-      e = norm_bwd(dy, dy2, S[i], bw.zsplat[i], bw.ssplat[i], grads.splat_beta[i], B * (hin / 2) * (hin / 2), cout);
-      if (e != hipSuccess) return e;
-      const Layer L{S[i - 1], S[i], net.splat_w[i], gr.splat_w[i], nullptr, hin, cin, hin / 2, cout, 3, 2};
-      e = launch_pair(L, B, dy, nullptr, false, buf(bs.ds[i - 1]), parts, &tab, s);
-      parts += dw_part_floats(B, L);
-      if (e != hipSuccess) return e;
-      dy = buf(bs.ds[i - 1]);
-      dy2 = nullptr;
-    } else {
-      const Layer L{lowres, S[0], net.splat_w[0], gr.splat_w[0], gr.splat_b[0], hin, cin, hin / 2, cout, 3, 2};
-      e = launch_dw(L, B, dy, dy2, true, parts, &tab, s);
-      parts += dw_part_floats(B, L);
-      if (e != hipSuccess) return e;
-    }
-  }
-  coeff_reduce_parts<<<dim3((unsigned)tab.first[tab.count]), 256, 0, s>>>(tab);
-  return hipGetLastError();
+  if (B < 2 || !train_supported(bn.net, B, max_b, &d)) return hipErrorInvalidValue;
+  return coefficients_backward(lowres, bn.net, grads.net, &bn, &grads, d, dcoeffs, B, fwd_ws, workspace, s);
 }
 
 }  // namespace hdrnet_amd

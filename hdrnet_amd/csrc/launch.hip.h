@@ -9,7 +9,7 @@
 
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_train.h"
-#include "coeff_fc_wide.hip.h"
+#include "coeff_fc_train.hip.h"
 #include "row_geom.h"
 
 namespace hdrnet_amd {
@@ -296,8 +296,8 @@ size_t coefficients_workspace_bytes(const hdrnet_coeff_net& net, int B);  // 0: 
 hipError_t launch_coefficients(const float* lowres, const hdrnet_coeff_net& net, float* coeffs, int B, void* workspace,
                                hipStream_t s, const char** name);
 // coeff_net_train.hip -- its VJP with respect to the parameters (no batch norm); fwd_ws = the forward's workspace.
-// `max_b`: the largest batch the caller admits, 8 (the C-ABI's first entry points) or 32 (their ..._wide twins, whose
-// fully connected layers run on coeff_fc_wide.hip's kernels above 8 images); the launches for B <= 8 are the same.
+// `max_b`: the largest batch the caller admits, 8 (the C-ABI's first entry points) or 32 (their ..._wide twins); the
+// launches of a batch are the same through both.
 size_t coefficients_grad_workspace_bytes(const hdrnet_coeff_net& net, int B, int max_b = kCoeffNarrowMaxB);  // 0: not supported
 hipError_t launch_coefficients_grad(const float* lowres, const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads& gr,
                                     const float* dcoeffs, int B, const void* fwd_ws, void* workspace, hipStream_t s,

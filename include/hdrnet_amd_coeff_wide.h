@@ -19,8 +19,8 @@ extern "C" {
  * hdrnet_coefficients_f32 itself, which takes any batch; its workspace is what hdrnet_coefficients_grad_wide_f32 reads.
  * Supported: what the twin supports with 1 <= B <= 32, with batch norm 2 <= B <= 32.  Up to B = 8 a wide entry point
  * issues exactly its twin's launches (one code path) and returns the same bits; from B = 9 on the fully connected layers'
- * backward and their batch norm run on the kernels of csrc/coeff_fc_wide.hip, every other launch is unchanged.  The first
- * entry points keep their range, B <= 8, and their texts.
+ * backward and their batch norm run on the 16- and 32-image instances of the kernels of csrc/coeff_fc_train.hip, every
+ * other launch is unchanged.  The first entry points keep their range, B <= 8, and their texts.
  * Refusals are the twins': the workspace queries return 0, the entry points return 1 with hdrnet_last_error() starting
  * with the entry point's own name, naming the limit and carrying B=<the batch>.  A workspace is sized by the query of the
  * same name (for B <= 8 the two queries agree). */

@@ -42,7 +42,7 @@ TRAIN_CASES = {
     "pred24": FORWARD_CASES["pred24"],
     "grid64": FORWARD_CASES["grid64"],
     "gl256": FORWARD_CASES["gl256"],               # the training bound: coeff_recompute's x2s[512] is exactly full
-    "pred12": (Shape(8, 4, 1, 4, 3, 4), 8),          # the largest batch coeff_fc_bwd holds (kMaxB)
+    "pred12": (Shape(8, 4, 1, 4, 3, 4), 8),          # the largest batch coeff_fc_bwd<8> holds
     "square_affine": FORWARD_CASES["square_affine"],
     "slab_doubling": (Shape(64, 32, 8, 1, 16, 16), 1),  # coeff_recompute needs more than its 32 slabs per image
     "batch7": (Shape(16, 4, 4, 1, 3, 4), 7),

@@ -1,4 +1,4 @@
-"""The coefficient network trained on the HIP kernels at batches of 9 to 32 images (csrc/coeff_fc_wide.hip behind the
+"""The coefficient network trained on the HIP kernels at batches of 9 to 32 images (csrc/coeff_fc_train.hip behind the
 ``..._wide`` entry points of include/hdrnet_amd_coeff_wide.h; hdrnet_ops.coefficients_train / coefficients_bn_train), with
 and without batch norm, against the same module in float64 on the CPU: forward, every gradient, the running statistics;
 determinism and buffer bounds through the C ABI; the wide entry points against the first ones where both run; a captured

@@ -38,7 +38,7 @@ def main():
     names = subprocess.run(["c++filt"], input="\n".join(rows), capture_output=True,
                            text=True).stdout.splitlines()
     for (name, f), dn in zip(rows.items(), names):
-        dn = re.sub(r"^void hdrnet_amd::\(anonymous namespace\)::", "", dn)
+        dn = re.sub(r"^(void )?hdrnet_amd::\(anonymous namespace\)::", "", dn)
         dn = re.sub(r"\(.*$", "", dn)
         if all(p in dn for p in pats):
             print(f"vgpr {f.get('VGPRs', '?'):>3s} agpr {f.get('AGPRs', '?'):>3s} sgpr {f.get('SGPRs', '?'):>3s} "

@@ -6,6 +6,21 @@ to the GPU box).  Box-to-box spread is ~5 %, run-to-run drift 1-2 %: a kernel ch
 only be measured like this.
 
     python tools/prev_vs_new.py --prev tools/exp/prev/libhdrnet_amd_prev.so [--workload 4k] [--rounds 7]
+
+--coeff: the coefficient network's training step (forward + gradient through the C ABI, with and without batch norm,
+through the first entry points and their ..._wide twins) instead of the slice-apply entry points:
+
+    --coeff bits     both builds on the same seeded network, input and cotangent: the output, every gradient and, with
+                     batch norm, the running statistics after three steps, compared byte for byte (exit status 1 on a
+                     difference)
+    --coeff times    alternating windows of steps on the default network; per case the medians and whether the new one
+                     exceeds the previous build's by more than that build's own spread over its rounds
+    --coeff trace --only new|prev
+                     the same cases, COEFF_TRACE_STEPS steps each, for one build: to be run under
+                     rocprofv3 --kernel-trace --stats --output-format csv
+    --coeff report --traces PREV_kernel_trace.csv NEW_kernel_trace.csv
+                     from two such traces: per case the mean time per launch of the fully connected layers' training
+                     kernels, and whether a step's ordered (kernel, grid) list is the same (needs no GPU)
 """
 import argparse
 import ctypes
@@ -24,7 +39,9 @@ from hdrnet_amd import _lib  # noqa: E402
 
 def bind(path):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _lib.SIGNATURES.items():
+    tables = (_lib.SIGNATURES, _lib.TRAIN_SIGNATURES, _lib.COEFF_BN_SIGNATURES, _lib.COEFF_WIDE_SIGNATURES,
+              _lib.PYRAMID_IO_SIGNATURES)
+    for name, (res, args) in ((n, sig) for table in tables for n, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -33,18 +50,230 @@ def bind(path):
     return lib
 
 
+COEFF_TINY = dict(net_input_size=64, spatial_bin=8)
+# (hyper-parameters, batches): the smallest shapes at which each piece of the training step can differ between two builds
+COEFF_BITS = [
+    (COEFF_TINY, (1, 2, 8, 9, 16, 17, 32)),                # either side of every image-count instance of the fc kernels
+    (dict(COEFF_TINY, channel_multiplier=2), (8, 16)),     # fc1 has 512 outputs: two 256-output chunks
+    (dict(COEFF_TINY, luma_bins=4), (3, 12)),              # fc3 with 32 outputs: partial workgroups
+    ({}, (4, 16)),                                         # the default network
+]
+COEFF_TIMES = [(4, False), (8, False), (16, True)]         # default network: (batch, through the ..._wide entry points)
+COEFF_TRACE_STEPS = 40
+COEFF_FC_KERNELS = ("coeff_fc_bwd", "coeff_bn_fc_bwd", "coeff_bn_fc")
+
+
+def coeff_net(params, bn):
+    """The coefficient network of a seeded model, every bias, beta and running statistic off its initial value."""
+    from hdrnet_amd import models
+    torch.manual_seed(21)
+    net = models.HDRNetPointwiseNNGuide(dict(batch_norm=bn, **params)).coefficients
+    g = torch.Generator().manual_seed(7)
+    with torch.no_grad():
+        for name, p in net.named_parameters():
+            if p.dim() == 1 and "bn.weight" not in name:
+                p.copy_(0.2 * torch.randn(p.shape, generator=g))
+        for name, b in net.named_buffers():
+            if name.endswith("running_mean"):
+                b.copy_(0.3 * torch.randn(b.shape, generator=g))
+            elif name.endswith("running_var"):
+                b.copy_(0.5 + torch.rand(b.shape, generator=g))
+    return net.to("cuda:0").train()
+
+
+def coeff_step(libs, net, bn, wide, low, dc):
+    """({build: a function that runs one forward + gradient of `net` through that build's C ABI}, the tensors they write:
+    the output, every gradient, the running statistics).  The builds share every buffer: where an allocation lies moves a
+    step's time by more than the builds differ."""
+    from hdrnet_amd import hdrnet_ops as ops
+    B, w = low.shape[0], "_wide" if wide else ""
+    ps, stats = net._train_params_bn() if bn else (net._train_params(), None)
+    n_splat = len(net.splat)
+    desc = ops._live_net_bn(net.hyper, net.n_out, net.n_in, ps, n_splat, stats, 1e-3, 1e-3)
+    grads = [torch.full_like(p, float("nan")) for p in ps]
+    gr = ops._coeff_fill(_lib.CoeffNetBnGrads() if bn else _lib.CoeffNetGrads(), n_splat, grads, bn)
+    if bn:
+        names = (f"hdrnet_coefficients_bn{w}_workspace_bytes", f"hdrnet_coefficients_bn_train{w}_f32",
+                 f"hdrnet_coefficients_bn_grad{w}_workspace_bytes", f"hdrnet_coefficients_bn_grad{w}_f32")
+    else:
+        names = ("hdrnet_coefficients_workspace_bytes", "hdrnet_coefficients_f32",
+                 f"hdrnet_coefficients_grad{w}_workspace_bytes", f"hdrnet_coefficients_grad{w}_f32")
+    sizes = {(getattr(lib, names[0])(ctypes.byref(desc), B), getattr(lib, names[2])(ctypes.byref(desc), B))
+             for lib in libs.values()}
+    assert len(sizes) == 1, ("the builds' workspaces differ", sizes)
+    (fbytes, bbytes), = sizes
+    assert fbytes > 0 and bbytes > 0, (names, B)
+    fws = torch.full((fbytes,), 0xA5, dtype=torch.uint8, device=low.device)
+    bws = torch.full((bbytes,), 0xA5, dtype=torch.uint8, device=low.device)
+    sb = net.hyper["spatial_bin"]
+    out = torch.full((B, sb, sb, net.gd, net.n_out, net.n_in), float("nan"), device=low.device)
+    stream = torch.cuda.current_stream(low.device).cuda_stream
+
+    def bound(lib):
+        fwd, bwd = getattr(lib, names[1]), getattr(lib, names[3])
+
+        def step():
+            if fwd(low.data_ptr(), ctypes.byref(desc), out.data_ptr(), B, fws.data_ptr(), fbytes, stream):
+                raise RuntimeError(lib.hdrnet_last_error().decode())
+            if bwd(low.data_ptr(), ctypes.byref(desc), fws.data_ptr(), dc.data_ptr(), ctypes.byref(gr), B, bws.data_ptr(),
+                   bbytes, stream):
+                raise RuntimeError(lib.hdrnet_last_error().decode())
+
+        step.keep = (desc, gr, ps, stats)  # the structs hold raw addresses
+        return step
+
+    return {which: bound(lib) for which, lib in libs.items()}, [out, *grads, *(t for st in stats or () for t in st)]
+
+
+def coeff_data(net, B):
+    g = torch.Generator(device="cuda:0").manual_seed(5)
+    N, sb = net.hyper["net_input_size"], net.hyper["spatial_bin"]
+    low = torch.rand((B, N, N, 3), device="cuda:0", generator=g)
+    dc = torch.randn((B, sb, sb, net.gd, net.n_out, net.n_in), device="cuda:0", generator=g)
+    return low, dc
+
+
+def coeff_bits(libs):
+    bad = 0
+    for params, batches in COEFF_BITS:
+        for B in batches:
+            for bn in (False, True):
+                for wide in (False, True):
+                    if (bn and B < 2) or (not wide and B > 8):
+                        continue
+                    got = {}
+                    for which, lib in libs.items():
+                        net = coeff_net(params, bn)
+                        low, dc = coeff_data(net, B)
+                        steps, results = coeff_step({which: lib}, net, bn, wide, low, dc)
+                        for _ in range(3):
+                            steps[which]()
+                        torch.cuda.synchronize()
+                        assert not any(bool(torch.isnan(t).any()) for t in results), "an element was not written"
+                        got[which] = [t.cpu().view(torch.int32) for t in results]  # bits: the sign of a zero counts
+                    diff = [i for i, (a, b) in enumerate(zip(got["prev"], got["new"])) if not torch.equal(a, b)]
+                    bad += bool(diff)
+                    print(f"{params or 'default'} B={B} {'bn' if bn else 'plain'} {'wide' if wide else 'first'}: "
+                          f"{len(got['new'])} tensors, " + (f"DIFFERENT: results {diff}" if diff else "equal"), flush=True)
+    print("coefficient training, bits:", "ALL EQUAL" if not bad else f"{bad} CASES DIFFER")
+    return 1 if bad else 0
+
+
+def coeff_cases(libs):
+    """The timed cases on the default network: (label, {build: step function})."""
+    for B, wide in COEFF_TIMES:
+        for bn in (False, True):
+            net = coeff_net({}, bn)
+            steps, _ = coeff_step(libs, net, bn, wide, *coeff_data(net, B))
+            yield f"B={B} {'bn' if bn else 'plain'} {'wide' if wide else 'first'}", steps
+
+
+def coeff_window(step, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+def coeff_times(libs, rounds):
+    worse = 0
+    print("case                 prev median (min .. max) us    new median (min .. max) us   new - prev   prev spread")
+    for label, steps in coeff_cases(libs):
+        n = max(50, int(0.3e6 / coeff_window(steps["prev"], 50)))  # a window of ~0.3 s
+        res = {"prev": [], "new": []}
+        for r in range(rounds):
+            for w in (("prev", "new"), ("new", "prev"))[r % 2]:  # the second of a pair measured 0.3-0.5 us slower: take turns
+                coeff_window(steps[w], 20)
+                res[w].append(coeff_window(steps[w], n))
+        mp, mn = statistics.median(res["prev"]), statistics.median(res["new"])
+        spread = max(res["prev"]) - min(res["prev"])
+        ok = mn - mp <= spread
+        worse += not ok
+        print(f"{label:20s} {mp:8.1f} ({min(res['prev']):7.1f} .. {max(res['prev']):7.1f})   {mn:8.1f} "
+              f"({min(res['new']):7.1f} .. {max(res['new']):7.1f})   {mn - mp:+8.1f}   {spread:8.1f}   "
+              f"{'ok' if ok else 'SLOWER'}   ({n} steps a window, {rounds} rounds)", flush=True)
+    return 1 if worse else 0
+
+
+def coeff_trace(libs, which):
+    for _, steps in coeff_cases({which: libs[which]}):
+        for _ in range(COEFF_TRACE_STEPS):
+            steps[which]()
+        torch.cuda.synchronize()
+
+
+def coeff_report(prev_csv, new_csv):
+    import csv
+    import re
+
+    def short(n):
+        n = re.sub(r"void |\(anonymous namespace\)::|hdrnet_amd::|\(.*$", "", n)
+        # one name for a fully connected kernel whether the build calls it coeff_fc_bwd / coeff_fc_bwd_wide<16> or
+        # coeff_fc_bwd<8> / coeff_fc_bwd<16>
+        return re.sub(r"^(coeff_(?:bn_)?fc(?:_bwd)?)<8>$", r"\1", n.replace("_wide<", "<"))
+
+    def cases(path):
+        rows = [r for r in csv.DictReader(open(path)) if "coeff_" in r["Kernel_Name"]]
+        rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+        starts = [i for i, r in enumerate(rows) if "coeff_conv_first" in r["Kernel_Name"]]  # the first launch of a step
+        assert len(starts) == 2 * len(COEFF_TIMES) * COEFF_TRACE_STEPS, len(starts)
+        starts.append(len(rows))
+        out = []
+        for c in range(2 * len(COEFF_TIMES)):
+            lo, hi = starts[c * COEFF_TRACE_STEPS], starts[(c + 1) * COEFF_TRACE_STEPS]
+            mean = {}
+            for k in COEFF_FC_KERNELS:
+                d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[lo:hi]
+                     if re.sub(r"[<(].*$", "", short(r["Kernel_Name"])).replace("_wide", "") == k]
+                mean[k] = (sum(d) / len(d), len(d) // COEFF_TRACE_STEPS) if d else None
+            last = rows[starts[(c + 1) * COEFF_TRACE_STEPS - 1]:hi]
+            out.append((mean, [(short(r["Kernel_Name"]), r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"]) for r in last]))
+        return out
+
+    prev, new = cases(prev_csv), cases(new_csv)
+    labels = [f"B={B} {'bn' if bn else 'plain'}" for B, _ in COEFF_TIMES for bn in (False, True)]
+    for label, (mp, lp), (mn, ln) in zip(labels, prev, new):
+        same = lp == ln
+        print(f"{label:12s} {len(ln)} launches a step, ordered (kernel, grid) list {'the same' if same else 'DIFFERENT'}")
+        if not same:
+            for a, b in zip(lp, ln):
+                if a != b:
+                    print("     ", a, "->", b)
+        for k in COEFF_FC_KERNELS:
+            if mn[k]:
+                print(f"    {k:16s} {mn[k][1]} launches a step: prev {mp[k][0]:6.2f} us   new {mn[k][0]:6.2f} us per launch")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--prev", required=True)
+    ap.add_argument("--prev")
     ap.add_argument("--workload", default="4k", choices=sorted(WORKLOADS))
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--cases", default="fwd,all,gg,g,v,slice_fwd,slice_bwd")
     ap.add_argument("--nsets", type=int, default=0, help="buffer sets to rotate over (default: enough to exceed the "
                     "Infinity Cache; 1 = cache-resident, for telling memory time from issue time)")
+    ap.add_argument("--coeff", choices=["bits", "times", "trace", "report"],
+                    help="the coefficient network's training step (see the top of the file)")
+    ap.add_argument("--only", choices=["new", "prev"], help="--coeff trace: the build to run")
+    ap.add_argument("--traces", nargs=2, metavar="CSV", help="--coeff report: the previous and the new build's kernel traces")
     args = ap.parse_args()
+    if args.coeff == "report":
+        return coeff_report(*args.traces)
+    if not args.prev:
+        ap.error("--prev is required")
     dev = torch.device("cuda:0")
     libs = {"new": _lib.load(), "prev": bind(os.path.abspath(args.prev))}
+    if args.coeff == "bits":
+        return coeff_bits(libs)
+    if args.coeff == "times":
+        return coeff_times(libs, args.rounds)
+    if args.coeff == "trace":
+        return coeff_trace(libs, args.only)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     Cin, Cout, C = 3, 3, 12
     npx = B * H * W
@@ -235,4 +464,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
