@@ -172,6 +172,18 @@ PYRAMID_IO_SIGNATURES = {
                                                  [_FP, _FP, _I, _U, _VP]),
 }
 
+# include/hdrnet_amd_pixel_formats.h: uint8 / uint16 frames in BGR, RGBA and BGRA order through the low-res gather and the
+# fused wire-format forwards (the hdrnet_lowres_input / ..._io_ex / ..._io_curves_prepared arguments plus the formats).
+PIXEL_FORMATS = {"rgb": 0, "bgr": 1, "rgba": 2, "bgra": 3}  # HDRNET_PX_*
+PIXEL_FORMAT_CHANNELS = {"rgb": 3, "bgr": 3, "rgba": 4, "bgra": 4}
+PIXEL_FORMAT_SIGNATURES = {
+    "hdrnet_lowres_input_px": (_I, [_FP, _I, ctypes.c_float] + [_I] * 3 + [_FP, _I, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_px": (_I, [_FP] * 4 + [_I] * 10 + [ctypes.c_float, _I] + [_FP] * 2 + [_I, _FP, _U, _I, _I,
+                                                                                                      _VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_px": (_I, [_FP] * 3 + [_I] * 10 + [ctypes.c_float, _I] + [_FP] * 4 +
+                                                  [_I, _VP, _FP, _I, _I, _VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -225,6 +237,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(COEFF_BN_SIGNATURES)
     table.update(COEFF_WIDE_SIGNATURES)
     table.update(PYRAMID_IO_SIGNATURES)
+    table.update(PIXEL_FORMAT_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():
@@ -258,6 +271,26 @@ def load_tools() -> ctypes.CDLL:
         if _tools_lib is None:
             _tools_lib = _open(tools=True)
     return _tools_lib
+
+
+def pixel_format(name, channels: int, dtype_is_float: bool, what: str, argument: str = "pixel_format") -> str:
+    """The pixel format of a frame with ``channels`` samples per pixel, checked against the rules of
+    include/hdrnet_amd_pixel_formats.h -- on the host, before anything touches the device.  ``None`` is ``"rgb"`` for three
+    channels; four channels need an explicit ``"rgba"`` / ``"bgra"`` (no guessing)."""
+    if name is None:
+        if channels == 4:
+            raise ValueError(f"{what}: a 4-channel frame needs {argument}='rgba' or {argument}='bgra' (the order of R and B "
+                             "is not guessed)")
+        name = "rgb"
+    if not isinstance(name, str) or name not in PIXEL_FORMATS:
+        raise ValueError(f"{what}: unknown {argument} {name!r} (takes {', '.join(repr(k) for k in PIXEL_FORMATS)})")
+    if PIXEL_FORMAT_CHANNELS[name] != channels:
+        raise ValueError(f"{what}: {argument}={name!r} is a {PIXEL_FORMAT_CHANNELS[name]}-channel format, the frame has "
+                         f"{channels} channels")
+    if dtype_is_float and name != "rgb":
+        raise ValueError(f"{what}: float32 frames take {argument}='rgb' only ({argument}={name!r} is for uint8 / uint16 "
+                         "frames)")
+    return name
 
 
 def enable_kernel_names(on: bool = True) -> None:

@@ -38,6 +38,8 @@ SOURCES = [
     # + MFMA results in VGPRs (gfx950's register file is unified): the guide network's 4x4x4 blocks are consumed by
     # the VALU at once, and the AGPR form costs a v_accvgpr_read per element
     ("apply_fwd_io.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    # the same kernel for frames in BGR / RGBA / BGRA order: twice the instantiations, a translation unit of its own
+    ("apply_fwd_io_px.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_upadd.hip", ["-fno-slp-vectorize"]),
     ("apply_bwd_rows.hip", ["-fno-slp-vectorize"]),
     ("apply_vjp_seg.hip", ["-fno-slp-vectorize"]),
@@ -103,7 +105,7 @@ def _usable_flags(cc: str, extra: List[str]) -> List[str]:
 def _deps() -> List[str]:
     out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"),
            os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.join(INCLUDE, "hdrnet_amd_coeff_wide.h"),
-           os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"), os.path.join(INCLUDE, "hdrnet_amd_pixel_formats.h"),
            os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):

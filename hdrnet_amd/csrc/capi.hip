@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "../../include/hdrnet_amd.h"
+#include "../../include/hdrnet_amd_pixel_formats.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
@@ -140,6 +141,43 @@ int check_io_format(int input_dtype, float input_white_level, int output_dtype) 
   return HDRNET_OK;
 }
 
+// the pixel formats of include/hdrnet_amd_pixel_formats.h: integer frames take all four, float32 frames RGB only; a
+// uint8 output has the input's format, a float32 output is RGB
+int check_pixel_formats(const char* what, int input_dtype, int output_dtype, int input_format, int output_format) {
+  if (input_format < HDRNET_PX_RGB || input_format > HDRNET_PX_BGRA || output_format < HDRNET_PX_RGB ||
+      output_format > HDRNET_PX_BGRA)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown pixel format code (input %d, output %d; 0 RGB, 1 BGR, 2 RGBA, 3 BGRA)",
+                what, input_format, output_format);
+  if (input_dtype == 0 && input_format != HDRNET_PX_RGB)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: float32 frames take HDRNET_PX_RGB only (input_format %d); the other pixel "
+                "formats are those of uint8 / uint16 frames", what, input_format);
+  if (output_dtype == 1 && output_format != input_format)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a uint8 output has the input's pixel format (input_format %d, output_format %d)",
+                what, input_format, output_format);
+  if (output_dtype == 0 && output_format != HDRNET_PX_RGB)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a float32 output is [B][H][W][3] in RGB order: output_format must be "
+                "HDRNET_PX_RGB (got %d)", what, output_format);
+  return HDRNET_OK;
+}
+
+// ... and what a frame in another format than RGB needs of the call: the 3 -> 3 op with offset, W % 4 == 0, 4-byte
+// aligned 3-channel and 16-byte aligned 4-channel integer buffers (`out`: the uint8 output, or null)
+int check_pixel_buffers(const char* what, int pixel_format, int Cin, int Cout, int has_offset, int W, const void* input,
+                        const void* out) {
+  if (pixel_format == HDRNET_PX_RGB) return HDRNET_OK;
+  if (Cin != 3 || Cout != 3 || !has_offset)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: pixel formats other than HDRNET_PX_RGB need Cin = Cout = 3 with offset (the "
+                "format says how the frame stores a pixel, not how many channels the op sees)", what);
+  if (W % 4 != 0)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: W %% 4 != 0 (W=%d): a lane owns 4 pixels", what, W);
+  const unsigned mask = pixel_format >= HDRNET_PX_RGBA ? 15u : 3u;
+  if (((uintptr_t)input | (uintptr_t)out) & mask)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: %s", what,
+                mask == 15u ? "4-channel frames (RGBA / BGRA) must be 16-B aligned (one 16-byte access per lane)"
+                            : "3-channel integer frames must be 4-B aligned");
+  return HDRNET_OK;
+}
+
 // any parameter the coefficient network reads (and, for the gradient, any it writes) missing?
 bool coeff_net_null_param(const hdrnet_coeff_net& net, const hdrnet_coeff_net_grads* grads) {
   int n_ds = 0;
@@ -261,6 +299,22 @@ int grad_dispatch(const hdrnet_amd::ApplyGradArgs& a, unsigned family, hipStream
 
 }  // namespace
 
+// the wire-format forwards for a frame in any pixel format (defined beside their entry points below)
+static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
+                         int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
+                         float* guide_out, unsigned flags, int pixel_format, void* stream);
+static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
+                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
+                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
+                                float* guide_out, int pixel_format, void* stream);
+static int prepare_impl(const char* what, const void* src_input, int input_dtype, float input_white_level,
+                        const void* src_target, int target_dtype, float target_white_level, int N, int Hs, int Ws,
+                        const int* ops, int B, float* image_input, float* image_target, int H, int W,
+                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged = false,
+                        long long n_samples = 0, const int* images = nullptr, int pixel_format = 0);
+
 extern "C" {
 
 // 0.2.4.1: + hdrnet_guide_nn_prescale_f32 / HDRNET_GUIDE_RELU_PRESCALED, hdrnet_curves_guide_prepare_f32 (with `usable`) /
@@ -277,7 +331,9 @@ extern "C" {
 //          where 281 returned a size: include/hdrnet_amd.h)
 // 0.2.8.5: + include/hdrnet_amd_pyramid_io.h: hdrnet_resize_bilinear_io, hdrnet_bilateral_slice_apply_upadd_io_ex (the
 //          pyramid model's wire formats)
-int hdrnet_version(void) { return 285; }
+// 0.2.8.6: + include/hdrnet_amd_pixel_formats.h: hdrnet_lowres_input_px, hdrnet_bilateral_slice_apply_io_px,
+//          hdrnet_bilateral_slice_apply_io_curves_px (uint8 / uint16 frames in BGR, RGBA and BGRA order)
+int hdrnet_version(void) { return 286; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -822,6 +878,59 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
                                        float input_white_level, int output_dtype,
                                        const float* guide_conv1, const float* guide_conv2, int n_feats,
                                        float* guide_out, unsigned flags, void* stream) {
+  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                       input_white_level, output_dtype, guide_conv1, guide_conv2, n_feats, guide_out, flags,
+                       HDRNET_PX_RGB, stream);
+}
+
+// ---- include/hdrnet_amd_pixel_formats.h: frames in BGR / RGBA / BGRA order -----------------------------------------
+int hdrnet_bilateral_slice_apply_io_px(const float* grid, const float* guide, const void* input, void* out, int B, int H,
+                                       int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype,
+                                       float input_white_level, int output_dtype, const float* guide_conv1,
+                                       const float* guide_conv2, int n_feats, float* guide_out, unsigned flags,
+                                       int input_format, int output_format, void* stream) {
+  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
+  if (int rc = check_pixel_formats("hdrnet_bilateral_slice_apply_io_px", input_dtype, output_dtype, input_format, output_format))
+    return rc;
+  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                       input_white_level, output_dtype, guide_conv1, guide_conv2, n_feats, guide_out, flags, input_format,
+                       stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_px(const float* grid, const void* input, void* out, int B, int H, int W, int GH,
+                                              int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype,
+                                              float input_white_level, int output_dtype, const float* guide_ccm,
+                                              const float* guide_shifts, const float* guide_slopes,
+                                              const float* guide_mix, int npts, const void* prepared, float* guide_out,
+                                              int input_format, int output_format, void* stream) {
+  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
+  if (int rc = check_pixel_formats("hdrnet_bilateral_slice_apply_io_curves_px", input_dtype, output_dtype, input_format,
+                                   output_format))
+    return rc;
+  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
+                              prepared, guide_out, input_format, stream);
+}
+
+int hdrnet_lowres_input_px(const void* frames, int dtype, float white_level, int B, int H, int W, float* lowres,
+                           int net_input_size, int pixel_format, void* stream) {
+  const char* what = "hdrnet_lowres_input_px";
+  if (pixel_format == HDRNET_PX_RGB) return hdrnet_lowres_input(frames, dtype, white_level, B, H, W, lowres, net_input_size, stream);
+  if (dtype < 0 || dtype > 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", what, dtype);
+  if (int rc = check_pixel_formats(what, dtype, 0, pixel_format, HDRNET_PX_RGB)) return rc;
+  if (B > 0 && !lowres) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (lowres)", what);
+  if (B > 0 && pixel_format >= HDRNET_PX_RGBA && ((uintptr_t)frames & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: 4-channel frames (RGBA / BGRA) must be 16-B aligned", what);
+  return prepare_impl(what, frames, dtype, white_level, nullptr, 0, 1.0f, B > 0 ? B : 1, H, W, nullptr, B, nullptr, nullptr,
+                      H, W, lowres, net_input_size, 0u, stream, false, 0, nullptr, pixel_format);
+}
+
+// the wire-format forward with a guide map or the guide network, for a frame in `pixel_format` (io_ex: HDRNET_PX_RGB)
+static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
+                         int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
+                         float* guide_out, unsigned flags, int pixel_format, void* stream) {
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
@@ -834,6 +943,10 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
   ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
                 input_dtype, output_dtype, input_white_level, guide_conv1, guide_conv2, n_feats,
                 guide_out};
+  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset, W, input,
+                                   output_dtype == 1 ? out : nullptr))
+    return rc;
+  a.pixel_format = pixel_format;
   if (int rc = check_guide_prescaled(flags, guide ? 0 : Cin, guide ? nullptr : guide_conv1, guide ? nullptr : guide_conv2)) return rc;
   a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
   a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
@@ -915,8 +1028,8 @@ int hdrnet_bilateral_slice_apply_upadd_io_ex(const float* grid, const float* gui
 static int prepare_impl(const char* what, const void* src_input, int input_dtype, float input_white_level,
                         const void* src_target, int target_dtype, float target_white_level, int N, int Hs, int Ws,
                         const int* ops, int B, float* image_input, float* image_target, int H, int W,
-                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged = false,
-                        long long n_samples = 0, const int* images = nullptr) {
+                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged,
+                        long long n_samples, const int* images, int pixel_format) {
   using namespace hdrnet_amd;
   if (ragged) Hs = Ws = 1;  // unused
   if (flags & ~HDRNET_SAMPLE_EVEN_TURNS_ONLY)
@@ -968,6 +1081,7 @@ static int prepare_impl(const char* what, const void* src_input, int input_dtype
                          lowres_input, lowres_input ? net_input_size : 0, (flags & HDRNET_SAMPLE_EVEN_TURNS_ONLY) != 0};
   a.images = images;
   a.n_samples = n_samples;
+  a.pixel_format = pixel_format;  // the low-res gather of hdrnet_lowres_input_px; every other caller: RGB
   return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what,
                        ragged ? "sample_prep_ragged" : "sample_prep");
 }
@@ -1047,6 +1161,17 @@ int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const voi
                                                     const float* guide_shifts, const float* guide_slopes,
                                                     const float* guide_mix, int npts, const void* prepared,
                                                     float* guide_out, void* stream) {
+  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
+                              prepared, guide_out, HDRNET_PX_RGB, stream);
+}
+
+// ... and with the curves guide (..._io_curves_prepared: HDRNET_PX_RGB)
+static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
+                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
+                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
+                                float* guide_out, int pixel_format, void* stream) {
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
@@ -1058,6 +1183,10 @@ int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const voi
   ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
                 input_dtype, output_dtype, input_white_level, guide_ccm, guide_mix, npts,
                 guide_out, guide_shifts, guide_slopes};
+  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout, has_offset, W,
+                                   input, output_dtype == 1 ? out : nullptr))
+    return rc;
+  a.pixel_format = pixel_format;
   if (prepared) {
     if (((uintptr_t)prepared & 15u) || Cin != 3 || npts > 16)
       return fail(HDRNET_INVALID_ARGUMENT, "prepared curves tables need Cin = 3, npts <= 16 and the 16-B aligned buffer "

@@ -52,6 +52,9 @@ struct ApplyIoArgs {
   bool fast_sigmoid = false;            // guide network: as ApplyArgs::fast_sigmoid
   bool guide_prescaled = false;         // guide network: as ApplyArgs::guide_prescaled
   const float* guide_prepared = nullptr;  // curves guide: the cell tables of hdrnet_curves_guide_prepare_f32, or null
+  // how `input` stores a pixel, HDRNET_PX_* (include/hdrnet_amd_pixel_formats.h): 0 RGB, 1 BGR, 2 RGBA, 3 BGRA; a uint8
+  // `out` has the same format, a float32 one is RGB.  Cin / Cout stay the op's 3 whatever the format (apply_fwd_io.hip only)
+  int pixel_format = 0;
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -217,6 +220,8 @@ struct SamplePrepArgs {
   // Hs / Ws are unused
   const int* images = nullptr;  // device [N][4] = {offset_lo, offset_hi, Hs, Ws}, the offset in samples
   long long n_samples = 0;
+  // the low-res gather alone (hdrnet_lowres_input_px): how src_input stores a pixel, HDRNET_PX_* as ApplyIoArgs::pixel_format
+  int pixel_format = 0;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 

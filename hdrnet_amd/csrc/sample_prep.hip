@@ -72,6 +72,9 @@ struct PrepParams {
   int even_only;
   const int* images;    // RAGGED: device [N][4] = {offset_lo, offset_hi, Hs, Ws}, the offset in samples
   long long n_samples;  // RAGGED: samples of each flat source buffer
+  // the low-res gather of a frame in another pixel format (hdrnet_lowres_input_px; the full-resolution jobs and the ragged
+  // flavour are RGB): samples per stored pixel, and whether B comes first
+  int px_stride, px_b_first;
 };
 
 typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
@@ -108,7 +111,7 @@ __device__ __forceinline__ Geom make_geom(const PrepParams& p, int b) {
     g.image = (long long)(((unsigned long long)(uint32_t)d.y << 32) | (uint32_t)d.x);
     Hs = d.z; Ws = d.w;
   } else {
-    g.image = (long long)index * p.Hs * p.Ws * 3;
+    g.image = (long long)index * p.Hs * p.Ws * p.px_stride;
   }
   g.Ws = Ws;
   g.odd = rot & 1;
@@ -133,7 +136,7 @@ __device__ __forceinline__ long long clampll(long long v, long long lo, long lon
 // index of the last dword of a source buffer of element type T
 template <typename T, bool RAGGED>
 __device__ __forceinline__ long long last_dword(const PrepParams& p) {
-  const long long samples = RAGGED ? p.n_samples : (long long)p.N * p.Hs * p.Ws * 3;
+  const long long samples = RAGGED ? p.n_samples : (long long)p.N * p.Hs * p.Ws * p.px_stride;
   return ((samples * (long long)sizeof(T)) - 1) >> 2;
 }
 
@@ -186,7 +189,8 @@ __device__ __forceinline__ void load_4px(const void* src, long long e, long long
   }
 }
 
-// one pixel (3 samples) at sample index e.  CLAMP: the pixel's position comes from a descriptor table that is not
+// one pixel (3 samples) at sample index e -- of a pixel with alpha too: its colour samples are the first three of its
+// 4 (uint8: one aligned dword; uint16: two), and alpha is never read into v.  CLAMP: the pixel's position comes from a descriptor table that is not
 // trusted, so every dword index is clamped (the uniform flavour's positions are inside the buffer by construction).
 template <typename T, bool CLAMP>
 __device__ __forceinline__ void load_1px(const void* src, long long e, long long last, const WhiteLevel& wl, float (&v)[3]) {
@@ -304,7 +308,12 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
       y = y < p.H - 1 ? y : p.H - 1;
       x = x < p.W - 1 ? x : p.W - 1;
       const int row = g.r0 + g.rs * (g.odd ? x : y), col = g.c0 + g.cs * (g.odd ? y : x);
-      load_1px<T, RAGGED>(job.src, g.image + ((long long)row * g.Ws + col) * 3, last, job.white, v[j]);
+      load_1px<T, RAGGED>(job.src, g.image + ((long long)row * g.Ws + col) * p.px_stride, last, job.white, v[j]);
+      if (p.px_b_first) {  // uniform: B, G, R as stored -> R, G, B
+        const float t = v[j][0];
+        v[j][0] = v[j][2];
+        v[j][2] = t;
+      }
     }
     if (vec) {
       const float* f = &v[0][0];
@@ -360,6 +369,8 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.even_only = a.even_turns_only ? 1 : 0;
   p.images = a.images;
   p.n_samples = a.n_samples;
+  p.px_stride = px_stored(a.pixel_format);
+  p.px_b_first = px_b_first(a.pixel_format) ? 1 : 0;
   const long long low_blocks = ((long long)a.n * a.n + 4 * kThreads - 1) / (4 * kThreads);
   const long long gx = full ? p.tiles : low_blocks;
   const dim3 grid((unsigned)gx, (unsigned)a.B, (unsigned)nj);

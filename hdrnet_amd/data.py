@@ -66,11 +66,22 @@ def _check_out(name: str, t: torch.Tensor, shape: Tuple[int, ...], device: torch
 
 
 def lowres_input(frames: torch.Tensor, net_input_size: int = 256, white_level: Optional[float] = None,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, pixel_format: str = "rgb") -> torch.Tensor:
     """``[B, H, W, 3]`` frames (uint8 / uint16 / float32, on the device) -> the coefficient network's input
     ``[B, n, n, 3]`` float32: nearest neighbour (TF1 / OpenCV rule, see the module text) of ``frames / white_level``.
     Default white levels are those of ``hdrnet_ops.bilateral_slice_apply_io``: 255 / 65535 / 1 (float32 is copied
-    unscaled).  One launch on the current stream; capturable."""
+    unscaled).  One launch on the current stream; capturable.
+
+    ``pixel_format``: ``"rgb"`` (default), ``"bgr"``, or ``"rgba"`` / ``"bgra"`` for ``[B, H, W, 4]`` frames
+    (uint8 / uint16 only; ``hdrnet_lowres_input_px``).  The result is RGB whatever the format -- the bits of this call on
+    the repacked frame -- and alpha is not read.  Training-side sample preparation (``prepare_batch``) stays RGB."""
+    if pixel_format != "rgb":
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise ValueError(f"frames should be [N, H, W, 3 or 4], got "
+                             f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames).__name__}")
+        pixel_format = _lib.pixel_format(pixel_format, frames.shape[3], frames.dtype == torch.float32, "lowres_input")
+    if pixel_format != "rgb":
+        return _lowres_input_px(frames, int(net_input_size), white_level, out, pixel_format)
     _check_sources("frames", frames)
     B, H, W, _ = frames.shape
     n = int(net_input_size)
@@ -83,6 +94,28 @@ def lowres_input(frames: torch.Tensor, net_input_size: int = 256, white_level: O
     with torch.cuda.device(frames.device):
         rc = _lib.load().hdrnet_lowres_input(frames.data_ptr(), _DTYPE_CODE[frames.dtype], float(white_level), B, H, W,
                                              out.data_ptr(), n, _stream(frames.device))
+    _lib.check(rc, "LowresInput")
+    return out
+
+
+def _lowres_input_px(frames, n: int, white_level, out, pixel_format: str) -> torch.Tensor:
+    if frames.dtype not in _DTYPE_CODE:
+        raise TypeError(f"frames must be float32, uint8 or uint16, got {frames.dtype}")
+    if not frames.is_cuda:
+        raise RuntimeError(f"frames is on {frames.device}: sample preparation runs on an MI355X (HIP) device only")
+    if not frames.is_contiguous():
+        raise ValueError("frames must be contiguous (NHWC)")
+    B, H, W, _ = frames.shape
+    if white_level is None:
+        white_level = _WHITE[frames.dtype]
+    if out is None:
+        out = torch.empty((B, n, n, 3), dtype=torch.float32, device=frames.device)
+    else:
+        _check_out("lowres_input", out, (B, n, n, 3), frames.device)
+    with torch.cuda.device(frames.device):
+        rc = _lib.load().hdrnet_lowres_input_px(frames.data_ptr(), _DTYPE_CODE[frames.dtype], float(white_level), B, H, W,
+                                                out.data_ptr(), n, _lib.PIXEL_FORMATS[pixel_format],
+                                                _stream(frames.device))
     _lib.check(rc, "LowresInput")
     return out
 

@@ -1096,12 +1096,37 @@ def curves_guide_prepare(shifts: torch.Tensor, slopes: torch.Tensor) -> Optional
     return out if usable.value else None
 
 
+def _out_channels(pixel_format: str, out_dtype, Cout: int) -> int:
+    """Channels of the output tensor: a uint8 output has the input's pixel format, a float32 output is RGB."""
+    return _lib.PIXEL_FORMAT_CHANNELS[pixel_format] if (pixel_format != "rgb" and out_dtype == torch.uint8) else Cout
+
+
+def _px_codes(pixel_format: str, out_dtype):
+    """``(input_format, output_format)`` of the ..._px entry points (HDRNET_PX_*)."""
+    code = _lib.PIXEL_FORMATS[pixel_format]
+    return code, (code if out_dtype == torch.uint8 else _lib.PIXEL_FORMATS["rgb"])
+
+
+def _check_io_px(grid, input, has_offset, pixel_format):  # noqa: A002
+    """``_check_io`` for a frame in another pixel format than RGB: the op sees three channels whatever the frame stores."""
+    if not isinstance(input, torch.Tensor) or input.dim() != 4:
+        raise ValueError("Input image should be 4D (batch_size, height, width, input_channels)")
+    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input[..., :3], has_offset)
+    if (Cin, Cout) != (3, 3) or not has_offset:
+        raise ValueError(f"pixel_format={pixel_format!r} needs the 3 -> 3 op with offset (a [.., 12] grid), got Cout = {Cout}, "
+                         f"has_offset = {bool(has_offset)}")
+    return B, H, W, GH, GW, GD, Cin, Cout
+
+
 def _apply_io_curves(grid, input, curves, input_white_level, out_dtype, has_offset, return_guide,  # noqa: A002
-                     prepared=None):
+                     prepared=None, pixel_format="rgb"):
     if len(curves) != 4:
         raise ValueError("guide_curves should be (ccm, shifts, slopes, mix)")
     ccm, shifts, slopes, mix = curves
-    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
+    if pixel_format == "rgb":
+        B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
+    else:
+        B, H, W, GH, GW, GD, Cin, Cout = _check_io_px(grid, input, has_offset, pixel_format)
     npts = shifts.shape[0] if shifts.dim() == 2 else -1
     for nm, t, shape in (("ccm", ccm, (Cin, Cin + 1)), ("shifts", shifts, (npts, Cin)),
                          ("slopes", slopes, (npts, Cin)), ("mix", mix, (Cin + 1,))):
@@ -1122,14 +1147,16 @@ def _apply_io_curves(grid, input, curves, input_white_level, out_dtype, has_offs
         _require_gpu("prepared", prepared)
         if not prepared.is_contiguous() or prepared.numel() * 4 < lib.hdrnet_curves_guide_prepared_bytes(Cin):
             raise ValueError("prepared should be the tensor curves_guide_prepare returned")
-    out = torch.empty((B, H, W, Cout), dtype=out_dtype, device=dev)
+    out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
     with torch.cuda.device(dev):
-        rc = lib.hdrnet_bilateral_slice_apply_io_curves_prepared(
-            grid.data_ptr(), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
-            int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
-            ccm.data_ptr(), shifts.data_ptr(), slopes.data_ptr(), mix.data_ptr(), npts, _ptr(prepared), _ptr(gout),
-            _stream(dev))
+        args = (grid.data_ptr(), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
+                int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
+                ccm.data_ptr(), shifts.data_ptr(), slopes.data_ptr(), mix.data_ptr(), npts, _ptr(prepared), _ptr(gout))
+        if pixel_format == "rgb":
+            rc = lib.hdrnet_bilateral_slice_apply_io_curves_prepared(*args, _stream(dev))
+        else:
+            rc = lib.hdrnet_bilateral_slice_apply_io_curves_px(*args, *_px_codes(pixel_format, out_dtype), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOCurves")
     return (out, gout) if return_guide else out
 
@@ -1143,7 +1170,7 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
                              has_offset: bool = True,
                              guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
                              return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
-                             curves_prepared: Optional[torch.Tensor] = None):
+                             curves_prepared: Optional[torch.Tensor] = None, pixel_format: str = "rgb"):
     """Inference forward with the product's wire formats fused in: ``input`` may be uint8 / uint16
     (``value / input_white_level``: 255, 65535, or 32767 for HDR+ -- hdrnet/data_pipeline.py:202-232,
     :267-274) and the output may be uint8 ``= (uint8)(255 * clip(out, 0, 1))`` (hdrnet/bin/run.py:95).
@@ -1156,38 +1183,55 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     sigmoid, <= 2 ulp of the guide away from the default (tf.nn.sigmoid's form) and ~10 % faster -- an explicit
     choice of the caller (HDRNET_GUIDE_SIGMOID_FAST), never implied by another argument.  ``prescaled`` (guide network):
     ``guide_conv1`` / ``guide_conv2`` are ``guide_nn_prescale``'s arrays (HDRNET_GUIDE_RELU_PRESCALED).
-    ``curves_prepared`` (``guide_curves``): the tables of ``curves_guide_prepare``.  No autograd."""
+    ``curves_prepared`` (``guide_curves``): the tables of ``curves_guide_prepare``.  No autograd.
+
+    ``pixel_format`` says how ``input`` stores a pixel (include/hdrnet_amd_pixel_formats.h): ``"rgb"`` (default),
+    ``"bgr"``, ``"rgba"`` or ``"bgra"`` -- ``[B, H, W, 3 or 4]`` as OpenCV, decoders and display surfaces deliver frames.
+    The op always sees R, G, B (a ``[.., 12]`` grid, the guide parameters in that order): the bytes are permuted in the
+    kernel's load and store, with every guide source.  uint8 / uint16 frames take all four, float32 frames ``"rgb"``
+    only.  A uint8 output has the input's format, with alpha carried over (the byte of a uint8 frame, ``alpha >> 8`` of a
+    uint16 one: alpha is never divided by the white level or quantised); a float32 output is ``[B, H, W, 3]`` RGB.
+    4-channel frames must be 16-byte aligned.  Out of scope: float32 frames in other orders, uint16 output."""
     if input.dim() != 4:
         raise ValueError(f"Input image should be 4D (batch_size, height, width, input_channels), got {tuple(input.shape)}")
     if input.dtype not in _DTYPE_CODE:
         raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
     if out_dtype not in (torch.float32, torch.uint8):
         raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+    if pixel_format != "rgb":  # "rgb": every rule below is the one it always was
+        pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32,
+                                         "bilateral_slice_apply_io")
     if guide_curves is not None:
         if guide is not None or guide_conv1 is not None or guide_conv2 is not None:
             raise ValueError("give exactly one of guide, (guide_conv1, guide_conv2), guide_curves")
         return _apply_io_curves(grid, input, guide_curves, input_white_level, out_dtype, has_offset, return_guide,
-                                curves_prepared)
+                                curves_prepared, pixel_format)
     if return_guide and guide is not None:
         raise ValueError("return_guide needs a guide computed by the kernel (guide network or guide_curves)")
     if (guide is None) == (guide_conv1 is None or guide_conv2 is None):
         raise ValueError("give either a guide map or both guide_conv1 and guide_conv2")
     if input_white_level is None:
         input_white_level = _DEFAULT_WHITE[input.dtype]
-    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
+    if pixel_format == "rgb":
+        B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
+    else:
+        B, H, W, GH, GW, GD, Cin, Cout = _check_io_px(grid, input, has_offset, pixel_format)
     guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), Cin)
     _require_gpu("grid", grid)
     _require_gpu("input", input)
     grid, inp = grid.detach().contiguous(), input.detach().contiguous()
     dev = inp.device
-    out = torch.empty((B, H, W, Cout), dtype=out_dtype, device=dev)
+    out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
     lib = _lib.load()
     with torch.cuda.device(dev):
-        rc = lib.hdrnet_bilateral_slice_apply_io_ex(
-            grid.data_ptr(), _ptr(guide), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
-            int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
-            _ptr(c1), _ptr(c2), n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
+        args = (grid.data_ptr(), _ptr(guide), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
+                int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
+                _ptr(c1), _ptr(c2), n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None))
+        if pixel_format == "rgb":
+            rc = lib.hdrnet_bilateral_slice_apply_io_ex(*args, _stream(dev))
+        else:
+            rc = lib.hdrnet_bilateral_slice_apply_io_px(*args, *_px_codes(pixel_format, out_dtype), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIO")
     return (out, gout) if return_guide else out
 

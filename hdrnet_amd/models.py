@@ -583,16 +583,25 @@ class HDRNetCurves(nn.Module):
         return {"guide_curves": arrays, "curves_prepared": self.guide.prepared() if self.prepare_curves else None}
 
     def process(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                white_level: Optional[float] = None) -> torch.Tensor:
+                white_level: Optional[float] = None, pixel_format: Optional[str] = None) -> torch.Tensor:
         """Frame in, frame out (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on the device ->
         ``data.lowres_input`` -> the coefficient network -> the fused guide + slice-apply, with the wire formats converted
         in registers (``hdrnet_ops.bilateral_slice_apply_io``): ``value / white_level`` in (255 / 65535 / 1 by default),
         float32 or uint8 ``= (uint8)(255 * clip(out, 0, 1))`` out (hdrnet/bin/run.py:95; default float32).  The guide
         parameters and the ``fast_sigmoid`` / ``prescale_guide`` / ``prepare_curves`` choices are the model's own.  For a
-        float32 frame with float32 out the result is exactly ``forward(data.lowres_input(frame), frame)``."""
-        from . import data, hdrnet_ops
-        if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] != 3:
-            raise ValueError("frame should be [B, H, W, 3]")
+        float32 frame with float32 out the result is exactly ``forward(data.lowres_input(frame), frame)``.
+
+        ``pixel_format``: how the frame stores a pixel -- ``"rgb"``, ``"bgr"``, or ``"rgba"`` / ``"bgra"`` for a
+        ``[B, H, W, 4]`` frame (uint8 / uint16 frames; float32 is ``"rgb"`` only).  ``None`` means ``"rgb"`` for a
+        3-channel frame; a 4-channel frame must name its format (the order of R and B is not guessed).  The model sees
+        R, G, B; the bytes are permuted in the kernels' loads and stores, not in a pass of their own.  A uint8 output has
+        the frame's format and its alpha (``alpha >> 8`` of a uint16 frame), a float32 output is ``[B, H, W, 3]`` RGB.
+        Out of scope: float32 frames in other orders, uint16 output, the pyramid model."""
+        from . import _lib, data, hdrnet_ops
+        if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] not in (3, 4):
+            raise ValueError("frame should be [B, H, W, 3] (or [B, H, W, 4] with pixel_format='rgba' / 'bgra')")
+        pixel_format = _lib.pixel_format(pixel_format, frame.shape[3], frame.dtype == torch.float32,
+                                         f"{type(self).__name__}.process")
         if frame.dtype not in self._process_dtypes:
             raise TypeError(f"{type(self).__name__}.process takes "
                             f"{' / '.join(str(d).replace('torch.', '') for d in self._process_dtypes)} frames, got {frame.dtype}")
@@ -605,14 +614,14 @@ class HDRNetCurves(nn.Module):
             raise RuntimeError("process() is inference: call eval() first")
         with torch.no_grad():
             frame = frame.contiguous()
-            lowres = data.lowres_input(frame, self.params["net_input_size"], white_level)
+            lowres = data.lowres_input(frame, self.params["net_input_size"], white_level, pixel_format=pixel_format)
             if frame.dtype == torch.float32 and out_dtype == torch.float32:  # float32 is never scaled
                 return self.forward(lowres, frame)
             coeffs = self.coefficients(lowres)
             gs = coeffs.shape
             return hdrnet_ops.bilateral_slice_apply_io(
                 coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), frame, input_white_level=white_level,
-                out_dtype=out_dtype, has_offset=True, **self._process_guide_args())
+                out_dtype=out_dtype, has_offset=True, pixel_format=pixel_format, **self._process_guide_args())
 
 
 class HDRNetPointwiseNNGuide(HDRNetCurves):
@@ -790,14 +799,19 @@ class HDRNetGaussianPyrNN(HDRNetPointwiseNNGuide):
         return current
 
     def process_wire(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                     white_level: Optional[float] = None) -> torch.Tensor:
+                     white_level: Optional[float] = None, pixel_format: Optional[str] = None) -> torch.Tensor:
         """Frame in, frame out with the wire formats (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on
         the device, float32 (default) or uint8 ``= (uint8)(255 * clip(out, 0, 1))`` out.  ``_forward_fused`` step for step,
         with level 1 resized from the frame as it arrives (``hdrnet_ops.resize_bilinear_io``) and the finest level's
         conversions in registers (``hdrnet_ops.bilateral_slice_apply_upadd_io``): no float32 copy of the frame exists.
         ``white_level``: 255 / 65535 / 1 by default.  A float32 frame with float32 out is ``process(frame)``.  The fused
-        path's own condition holds: W % 16 == 0.  (``process`` keeps its float32-only contract.)"""
+        path's own condition holds: W % 16 == 0.  (``process`` keeps its float32-only contract.)  ``pixel_format``: the
+        pyramid's resize and up-add kernels read RGB frames only -- anything but ``None`` / ``"rgb"`` is refused (the
+        single-level models' ``process`` takes BGR / RGBA / BGRA frames)."""
         from . import data, hdrnet_ops
+        if pixel_format not in (None, "rgb"):
+            raise ValueError(f"{type(self).__name__}.process_wire takes pixel_format='rgb' only, got {pixel_format!r}: the "
+                             "pyramid model's resize and up-add kernels have no other pixel format")
         if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] != 3:
             raise ValueError("frame should be [B, H, W, 3]")
         if frame.dtype not in (torch.float32, torch.uint8, torch.uint16):

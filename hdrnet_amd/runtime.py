@@ -79,25 +79,30 @@ class GraphedInference:
 class _Process(torch.nn.Module):
     """``model.process`` as the module a ``GraphedInference`` captures (parameters and buffers are the model's)."""
 
-    def __init__(self, model: torch.nn.Module, out_dtype, white_level):
+    def __init__(self, model: torch.nn.Module, out_dtype, white_level, pixel_format=None):
         super().__init__()
-        self.model, self.out_dtype, self.white_level = model, out_dtype, white_level
+        self.model, self.out_dtype, self.white_level, self.pixel_format = model, out_dtype, white_level, pixel_format
 
     def forward(self, frame: torch.Tensor) -> torch.Tensor:
         # a model whose process() is float32-only offers its wire formats as process_wire() (HDRNetGaussianPyrNN)
         if hasattr(self.model, "process_wire") and (frame.dtype != torch.float32 or self.out_dtype == torch.uint8):
+            if self.pixel_format is not None:
+                return self.model.process_wire(frame, self.out_dtype, self.white_level, pixel_format=self.pixel_format)
             return self.model.process_wire(frame, self.out_dtype, self.white_level)
+        if self.pixel_format is not None:
+            return self.model.process(frame, self.out_dtype, self.white_level, pixel_format=self.pixel_format)
         return self.model.process(frame, self.out_dtype, self.white_level)
 
 
 class FrameInference(GraphedInference):
     """Frame in, frame out from a hipGraph: a ``GraphedInference`` whose captured callable is ``model.process`` (low-res
     input, coefficient network, fused guide + slice-apply with the wire formats in registers).  One input, the frame
-    (uint8 / uint16 / float32 ``[B, H, W, 3]``); ``out_dtype`` float32 (default) or uint8."""
+    (uint8 / uint16 / float32 ``[B, H, W, 3]``); ``out_dtype`` float32 (default) or uint8.  ``pixel_format``: as
+    ``model.process`` -- with ``"bgra"`` the captured graph replays ``[B, H, W, 4]`` frames as a decoder delivers them."""
 
     def __init__(self, model: torch.nn.Module, example_frame: torch.Tensor, out_dtype=None, white_level=None,
-                 warmup: int = 3, check_parameters: bool = True):
-        super().__init__(_Process(model.eval(), out_dtype, white_level), [example_frame], warmup=warmup,
+                 warmup: int = 3, check_parameters: bool = True, pixel_format=None):
+        super().__init__(_Process(model.eval(), out_dtype, white_level, pixel_format), [example_frame], warmup=warmup,
                          check_parameters=check_parameters)
 
 

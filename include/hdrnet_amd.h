@@ -102,7 +102,9 @@ extern "C" {
  *   284  + the ..._wide twins of the coefficient network's three training entry points and their workspace queries in
  *        hdrnet_amd_coeff_wide.h, which hdrnet_amd_train.h includes: batches up to 32 (the first ones stay at 8).
  *   285  + hdrnet_resize_bilinear_io / hdrnet_bilateral_slice_apply_upadd_io_ex in hdrnet_amd_pyramid_io.h (a header of
- *        its own, beside this one): the pyramid model's uint8 / uint16 wire formats. */
+ *        its own, beside this one): the pyramid model's uint8 / uint16 wire formats.
+ *   286  + hdrnet_lowres_input_px / hdrnet_bilateral_slice_apply_io_px / hdrnet_bilateral_slice_apply_io_curves_px in
+ *        hdrnet_amd_pixel_formats.h (a header of its own): uint8 / uint16 frames in BGR, RGBA and BGRA order. */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -13,7 +13,10 @@ packed set of images of mixed extents (hdrnet_prepare_batch_ragged) against the 
 the training step's loss at 4 x 1080p three ways, interleaved: l2_loss with its gradient, l2_loss + metrics.psnr, and
 metrics.Monitor (loss, PSNR and both moving averages from csrc/loss_psnr.hip); `pyramid_io` = the pyramid model frame in,
 frame out at 4K and 1080p, u8 -> u8 and u16 / 32767 -> f32: FrameInference over process_wire against the chain a caller had
-before it (frame.float() / wl -> FrameInference over process -> quantise), alternating in one process.  --tools loads the tools build and adds the round-1
+before it (frame.float() / wl -> FrameInference over process -> quantise), alternating in one process; `pixel_formats` =
+HDRNetPointwiseNNGuide on BGRA u8 frames at 4K and 1080p: a hipGraph of process(..., pixel_format="bgra") against a hipGraph
+of the chain a caller wrote before it (index-select to RGB -> process -> flip + cat alpha), alternating, and beside it the
+fused kernel alone, BGRA u8 -> u8 against RGB u8 -> u8.  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -86,6 +89,8 @@ def main():
         return metrics_monitor(dev, args)
     if args.workload == "pyramid_io":
         return pyramid_io(dev, args)
+    if args.workload == "pixel_formats":
+        return pixel_formats(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -519,6 +524,97 @@ def pyramid_io(dev, args):
                   f"faster by more than the baseline's spread: {mb - mn > spread}")
     if args.json:
         json.dump(dict(workload="pyramid_io", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _RepackChain(torch.nn.Module):
+    """What a caller with a BGRA frame wrote before process() took the format: index-select to RGB (drops alpha), process,
+    flip the result and put the frame's alpha back -- two stock-op passes around the fused kernels."""
+
+    def __init__(self, model, dev):
+        super().__init__()
+        self.model = model
+        self.register_buffer("bgr", torch.tensor([2, 1, 0], device=dev), persistent=False)
+
+    def forward(self, frame):
+        out = self.model.process(frame.index_select(3, self.bgr), out_dtype=torch.uint8)
+        return torch.cat([out.index_select(3, self.bgr), frame[..., 3:]], -1)
+
+
+def pixel_formats(lib, dev, args):
+    """BGRA uint8 frames in, BGRA uint8 frames out through HDRNetPointwiseNNGuide at 4K and 1080p: one hipGraph of
+    process(frame, uint8, pixel_format="bgra") -- the permutation in the kernels' loads and stores -- against one hipGraph of
+    _RepackChain.  Both are warmed, then run ALTERNATING three times each in one process; reported: the mean of the three
+    and their range.  The new path counts as faster where its mean is below the chain's by more than the chain's own
+    spread.  Beside it, without a bar: the fused guide-network kernel alone, BGRA u8 -> u8 (8 bytes per pixel) against RGB
+    u8 -> u8 (6), over buffer sets that together exceed the Infinity Cache, alternating the same way."""
+    from hdrnet_amd import models
+    from hdrnet_amd.runtime import FrameInference, GraphedInference
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = []
+
+    def alternate(run_a, run_b):
+        for k in range(30):  # both warmed with their shapes
+            run_a(k)
+            run_b(k)
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(3):
+            a.append(timeit(run_a, args.steps, rounds=1)[0])
+            b.append(timeit(run_b, args.steps, rounds=1)[0])
+        return a, b
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        frames = [torch.randint(0, 256, (1, H, W, 4), device=dev, dtype=torch.int32, generator=gen).to(torch.uint8)
+                  for _ in range(3)]
+        new = FrameInference(m, frames[0], out_dtype=torch.uint8, pixel_format="bgra")
+        chain_module = _RepackChain(m, dev)
+        base = GraphedInference(chain_module, [frames[0]])
+        assert torch.equal(new(frames[1]), base(frames[1])), "the two paths return the same frame"
+        b, n = alternate(lambda k: base(frames[k % 3]), lambda k: new(frames[k % 3]))
+        mb, mn = statistics.mean(b), statistics.mean(n)
+        spread = max(b) - min(b)
+        name = f"{H}x{W} model, bgra u8 -> bgra u8"
+        rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                         us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                         faster_beyond_chain_spread=bool(mb - mn > spread)))
+        print(f"{name:40s} repack chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   pixel_format='bgra' {mn:8.2f} us "
+              f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+              f"faster by more than the chain's spread: {mb - mn > spread}")
+        del new, base
+
+        # the kernel alone: the same grid and guide network, frames of 4 against 3 bytes per pixel
+        GH, GW, GD = 16, 16, 8
+        nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 6)))
+        grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+        conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+        conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+        sets = [dict(rgb=torch.randint(0, 256, (1, H, W, 3), device=dev, dtype=torch.int32, generator=gen).to(torch.uint8),
+                     bgra=torch.randint(0, 256, (1, H, W, 4), device=dev, dtype=torch.int32, generator=gen).to(torch.uint8),
+                     out3=torch.empty((1, H, W, 3), device=dev, dtype=torch.uint8),
+                     out4=torch.empty((1, H, W, 4), device=dev, dtype=torch.uint8)) for _ in range(nsets)]
+
+        def kernel(k, fmt):
+            t = sets[k % nsets]
+            src, dst = (t["bgra"], t["out4"]) if fmt else (t["rgb"], t["out3"])
+            rc = lib.hdrnet_bilateral_slice_apply_io_px(grid.data_ptr(), None, src.data_ptr(), dst.data_ptr(), 1, H, W, GH, GW,
+                                                        GD, 3, 3, 1, 1, 255.0, 1, conv1.data_ptr(), conv2.data_ptr(), 16, None,
+                                                        _lib.GUIDE_SIGMOID_FAST, fmt, fmt, stream)
+            if rc:
+                raise RuntimeError(lib.hdrnet_last_error().decode())
+
+        r, q = alternate(lambda k: kernel(k, 0), lambda k: kernel(k, 3))
+        mr, mq = statistics.mean(r), statistics.mean(q)
+        name = f"{H}x{W} kernel, u8 -> u8 +nnguide"
+        rows.append(dict(op=name, us_rgb=round(mr, 2), us_rgb_min=round(min(r), 2), us_rgb_max=round(max(r), 2),
+                         us_bgra=round(mq, 2), us_bgra_min=round(min(q), 2), us_bgra_max=round(max(q), 2)))
+        print(f"{name:40s} rgb (6 B/px) {mr:8.2f} us ({min(r):8.2f} .. {max(r):8.2f})   bgra (8 B/px) {mq:8.2f} us "
+              f"({min(q):8.2f} .. {max(q):8.2f})   bgra / rgb {mq / mr:6.3f}")
+        del sets
+    if args.json:
+        json.dump(dict(workload="pixel_formats", rows=rows), open(args.json, "w"), indent=1)
 
 
 def metrics_monitor(dev, args):
