@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void apply_vjp_rows_vec4(
   const RowCtx r = stage_row<C, false>(colY, grid_b, y, xs, xe, GH, GW, GD, scale_x, scale_y);
 
   const float gs[4] = {g4.x, g4.y, g4.z, g4.w};
-  const float xf0 = (float)x + 0.5f;
+  const float xf0 = (float)x + 0.5f;  // xf0 + k == (x + k) + 0.5f exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
   const float* inf = reinterpret_cast<const float*>(iv);
   const float* df = reinterpret_cast<const float*>(dv);
   float4 dgv = make_float4(0.f, 0.f, 0.f, 0.f);

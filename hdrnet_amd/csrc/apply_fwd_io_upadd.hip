@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_upadd_rows(const IoUpParams 
   stage_image<C, FOLD_WL>(lds, grid_b, y, sc.cmin, sc.ncols, p.GH, p.GW, p.GD, p.scale_y, p.inv_col, tid, (int)blockDim.x,
                           p.white.inv);
   XTermLean xt[kPxPerThread];
-  const float xf0 = (float)x + 0.5f;
+  const float xf0 = (float)x + 0.5f;  // xf0 + k == (x + k) + 0.5f exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
   const float colb_f = (float)colb, xbase_f = (float)(CB - sc.cmin * colb);
 #pragma unroll
   for (int k = 0; k < kPxPerThread; ++k) xt[k] = x_term_lean(xf0 + (float)k, p.scale_x, colb_f, xbase_f);

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
   }
 
   float gs[4] = {g4.x, g4.y, g4.z, g4.w};
-  const float xf0 = (float)x + 0.5f;  // (x + k) + 0.5f == xf0 + k exactly (x < 2^23)
+  const float xf0 = (float)x + 0.5f;  // (x + k) + 0.5f == xf0 + k exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
   const float* inf = reinterpret_cast<const float*>(iv);
   float4 ov[(COUT * kPxPerThread) / 4];
   float* of = reinterpret_cast<float*>(ov);

@@ -172,7 +172,7 @@ __device__ __forceinline__ void seg_task(const SegParams& p, float* __restrict__
 
   // x-only terms of this thread's 4 pixels (the lean pixel phase of seg_common.hip.h)
   XTermLean xl[kPxPerThread];
-  const float xf0 = (float)x + 0.5f;  // (x + k) + 0.5f == xf0 + k exactly (x < 2^23)
+  const float xf0 = (float)x + 0.5f;  // (x + k) + 0.5f == xf0 + k exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
   {
     const float colb_f = (float)colb, xbase_f = (float)(CB - cmin * colb);  // exact: |.| < 2^24
 #pragma unroll

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_multiquad(
     const int x = xs + kPxPerThread * (q * nthreads + (int)threadIdx.x);
     const bool active = x < xe;
     const float gs[4] = {g4[q].x, g4[q].y, g4[q].z, g4[q].w};
-    const float xf0 = (float)x + 0.5f;
+    const float xf0 = (float)x + 0.5f;  // exact for x < W <= 2^23 (row_geom.h, kMaxFloatX)
     const float* inf = reinterpret_cast<const float*>(iv[q]);
     float4 ov[COUT];
     float* of = reinterpret_cast<float*>(ov);
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void apply_fwd_wave_vec4(
   if (!active) return;
 
   const float gs[4] = {g4.x, g4.y, g4.z, g4.w};
-  const float xf0 = (float)x + 0.5f;
+  const float xf0 = (float)x + 0.5f;  // exact for x < W <= 2^23 (row_geom.h, kMaxFloatX)
   const float* inf = reinterpret_cast<const float*>(iv);
   float4 ov[(COUT * kPxPerThread) / 4];
   float* of = reinterpret_cast<float*>(ov);

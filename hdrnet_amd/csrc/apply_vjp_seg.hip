@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void apply_vjp_seg(const VjpSegParams p) {
   const float gd_f = (float)p.GD, zhi = (float)(p.GD - 1);
   stage_image<C>(lds, grid_b, y, sc.cmin, sc.ncols, p.GH, p.GW, p.GD, p.scale_y, p.inv_col, tid, (int)blockDim.x);
   XTerm xt[kPxPerThread];
-  const float xf0 = (float)x + 0.5f;
+  const float xf0 = (float)x + 0.5f;  // xf0 + k == (x + k) + 0.5f exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
 #pragma unroll
   for (int k = 0; k < kPxPerThread; ++k) xt[k] = x_term(xf0 + (float)k, p.scale_x, sc.cmin, colb, CB);
   __syncthreads();  // image complete; the compiler drains the LDS-DMA (vmcnt) here too

@@ -110,6 +110,24 @@ int check_common(int B, int H, int W, int GH, int GW, int GD) {
   return HDRNET_OK;
 }
 
+// The generic kernels launch one thread per pixel on a one-dimensional grid, and the HIP runtime refuses a launch of 2^32
+// threads or more: a frame that no LDS-staged kernel takes and that is this large has no kernel at all.
+constexpr long long kGenericMaxPixels = 0xffffffffLL - 255;
+int refuse_generic(const char* what, long long npix) {
+  return fail(HDRNET_INVALID_ARGUMENT, "%s: no kernel for this frame: the generic kernels take at most 2^32 - 256 pixels "
+              "(B * H * W = %lld)", what, npix);
+}
+
+// The refusal of a fused forward, which has no other kernel to fall back to: where the frame's EXTENTS break a limit of
+// the last kernel family the entry point could take (`limits`: row_geom.h; `row_channels`: floats per pixel of its
+// widest pixel stream), the text names that limit; else it is `otherwise`, the entry point's shape and alignment rules.
+int refuse_fused(int B, int H, int W, int GW, int GD, int row_channels, unsigned limits, const char* otherwise) {
+  using namespace hdrnet_amd::rows;
+  if (const char* limit = extent_refusal(Frame{B, H, W, GW, GD}, row_channels, limits))
+    return fail(HDRNET_INVALID_ARGUMENT, "frame beyond the fused kernels' extents (B=%d, H=%d, W=%d): %s", B, H, W, limit);
+  return fail(HDRNET_INVALID_ARGUMENT, "%s", otherwise);
+}
+
 // flags: bits 0..7 kernel family (HDRNET_KERNEL_*), bits 8..15 variant inside the family
 // (0 = the library's default; used by benchmarks for A/B runs), rest must be zero.
 // flags of the guide-network entry points (..._nnguide_f32_ex, ..._upadd_f32_ex, ..._io_ex): the sigmoid choice and
@@ -286,6 +304,7 @@ int grad_dispatch(const hdrnet_amd::ApplyGradArgs& a, unsigned family, hipStream
     }
   }
   if (rest.dgrid || rest.dguide || rest.dinput) {
+    if (npix > kGenericMaxPixels) return refuse_generic(what, npix);
     if (rest.dgrid && family == HDRNET_KERNEL_AUTO && npix > kWarnGenericPixels)
       warn_generic_grid_grad(what, npix, a.GD, a.Cout * a.Cj, /*no_fast_shape=*/!grad_fast_shape(a) ||
                              grid_grad_mfma_workspace(a.B, a.H, a.W, a.GH, a.GW, a.GD, a.Cout * a.Cj) == 0);
@@ -386,6 +405,7 @@ static int apply_fwd_impl(const float* grid, const float* guide, const float* in
     const hipError_t e = band ? launch_apply_fwd_seg(a, s, &name) : launch_apply_fwd_rows(a, s, &name);
     return finish_launch(e, "BilateralSliceApply", name);
   }
+  if (npix > kGenericMaxPixels) return refuse_generic("BilateralSliceApply", npix);
   return finish_launch(launch_apply_fwd_generic(a, s), "BilateralSliceApply", "apply_fwd_generic");
 }
 
@@ -448,9 +468,9 @@ int hdrnet_bilateral_slice_apply_nnguide_f32_ex(const float* grid, const float* 
   a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
   a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
   if (!apply_fwd_nnguide_supported(a, guide_out))
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "fused guide + slice-apply needs (Cin, Cout) in {(3,3), (1,1)}, W %% 4 == 0 and 16-B "
-                "aligned buffers; run the guide network and hdrnet_bilateral_slice_apply_f32 instead");
+    return refuse_fused(B, H, W, GW, GD, Cin > Cout ? Cin : Cout, rows::kNeedVec4 | rows::kRowsLimits,
+                        "fused guide + slice-apply needs (Cin, Cout) in {(3,3), (1,1)}, W % 4 == 0 and 16-B "
+                        "aligned buffers; run the guide network and hdrnet_bilateral_slice_apply_f32 instead");
   const char* name = "";
   const hipError_t e = launch_apply_fwd_nnguide(a, guide_conv1, guide_conv2, n_feats, guide_out,
                                                 static_cast<hipStream_t>(stream), &name);
@@ -489,9 +509,9 @@ int hdrnet_bilateral_slice_apply_upadd_f32_ex(const float* grid, const float* gu
   a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
   a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
   if (!apply_fwd_upadd_supported(a, coarse, guide_conv1 != nullptr))
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "slice-apply + up-add needs Cin = Cout = 3 with offset, W %% 4 == 0 and 16-B aligned "
-                "buffers; compose hdrnet_bilateral_slice_apply_f32 and hdrnet_resize_bilinear_f32 instead");
+    return refuse_fused(B, H, W, GW, GD, Cin > Cout ? Cin : Cout, rows::kNeedVec4 | rows::kRowsLimits,
+                        "slice-apply + up-add needs Cin = Cout = 3 with offset, W % 4 == 0 and 16-B aligned "
+                        "buffers; compose hdrnet_bilateral_slice_apply_f32 and hdrnet_resize_bilinear_f32 instead");
   const char* name = "";
   const hipError_t e = launch_apply_fwd_upadd(a, coarse, Hc, Wc, guide_conv1, guide_conv2, n_feats,
                                               static_cast<hipStream_t>(stream), &name);
@@ -951,9 +971,9 @@ static int apply_io_impl(const float* grid, const float* guide, const void* inpu
   a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
   a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
   if (!apply_fwd_io_supported(a))
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "the wire-format forward supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
-                "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32");
+    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
+                        "the wire-format forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                        "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32");
   const char* name = "";
   const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
   return finish_launch(e, "BilateralSliceApplyIO", name);
@@ -1015,9 +1035,9 @@ int hdrnet_bilateral_slice_apply_upadd_io_ex(const float* grid, const float* gui
   a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
   a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
   if (!apply_fwd_io_upadd_supported(a, coarse))
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
-                "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32");
+    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
+                        "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                        "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32");
   const hipError_t e = launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name);
   return finish_launch(e, "BilateralSliceApplyUpAddIO", name);
 }
@@ -1194,9 +1214,9 @@ static int apply_io_curves_impl(const float* grid, const void* input, void* out,
     a.guide_prepared = static_cast<const float*>(prepared);
   }
   if (!apply_fwd_io_supported(a))
-    return fail(HDRNET_INVALID_ARGUMENT,
-                "the fused curves-guide forward supports Cin = Cout = 3 with offset, W %% 4 == 0, aligned "
-                "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32");
+    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
+                        "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                        "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32");
   const char* name = "";
   const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
   return finish_launch(e, "BilateralSliceApplyIOCurves", name);
@@ -1258,6 +1278,7 @@ int hdrnet_bilateral_slice_f32_ex(const float* grid, const float* guide, float* 
     const hipError_t e = launch_slice_fwd_rows(a, s, &name);
     return finish_launch(e, "BilateralSlice", name);
   }
+  if ((long long)B * H * W > kGenericMaxPixels) return refuse_generic("BilateralSlice", (long long)B * H * W);
   return finish_launch(launch_slice_fwd_generic(a, s), "BilateralSlice", "slice_fwd_generic");
 }
 

@@ -350,7 +350,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
       // nontemporal only where ONE instruction covers the wave's whole run of a tensor (<= 16 B per
       // pixel): an nt line is not kept for a second instruction touching it (profiles/r01, r02/exp6)
       buf_load<1, kLoadAux>(grs, px * 4u, &bt.g[cb]);
-      // (24-bit multiplies -- pixel and plane indices are far below 2^24: v_mul_u32_u24 / v_mad_u32_u24 are
+      // (24-bit multiplies -- px < W <= 2^23 (gg_plan), plane indices far below: v_mul_u32_u24 / v_mad_u32_u24 are
       //  full-rate, the 32-bit v_mul_lo_u32 / v_mad_u64_u32 the compiler picks otherwise quarter-rate)
       if constexpr (APPLY && CIN > 0) buf_load<CIN, (CIN <= 4 ? kLoadAux : 0)>(irs, __umul24(px, 4u * CIN), bt.in[cb]);
       buf_load<COUT, (COUT <= 4 ? kLoadAux : 0)>(drs, __umul24(px, 4u * COUT), bt.d[cb]);
@@ -940,6 +940,9 @@ constexpr int kMaxOcc = 8;  // workgroups per CU a stage-1 kernel can have (8 wa
 
 bool gg_plan(int B, int H, int W, int GH, int GW, int GD, int C, long long slots, GGPlan* pl) {
   if (GD > 16 || C > 32 || C < 1) return false;
+  // a row's column intervals come from the float pixel centre x + 0.5f (interval_start) and a pixel's byte offset from
+  // a 24-bit multiply (load_batch): both hold for x < 2^23 (row_geom.h)
+  if (W > rows::kMaxFloatX) return false;
   const int nh = GD > 8 ? 2 : 1;  // plane halves: a task writes one [3][16][16] tile per half
   const int nw = C > 16 ? 2 : 1;  // channel windows: one stage-1 launch and one set of partial tiles per window
   const int cell = H / GH > 1 ? H / GH : 1;

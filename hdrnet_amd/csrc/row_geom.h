@@ -19,6 +19,13 @@ inline bool lds_fits(size_t bytes) { return bytes <= kMaxLdsBytes; }
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The widest row whose pixel centres are formed in float32 lane by lane.  The kernels that give a lane four consecutive
+// pixels compute xf0 = (float)x + 0.5f once and take xf0 + k for pixel x + k: equal to the reference's (x + k) + 0.5f
+// while x + 0.5 is exact, i.e. for x < 2^23; beyond, the two round differently (ties to even).  The gradient pass
+// (grid_grad_mfma.hip) cuts a row into column intervals with the same float coordinate and forms a pixel's byte offset
+// with a 24-bit multiply.  None of them runs a wider row: Plan::vec4 is false there and gg_plan refuses.
+constexpr int kMaxFloatX = 1 << 23;
+
 // Grid columns `npx` consecutive pixels can touch: floor differences of gx0 over npx-1 pixels (<= floor(d)+1), +1 for
 // the upper neighbour, +1 for the count, +1 slack for float rounding of the coordinates.  Unclamped: the padded image
 // of the segment family materialises the clamped copies.
@@ -35,7 +42,7 @@ inline int max_cols_for(int npx, int GW, int W) {
 // W = 1920 -> 2 x 960 px / 256 threads with 16 idle lanes).
 struct Plan {
   int threads, nseg, seg, max_cols;
-  bool vec4;  // 16-B accesses usable: W % 4 == 0 and 16-B aligned buffers
+  bool vec4;  // four pixels per lane, 16-B accesses: W % 4 == 0, 16-B aligned buffers and W <= kMaxFloatX
 };
 
 inline Plan make_row_plan(int W, int GW, bool aligned16) {
@@ -52,7 +59,7 @@ inline Plan make_row_plan(int W, int GW, bool aligned16) {
       best.nseg = nseg;
     }
   }
-  best.vec4 = aligned16 && (W % 4 == 0);
+  best.vec4 = aligned16 && (W % 4 == 0) && W <= kMaxFloatX;
   best.seg = round_up((W + best.nseg - 1) / best.nseg, 4);
   // (Round 4: rounding the segments to 32-px multiples -- W = 4000 as 1024 / 1024 / 1024 / 928 instead of 4 x 1000,
   // so that every output run is whole 128-B lines and the forward may store write-through -- measured 61.3 vs
@@ -77,12 +84,36 @@ enum : unsigned {
   kLimImage = 1u << 3,      // staged image elements < 2^20 (a staging element's column comes from a float multiply)
   kLimBH = 1u << 4,         // B, H <= 65535: the 3-D launch grid (segment, row, image)
   kLimRowBytes = 1u << 5,   // bytes of the widest pixel row < 2^31: 32-bit offsets within a row / descriptor range
-  kLimBlocks = 1u << 6,     // B * H * nseg <= 2^31 - 1: the 1-D launch grid of the row family
+  kLimBlocks = 1u << 6,     // B * H * nseg * threads <= 2^32 - 1: the 1-D launch grid of the row family (the HIP runtime
+                            // refuses a launch of 2^32 threads or more in a dimension: "invalid configuration argument")
 };
 
 struct Frame {
   int B, H, W, GW, GD;
 };
+
+// The limits of `limits` that the EXTENTS of a frame break, whatever its channels, alignment or LDS need (0: none).
+// kNeedVec4 is reported where the row is wider than kMaxFloatX.  row_geom below decides `ok` with it, and an entry point
+// without a fallback names the limit in its refusal with extent_refusal: one function for both.
+inline unsigned extent_limits_broken(const Frame& f, int row_channels, const Plan& pl, unsigned limits) {
+  unsigned broken = 0;
+  if ((limits & kLimBH) && (f.B > 65535 || f.H > 65535)) broken |= kLimBH;
+  if ((limits & kLimRowBytes) && (long long)f.W * row_channels * 4 >= (1LL << 31)) broken |= kLimRowBytes;
+  if ((limits & kLimBlocks) && (long long)f.B * f.H * pl.nseg * pl.threads > 0xffffffffLL) broken |= kLimBlocks;
+  if ((limits & kNeedVec4) && f.W > kMaxFloatX) broken |= kNeedVec4;
+  return broken;
+}
+
+// ... in words (null: the extents break none of `limits`).
+inline const char* extent_refusal(const Frame& f, int row_channels, unsigned limits) {
+  const unsigned broken = extent_limits_broken(f, row_channels, make_row_plan(f.W, f.GW, true), limits);
+  if (broken & kLimBH) return "B and H may be at most 65535 (the launch grid is segment x row x image)";
+  if (broken & kLimRowBytes) return "a pixel row must be shorter than 2^31 bytes (32-bit offsets within a row)";
+  if (broken & kNeedVec4) return "W may be at most 2^23 = 8388608 (pixel centres x + 0.5 are formed in float32)";
+  if (broken & kLimBlocks)
+    return "B * H * (segments of a row) * (threads of a segment) may be at most 2^32 - 1 (the launch grid is one-dimensional)";
+  return nullptr;
+}
 
 // One row-segment launch.  Dynamic LDS is [tab_floats of tables][the image][one slab per wavefront].
 struct RowLaunch {
@@ -128,14 +159,13 @@ inline RowGeom row_geom(const RowLaunch& d) {
   const unsigned lim = d.limits;
   g.ok = (!(lim & kNeedAligned) || aligned) && (!(lim & kNeedVec4) || g.pl.vec4) &&
          (!(lim & kLimLds) || lds_fits((size_t)ok_floats * sizeof(float))) &&
-         (!(lim & kLimImage) || staged < (1 << 20)) && (!(lim & kLimBH) || (f.B <= 65535 && f.H <= 65535)) &&
-         (!(lim & kLimRowBytes) || (long long)f.W * d.row_channels * 4 < (1LL << 31)) &&
-         (!(lim & kLimBlocks) || (long long)f.B * f.H * g.pl.nseg <= 0x7fffffffLL);
+         (!(lim & kLimImage) || staged < (1 << 20)) && extent_limits_broken(f, d.row_channels, g.pl, lim) == 0;
   return g;
 }
 
 // ---- the families ----------------------------------------------------------------------------------------------------
 constexpr unsigned kSegLimits = kNeedVec4 | kLimLds | kLimImage | kLimBH | kLimRowBytes;  // padded image, 3-D launch grid
+constexpr unsigned kRowsLimits = kLimLds | kLimBlocks;                                     // clamped image, 1-D launch grid
 
 // apply_fwd_seg.hip: slab = the wave's input run, then its output run (+ its guide run where LDS-DMA brings a guide map).
 inline RowGeom seg_fwd_geom(const Frame& f, int Cin, int Cout, int Cj, bool dma, bool guide_map, uintptr_t align_bits) {
@@ -160,14 +190,14 @@ inline RowGeom vjp_seg_geom(const Frame& f, int Cin, int Cout, int Cj, uintptr_t
 // apply_fwd_rows.hip: slab = the wave's input run, then its output run (vec4 kernel).  Unaligned buffers and W % 4 != 0
 // are served too (the scalar kernel): Plan::vec4 picks.
 inline RowGeom rows_fwd_geom(const Frame& f, int Cin, int Cout, int Cj, uintptr_t align_bits) {
-  RowLaunch d{f, Cout * Cj, false, kWaveRun * (Cin > Cout ? Cin : Cout), 0, align_bits, kLimLds | kLimBlocks};
+  RowLaunch d{f, Cout * Cj, false, kWaveRun * (Cin > Cout ? Cin : Cout), 0, align_bits, kRowsLimits};
   d.ok_image_plus4 = true;  // the predicate's bound: image + 4 floats; the launcher allocates round_up(image, 4)
   return row_geom(d);
 }
 
 // apply_bwd_rows.hip: slab = the wave's dinput run, where dinput is wanted.
 inline RowGeom vjp_rows_geom(const Frame& f, int Cin, int Cout, int Cj, bool want_dinput, uintptr_t align_bits) {
-  RowLaunch d{f, Cout * Cj, false, want_dinput ? kWaveRun * Cin : 0, 0, align_bits, kNeedVec4 | kLimLds | kLimBlocks};
+  RowLaunch d{f, Cout * Cj, false, want_dinput ? kWaveRun * Cin : 0, 0, align_bits, kNeedVec4 | kRowsLimits};
   d.ok_slab_floats = kWaveRun * (Cin > 0 ? Cin : 1);  // the predicate's bound: a slab whether dinput is wanted or not
   d.ok_image_plus4 = true;                            // ... and image + 4 floats for the launcher's round_up(image, 4)
   return row_geom(d);
@@ -175,7 +205,7 @@ inline RowGeom vjp_rows_geom(const Frame& f, int Cin, int Cout, int Cj, bool wan
 
 // slice_fwd_rows.hip: slab = 64 pixels x C floats per wave; the guide is read per pixel, so any W.
 inline RowGeom slice_fwd_geom(const Frame& f, int C, uintptr_t align_bits) {
-  return row_geom(RowLaunch{f, C, false, 64 * C, 0, align_bits, kNeedAligned | kLimLds | kLimBlocks});
+  return row_geom(RowLaunch{f, C, false, 64 * C, 0, align_bits, kNeedAligned | kRowsLimits});
 }
 
 }  // namespace rows

@@ -17,8 +17,9 @@ namespace hdrnet_amd {
 // unless wl's significand is all ones (Markstein, "Computation of elementary functions on the IBM RISC
 // System/6000 processor", 1990, theorem on division by a correctly rounded reciprocal); v <= 65535 and
 // wl in [2^-40, 2^40] keep every intermediate normal.  The host (io_white_level) checks those conditions and
-// otherwise selects the plain divide; tests/test_gpu_parity.py compares both forms exhaustively over
-// all 65536 sample values for the white levels of hdrnet/data_pipeline.py:202-232,267-274.
+// otherwise selects the plain divide; tests/test_host_logic.py steps through the three instructions in exact rational
+// arithmetic for every sample value of the white levels of hdrnet/data_pipeline.py:202-232,267-274 (255, 65535, 32767)
+// and compares with the IEEE division.
 struct WhiteLevel {
   float wl, rcp;  // rcp = 0: use the IEEE divide
   float inv;      // RN(1 / wl), always: the factor folded into the coefficient image where the input feeds the affine only

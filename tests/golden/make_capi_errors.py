@@ -92,27 +92,38 @@ PREP_COMMON = [("unknown flags", dict(flags=2)), ("dtype code", dict(target_dtyp
                ("null buffer", dict(src_input=None)), ("target without source", dict(src_target=None)),
                ("no output", dict(image_input=None, image_target=None)), ("W not a multiple of 4", dict(W=6)),
                ("misaligned output", dict(image_input=Q)), ("misaligned source", dict(src_input=ODD))]
+# the first extents beyond a limit of the launch geometry (hdrnet_amd/csrc/row_geom.h): an entry point without another
+# kernel to fall back to names the limit (tests/extent_cases.py derives the extents, tests/test_extent_edges_host.py
+# calls every such entry point with them)
+WIDE = (1 << 23) + 4                 # the first W % 4 == 0 beyond kMaxFloatX
+ROW_2G = -(-(1 << 31) // 48) * 4     # the first W % 4 == 0 whose 3-channel float row reaches 2^31 bytes
+ROWS_EXTENT_ROWS = [("W beyond 2^23", dict(H=1, W=WIDE)), ("launch beyond 2^32 - 1 threads", dict(B=1024, H=65536))]
+GENERIC_EXTENT_ROWS = [("no kernel beyond 2^32 - 256 pixels", dict(B=65536, H=65536, W=1))]
+SEG_EXTENT_ROWS = [("H beyond 65535", dict(H=65536)), ("B beyond 65535", dict(B=65536, H=1)),
+                   ("W beyond 2^23", dict(H=1, W=WIDE)), ("row beyond 2^31 bytes", dict(H=1, W=ROW_2G))]
+PREP_EXTENT_ROWS = [("image too large", dict(Hs=16384, Ws=16384, H=16384, W=16384))]
 ADAM_ROWS = [("wrong extents", dict(n=0)), ("null buffer", dict(step=None)), ("misaligned pointer", dict(grad=Q))]
 
 # function -> (base arguments by name, [(case, overrides)])
 TABLE = {
-    "hdrnet_bilateral_slice_apply_f32": (APPLY, APPLY_ROWS),
-    "hdrnet_bilateral_slice_apply_f32_ex": (APPLY, APPLY_ROWS + FLAG_ROWS),
+    "hdrnet_bilateral_slice_apply_f32": (APPLY, APPLY_ROWS + GENERIC_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_apply_f32_ex": (APPLY, APPLY_ROWS + FLAG_ROWS + GENERIC_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_rows_f32": (ROWS_, BAND_ROWS),
     "hdrnet_bilateral_slice_apply_rows_f32_ex": (ROWS_, BAND_ROWS + FLAG_ROWS),
-    "hdrnet_bilateral_slice_apply_nnguide_f32": (NNG, NNG_ROWS),
+    "hdrnet_bilateral_slice_apply_nnguide_f32": (NNG, NNG_ROWS + ROWS_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_nnguide_f32_ex": (NNG, NNG_ROWS + GUIDE_FLAG_ROWS + [
-        ("prescaled needs Cin = 3", dict(flags=0x20000, Cin=1, Cout=1)), ("prescaled misaligned", dict(flags=0x30000, guide_conv1=Q))]),
-    "hdrnet_bilateral_slice_apply_io_curves": (CURVES, CURVES_ROWS),
+        ("prescaled needs Cin = 3", dict(flags=0x20000, Cin=1, Cout=1)), ("prescaled misaligned", dict(flags=0x30000, guide_conv1=Q))]
+        + ROWS_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_apply_io_curves": (CURVES, CURVES_ROWS + SEG_EXTENT_ROWS),
     "hdrnet_curves_guide_prepare_f32": (
         dict(guide_shifts=P, guide_slopes=P, npts=16, Cin=3, prepared=P, prepared_bytes=1 << 20, usable={"int": 7}),
         [("wrong extents", dict(npts=17)), ("channel count", dict(Cin=1)), ("null buffer", dict(guide_slopes=None)),
          ("buffer too small", dict(prepared_bytes=64)), ("misaligned pointer", dict(prepared=Q)), ("nowhere to report", dict(usable=None))]),
     "hdrnet_bilateral_slice_apply_io_curves_prepared": (CURVES, CURVES_ROWS + [
-        ("misaligned tables", dict(prepared=Q)), ("too many knots for tables", dict(npts=20))]),
-    "hdrnet_bilateral_slice_apply_upadd_f32": (UPADD, UPADD_ROWS),
+        ("misaligned tables", dict(prepared=Q)), ("too many knots for tables", dict(npts=20))] + SEG_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_apply_upadd_f32": (UPADD, UPADD_ROWS + ROWS_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_upadd_f32_ex": (UPADD, UPADD_ROWS + GUIDE_FLAG_ROWS + [
-        ("prescaled with a guide map", dict(flags=0x20000))]),
+        ("prescaled with a guide map", dict(flags=0x20000))] + ROWS_EXTENT_ROWS),
     "hdrnet_resize_bilinear_f32": (dict({"in": P}, out=P, B=1, Hin=4, Win=4, Hout=8, Wout=8, C=3),
                                    [("wrong extents", dict(Hin=0)), ("null buffer", dict(out=None)), ("channel count", dict(C=0)),
                                     ("zero size", dict(Hout=0))]),
@@ -160,18 +171,20 @@ TABLE = {
          ("null parameter", dict(net=net(fc_w=[P, None, P]))), ("null gradient", dict(grads=grads(local_w=[P, None]))),
          ("null buffer", dict(forward_workspace=None)), ("workspace too small", dict(workspace_bytes=16)),
          ("misaligned workspace", dict(workspace=Q))]),
-    "hdrnet_bilateral_slice_apply_io": (IO, IO_ROWS),
-    "hdrnet_bilateral_slice_apply_io_ex": (IO, IO_ROWS + GUIDE_FLAG_ROWS + [("prescaled with a guide map", dict(flags=0x20000))]),
+    "hdrnet_bilateral_slice_apply_io": (IO, IO_ROWS + SEG_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_apply_io_ex": (IO, IO_ROWS + GUIDE_FLAG_ROWS + [("prescaled with a guide map", dict(flags=0x20000))]
+                                           + SEG_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_grad_f32": (GRAD, GRAD_ROWS),
     "hdrnet_bilateral_slice_apply_grad_f32_ex": (GRAD, GRAD_ROWS + FLAG_ROWS),
-    "hdrnet_bilateral_slice_f32": (SLICE, SLICE_ROWS),
-    "hdrnet_bilateral_slice_f32_ex": (SLICE, SLICE_ROWS + FLAG_ROWS),
+    "hdrnet_bilateral_slice_f32": (SLICE, SLICE_ROWS + GENERIC_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_f32_ex": (SLICE, SLICE_ROWS + FLAG_ROWS + GENERIC_EXTENT_ROWS),
     "hdrnet_bilateral_slice_grad_f32": (SLICE, SLICE_GRAD_ROWS),
     "hdrnet_bilateral_slice_grad_f32_ex": (SLICE, SLICE_GRAD_ROWS + FLAG_ROWS),
     "hdrnet_lowres_input": (dict(frames=P, dtype=1, white_level=255.0, B=1, H=64, W=64, lowres=P, net_input_size=16),
                             [("wrong extents", dict(H=0)), ("null buffer", dict(lowres=None)), ("null frames", dict(frames=None)),
                              ("dtype code", dict(dtype=7)), ("white level", dict(white_level=0.0)),
-                             ("misaligned pointer", dict(lowres=Q)), ("zero size", dict(B=0))]),
+                             ("misaligned pointer", dict(lowres=Q)), ("zero size", dict(B=0)),
+                             ("batch too large", dict(B=65536)), ("image too large", dict(H=16384, W=16384))]),
     "hdrnet_l2_loss_with_grad_f32": (
         dict(prediction=P, target=P, n=16, loss=P, dprediction_unit=P, workspace=P, workspace_bytes=1 << 20),
         [("wrong extents", dict(n=0)), ("null buffer", dict(loss=None)), ("workspace too small", dict(workspace_bytes=8)),
@@ -193,10 +206,10 @@ TABLE = {
     "hdrnet_adam_step_tf_f32": (ADAM, ADAM_ROWS),
     "hdrnet_prepare_batch": (PREP, PREP_COMMON + [
         ("crop does not fit", dict(H=16)), ("crop does not fit turned", dict(Ws=16, W=12)),
-        ("identity needs the whole image", dict(ops=None)), ("misaligned ops", dict(ops=ODD))]),
+        ("identity needs the whole image", dict(ops=None)), ("misaligned ops", dict(ops=ODD))] + PREP_EXTENT_ROWS),
     "hdrnet_prepare_batch_ragged": (PREP, PREP_COMMON + [
         ("empty table", dict(N=0)), ("empty sources", dict(n_samples=0)), ("null table", dict(images=None)),
-        ("null ops", dict(ops=None)), ("misaligned table", dict(images=Q))]),
+        ("null ops", dict(ops=None)), ("image too large", dict(H=16384, W=16384)), ("misaligned table", dict(images=Q))]),
 }
 # the training-loop helpers that kept no error text before 0.2.8.1: the fixture holds their return codes only
 NO_TEXT = ("hdrnet_l2_loss_with_grad_f32", "hdrnet_l2_loss_grad_scale_f32", "hdrnet_loss_psnr_f32", "hdrnet_resize_add_f32",

@@ -39,3 +39,142 @@ def io_fits(W, GW, GD):
     threads, _, seg = row_plan(W)
     cols = (seg - 1) * GW // W + 4
     return (768 + _rup(cols * (GD + 2) * 12, 4) + threads // 64 * 256 * 3) * 4 <= 65536
+
+
+# ---- the extent limits (row_geom.h: kMaxFloatX, kLimBH, kLimRowBytes, kLimBlocks, kLimImage; grid_grad_mfma.hip: gg_plan;
+# capi.hip: kGenericMaxPixels)
+# and, from them, the kernel a 3 -> 3 call with offset on 16-B aligned buffers reaches (tests/extent_cases.py,
+# tests/test_gpu_extent_edges.py).
+MAX_FLOAT_X = 1 << 23      # widest row of the four-pixels-per-lane kernels and of the gradient pass: x + 0.5f exact
+MAX_BH = 65535             # B and H of the 3-D launch grids
+MAX_ROW_BYTES = 1 << 31    # a pixel row is shorter than this
+MAX_LAUNCH_THREADS = (1 << 32) - 1  # B * H * nseg * threads of the 1-D launch grids (the HIP runtime's bound)
+MAX_GENERIC_PIXELS = (1 << 32) - 256  # the generic kernels: one thread per pixel in workgroups of 256
+MI355X_CUS = 256
+
+
+def vec4(W, aligned=True):
+    """Plan::vec4."""
+    return aligned and W % 4 == 0 and W <= MAX_FLOAT_X
+
+
+def extent_limit(B, H, W, family, row_channels=3):
+    """extent_refusal: the extent limit a frame breaks for `family` ("seg": kSegLimits; "rows4": the four-pixel kernels
+    of the row family, kNeedVec4 | kRowsLimits), as the word the refusal text carries; None: it breaks none."""
+    if family == "seg":
+        if B > MAX_BH or H > MAX_BH:
+            return "65535"
+        if W * row_channels * 4 >= MAX_ROW_BYTES:
+            return "2^31 bytes"
+    if W > MAX_FLOAT_X:
+        return "2^23"
+    if family == "rows4" and not launch_fits(B, H, W):
+        return "2^32 - 1"
+    return None
+
+
+def launch_fits(B, H, W):
+    """kLimBlocks: the workgroups of a 1-D launch times their threads."""
+    threads, nseg, _ = row_plan(W)
+    return B * H * nseg * threads <= MAX_LAUNCH_THREADS
+
+
+def seg_reaches(B, H, W, GW, GD, guide_map=True, io=False):
+    """The segment family's predicate for a frame: shape and LDS as above, and the extents."""
+    _, _, seg = row_plan(W)
+    staged = ((seg - 1) * GW // W + 4) * GD * 12
+    fits = io_fits(W, GW, GD) if io else seg_fits(W, GW, GD, guide_map)
+    return vec4(W) and fits and staged < (1 << 20) and extent_limit(B, H, W, "seg") is None
+
+
+def rows_reaches(B, H, W, GW, GD, aligned=True):
+    """rows_fwd_geom(...).ok for a frame, and whether the four-pixel kernel serves it."""
+    ok = rows_fits(W, GW, GD) and launch_fits(B, H, W)
+    return ok, ok and vec4(W, aligned)
+
+
+def forward_kernel(B, H, W, GW, GD, aligned=True):
+    """hdrnet_bilateral_slice_apply_f32 under HDRNET_KERNEL_AUTO."""
+    ok, four = rows_reaches(B, H, W, GW, GD, aligned)
+    if not ok:
+        return "apply_fwd_generic"
+    if aligned and seg_reaches(B, H, W, GW, GD):
+        return "apply_fwd_seg/vec4"
+    return "apply_fwd_rows/vec4" if four else "apply_fwd_rows/scalar"
+
+
+def fused_forward_kernel(B, H, W, GW, GD, flavour):
+    """..._nnguide_f32 / ..._upadd_f32 (`flavour` "nnguide", "upadd", "nnguide+upadd"): the segment kernel, else the
+    four-pixel row kernel, else None -- the entry point refuses."""
+    if seg_reaches(B, H, W, GW, GD, guide_map="nnguide" not in flavour):
+        return "apply_fwd_seg/vec4+" + flavour
+    return "apply_fwd_rows/vec4+" + flavour if rows_reaches(B, H, W, GW, GD)[1] else None
+
+
+def slice_kernel(B, H, W, GW, GD, C):
+    """hdrnet_bilateral_slice_f32 for a channel count the row kernel is instantiated for: GD planes of at most GW
+    columns + 64 x C floats per wave in 64 KiB, the 1-D launch grid."""
+    threads, nseg, seg = row_plan(W)
+    cols = min((seg - 1) * GW // W + 4, GW)
+    lds = (_rup(cols * GD * C, 4) + threads // 64 * 64 * C) * 4
+    return "slice_fwd_rows" if lds <= 65536 and launch_fits(B, H, W) else "slice_fwd_generic"
+
+
+def gg_plan(B, H, W, GH, GW, GD, C, slots):
+    """gg_plan of grid_grad_mfma.hip: (rg, nyg) of the gradient pass on `slots` resident workgroups, or None where it
+    refuses."""
+    if GD > 16 or C > 32 or C < 1 or W > MAX_FLOAT_X:
+        return None
+    cell = max(H // GH, 1)
+    rg_lo = min(cell, 4)
+    cols = B * (GW + 1)
+    rg, best = rg_lo, -1.0
+    for R in range(1, 7):
+        per_col = slots * R // cols
+        if per_col < 1:
+            continue
+        cand = -(-H // per_col)
+        if cand > cell:
+            continue
+        cand = max(cand, rg_lo)
+        ntasks = cols * -(-H // cand)
+        eff = ntasks / (-(-ntasks // slots) * slots)
+        if eff > best + 1e-9:
+            best, rg = eff, cand
+    if best < 0.0:
+        rg = cell
+    rg = max(rg, 1)
+    nyg = -(-H // rg)
+    if cols * nyg > 0x7fffffff or B * GH * GW * GD > 0x7fffffff or nyg > 65535 or B > 65535 or GH > 65535:
+        return None
+    return rg, nyg
+
+
+def gg_reaches(B, H, W, GH, GW, GD, C=12, cus=MI355X_CUS):
+    """gg_ws_bound: the pass runs where the plan holds for every occupancy (1 .. 8 workgroups per CU) a launch may have."""
+    return all(gg_plan(B, H, W, GH, GW, GD, C, occ * cus) is not None for occ in range(1, 9))
+
+
+def vjp_kernel(B, H, W, GW, GD, want_dinput=True):
+    """The per-pixel gradients alone: apply_vjp_seg, the row family's four-pixel kernel, or None (the generic ones)."""
+    threads, nseg, seg = row_plan(W)
+    if not vec4(W):
+        return None
+    cols = (seg - 1) * GW // W + 4
+    seg_lds = (_rup(cols * (GD + 2) * 12, 4) + threads // 64 * 256 * 7) * 4
+    if seg_lds <= 65536 and cols * GD * 12 < (1 << 20) and extent_limit(B, H, W, "seg") is None:
+        return "apply_vjp_seg/vec4"
+    rows_lds = (min(cols, GW) * GD * 12 + 4 + threads // 64 * 256 * 3) * 4
+    return "apply_vjp_rows/vec4" if rows_lds <= 65536 and launch_fits(B, H, W) else None
+
+
+def grad_kernels(B, H, W, GH, GW, GD, need_guide, need_input):
+    """hdrnet_bilateral_slice_apply_grad_f32 asked for dgrid and the given per-pixel gradients, with the workspace its
+    query answers: hdrnet_last_kernel()."""
+    mfma = gg_reaches(B, H, W, GH, GW, GD)
+    if not (need_guide or need_input):
+        return "grid_grad_mfma" if mfma else "apply_grad_generic"
+    if mfma:
+        return "apply_bwd_fused/mfma"
+    pix = vjp_kernel(B, H, W, GW, GD, need_input)
+    return pix + "+apply_grad_generic" if pix else "apply_grad_generic"
