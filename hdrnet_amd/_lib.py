@@ -184,6 +184,22 @@ PIXEL_FORMAT_SIGNATURES = {
                                                   [_I, _VP, _FP, _I, _I, _VP]),
 }
 
+# include/hdrnet_amd_yuv.h: semi-planar YUV 4:2:0 surfaces (NV12, P010 / P016) through the low-res gather and the fused
+# wire-format forwards, NV12 out.  A surface travels as (y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y,
+# image_stride_uv); B, H, W and the 12 constants follow it.
+_LL = ctypes.c_longlong
+_SURFACE = [_FP, _FP, _I, _I, _I, _LL, _LL]
+YUV_OUT = {"rgb_f32": 0, "rgb_u8": 1, "nv12": 2}  # HDRNET_YUV_OUT_*
+_YUV_OUTPUT = [_I, _FP, _FP, _I, _I, _LL, _LL, _FP]  # output_kind, out, out_uv, pitches, image strides, from_rgb
+YUV_SIGNATURES = {
+    "hdrnet_yuv_to_rgb_f32": (_I, _SURFACE + [_I] * 3 + [_FP, _FP, _VP]),
+    "hdrnet_lowres_input_yuv": (_I, _SURFACE + [_I] * 3 + [_FP, _FP, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv": (_I, [_FP, _FP] + _SURFACE + [_I] * 3 + [_FP] + [_I] * 6 + [_FP, _FP, _I, _FP, _U] +
+                                            _YUV_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv": (_I, [_FP] + _SURFACE + [_I] * 3 + [_FP] + [_I] * 6 + [_FP] * 4 +
+                                                   [_I, _VP, _FP] + _YUV_OUTPUT + [_VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -238,6 +254,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(COEFF_WIDE_SIGNATURES)
     table.update(PYRAMID_IO_SIGNATURES)
     table.update(PIXEL_FORMAT_SIGNATURES)
+    table.update(YUV_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

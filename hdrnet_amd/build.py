@@ -40,6 +40,8 @@ SOURCES = [
     ("apply_fwd_io.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     # the same kernel for frames in BGR / RGBA / BGRA order: twice the instantiations, a translation unit of its own
     ("apply_fwd_io_px.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    # ... and for semi-planar YUV surfaces in, RGB or NV12 out (include/hdrnet_amd_yuv.h), with the surface -> RGB kernel
+    ("apply_fwd_io_yuv.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_upadd.hip", ["-fno-slp-vectorize"]),
     ("apply_bwd_rows.hip", ["-fno-slp-vectorize"]),
     ("apply_vjp_seg.hip", ["-fno-slp-vectorize"]),
@@ -106,6 +108,7 @@ def _deps() -> List[str]:
     out = [os.path.join(INCLUDE, "hdrnet_amd.h"), os.path.join(INCLUDE, "hdrnet_amd_train.h"),
            os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.join(INCLUDE, "hdrnet_amd_coeff_wide.h"),
            os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"), os.path.join(INCLUDE, "hdrnet_amd_pixel_formats.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_yuv.h"),
            os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):

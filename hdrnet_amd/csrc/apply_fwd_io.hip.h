@@ -19,8 +19,15 @@
 // uint8 epilogue fills -- 12 bytes per lane without alpha, 16 with (one dwordx4 each way) -- and nothing in between, so
 // every format computes the RGB instantiation's values.  Alpha travels in registers from the load to the store.
 //
+// YUV SURFACES (include/hdrnet_amd_yuv.h): the frame may also be a semi-planar 4:2:0 surface, NV12 or P010 / P016.  PX =
+// kPxYuv replaces the load -- a lane's 4 pixels are one dword of Y and one of UV (two each for uint16 samples), converted
+// by yuv_convert.hip.h's one function into the same inf[] -- and OUT = kOutNV12 the store: a workgroup then owns a row
+// PAIR, runs the stage-image / pixel phase twice over the same LDS region and keeps the 2 x 2 blocks' chroma sums in
+// registers in between.  Neither changes a line of what the other instantiations compile.
+//
 // This header holds the kernel and its launch; the RGB instantiations are compiled by apply_fwd_io.hip, those of the
-// other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many).
+// other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many), those of the YUV
+// surfaces by apply_fwd_io_yuv.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,6 +58,11 @@ using namespace rows;
 constexpr int kGuideMap = 0, kGuideNN = 1, kGuideCurves = 2;
 constexpr int kGuideCurvesScan = 3;  // the curves guide evaluated knot by knot: more than kCurveMaxKnots knots per channel
 constexpr int kGuideCurvesCells = 4;  // the curves guide from the PREPARED uniform cell tables (CurveCells below)
+
+// PX beyond the packed formats of white_level.hip.h: the frame is a YUV surface (IoParams::yin); the op still sees R, G, B
+constexpr int kPxYuv = 4;
+// what the kernel stores: a frame of TO in the input's packed format / RGB -- or an NV12 surface (IoParams::yout)
+constexpr int kOutFrame = 0, kOutNV12 = 1;
 
 struct GuideNet {
   const float* conv1;  // NN: [n][CIN + 1]            curves: ccm [CIN][CIN + 1] (row = output channel)
@@ -559,14 +571,22 @@ struct IoParams {
   SegTab tab;      // (cmin, ncols) per segment, from the host (seg_common.hip.h)
   GuideNet gn;
   int nn_mfma;     // tools build, knob 5: the guide network's hidden layer on the matrix cores (uint8 input)
+  // YUV surfaces (PX == kPxYuv / OUT == kOutNV12; unused by every other instantiation)
+  YuvSurface yin, yout;
+  const float* to_rgb;    // 12 floats each (yuv_convert.hip.h)
+  const float* from_rgb;
 };
 
 // Geometry, LDS image and pixel core are apply_fwd_seg.hip's (seg_common.hip.h): a workgroup owns a row
 // segment, 3-D launch grid (segment, row, image), padded y-pre-lerped coefficient image.
-template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB>
+template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
 __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   static_assert(PX == kPxRGB || (CIN == 3 && COUT == 3 && sizeof(TI) < 4), "pixel formats: integer frames, 3 -> 3");
-  constexpr int SPX = PX == kPxRGB ? CIN : px_stored(PX);  // samples per stored pixel of the frame
+  constexpr bool YUV = PX == kPxYuv;          // the input is a YUV surface; the frame the kernel stores is RGB
+  constexpr bool NV12OUT = OUT == kOutNV12;   // ... unless the output is an NV12 surface: a workgroup owns a row pair
+  static_assert(!NV12OUT || (YUV && sizeof(TO) == 1), "NV12 out: uint8 planes, from a YUV surface");
+  constexpr bool PACKED = PX != kPxRGB && !YUV;  // BGR / RGBA / BGRA
+  constexpr int SPX = PACKED ? px_stored(PX) : CIN;  // samples per stored pixel of the frame
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   constexpr int CB = C * (int)sizeof(float);
   constexpr int NI = CIN * kPxPerThread, NO = COUT * kPxPerThread;
@@ -575,7 +595,8 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   // Integer samples with a guide MAP: the input is used by the affine only, so the white level goes into the staged
   // coefficients (coef / wl) * v, and the 12 divisions per lane (3 instructions each) disappear: u8 -> u8 26.7 -> ... us.
   // (With a guide NETWORK the guide's own input stays v / wl, IEEE-rounded as TensorFlow's division.)
-  constexpr bool FOLD_WL = GUIDE == kGuideMap && sizeof(TI) < 4 && C == 12;
+  // (A YUV surface's conversion clamps: its pixels enter as the converted floats, nothing to fold.)
+  constexpr bool FOLD_WL = GUIDE == kGuideMap && sizeof(TI) < 4 && C == 12 && !YUV;
 #ifdef HDRNET_TOOLS_BUILD
   constexpr bool NN_MFMA = GUIDE == kGuideNN && sizeof(TI) == 1 && CIN == 3 && PX == kPxRGB;  // experiment: hidden layer on the bf16 matrix cores
 #else
@@ -602,144 +623,192 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int xs = blockIdx.x * p.seg;
   const int xe = min(xs + p.seg, p.W);
-  const int y = blockIdx.y;
   const int b = blockIdx.z;
   const float* grid_b = p.grid + (size_t)b * (unsigned)p.grid_image;
   const int x = xs + kPxPerThread * tid;
   const bool active = x < xe;
-  const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (kLimBH, row_geom.h)
-  const size_t px = row * p.W + x;
-  const TI* input = static_cast<const TI*>(p.input);
+  // NV12 out: the linear parts of U and V of the lane's two 2 x 2 blocks, summed over the row pair (yuv_convert.hip.h)
+  [[maybe_unused]] float csum[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+  // One image row per workgroup -- or, for an NV12 output, the two rows of a chroma row, one after the other through the
+  // same LDS image.  (The loop's condition is a compile-time `false` for one row: no back edge, r == 0, and the
+  // single-row kernels compile to the straight code they were.)
+  constexpr int ROWS = NV12OUT ? 2 : 1;
+  int r = 0;
+  do {
+    const int y = NV12OUT ? 2 * (int)blockIdx.y + r : (int)blockIdx.y;
+    const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (kLimBH, row_geom.h)
+    const size_t px = row * p.W + x;
+    const TI* input = static_cast<const TI*>(p.input);
 
-  float gs[kPxPerThread] = {0.f, 0.f, 0.f, 0.f};
-  float inf[NI];
-  [[maybe_unused]] uint32_t raw[3] = {};
-  [[maybe_unused]] uint32_t alpha[kPxPerThread] = {};  // RGBA / BGRA: the 4 pixels' alpha samples as stored
+    float gs[kPxPerThread] = {0.f, 0.f, 0.f, 0.f};
+    float inf[NI];
+    [[maybe_unused]] uint32_t raw[3] = {};
+    [[maybe_unused]] uint32_t alpha[kPxPerThread] = {};  // RGBA / BGRA: the 4 pixels' alpha samples as stored
 #pragma unroll
-  for (int q = 0; q < NI; ++q) inf[q] = 0.0f;
-  if (active) {
-    if constexpr (GUIDE == kGuideMap) {
-      const float4 g4 = *reinterpret_cast<const float4*>(p.guide + px);
-      gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
-    }
-    if constexpr (NN_MFMA) load_pixels<TI, NI>(input, px * CIN, p.white, inf, raw);
-    else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
-  }
-  const bool nn_mfma = NN_MFMA && p.nn_mfma && p.gn.n <= 16 && (p.gn.n & 3) == 0;  // uniform
-  if constexpr (NN_MFMA) {
-    if (nn_mfma && wave == 0)
-      nn_build_tables(reinterpret_cast<unsigned*>(lds_all), lds_all + NnTab::kWords - 4, p.gn, p.white.wl, lane);
-  }
-
-  if constexpr (GUIDE == kGuideCurves) {
-    if (wave == 0) curves_build_tables<CIN>(ctab, p.gn, lane);  // published by the barrier below
-  }
-  if constexpr (GUIDE == kGuideCurvesCells) {  // the prepared cell tables: 3 KB copied by the whole workgroup (barrier below)
-    const f32x4* src = reinterpret_cast<const f32x4*>(p.gn.prepared);
-    for (int e = tid; e < CIN * kCurveCells; e += (int)blockDim.x) reinterpret_cast<f32x4*>(ctab)[e] = src[e];
-  }
-  const SegCols sc = seg_cols_tab(p.tab, blockIdx.x, xs, xe, p.scale_x);
-  const int colb = (p.GD + 2) * CB;
-  const float gd_f = (float)p.GD, zhi = (float)(p.GD - 1);
-  stage_image<C, FOLD_WL>(lds, grid_b, y, sc.cmin, sc.ncols, p.GH, p.GW, p.GD, p.scale_y, p.inv_col, tid, (int)blockDim.x,
-                          p.white.inv);
-  // the lean pixel phase of the product forward (seg_common.hip.h)
-  XTermLean xt[kPxPerThread];
-  const float xf0 = (float)x + 0.5f;  // xf0 + k == (x + k) + 0.5f exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
-  const float colb_f = (float)colb, xbase_f = (float)(CB - sc.cmin * colb);
-#pragma unroll
-  for (int k = 0; k < kPxPerThread; ++k) xt[k] = x_term_lean(xf0 + (float)k, p.scale_x, colb_f, xbase_f);
-  __syncthreads();
-
-  float of[NO];
-  if (active) {
-    if constexpr (GUIDE != kGuideMap) {
-      if constexpr (GUIDE == kGuideNN) {
-        bool done = false;
-        if constexpr (NN_MFMA) {
-          if (nn_mfma) {
-            guide_nn_quad_mfma_u8(reinterpret_cast<const unsigned*>(lds_all), p.gn, raw, lane, gs);
-            done = true;
-          }
-        }
-        if (!done) guide_nn_quad<CIN>(GuideNN{p.gn.conv1, p.gn.conv2, p.gn.guide_out, p.gn.n, p.gn.fast_sigmoid, p.gn.prescaled}, inf, gs);  // (writes nothing itself)
-      }
-      else if constexpr (GUIDE == kGuideCurves)
-        guide_curves_quad<CIN>(ctab, p.gn, inf, gs);
-      else if constexpr (GUIDE == kGuideCurvesCells)
-        guide_curves_quad_cells<CIN>(ctab, p.gn, inf, gs);
-      else
-        guide_curves_scan_quad<CIN>(p.gn, inf, gs);
-      if (p.gn.guide_out) *reinterpret_cast<float4*>(p.gn.guide_out + px) = make_float4(gs[0], gs[1], gs[2], gs[3]);
-    }
-#pragma unroll
-    for (int k = 0; k < kPxPerThread; ++k) {
-      float in[CIN], o[COUT];
-#pragma unroll
-      for (int j = 0; j < CIN; ++j) in[j] = inf[k * CIN + j];
-      seg_pixel_lean<CIN, COUT, OFFSET, true>(lds, gd_f, zhi, colb, xt[k], gs[k], in, o);
-#pragma unroll
-      for (int i = 0; i < COUT; ++i) of[k * COUT + i] = o[i];
-    }
-  }
-
-  if constexpr (sizeof(TO) == 1) {
-    // tf.cast(255 * clip(out, 0, 1), uint8): truncation.  12 bytes per lane, contiguous across
-    // the wave: plain per-lane stores are already dense.
-    static_assert(NO % 4 == 0, "whole dwords per thread");
-    if constexpr (PX != kPxRGB) {
-      // the input's own pixel format: colour channel c of pixel k goes where load_pixels found it, alpha beside it
-      // (copied; the upper byte of a uint16 alpha) -- 12 or 16 bytes per lane, contiguous across the wave
-      if (active) {
-        uint32_t w[SPX];
-#pragma unroll
-        for (int q = 0; q < SPX; ++q) w[q] = 0;
-#pragma unroll
-        for (int k = 0; k < kPxPerThread; ++k) {
-#pragma unroll
-          for (int i = 0; i < COUT; ++i) {
-            const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);
-            const int pos = px_sample(PX, k, i);
-            w[pos >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (pos & 3));
-          }
-          if constexpr (SPX == 4) w[k] |= (sizeof(TI) == 2 ? alpha[k] >> 8 : alpha[k]) << 24;
-        }
-        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SPX);
-        if constexpr (SPX == 4) {
-          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-          *reinterpret_cast<u32x4*>(op) = u32x4{w[0], w[1], w[2], w[3]};
-        } else {
-#pragma unroll
-          for (int q = 0; q < SPX; ++q) op[q] = w[q];
-        }
-      }
-    } else if (active) {
-      uint32_t w[NO / 4];
-#pragma unroll
-      for (int q = 0; q < NO / 4; ++q) w[q] = 0;
-#pragma unroll
-      for (int q = 0; q < NO; ++q) {
-        const float c = __builtin_amdgcn_fmed3f(of[q], 0.0f, 1.0f);  // clip: folds into the affine's last fma (clamp)
-        w[q >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (q & 3));
-      }
-      uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * COUT);
-#pragma unroll
-      for (int q = 0; q < NO / 4; ++q) op[q] = w[q];
-    }
-  } else {
-    // float output: lane-contiguous nontemporal buffer stores through the per-wave LDS slab
-    // (apply_fwd_seg.hip); the descriptor covers exactly the row segment
-    float4* slab = reinterpret_cast<float4*>(lds + p.slab_off) + wave * (64 * COUT);
+    for (int q = 0; q < NI; ++q) inf[q] = 0.0f;
     if (active) {
-#pragma unroll
-      for (int q = 0; q < COUT; ++q)
-        slab[lane * COUT + q] = make_float4(of[4 * q], of[4 * q + 1], of[4 * q + 2], of[4 * q + 3]);
+      if constexpr (GUIDE == kGuideMap) {
+        const float4 g4 = *reinterpret_cast<const float4*>(p.guide + px);
+        gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
+      }
+      if constexpr (YUV) yuv_load_quad<TI>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      else if constexpr (NN_MFMA) load_pixels<TI, NI>(input, px * CIN, p.white, inf, raw);
+      else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
     }
-    wave_lds_sync();
-    const unsigned wpx = kPxPerThread * 64u * (unsigned)wave;
-    float* oseg = static_cast<float*>(p.out) + (row * p.W + xs) * COUT;
-    store_slab_seg<COUT>(slab, oseg, (unsigned)(xe - xs), wpx, lane);
-  }
+    const bool nn_mfma = NN_MFMA && p.nn_mfma && p.gn.n <= 16 && (p.gn.n & 3) == 0;  // uniform
+    if constexpr (NN_MFMA) {
+      if (nn_mfma && wave == 0)
+        nn_build_tables(reinterpret_cast<unsigned*>(lds_all), lds_all + NnTab::kWords - 4, p.gn, p.white.wl, lane);
+    }
+
+    // (the guide's tables depend on the parameters only: built for the first row, read for both)
+    if constexpr (GUIDE == kGuideCurves) {
+      if (r == 0 && wave == 0) curves_build_tables<CIN>(ctab, p.gn, lane);  // published by the barrier below
+    }
+    if constexpr (GUIDE == kGuideCurvesCells) {  // the prepared cell tables: 3 KB copied by the whole workgroup (barrier below)
+      const f32x4* src = reinterpret_cast<const f32x4*>(p.gn.prepared);
+      if (r == 0)
+        for (int e = tid; e < CIN * kCurveCells; e += (int)blockDim.x) reinterpret_cast<f32x4*>(ctab)[e] = src[e];
+    }
+    const SegCols sc = seg_cols_tab(p.tab, blockIdx.x, xs, xe, p.scale_x);
+    const int colb = (p.GD + 2) * CB;
+    const float gd_f = (float)p.GD, zhi = (float)(p.GD - 1);
+    // second row of a pair: the image region is staged AGAIN, once every lane has read the first row's coefficients
+    if (r > 0) __syncthreads();
+    stage_image<C, FOLD_WL>(lds, grid_b, y, sc.cmin, sc.ncols, p.GH, p.GW, p.GD, p.scale_y, p.inv_col, tid, (int)blockDim.x,
+                            p.white.inv);
+    // the lean pixel phase of the product forward (seg_common.hip.h)
+    XTermLean xt[kPxPerThread];
+    const float xf0 = (float)x + 0.5f;  // xf0 + k == (x + k) + 0.5f exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
+    const float colb_f = (float)colb, xbase_f = (float)(CB - sc.cmin * colb);
+#pragma unroll
+    for (int k = 0; k < kPxPerThread; ++k) xt[k] = x_term_lean(xf0 + (float)k, p.scale_x, colb_f, xbase_f);
+    __syncthreads();
+
+    float of[NO];
+    if (active) {
+      if constexpr (GUIDE != kGuideMap) {
+        if constexpr (GUIDE == kGuideNN) {
+          bool done = false;
+          if constexpr (NN_MFMA) {
+            if (nn_mfma) {
+              guide_nn_quad_mfma_u8(reinterpret_cast<const unsigned*>(lds_all), p.gn, raw, lane, gs);
+              done = true;
+            }
+          }
+          if (!done) guide_nn_quad<CIN>(GuideNN{p.gn.conv1, p.gn.conv2, p.gn.guide_out, p.gn.n, p.gn.fast_sigmoid, p.gn.prescaled}, inf, gs);  // (writes nothing itself)
+        }
+        else if constexpr (GUIDE == kGuideCurves)
+          guide_curves_quad<CIN>(ctab, p.gn, inf, gs);
+        else if constexpr (GUIDE == kGuideCurvesCells)
+          guide_curves_quad_cells<CIN>(ctab, p.gn, inf, gs);
+        else
+          guide_curves_scan_quad<CIN>(p.gn, inf, gs);
+        if (p.gn.guide_out) *reinterpret_cast<float4*>(p.gn.guide_out + px) = make_float4(gs[0], gs[1], gs[2], gs[3]);
+      }
+#pragma unroll
+      for (int k = 0; k < kPxPerThread; ++k) {
+        float in[CIN], o[COUT];
+#pragma unroll
+        for (int j = 0; j < CIN; ++j) in[j] = inf[k * CIN + j];
+        seg_pixel_lean<CIN, COUT, OFFSET, true>(lds, gd_f, zhi, colb, xt[k], gs[k], in, o);
+#pragma unroll
+        for (int i = 0; i < COUT; ++i) of[k * COUT + i] = o[i];
+      }
+    }
+
+    if constexpr (NV12OUT) {
+      // An NV12 surface: one dword of Y per lane and row; the chroma of the lane's two 2 x 2 blocks after the second row,
+      // one dword (U0 V0 U1 V1) into the pair's interleaved UV row.  Padding beyond the row is not written.
+      if (active) {
+        const YuvMatrix fk = yuv_load_matrix(p.from_rgb);
+        uint32_t wy = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          float pu[2], pv[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int k = 2 * h + i;
+            float c[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) c[j] = __builtin_amdgcn_fmed3f(of[k * COUT + j], 0.0f, 1.0f);
+            wy |= yuv_luma_code(fk, c) << (8 * k);
+            pu[i] = yuv_chroma_linear(fk, 1, c);
+            pv[i] = yuv_chroma_linear(fk, 2, c);
+          }
+          csum[h][0] += pu[0] + pu[1];  // horizontal pair first; even row (onto 0), then odd row
+          csum[h][1] += pv[0] + pv[1];
+        }
+        char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y + x;
+        *reinterpret_cast<uint32_t*>(yo) = wy;
+        if (r == ROWS - 1) {
+          uint32_t wc = 0;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            wc |= (yuv_chroma_code(fk, 1, csum[h][0]) | (yuv_chroma_code(fk, 2, csum[h][1]) << 8)) << (16 * h);
+          char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
+                     (long long)(y >> 1) * p.yout.pitch_uv + x;
+          *reinterpret_cast<uint32_t*>(co) = wc;
+        }
+      }
+    } else if constexpr (sizeof(TO) == 1) {
+      // tf.cast(255 * clip(out, 0, 1), uint8): truncation.  12 bytes per lane, contiguous across
+      // the wave: plain per-lane stores are already dense.
+      static_assert(NO % 4 == 0, "whole dwords per thread");
+      if constexpr (PACKED) {
+        // the input's own pixel format: colour channel c of pixel k goes where load_pixels found it, alpha beside it
+        // (copied; the upper byte of a uint16 alpha) -- 12 or 16 bytes per lane, contiguous across the wave
+        if (active) {
+          uint32_t w[SPX];
+#pragma unroll
+          for (int q = 0; q < SPX; ++q) w[q] = 0;
+#pragma unroll
+          for (int k = 0; k < kPxPerThread; ++k) {
+#pragma unroll
+            for (int i = 0; i < COUT; ++i) {
+              const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);
+              const int pos = px_sample(PX, k, i);
+              w[pos >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (pos & 3));
+            }
+            if constexpr (SPX == 4) w[k] |= (sizeof(TI) == 2 ? alpha[k] >> 8 : alpha[k]) << 24;
+          }
+          uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SPX);
+          if constexpr (SPX == 4) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<u32x4*>(op) = u32x4{w[0], w[1], w[2], w[3]};
+          } else {
+#pragma unroll
+            for (int q = 0; q < SPX; ++q) op[q] = w[q];
+          }
+        }
+      } else if (active) {
+        uint32_t w[NO / 4];
+#pragma unroll
+        for (int q = 0; q < NO / 4; ++q) w[q] = 0;
+#pragma unroll
+        for (int q = 0; q < NO; ++q) {
+          const float c = __builtin_amdgcn_fmed3f(of[q], 0.0f, 1.0f);  // clip: folds into the affine's last fma (clamp)
+          w[q >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (q & 3));
+        }
+        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * COUT);
+#pragma unroll
+        for (int q = 0; q < NO / 4; ++q) op[q] = w[q];
+      }
+    } else {
+      // float output: lane-contiguous nontemporal buffer stores through the per-wave LDS slab
+      // (apply_fwd_seg.hip); the descriptor covers exactly the row segment
+      float4* slab = reinterpret_cast<float4*>(lds + p.slab_off) + wave * (64 * COUT);
+      if (active) {
+#pragma unroll
+        for (int q = 0; q < COUT; ++q)
+          slab[lane * COUT + q] = make_float4(of[4 * q], of[4 * q + 1], of[4 * q + 2], of[4 * q + 3]);
+      }
+      wave_lds_sync();
+      const unsigned wpx = kPxPerThread * 64u * (unsigned)wave;
+      float* oseg = static_cast<float*>(p.out) + (row * p.W + xs) * COUT;
+      store_slab_seg<COUT>(slab, oseg, (unsigned)(xe - xs), wpx, lane);
+    }
+  } while (NV12OUT && ++r < ROWS);
 }
 
 // The curves instantiations keep their lookup tables in STATIC LDS: no launch passes those bytes, but the workgroup
@@ -756,7 +825,7 @@ RowGeom io_geom(const ApplyIoArgs& a, int tab_floats) {
                               a.input_dtype == 0 ? a.input : nullptr));
 }
 
-template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB>
+template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
 hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   const RowGeom g = io_geom(a, (kToolsBuild && GUIDE == kGuideNN) ? NnTab::kWords : 0);
@@ -781,8 +850,17 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
 #else
   p.nn_mfma = 0;
 #endif
-  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)a.H, (unsigned)a.B);
-  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX><<<grid3, g.pl.threads, g.lds, s>>>(p);
+  p.yin = p.yout = YuvSurface{};
+  p.to_rgb = p.from_rgb = nullptr;
+  if constexpr (PX == kPxYuv) {
+    p.yin = a.yuv->in;
+    p.to_rgb = a.yuv->to_rgb;
+    p.yout = a.yuv->out;
+    p.from_rgb = a.yuv->from_rgb;
+  }
+  // an NV12 output: one workgroup per row PAIR of a segment (H % 2 == 0)
+  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT == kOutNV12 ? a.H / 2 : a.H), (unsigned)a.B);
+  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT><<<grid3, g.pl.threads, g.lds, s>>>(p);
   return hipGetLastError();
 }
 
@@ -829,5 +907,6 @@ hipError_t dispatch_guides(const ApplyIoArgs& a, hipStream_t s) {
 
 // apply_fwd_io_px.hip: the same launch for a frame in BGR, RGBA or BGRA order (a.pixel_format != 0)
 hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
+// apply_fwd_io_yuv.hip (launch.hip.h): the same launch for a YUV surface (a.yuv)
 
 }  // namespace hdrnet_amd

@@ -12,6 +12,7 @@
 
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_pixel_formats.h"
+#include "../../include/hdrnet_amd_yuv.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
@@ -352,7 +353,9 @@ extern "C" {
 //          pyramid model's wire formats)
 // 0.2.8.6: + include/hdrnet_amd_pixel_formats.h: hdrnet_lowres_input_px, hdrnet_bilateral_slice_apply_io_px,
 //          hdrnet_bilateral_slice_apply_io_curves_px (uint8 / uint16 frames in BGR, RGBA and BGRA order)
-int hdrnet_version(void) { return 286; }
+// 0.2.8.7: + include/hdrnet_amd_yuv.h: hdrnet_yuv_to_rgb_f32, hdrnet_lowres_input_yuv, hdrnet_bilateral_slice_apply_io_yuv,
+//          hdrnet_bilateral_slice_apply_io_curves_yuv (NV12 / P010 / P016 surfaces in, RGB or NV12 out)
+int hdrnet_version(void) { return 287; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -944,6 +947,199 @@ int hdrnet_lowres_input_px(const void* frames, int dtype, float white_level, int
     return fail(HDRNET_INVALID_ARGUMENT, "%s: 4-channel frames (RGBA / BGRA) must be 16-B aligned", what);
   return prepare_impl(what, frames, dtype, white_level, nullptr, 0, 1.0f, B > 0 ? B : 1, H, W, nullptr, B, nullptr, nullptr,
                       H, W, lowres, net_input_size, 0u, stream, false, 0, nullptr, pixel_format);
+}
+
+
+// ---- include/hdrnet_amd_yuv.h: semi-planar YUV 4:2:0 surfaces ------------------------------------------------------------
+// The rules of a surface (`which`: "input" / "output"), checked before any HIP call; `bytes`: per sample.
+static int check_yuv_extents(const char* what, int B, int H, int W) {
+  if (B < 0 || H < 0 || W < 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: negative image extent (B=%d, H=%d, W=%d)", what, B, H, W);
+  if (H % 2 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: H %% 2 != 0 (H=%d): a chroma row serves two image rows", what, H);
+  if (W % 4 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: W %% 4 != 0 (W=%d): a lane owns 4 pixels", what, W);
+  if (B > 65535 || H > 65535 || (long long)W * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large (B, H <= 65535)", what);
+  return HDRNET_OK;
+}
+
+static int check_yuv_surface(const char* what, const char* which, int sample_dtype, int pitch_y, int pitch_uv,
+                             long long image_stride_y, long long image_stride_uv, int B, int H, int W) {
+  if (sample_dtype != 1 && sample_dtype != 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
+                sample_dtype);
+  const long long row = (long long)W * sample_dtype;
+  if (pitch_y < row || pitch_uv < row)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a pitch of the %s surface is below the row's %lld bytes (pitch_y=%d, "
+                "pitch_uv=%d)", what, which, row, pitch_y, pitch_uv);
+  if ((pitch_y | pitch_uv) & 3)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitches of the %s surface must be multiples of 4 (pitch_y=%d, pitch_uv=%d)",
+                what, which, pitch_y, pitch_uv);
+  if (image_stride_y < 0 || image_stride_uv < 0 || ((image_stride_y | image_stride_uv) & 3))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4", what,
+                which);
+  if (B > 1 && (image_stride_y < (long long)pitch_y * H || image_stride_uv < (long long)pitch_uv * (H / 2)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
+  return HDRNET_OK;
+}
+
+static int check_yuv_pointers(const char* what, const char* which, const void* y, const void* uv, const float* coef) {
+  if (!y || !uv) return fail(HDRNET_INVALID_ARGUMENT, "%s: null plane of the %s surface", what, which);
+  if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
+  if (((uintptr_t)y | (uintptr_t)uv | (uintptr_t)coef) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the planes and constants of the %s surface must be 4-B aligned", what, which);
+  return HDRNET_OK;
+}
+
+int hdrnet_yuv_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                          long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                          float* rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_yuv_to_rgb_f32";
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
+    return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  return finish_launch(launch_yuv_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, static_cast<hipStream_t>(stream)), what,
+                       "yuv_to_rgb");
+}
+
+int hdrnet_lowres_input_yuv(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                            long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                            float* lowres, int net_input_size, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_lowres_input_yuv";
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
+    return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
+                   false};
+  a.yuv = &in;
+  a.yuv_to_rgb = to_rgb;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+// what both fused entry points check of their surfaces and output, and the bundle they launch with
+static int yuv_io_args(const char* what, const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                       long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb, int Cin,
+                       int Cout, int has_offset, int output_kind, void* out, void* out_uv, int out_pitch_y, int out_pitch_uv,
+                       long long out_image_stride_y, long long out_image_stride_uv, const float* from_rgb, bool* noop,
+                       hdrnet_amd::YuvIo* io) {
+  using namespace hdrnet_amd;
+  *noop = false;
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
+    return rc;
+  if (output_kind < HDRNET_YUV_OUT_RGB_F32 || output_kind > HDRNET_YUV_OUT_NV12)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 NV12)", what, output_kind);
+  if (Cin != 3 || Cout != 3 || !has_offset)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
+  if (output_kind == HDRNET_YUV_OUT_NV12)
+    if (int rc = check_yuv_surface(what, "output", 1, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv, B, H, W))
+      return rc;
+  if ((long long)B * H * W == 0) {
+    *noop = true;
+    return HDRNET_OK;
+  }
+  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
+  if (output_kind == HDRNET_YUV_OUT_NV12) {
+    if (int rc = check_yuv_pointers(what, "output", out, out_uv, from_rgb)) return rc;
+  } else if (!out || ((uintptr_t)out & (output_kind == HDRNET_YUV_OUT_RGB_F32 ? 15u : 3u))) {
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
+  }
+  io->in = YuvSurface{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  io->to_rgb = to_rgb;
+  io->out_kind = output_kind;
+  io->out = output_kind == HDRNET_YUV_OUT_NV12
+                ? YuvSurface{out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}
+                : YuvSurface{};
+  io->from_rgb = output_kind == HDRNET_YUV_OUT_NV12 ? from_rgb : nullptr;
+  return HDRNET_OK;
+}
+
+static int yuv_io_launch(const char* what, hdrnet_amd::ApplyIoArgs& a, const hdrnet_amd::YuvIo& io, void* out, void* stream) {
+  using namespace hdrnet_amd;
+  a.pixel_format = 0;
+  a.yuv = &io;
+  a.input = nullptr;
+  a.out = io.out_kind == HDRNET_YUV_OUT_NV12 ? nullptr : out;
+  if (!apply_fwd_io_yuv_supported(a))
+    return refuse_fused(a.B, a.H, a.W, a.GW, a.GD, a.Cout, rows::kSegLimits,
+                        "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers");
+  const char* name = "";
+  const hipError_t e = launch_apply_fwd_io_yuv(a, static_cast<hipStream_t>(stream), &name);
+  return finish_launch(e, what, name);
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv(const float* grid, const float* guide, const void* y, const void* uv,
+                                        int sample_dtype, int pitch_y, int pitch_uv, long long image_stride_y,
+                                        long long image_stride_uv, int B, int H, int W, const float* to_rgb, int GH, int GW,
+                                        int GD, int Cin, int Cout, int has_offset, const float* guide_conv1,
+                                        const float* guide_conv2, int n_feats, float* guide_out, unsigned flags,
+                                        int output_kind, void* out, void* out_uv, int out_pitch_y, int out_pitch_uv,
+                                        long long out_image_stride_y, long long out_image_stride_uv,
+                                        const float* from_rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_bilateral_slice_apply_io_yuv";
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_guide_flags(flags)) return rc;
+  bool noop = false;
+  YuvIo io{};
+  if (int rc = yuv_io_args(what, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb, Cin,
+                           Cout, has_offset, output_kind, out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y,
+                           out_image_stride_uv, from_rgb, &noop, &io))
+    return rc;
+  if (noop) return finish_noop();
+  if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
+  if (!guide && (!guide_conv1 || !guide_conv2 || n_feats <= 0 || n_feats > 4096))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: either a guide map or the guide network must be given", what);
+  ApplyIoArgs a{grid, guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_conv1, guide_conv2, n_feats, guide_out};
+  if (int rc = check_guide_prescaled(flags, guide ? 0 : Cin, guide ? nullptr : guide_conv1, guide ? nullptr : guide_conv2)) return rc;
+  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
+  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
+  return yuv_io_launch("BilateralSliceApplyIOYuv", a, io, out, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv(const float* grid, const void* y, const void* uv, int sample_dtype,
+                                               int pitch_y, int pitch_uv, long long image_stride_y,
+                                               long long image_stride_uv, int B, int H, int W, const float* to_rgb, int GH,
+                                               int GW, int GD, int Cin, int Cout, int has_offset, const float* guide_ccm,
+                                               const float* guide_shifts, const float* guide_slopes,
+                                               const float* guide_mix, int npts, const void* prepared, float* guide_out,
+                                               int output_kind, void* out, void* out_uv, int out_pitch_y,
+                                               int out_pitch_uv, long long out_image_stride_y,
+                                               long long out_image_stride_uv, const float* from_rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv";
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (npts <= 0 || npts > 4096) return fail(HDRNET_INVALID_ARGUMENT, "%s: bad number of curve knots (%d)", what, npts);
+  bool noop = false;
+  YuvIo io{};
+  if (int rc = yuv_io_args(what, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb, Cin,
+                           Cout, has_offset, output_kind, out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y,
+                           out_image_stride_uv, from_rgb, &noop, &io))
+    return rc;
+  if (noop) return finish_noop();
+  if (!grid || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
+  ApplyIoArgs a{grid, nullptr, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_ccm, guide_mix, npts,
+                guide_out, guide_shifts, guide_slopes};
+  if (prepared) {
+    if (((uintptr_t)prepared & 15u) || npts > 16)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: prepared curves tables need npts <= 16 and the 16-B aligned buffer "
+                                           "hdrnet_curves_guide_prepare_f32 wrote (and reported usable)", what);
+    a.guide_prepared = static_cast<const float*>(prepared);
+  }
+  return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, out, stream);
 }
 
 // the wire-format forward with a guide map or the guide network, for a frame in `pixel_format` (io_ex: HDRNET_PX_RGB)

@@ -11,6 +11,7 @@
 #include "../../include/hdrnet_amd_train.h"
 #include "coeff_fc_train.hip.h"
 #include "row_geom.h"
+#include "yuv_convert.hip.h"
 
 namespace hdrnet_amd {
 
@@ -55,6 +56,18 @@ struct ApplyIoArgs {
   // how `input` stores a pixel, HDRNET_PX_* (include/hdrnet_amd_pixel_formats.h): 0 RGB, 1 BGR, 2 RGBA, 3 BGRA; a uint8
   // `out` has the same format, a float32 one is RGB.  Cin / Cout stay the op's 3 whatever the format (apply_fwd_io.hip only)
   int pixel_format = 0;
+  // a semi-planar YUV surface in place of `input` (include/hdrnet_amd_yuv.h; apply_fwd_io_yuv.hip): input_dtype is then the
+  // surface's sample dtype (1 u8 = NV12, 2 u16 = P010 / P016), `input` is unused, and `out` is the RGB frame of
+  // output_dtype -- or, with yuv->out_kind == HDRNET_YUV_OUT_NV12 (output_dtype = 1), unused too
+  const struct YuvIo* yuv = nullptr;
+};
+
+struct YuvIo {
+  YuvSurface in;
+  const float* to_rgb;    // device, 12 floats
+  int out_kind;           // HDRNET_YUV_OUT_*
+  YuvSurface out;         // out_kind == HDRNET_YUV_OUT_NV12
+  const float* from_rgb;  // device, 12 floats
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -222,12 +235,20 @@ struct SamplePrepArgs {
   long long n_samples = 0;
   // the low-res gather alone (hdrnet_lowres_input_px): how src_input stores a pixel, HDRNET_PX_* as ApplyIoArgs::pixel_format
   int pixel_format = 0;
+  // the low-res gather of a YUV surface (hdrnet_lowres_input_yuv): src_input is unused, input_dtype the sample dtype
+  const YuvSurface* yuv = nullptr;
+  const float* yuv_to_rgb = nullptr;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 
 bool apply_fwd_io_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char** name);
 rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a);  // the launch geometry both of them, and the sibling below, read
+// apply_fwd_io_yuv.hip -- the same forward reading a YUV surface (a.yuv), and the surface -> float32 RGB conversion
+bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_yuv(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_yuv_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,
+                             hipStream_t s);
 // apply_fwd_io_upadd.hip -- the same forward + the up-add of the coarser pyramid level (guide map or guide network; every
 // dtype pair but f32 -> f32, which is launch_apply_fwd_upadd's)
 bool apply_fwd_io_upadd_supported(const ApplyIoArgs& a, const float* coarse);

@@ -60,7 +60,7 @@ struct PrepJob {
   float* dst;
   WhiteLevel white;
   int dtype;   // 0 f32 (copied unscaled), 1 u8, 2 u16
-  int lowres;  // 0: [B][H][W][3];  1: [B][n][n][3]
+  int lowres;  // 0: [B][H][W][3];  1: [B][n][n][3];  2: [B][n][n][3] gathered from a YUV surface (PrepParams::yuv)
 };
 
 struct PrepParams {
@@ -75,6 +75,10 @@ struct PrepParams {
   // the low-res gather of a frame in another pixel format (hdrnet_lowres_input_px; the full-resolution jobs and the ragged
   // flavour are RGB): samples per stored pixel, and whether B comes first
   int px_stride, px_b_first;
+  // the low-res gather of a semi-planar YUV surface (hdrnet_lowres_input_yuv, job kind 2): the planes and the 12 constants
+  // of yuv_convert.hip.h; the job's dtype is the sample dtype
+  YuvSurface yuv;
+  const float* yuv_to_rgb;
 };
 
 typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
@@ -292,6 +296,24 @@ __device__ __forceinline__ void full_tile(const PrepParams& p, const PrepJob& jo
   }
 }
 
+// 4 consecutive samples of a low-res image of npx samples, starting at sample px0 (a multiple of 4)
+__device__ __forceinline__ void store_lowres_4px(float* __restrict__ out, int px0, int npx, bool vec, const float (&v)[4][3]) {
+  if (vec) {
+    const float* f = &v[0][0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      *reinterpret_cast<float4*>(out + (long long)px0 * 3 + 4 * k) = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (px0 + j < npx) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(long long)(px0 + j) * 3 + c] = v[j][c];
+      }
+    }
+  }
+}
+
 template <typename T, bool RAGGED>
 __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& job, const Geom& g, int b) {
   const long long last = last_dword<T, RAGGED>(p);
@@ -315,20 +337,31 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
         v[j][2] = t;
       }
     }
-    if (vec) {
-      const float* f = &v[0][0];
+    store_lowres_4px(out, px0, npx, vec, v);
+  }
+}
+
+// The same gather from a YUV surface: output sample (yl, xl) takes the source pixel lowres_job takes (identity geometry:
+// hdrnet_lowres_input's), its luma from (y, x) and its chroma from (y >> 1, x >> 1), converted by yuv_to_rgb_px -- the
+// bits of lowres_job on the float32 frame hdrnet_yuv_to_rgb_f32 writes.
+template <typename T>
+__device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const PrepJob& job, int b) {
+  const int npx = p.n * p.n;
+  float* out = job.dst + (long long)b * npx * 3;
+  const bool vec = (npx & 3) == 0;
+  const YuvMatrix k = yuv_load_matrix(p.yuv_to_rgb);
+  for (int px0 = 4 * (blockIdx.x * kThreads + threadIdx.x); px0 < npx; px0 += 4 * gridDim.x * kThreads) {
+    float v[4][3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-        *reinterpret_cast<float4*>(out + (long long)px0 * 3 + 4 * k) = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (px0 + j < npx) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) out[(long long)(px0 + j) * 3 + c] = v[j][c];
-        }
-      }
+    for (int j = 0; j < 4; ++j) {
+      const int px = px0 + j < npx ? px0 + j : npx - 1;
+      const int yl = px / p.n, xl = px % p.n;
+      int y = (int)__builtin_floorf((float)yl * p.scale_y), x = (int)__builtin_floorf((float)xl * p.scale_x);
+      y = y < p.H - 1 ? y : p.H - 1;
+      x = x < p.W - 1 ? x : p.W - 1;
+      yuv_load_px<T>(p.yuv, k, b, y, x, v[j]);
     }
+    store_lowres_4px(out, px0, npx, vec, v);
   }
 }
 
@@ -337,6 +370,13 @@ __global__ __launch_bounds__(kThreads) void sample_prep_kernel(const PrepParams 
   __shared__ __attribute__((aligned(16))) float tile[kTileH * kPitch];
   const PrepJob& job = p.job[blockIdx.z];
   const int b = blockIdx.y;
+  if (job.lowres == 2) {  // a YUV surface: no geometry record, no packed source
+    if constexpr (!RAGGED) {
+      if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, job, b);
+      else lowres_job_yuv<uint16_t>(p, job, b);
+    }
+    return;
+  }
   const Geom g = make_geom<RAGGED>(p, b);
   if (job.lowres) {
     if (job.dtype == 1) lowres_job<uint8_t, RAGGED>(p, job, g, b);
@@ -358,7 +398,8 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   bool full = false;
   if (a.image_input) { p.job[nj++] = PrepJob{a.src_input, a.image_input, io_white_level(a.input_white_level), a.input_dtype, 0}; full = true; }
   if (a.image_target) { p.job[nj++] = PrepJob{a.src_target, a.image_target, io_white_level(a.target_white_level), a.target_dtype, 0}; full = true; }
-  if (a.lowres_input) p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype, 1};
+  if (a.lowres_input)
+    p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype, a.yuv ? 2 : 1};
   if (nj == 0 || a.B == 0) return hipSuccess;
   p.ops = a.ops;
   p.N = a.N; p.Hs = a.Hs; p.Ws = a.Ws; p.B = a.B; p.H = a.H; p.W = a.W; p.n = a.n;
@@ -371,6 +412,10 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.n_samples = a.n_samples;
   p.px_stride = px_stored(a.pixel_format);
   p.px_b_first = px_b_first(a.pixel_format) ? 1 : 0;
+  if (a.yuv) {
+    p.yuv = *a.yuv;
+    p.yuv_to_rgb = a.yuv_to_rgb;
+  }
   const long long low_blocks = ((long long)a.n * a.n + 4 * kThreads - 1) / (4 * kThreads);
   const long long gx = full ? p.tiles : low_blocks;
   const dim3 grid((unsigned)gx, (unsigned)a.B, (unsigned)nj);

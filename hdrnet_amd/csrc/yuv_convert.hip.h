@@ -1,0 +1,107 @@
+// Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out.
+//
+// Every kernel that reads a surface -- hdrnet_yuv_to_rgb_f32 (apply_fwd_io_yuv.hip), the low-res gather
+// (sample_prep.hip) and the fused forward (apply_fwd_io.hip.h) -- converts a pixel with the ONE function below, and the
+// NV12 store of the fused forward encodes with the other two.  The kernels know nothing of colour standards or ranges:
+// they apply 12 floats (hdrnet_amd/yuv.py: yuv_coefficients) to the samples as stored.  The chains are written with
+// explicit fmaf / fmed3 so that no instantiation contracts them differently: the fused paths are held bit for bit
+// against hdrnet_yuv_to_rgb_f32 followed by the RGB forward.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+namespace hdrnet_amd {
+
+// One plane pair of a batch: bytes per row, bytes between images (hdrnet_amd_yuv.h).  Padding beyond a row's samples is
+// never read and never written.
+struct YuvSurface {
+  const void* y;
+  const void* uv;
+  int pitch_y, pitch_uv;
+  long long image_y, image_uv;
+};
+
+typedef __attribute__((address_space(4))) const float yuv_cfloat;  // the 12 constants: wave-uniform, s_load
+
+// m = [row 0: m00 m01 m02][row 1][row 2][bias0 bias1 bias2]
+struct YuvMatrix {
+  float m[9], bias[3];
+};
+
+__device__ __forceinline__ YuvMatrix yuv_load_matrix(const float* coef) {
+  yuv_cfloat* c = (yuv_cfloat*)coef;
+  YuvMatrix k;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) k.m[i] = c[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) k.bias[i] = c[9 + i];
+  return k;
+}
+
+// c_i = fmed3(fmaf(m_i2, V, fmaf(m_i1, U, fmaf(m_i0, Y, bias_i))), 0, 1) on the raw stored samples as floats.
+__device__ __forceinline__ void yuv_to_rgb_px(const YuvMatrix& k, float Y, float U, float V, float* __restrict__ rgb) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float t = __builtin_fmaf(k.m[3 * i + 2], V, __builtin_fmaf(k.m[3 * i + 1], U, __builtin_fmaf(k.m[3 * i], Y, k.bias[i])));
+    rgb[i] = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
+  }
+}
+
+// A lane's 4 pixels x .. x + 3 of image row `row` (x % 4 == 0): one dword of Y and one of UV for uint8 samples, two of
+// each for uint16 -- the chroma pairs (x >> 1) and (x >> 1) + 1 of chroma row (row >> 1) start at the same sample offset x
+// of their row as the luma does in its own.  rgb[3 q + c]: pixel q, channel c (R, G, B).  Chroma is replicated.
+template <typename TI>
+__device__ __forceinline__ void yuv_load_quad(const YuvSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                              float* __restrict__ rgb) {
+  static_assert(sizeof(TI) == 1 || sizeof(TI) == 2, "uint8 or uint16 samples");
+  const char* yp = static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y + (size_t)x * sizeof(TI);
+  const char* cp = static_cast<const char*>(s.uv) + (long long)b * s.image_uv + (long long)(row >> 1) * s.pitch_uv + (size_t)x * sizeof(TI);
+  float Y[4], U[2], V[2];
+  if constexpr (sizeof(TI) == 1) {
+    const uint32_t wy = *reinterpret_cast<const uint32_t*>(yp);
+    const uint32_t wc = *reinterpret_cast<const uint32_t*>(cp);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Y[q] = (float)((wy >> (8 * q)) & 0xffu);
+    U[0] = (float)(wc & 0xffu); V[0] = (float)((wc >> 8) & 0xffu);
+    U[1] = (float)((wc >> 16) & 0xffu); V[1] = (float)(wc >> 24);
+  } else {
+    // (two dwords each: the planes promise 4-byte alignment, not 8)
+    const uint2 wy = make_uint2(reinterpret_cast<const uint32_t*>(yp)[0], reinterpret_cast<const uint32_t*>(yp)[1]);
+    const uint2 wc = make_uint2(reinterpret_cast<const uint32_t*>(cp)[0], reinterpret_cast<const uint32_t*>(cp)[1]);
+    Y[0] = (float)(wy.x & 0xffffu); Y[1] = (float)(wy.x >> 16);
+    Y[2] = (float)(wy.y & 0xffffu); Y[3] = (float)(wy.y >> 16);
+    U[0] = (float)(wc.x & 0xffffu); V[0] = (float)(wc.x >> 16);
+    U[1] = (float)(wc.y & 0xffffu); V[1] = (float)(wc.y >> 16);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) yuv_to_rgb_px(k, Y[q], U[q >> 1], V[q >> 1], rgb + 3 * q);
+}
+
+// One pixel (row, x) of a surface, any x: scalar sample loads (the low-res gather).
+template <typename TI>
+__device__ __forceinline__ void yuv_load_px(const YuvSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                            float* __restrict__ rgb) {
+  const TI* yp = reinterpret_cast<const TI*>(static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y);
+  const TI* cp = reinterpret_cast<const TI*>(static_cast<const char*>(s.uv) + (long long)b * s.image_uv +
+                                             (long long)(row >> 1) * s.pitch_uv);
+  const int xc = (x >> 1) * 2;
+  yuv_to_rgb_px(k, (float)yp[x], (float)cp[xc], (float)cp[xc + 1], rgb);
+}
+
+// NV12 output (uint8 code values; the + 0.5 of the rounding is in the bias of from_rgb).  c: R, G, B already clipped to
+// [0, 1].  Luma per pixel; the LINEAR part of chroma row i per pixel, summed over the 2 x 2 block by the caller --
+// horizontal pair first, even row then odd row -- and finished by yuv_chroma_code (x 0.25, + bias, clamp).
+__device__ __forceinline__ uint32_t yuv_luma_code(const YuvMatrix& k, const float* c) {
+  const float t = __builtin_fmaf(k.m[2], c[2], __builtin_fmaf(k.m[1], c[1], __builtin_fmaf(k.m[0], c[0], k.bias[0])));
+  return (uint32_t)__builtin_amdgcn_fmed3f(t, 0.0f, 255.0f);
+}
+__device__ __forceinline__ float yuv_chroma_linear(const YuvMatrix& k, int i, const float* c) {
+  return __builtin_fmaf(k.m[3 * i + 2], c[2], __builtin_fmaf(k.m[3 * i + 1], c[1], k.m[3 * i] * c[0]));
+}
+__device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum4) {
+  return (uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, 255.0f);
+}
+
+}  // namespace hdrnet_amd

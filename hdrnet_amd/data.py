@@ -34,7 +34,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["lowres_input", "draw_ops", "check_ops", "prepare_batch", "DeviceDataset", "pack_images",
+__all__ = ["lowres_input", "lowres_input_yuv", "draw_ops", "check_ops", "prepare_batch", "DeviceDataset", "pack_images",
            "prepare_batch_ragged", "RaggedDeviceDataset"]
 
 _DTYPE_CODE = {torch.float32: 0, torch.uint8: 1, torch.uint16: 2}
@@ -116,6 +116,35 @@ def _lowres_input_px(frames, n: int, white_level, out, pixel_format: str) -> tor
         rc = _lib.load().hdrnet_lowres_input_px(frames.data_ptr(), _DTYPE_CODE[frames.dtype], float(white_level), B, H, W,
                                                 out.data_ptr(), n, _lib.PIXEL_FORMATS[pixel_format],
                                                 _stream(frames.device))
+    _lib.check(rc, "LowresInput")
+    return out
+
+
+def lowres_input_yuv(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, net_input_size: int = 256,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``lowres_input`` of a semi-planar YUV 4:2:0 surface (``hdrnet_lowres_input_yuv``, include/hdrnet_amd_yuv.h): ``y``
+    ``[B, H, W]``, ``uv`` ``[B, H / 2, W]`` (interleaved U, V), uint8 (NV12) or uint16 (P010 / P016), possibly pitched;
+    ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients`` on the device.  The same source pixel per output sample as
+    ``lowres_input``, its chroma from ``(y >> 1, x >> 1)``: the bits of ``lowres_input(hdrnet_ops.yuv_to_rgb(y, uv,
+    to_rgb))`` without the float32 frame.  One launch on the current stream; capturable."""
+    from . import hdrnet_ops
+    what = "lowres_input_yuv"
+    y, uv, B, H, W, surf = hdrnet_ops._yuv_surface(y, uv, what)
+    to_rgb = hdrnet_ops._yuv_constants("to_rgb", to_rgb, what)
+    n = int(net_input_size)
+    if n <= 0:
+        raise ValueError(f"{what}: net_input_size must be positive, got {net_input_size}")
+    for nm, t in (("y", y), ("uv", uv), ("to_rgb", to_rgb)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{nm} is on {t.device}: sample preparation runs on an MI355X (HIP) device only")
+    k = to_rgb.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, n, n, 3), dtype=torch.float32, device=y.device)
+    else:
+        _check_out("lowres_input", out, (B, n, n, 3), y.device)
+    with torch.cuda.device(y.device):
+        rc = _lib.load().hdrnet_lowres_input_yuv(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(), n,
+                                                 _stream(y.device))
     _lib.check(rc, "LowresInput")
     return out
 

@@ -1236,6 +1236,174 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     return (out, gout) if return_guide else out
 
 
+# ---- semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h) ------------------------------------------------------------
+_YUV_SAMPLE = {torch.uint8: 1, torch.uint16: 2}
+
+
+def _yuv_surface(y, uv, what: str, names=("y", "uv")):
+    """The rules of a surface, on the host: ``y`` ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (interleaved U, V; or
+    ``[B, H / 2, W / 2, 2]``) of one dtype, uint8 or uint16, last-dimension stride 1, row stride >= W samples.  Returns
+    ``(y, uv, B, H, W, (sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv))``, pitches in bytes."""
+    ny, nuv = names
+    for nm, t in ((ny, y), (nuv, uv)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {nm} must be a torch.Tensor, got {type(t).__name__}")
+    if y.dim() != 3:
+        raise ValueError(f"{what}: {ny} should be [B, H, W], got {tuple(y.shape)}")
+    B, H, W = y.shape
+    if uv.dim() == 4 and uv.shape[3] == 2 and uv.stride(3) == 1 and uv.stride(2) == 2:
+        uv = uv.as_strided((uv.shape[0], uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))
+    if y.dtype not in _YUV_SAMPLE or uv.dtype != y.dtype:
+        raise TypeError(f"{what}: {ny} and {nuv} must both be uint8 (NV12) or uint16 (P010 / P016), got {y.dtype}, {uv.dtype}")
+    if H % 2 != 0:
+        raise ValueError(f"{what}: H must be even (a chroma row serves two image rows), got H = {H}")
+    if W % 4 != 0:
+        raise ValueError(f"{what}: W % 4 != 0 (W = {W})")
+    if uv.dim() != 3 or tuple(uv.shape) != (B, H // 2, W):
+        raise ValueError(f"{what}: {nuv} should be [B, H / 2, W] = {[B, H // 2, W]} (interleaved U, V), got {list(uv.shape)}")
+    size = y.element_size()
+    for nm, t in ((ny, y), (nuv, uv)):
+        if B * H * W and (t.stride(2) != 1 or t.stride(1) < W or (t.stride(1) * size) % 4 or (t.stride(0) * size) % 4):
+            raise ValueError(f"{what}: {nm} must have last-dimension stride 1, a row stride >= W samples and pitches that are "
+                             f"multiples of 4 bytes, got strides {tuple(t.stride())}")
+    return y, uv, B, H, W, (_YUV_SAMPLE[y.dtype], y.stride(1) * size, uv.stride(1) * size, y.stride(0) * size,
+                            uv.stride(0) * size)
+
+
+def _yuv_constants(name: str, t, what: str) -> torch.Tensor:
+    _require_f32(name, t)
+    if t.numel() != 12:
+        raise ValueError(f"{what}: {name} should hold 12 floats (yuv.yuv_coefficients), got {tuple(t.shape)}")
+    return t
+
+
+def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor) -> torch.Tensor:
+    """A semi-planar YUV 4:2:0 surface -> float32 ``[B, H, W, 3]`` RGB in [0, 1] (``hdrnet_yuv_to_rgb_f32``): ``y``
+    ``[B, H, W]``, ``uv`` ``[B, H / 2, W]`` (interleaved), uint8 (NV12) or uint16 (P010 / P016); ``to_rgb`` the 12 floats of
+    ``yuv.yuv_coefficients`` on the device.  Chroma is replicated over its 2 x 2 block; the result is clamped.  Planes may
+    be pitched (row stride > W); padding is not read.  The yardstick of ``bilateral_slice_apply_io_yuv``.  No autograd."""
+    what = "yuv_to_rgb"
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    for nm, t in (("y", y), ("uv", uv), ("to_rgb", to_rgb)):
+        _require_gpu(nm, t)
+    dev = y.device
+    k = to_rgb.detach().contiguous()
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().hdrnet_yuv_to_rgb_f32(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
+                                               _stream(dev))
+    _lib.check(rc, "YuvToRgb")
+    return out
+
+
+def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
+                                 guide: Optional[torch.Tensor] = None,
+                                 guide_conv1: Optional[torch.Tensor] = None,
+                                 guide_conv2: Optional[torch.Tensor] = None,
+                                 guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
+                                 return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
+                                 curves_prepared: Optional[torch.Tensor] = None,
+                                 out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                                 from_rgb: Optional[torch.Tensor] = None, out_planes=None):
+    """``bilateral_slice_apply_io`` for a semi-planar YUV 4:2:0 surface in (include/hdrnet_amd_yuv.h): ``y`` ``[B, H, W]``,
+    ``uv`` ``[B, H / 2, W]``, uint8 (NV12) or uint16 (P010 / P016), converted in the kernel's load by ``to_rgb`` (12
+    floats, ``yuv.yuv_coefficients``) -- exactly ``bilateral_slice_apply_io(grid, yuv_to_rgb(y, uv, to_rgb), ...)`` on
+    the float32 frame, bit for bit, without that frame.  The guide arguments are those of ``bilateral_slice_apply_io``.
+
+    ``out="rgb"``: ``[B, H, W, 3]`` RGB, ``out_dtype`` float32 (default) or uint8 ``= (uint8)(255 * clip(., 0, 1))``.
+    ``out="nv12"``: an NV12 uint8 surface, returned as ``(y_out [B, H, W], uv_out [B, H / 2, W])``, encoded by
+    ``from_rgb`` (12 floats): Y per pixel, U and V from the mean of each 2 x 2 block, truncated.  ``out_planes``: a
+    ``(y_out, uv_out)`` pair to write into (pitched planes are fine; padding is not written).  Planes of the input may be
+    pitched too.  ``return_guide`` appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd."""
+    what = "bilateral_slice_apply_io_yuv"
+    if out not in ("rgb", "nv12"):
+        raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12')")
+    if out == "rgb":
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"{what}: out_dtype must be float32 or uint8, got {out_dtype}")
+        if from_rgb is not None or out_planes is not None:
+            raise ValueError(f"{what}: from_rgb / out_planes belong to out='nv12'")
+    else:
+        if out_dtype not in (None, torch.uint8):
+            raise TypeError(f"{what}: an NV12 output is uint8, got out_dtype = {out_dtype}")
+        if from_rgb is None:
+            raise ValueError(f"{what}: out='nv12' needs from_rgb (yuv.yuv_coefficients)")
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    _require_f32("grid", grid)
+    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
+        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
+                         f"{tuple(grid.shape)}")
+    GH, GW, GD = grid.shape[1:4]
+    n_given = sum(x is not None for x in (guide, guide_curves)) + int(guide_conv1 is not None or guide_conv2 is not None)
+    if n_given != 1 or (guide_conv1 is None) != (guide_conv2 is None):
+        raise ValueError("give exactly one of guide, (guide_conv1, guide_conv2), guide_curves")
+    if return_guide and guide is not None:
+        raise ValueError("return_guide needs a guide computed by the kernel (guide network or guide_curves)")
+    tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb)]
+    oy = ouv = None
+    if out == "nv12":
+        from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+        tensors.append(("from_rgb", from_rgb))
+        if out_planes is not None:
+            oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
+            if (oB, oH, oW) != (B, H, W) or oy.dtype != torch.uint8:
+                raise ValueError(f"{what}: out_planes should be a uint8 surface of {[B, H, W]}, got {oy.dtype} {[oB, oH, oW]}")
+            tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
+    if guide_curves is not None:
+        if len(guide_curves) != 4:
+            raise ValueError("guide_curves should be (ccm, shifts, slopes, mix)")
+        ccm, shifts, slopes, mix = guide_curves
+        npts = shifts.shape[0] if shifts.dim() == 2 else -1
+        for nm, t, shape in (("ccm", ccm, (3, 4)), ("shifts", shifts, (npts, 3)), ("slopes", slopes, (npts, 3)),
+                             ("mix", mix, (4,))):
+            _require_f32(f"guide_curves.{nm}", t)
+            if tuple(t.shape) != shape or npts <= 0:
+                raise ValueError(f"guide_curves.{nm} should be {list(shape)}, got {list(t.shape)}")
+            tensors.append((f"guide_curves.{nm}", t))
+    else:
+        guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), 3)
+    for nm, t in tensors:
+        _require_gpu(nm, t)
+    dev = y.device
+    lib = _lib.load()
+    grid = grid.detach().contiguous()
+    k_in = to_rgb.detach().contiguous()
+    if out == "nv12":
+        if oy is None:
+            oy = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+            ouv = torch.empty((B, H // 2, W), dtype=torch.uint8, device=dev)
+            osurf = (1, W, W, H * W, (H // 2) * W)
+        k_out = from_rgb.detach().contiguous()
+        output = (_lib.YUV_OUT["nv12"], oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr())
+        result = (oy, ouv)
+    else:
+        frame = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
+        output = (_lib.YUV_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], frame.data_ptr(), None, 0, 0, 0, 0, None)
+        result = frame
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    with torch.cuda.device(dev):
+        if guide_curves is not None:
+            if curves_prepared is not None:
+                _require_f32("curves_prepared", curves_prepared)
+                _require_gpu("curves_prepared", curves_prepared)
+                if not curves_prepared.is_contiguous() or curves_prepared.numel() * 4 < lib.hdrnet_curves_guide_prepared_bytes(3):
+                    raise ValueError("curves_prepared should be the tensor curves_guide_prepare returned")
+            ccm, shifts, slopes, mix = (t.detach().contiguous() for t in guide_curves)
+            rc = lib.hdrnet_bilateral_slice_apply_io_curves_yuv(
+                grid.data_ptr(), *head, ccm.data_ptr(), shifts.data_ptr(), slopes.data_ptr(), mix.data_ptr(), npts,
+                _ptr(curves_prepared), _ptr(gout), *output, _stream(dev))
+        else:
+            rc = lib.hdrnet_bilateral_slice_apply_io_yuv(
+                grid.data_ptr(), _ptr(guide), *head, _ptr(c1), _ptr(c2), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and guide is None), *output, _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOYuv")
+    return (result, gout) if return_guide else result
+
+
 def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002
                        white_level: Optional[float] = None) -> torch.Tensor:
     """``resize_bilinear(input / white_level, height, width)`` of a wire-format RGB frame in one pass: ``input``

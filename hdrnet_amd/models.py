@@ -624,6 +624,56 @@ class HDRNetCurves(nn.Module):
                 out_dtype=out_dtype, has_offset=True, pixel_format=pixel_format, **self._process_guide_args())
 
 
+    # ---- YUV surface in, frame or NV12 surface out ------------------------------------------------------------------------
+    def _yuv_constants(self, standard: str, full_range: bool, bits: int, device: torch.device):
+        """``(to_rgb, from_rgb)`` of ``yuv.yuv_coefficients`` on ``device``, cached per (standard, range, bits): a
+        captured graph holds pointers to them."""
+        from . import yuv
+        cache = self.__dict__.setdefault("_yuv_cache", {})
+        key = (standard, bool(full_range), int(bits), str(device))
+        if key not in cache:
+            to_rgb, from_rgb = yuv.yuv_coefficients(standard, full_range, bits)
+            cache[key] = (torch.from_numpy(to_rgb).to(device), torch.from_numpy(from_rgb).to(device))
+        return cache[key]
+
+    def process_yuv(self, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False,
+                    bits: Optional[int] = None, out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                    out_planes=None):
+        """``process`` for a semi-planar YUV 4:2:0 surface as a video decoder delivers it (include/hdrnet_amd_yuv.h): ``y``
+        ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (interleaved U, V) on the device, uint8 (NV12) or uint16 (P010 with
+        ``bits=10``, P016 with ``bits=16``; ``bits=None`` is 8 for uint8 and 16 for uint16).  ``process`` step for step --
+        ``data.lowres_input_yuv`` -> the coefficient network -> ``hdrnet_ops.bilateral_slice_apply_io_yuv`` -- with the
+        conversion (``standard`` ``"bt601"`` / ``"bt709"`` / ``"bt2020"``, ``full_range``) in the kernels' loads: no RGB
+        frame exists.  ``out="rgb"``: ``[B, H, W, 3]`` float32 (default) or uint8; ``out="nv12"``: an NV12 uint8 surface
+        ``(y_out, uv_out)`` of the same standard and range for an encoder (``out_planes``: the pair to write into).  Planes
+        may be pitched.  Chroma is replicated on the way in and the 2 x 2 mean on the way out.  Capturable."""
+        from . import data, hdrnet_ops, yuv
+        what = f"{type(self).__name__}.process_yuv"
+        if self._process_dtypes == (torch.float32,):
+            raise ValueError(f"{what}: the pyramid model's resize and up-add kernels read RGB frames only: there is no YUV "
+                             "surface path (the single-level models' process_yuv takes NV12 / P010 / P016)")
+        if standard not in yuv.STANDARDS:
+            raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
+        if out not in ("rgb", "nv12"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12')")
+        y, uv, B, H, W, _ = hdrnet_ops._yuv_surface(y, uv, what)
+        if bits is None:
+            bits = 8 if y.dtype == torch.uint8 else 16
+        if bits not in yuv.BITS or (bits == 8) != (y.dtype == torch.uint8):
+            raise ValueError(f"{what}: bits = {bits!r} does not fit {y.dtype} planes (uint8: 8; uint16: 10 or 16)")
+        if self.training:
+            raise RuntimeError("process_yuv() is inference: call eval() first")
+        hdrnet_ops._require_gpu("y", y)
+        with torch.no_grad():
+            to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, y.device)
+            lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"])
+            coeffs = self.coefficients(lowres)
+            gs = coeffs.shape
+            return hdrnet_ops.bilateral_slice_apply_io_yuv(
+                coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), y, uv, to_rgb, out=out, out_dtype=out_dtype,
+                from_rgb=from_rgb if out == "nv12" else None, out_planes=out_planes, **self._process_guide_args())
+
+
 class HDRNetPointwiseNNGuide(HDRNetCurves):
     """``hdrnet/models.py:199-210``.  The guide network is FUSED into the slice-apply kernel
     (SURVEY.md section 8f row 2): the 16-channel full-resolution intermediate is never

@@ -106,6 +106,35 @@ class FrameInference(GraphedInference):
                          check_parameters=check_parameters)
 
 
+class _ProcessYuv(torch.nn.Module):
+    """``model.process_yuv`` as the module a ``GraphedInference`` captures."""
+
+    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype):
+        super().__init__()
+        self.model, self.standard, self.full_range, self.bits = model, standard, full_range, bits
+        self.out, self.out_dtype = out, out_dtype
+
+    def forward(self, y: torch.Tensor, uv: torch.Tensor):
+        return self.model.process_yuv(y, uv, standard=self.standard, full_range=self.full_range, bits=self.bits,
+                                      out=self.out, out_dtype=self.out_dtype)
+
+
+class YuvFrameInference(GraphedInference):
+    """A decoder surface in, a frame or an encoder surface out, from a hipGraph: a ``GraphedInference`` whose captured
+    callable is ``model.process_yuv`` (low-res gather, coefficient network, fused guide + slice-apply, the YUV conversions
+    in the kernels' loads and stores).  Two inputs, the planes ``y`` ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (uint8 NV12
+    or uint16 P010 / P016), copied into static planes unless they ARE the static planes (``static_inputs``: a decoder can
+    write into them in place).  ``out="nv12"``: the static output is the ``(y_out, uv_out)`` pair of an NV12 uint8
+    surface; ``out="rgb"``: a ``[B, H, W, 3]`` frame of ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
+    ``process_yuv``.  Beside ``FrameInference``, which keeps its signature."""
+
+    def __init__(self, model: torch.nn.Module, y_like: torch.Tensor, uv_like: torch.Tensor, standard: str = "bt709",
+                 full_range: bool = False, bits=None, out: str = "nv12", out_dtype=None, warmup: int = 3,
+                 check_parameters: bool = True):
+        super().__init__(_ProcessYuv(model.eval(), standard, full_range, bits, out, out_dtype), [y_like, uv_like],
+                         warmup=warmup, check_parameters=check_parameters)
+
+
 class FramePipeline:
     """Independent frames round-robin over ``depth`` HIP streams.
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -16,7 +16,10 @@ frame out at 4K and 1080p, u8 -> u8 and u16 / 32767 -> f32: FrameInference over 
 before it (frame.float() / wl -> FrameInference over process -> quantise), alternating in one process; `pixel_formats` =
 HDRNetPointwiseNNGuide on BGRA u8 frames at 4K and 1080p: a hipGraph of process(..., pixel_format="bgra") against a hipGraph
 of the chain a caller wrote before it (index-select to RGB -> process -> flip + cat alpha), alternating, and beside it the
-fused kernel alone, BGRA u8 -> u8 against RGB u8 -> u8.  --tools loads the tools build and adds the round-1
+fused kernel alone, BGRA u8 -> u8 against RGB u8 -> u8; `yuv` = HDRNetPointwiseNNGuide on NV12 surfaces at 4K and 1080p: a
+hipGraph of process_yuv(..., out="nv12") against a hipGraph of the stock chain (planes -> repeat_interleave -> affine + clamp
+-> process -> affine -> 2 x 2 mean -> quantise), alternating, and beside it the fused kernel alone, NV12 -> NV12 and NV12 ->
+u8 RGB against RGB u8 -> u8.  --tools loads the tools build and adds the round-1
 kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -91,6 +94,8 @@ def main():
         return pyramid_io(dev, args)
     if args.workload == "pixel_formats":
         return pixel_formats(lib, dev, args)
+    if args.workload == "yuv":
+        return yuv_surfaces(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -615,6 +620,130 @@ def pixel_formats(lib, dev, args):
         del sets
     if args.json:
         json.dump(dict(workload="pixel_formats", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _YuvStockChain(torch.nn.Module):
+    """What a caller with a decoded NV12 surface writes around process(): slice the chroma, repeat_interleave it, three
+    affine ops and a clamp into a float32 RGB frame, process, and for the encoder the mirror image -- an affine to Y, U, V,
+    the 2 x 2 mean of the chroma, quantise, interleave."""
+
+    def __init__(self, model, to_rgb, from_rgb):
+        super().__init__()
+        self.model = model
+        self.register_buffer("m_in", to_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)   # [Y U V] @ m_in -> RGB
+        self.register_buffer("b_in", to_rgb[9:].contiguous(), persistent=False)
+        self.register_buffer("m_out", from_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)
+        self.register_buffer("b_out", from_rgb[9:].contiguous(), persistent=False)
+
+    def forward(self, y, uv):
+        B, H, W = y.shape
+        c = uv.view(B, H // 2, W // 2, 2).repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+        yuv = torch.cat([y.unsqueeze(-1), c], -1).float()
+        rgb = (yuv @ self.m_in + self.b_in).clamp_(0.0, 1.0)
+        out = self.model.process(rgb).clamp_(0.0, 1.0)
+        enc = out @ self.m_out
+        yq = (enc[..., 0] + self.b_out[0]).clamp_(0.0, 255.0).to(torch.uint8)
+        cm = enc[..., 1:].reshape(B, H // 2, 2, W // 2, 2, 2).mean(dim=(2, 4)) + self.b_out[1:]
+        return yq, cm.clamp_(0.0, 255.0).to(torch.uint8).reshape(B, H // 2, W)
+
+
+def yuv_surfaces(lib, dev, args):
+    """NV12 uint8 surfaces in, NV12 uint8 surfaces out through HDRNetPointwiseNNGuide at 4K and 1080p: one hipGraph of
+    process_yuv(y, uv, out="nv12") -- the conversions in the kernels' loads and stores -- against one hipGraph of
+    _YuvStockChain.  Both are warmed, then run ALTERNATING three times each in one process; reported: the mean of the three
+    and their range (device events around `steps` replays).  Beside it, without a bar: the fused guide-network kernel alone,
+    NV12 -> NV12 (3 bytes per pixel) and NV12 -> u8 RGB (4.5) against RGB u8 -> u8 (6), over buffer sets that together exceed
+    the Infinity Cache, alternating the same way."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import GraphedInference, YuvFrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    to_rgb, from_rgb = (torch.from_numpy(a).to(dev) for a in yuv.yuv_coefficients("bt709", False, 8))
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def u8(*shape):
+        return torch.randint(0, 256, shape, device=dev, dtype=torch.int32, generator=gen).to(torch.uint8)
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        surfaces = [(u8(1, H, W), u8(1, H // 2, W)) for _ in range(3)]
+        new = YuvFrameInference(m, *surfaces[0], out="nv12")
+        base = GraphedInference(_YuvStockChain(m, to_rgb, from_rgb), list(surfaces[0]))
+        (ny, nuv), (by, buv) = new(*surfaces[1]), base(*surfaces[1])
+        dy = (ny.int() - by.int()).abs()
+        duv = (nuv.int() - buv.int()).abs()
+        # (the chain rounds its affine ops in another order: it is a timing opponent, not the reference of the tests)
+        print(f"{H}x{W}: fused vs chain, codes that differ: Y {int((dy > 0).sum())} (max {int(dy.max())}), "
+              f"UV {int((duv > 0).sum())} (max {int(duv.max())}) of {dy.numel()} + {duv.numel()}")
+        assert int(dy.max()) <= 1 and int(duv.max()) <= 1, "the two paths encode the same surface to within a code"
+        b, n = alternate(lambda k: base(*surfaces[k % 3]), lambda k: new(*surfaces[k % 3]))
+        mb, mn = statistics.mean(b), statistics.mean(n)
+        spread = max(b) - min(b)
+        name = f"{H}x{W} model, nv12 -> nv12"
+        rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                         us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                         faster_beyond_chain_spread=bool(mb - mn > spread)))
+        print(f"{name:40s} stock chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_yuv {mn:8.2f} us "
+              f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+              f"faster by more than the chain's spread: {mb - mn > spread}")
+        del new, base
+
+        # the kernel alone: the same grid and guide network over three frame layouts
+        GH, GW, GD = 16, 16, 8
+        nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 3)))
+        grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+        conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+        conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+        sets = [dict(rgb=u8(1, H, W, 3), y=u8(1, H, W), uv=u8(1, H // 2, W),
+                     out3=torch.empty((1, H, W, 3), device=dev, dtype=torch.uint8),
+                     oy=torch.empty((1, H, W), device=dev, dtype=torch.uint8),
+                     ouv=torch.empty((1, H // 2, W), device=dev, dtype=torch.uint8)) for _ in range(nsets)]
+
+        def check(rc):
+            if rc:
+                raise RuntimeError(lib.hdrnet_last_error().decode())
+
+        def rgb_kernel(k):
+            t = sets[k % nsets]
+            check(lib.hdrnet_bilateral_slice_apply_io_ex(grid.data_ptr(), None, t["rgb"].data_ptr(), t["out3"].data_ptr(), 1, H, W,
+                                                         GH, GW, GD, 3, 3, 1, 1, 255.0, 1, conv1.data_ptr(), conv2.data_ptr(), 16,
+                                                         None, _lib.GUIDE_SIGMOID_FAST, stream))
+
+        def yuv_kernel(k, nv12_out):
+            t = sets[k % nsets]
+            out = ((2, t["oy"].data_ptr(), t["ouv"].data_ptr(), W, W, H * W, H // 2 * W, from_rgb.data_ptr()) if nv12_out
+                   else (1, t["out3"].data_ptr(), None, 0, 0, 0, 0, None))
+            check(lib.hdrnet_bilateral_slice_apply_io_yuv(grid.data_ptr(), None, t["y"].data_ptr(), t["uv"].data_ptr(), 1, W, W,
+                                                          H * W, H // 2 * W, 1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1,
+                                                          conv1.data_ptr(), conv2.data_ptr(), 16, None,
+                                                          _lib.GUIDE_SIGMOID_FAST, *out, stream))
+
+        r, q, v = alternate(rgb_kernel, lambda k: yuv_kernel(k, True), lambda k: yuv_kernel(k, False))
+        name = f"{H}x{W} kernel, +nnguide"
+        row = dict(op=name)
+        text = []
+        for key, label, t in (("rgb_u8_u8", "rgb u8 -> u8 (6 B/px)", r), ("nv12_nv12", "nv12 -> nv12 (3 B/px)", q),
+                              ("nv12_rgb_u8", "nv12 -> u8 rgb (4.5 B/px)", v)):
+            row.update({f"us_{key}": round(statistics.mean(t), 2), f"us_{key}_min": round(min(t), 2),
+                        f"us_{key}_max": round(max(t), 2)})
+            text.append(f"{label} {statistics.mean(t):8.2f} us ({min(t):8.2f} .. {max(t):8.2f})")
+        rows.append(row)
+        print(f"{name:28s} " + "   ".join(text))
+        del sets
+    if args.json:
+        json.dump(dict(workload="yuv", rows=rows), open(args.json, "w"), indent=1)
 
 
 def metrics_monitor(dev, args):
