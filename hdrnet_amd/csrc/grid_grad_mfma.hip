@@ -937,6 +937,9 @@ struct GGPlan {
 // clamped grid rows).  slots <= 0: the smallest rg any launch may pick -- the workspace bound.
 constexpr int kMinRg = 4, kMaxRounds = 6;
 constexpr int kMaxOcc = 8;  // workgroups per CU a stage-1 kernel can have (8 waves per SIMD, 4-wave workgroups)
+#ifdef HDRNET_TOOLS_BUILD
+constexpr int kKnobForceRg = 3;  // hdrnet_tools_set_knob (include/hdrnet_amd_tools.h)
+#endif
 
 bool gg_plan(int B, int H, int W, int GH, int GW, int GD, int C, long long slots, GGPlan* pl) {
   if (GD > 16 || C > 32 || C < 1) return false;
@@ -968,7 +971,12 @@ bool gg_plan(int B, int H, int W, int GH, int GW, int GD, int C, long long slots
     if (best < 0.0) rg = cell;  // fewer tasks than slots even at the largest rg a cell allows
   }
 #ifdef HDRNET_TOOLS_BUILD
-  if (const char* e = getenv("HDRNET_GG_RG")) rg = atoi(e) < cell ? atoi(e) : cell;  // experiments only
+  // tools knob 3: rows per task, forced (tests/test_gpu_grad_plans.py runs every plan the fit above can return; timing
+  // experiments).  1 .. cell only -- a task's rows span at most 3 clamped grid rows; anything else refuses the pass.
+  if (const int forced = tools_knob(kKnobForceRg)) {
+    if (forced < 1 || forced > cell) return false;
+    rg = forced;
+  }
 #endif
   if (rg < 1) rg = 1;
   pl->rg = rg;
@@ -990,7 +998,13 @@ bool gg_ws_bound(int B, int H, int W, int GH, int GW, int GD, int C, size_t* byt
   struct Key {
     int B, H, W, GH, GW, GD, C;
     long long cus;
+#ifdef HDRNET_TOOLS_BUILD
+    int forced_rg;  // tools knob 3: the bound of a forced plan is that plan's size
+#endif
     bool operator==(const Key& o) const {
+#ifdef HDRNET_TOOLS_BUILD
+      if (forced_rg != o.forced_rg) return false;
+#endif
       return B == o.B && H == o.H && W == o.W && GH == o.GH && GW == o.GW && GD == o.GD && C == o.C && cus == o.cus;
     }
   };
@@ -998,7 +1012,11 @@ bool gg_ws_bound(int B, int H, int W, int GH, int GW, int GD, int C, size_t* byt
   thread_local size_t last_bytes = 0;
   thread_local bool last_ok = false, have = false;
   const long long cus = rows::num_cus();
+#ifdef HDRNET_TOOLS_BUILD
+  const Key k{B, H, W, GH, GW, GD, C, cus, tools_knob(kKnobForceRg)};
+#else
   const Key k{B, H, W, GH, GW, GD, C, cus};
+#endif
   if (!have || !(last == k)) {
     size_t worst = 0;
     bool ok = true;

@@ -23,7 +23,7 @@
  *             pass with per-chunk phase stamps of wave 0 ([task][16][5] clock64 values in the buffer
  *             given to hdrnet_tools_set_trace; tools/exp/r02_exp29.py)
  *       11    (dgrid == NULL) the round-1 per-pixel VJP kernel (apply_vjp_rows) instead of apply_vjp_seg
- *       HDRNET_GG_RG (environment): rows per workgroup task
+ *       knob 3 (hdrnet_tools_set_knob): rows per workgroup task of the fast gradient pass, forced
  *   - hdrnet_tools_set_trace: device buffer for the phase trace of gradient variant 9 and the coefficient network's
  *     per-workgroup timeline (tools/coeff_trace.py).
  *
@@ -41,8 +41,17 @@ extern "C" {
 /* device_buf: sized by the tracing tool (tools/coeff_trace.py, tools/exp/r02_exp29.py); NULL disables. */
 void hdrnet_tools_set_trace(void* device_buf);
 
-/* Experiment knobs read at launch (knobs 0-2 and 7 drove the product kernel's removed flavours):
- *   5  hdrnet_bilateral_slice_apply_io, uint8 input + guide network: 1 = the hidden layer as bf16-split 4x4x4 matrix
+/* Experiment knobs read at launch (knobs 0, 2 and 7 drove the product kernel's removed flavours):
+ *   1  gradient pass (grid_grad_mfma.hip): bytes of unused dynamic LDS per stage-1 workgroup -- fewer resident workgroups
+ *      per CU, the row groups re-fitted to them (tools/bwd_ab.py)
+ *   3  gradient pass: rg, the rows per workgroup task, FORCED instead of fitted to the device (gg_plan); 0 = fitted.
+ *      Accepted: 1 .. cell, cell = max(H / GH, 1) -- a task's rows may span at most three clamped grid rows.  With any
+ *      other value the pass refuses the shape: hdrnet_bilateral_slice{,_apply}_grad_workspace_bytes returns 0 and the
+ *      gradient entry points take their other kernels.  While it is set the workspace query answers with exactly the
+ *      forced plan's size, B * (GW + 1) * ceil(H / rg) tasks x (GD > 8 ? 2 : 1) x (C > 16 ? 2 : 1) tiles of
+ *      3 x 16 x 16 floats: query after setting it.  Process-wide, like every knob: set it back to 0.  The planner
+ *      itself returns min(cell, 4) .. cell; tests/test_gpu_grad_plans.py runs every such plan on small frames.
+ *   5 hdrnet_bilateral_slice_apply_io, uint8 input + guide network: 1 = the hidden layer as bf16-split 4x4x4 matrix
  *      instructions (apply_fwd_io.hip; rejected on time, kept for the record) */
 void hdrnet_tools_set_knob(int idx, int value);
 

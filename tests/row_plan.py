@@ -1,6 +1,7 @@
 """The row plan of the row-segment kernels, restated (hdrnet_amd/csrc/row_geom.h: make_row_plan, seg_fwd_geom,
 rows_fwd_geom, io_fwd_geom) for Cin = Cout = 3 with offset (C = 12): the GPU tests predict from it which kernel a shape
 reaches (tests/test_gpu_fused_fullsize.py), and tests/test_row_geom.py holds the header to it cell by cell."""
+import numpy as np
 
 
 def _rup(v, m):
@@ -178,3 +179,64 @@ def grad_kernels(B, H, W, GH, GW, GD, need_guide, need_input):
         return "apply_bwd_fused/mfma"
     pix = vjp_kernel(B, H, W, GW, GD, need_input)
     return pix + "+apply_grad_generic" if pix else "apply_grad_generic"
+
+
+# ---- the gradient pass's workspace and stage 2's view of the row groups (grid_grad_mfma.hip: gg_plan, gg_ws_bound,
+# gy_base_of, grid_grad_stage2), restated so that tests/test_grad_plan_host.py can hold the float arithmetic of the two
+# stages against each other on the CPU and tests/test_gpu_grad_plans.py can size a workspace for a plan it forces.
+GG_TILE_FLOATS = 3 * 16 * 16   # kTileFloats: a task's partial tile, [rel 3][k 16][c 16]
+GG_MAX_OCC = 8                 # kMaxOcc: workgroups per CU a stage-1 kernel can have
+GG_MIN_RG = 4                  # kMinRg
+
+
+def gg_cell(H, GH):
+    return max(H // GH, 1)
+
+
+def gg_rg_range(H, GH):
+    """The rows per task gg_plan can return: min(cell, 4) .. cell."""
+    cell = gg_cell(H, GH)
+    return range(min(cell, GG_MIN_RG), cell + 1)
+
+
+def gg_plan_bytes(B, H, GW, GD, C, rg):
+    """GGPlan::ws_bytes of the plan with `rg` rows per task: one tile per task, plane half and channel window."""
+    ntasks = B * (GW + 1) * -(-H // rg)
+    return ntasks * (2 if GD > 8 else 1) * (2 if C > 16 else 1) * GG_TILE_FLOATS * 4
+
+
+def gg_ws_bound(B, H, W, GH, GW, GD, C, cus=MI355X_CUS):
+    """gg_ws_bound: the largest plan over 1 .. 8 workgroups per CU of a `cus`-CU device; 0 where a plan refuses."""
+    worst = 0
+    for occ in range(1, GG_MAX_OCC + 1):
+        plan = gg_plan(B, H, W, GH, GW, GD, C, occ * cus)
+        if plan is None:
+            return 0
+        worst = max(worst, gg_plan_bytes(B, H, GW, GD, C, plan[0]))
+    return worst
+
+
+def gg_scale_y(H, GH):
+    """(float)GH / H, as both stages receive it."""
+    return np.float32(GH) / np.float32(H)
+
+
+def gg_gy0(y, scale_y):
+    """floor_to_int(mul_rn(y + 0.5f, scale_y) - 0.5f) of the rows `y` (an integer array), in float32."""
+    gyf = (np.asarray(y).astype(np.float32) + np.float32(0.5)) * scale_y
+    return np.floor(gyf - np.float32(0.5)).astype(np.int64)
+
+
+def gg_gy_base(y_first, scale_y, GH):
+    """gy_base_of: the first of the three clamped grid rows the tile of the task starting at row `y_first` holds."""
+    return np.clip(gg_gy0(y_first, scale_y), 0, GH - 1)
+
+
+def gg_stage2_window(gy, scale_y, rg, nyg):
+    """(yg_lo, yg_hi) of grid_grad_stage2 for the grid rows `gy`: the row groups it looks at.  C's int division
+    truncates toward zero, which matters for the negative numerators of gy < 2."""
+    gy = np.asarray(gy).astype(np.float32)
+    lo = np.floor((gy - np.float32(2.0)) / scale_y).astype(np.int64)
+    hi = np.ceil((gy + np.float32(2.5)) / scale_y).astype(np.int64)
+    trunc_div = lambda a: np.sign(a) * (np.abs(a) // rg)  # noqa: E731
+    return np.maximum(0, trunc_div(lo) - 1), np.minimum(nyg, trunc_div(hi) + 2)
