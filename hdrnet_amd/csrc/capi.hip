@@ -141,22 +141,56 @@ int check_guide_flags(unsigned flags) {
   return HDRNET_OK;
 }
 
+// ... and what the flags ask of the launch (`a`: ApplyArgs or ApplyIoArgs), once the pointers count.
 // HDRNET_GUIDE_RELU_PRESCALED: a guide NETWORK of three input channels whose arrays are 16-B aligned ([n][4] rows, s_load_dwordx4)
-int check_guide_prescaled(unsigned flags, int Cin, const float* conv1, const float* conv2) {
-  if (!(flags & HDRNET_GUIDE_RELU_PRESCALED)) return HDRNET_OK;
-  if (!conv1 || !conv2 || Cin != 3)
-    return fail(HDRNET_INVALID_ARGUMENT, "HDRNET_GUIDE_RELU_PRESCALED needs a guide network with Cin = 3 (Cin=%d)", Cin);
-  if (((uintptr_t)conv1 | (uintptr_t)conv2) & 15u)
-    return fail(HDRNET_INVALID_ARGUMENT, "HDRNET_GUIDE_RELU_PRESCALED needs 16-B aligned guide_conv1 / guide_conv2 "
-                                         "(the arrays hdrnet_guide_nn_prescale_f32 wrote)");
+template <class Args>
+int set_guide_flags(Args& a, unsigned flags, int Cin, const float* conv1, const float* conv2) {
+  if (flags & HDRNET_GUIDE_RELU_PRESCALED) {
+    if (!conv1 || !conv2 || Cin != 3)
+      return fail(HDRNET_INVALID_ARGUMENT, "HDRNET_GUIDE_RELU_PRESCALED needs a guide network with Cin = 3 (Cin=%d)", Cin);
+    if (((uintptr_t)conv1 | (uintptr_t)conv2) & 15u)
+      return fail(HDRNET_INVALID_ARGUMENT, "HDRNET_GUIDE_RELU_PRESCALED needs 16-B aligned guide_conv1 / guide_conv2 "
+                                           "(the arrays hdrnet_guide_nn_prescale_f32 wrote)");
+  }
+  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
+  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
   return HDRNET_OK;
 }
 
-// the wire formats of the ..._io entry points: 0 f32, 1 u8, 2 u16 in; 0 f32, 1 u8 out
+// The up-add entry points name their guide source before the no-op: a map or the network, never both, and a network whole.
+int check_upadd_values(int Hc, int Wc, const float* guide, const float* conv1, const float* conv2, int n_feats) {
+  if (Hc <= 0 || Wc <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad coarse extents (%d x %d)", Hc, Wc);
+  if ((guide != nullptr) == (conv1 != nullptr))
+    return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
+  if (conv1 && (!conv2 || n_feats <= 0 || n_feats > 4096))
+    return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
+  return HDRNET_OK;
+}
+
+// ---- The wire-format forwards (..._io_ex / _px, ..._io_curves_prepared / _px, ..._upadd_io_ex, ..._io_yuv, ..._io_curves_yuv)
+// fill one ApplyIoArgs from a pixel source, a guide source and a launch.  Each side checks values before the zero-size
+// no-op and pointers after it, as two functions: a frame's are check_frame_values / check_pixel_buffers, a YUV surface's
+// check_yuv_io_values / check_yuv_io_pointers; a guide map or network's check_guide_flags / check_guide_given /
+// set_io_guide_flags, the curves guide's check_curves_knots / set_curves_prepared; launch_io is the tail of all five.
+// `prefix`: "" for the entry points of include/hdrnet_amd.h, whose texts predate naming the function, else "<function>: ".
+
+// Pixel side, a frame: channel counts and the wire formats (0 f32, 1 u8, 2 u16 in; 0 f32, 1 u8 out)
 int check_io_format(int input_dtype, float input_white_level, int output_dtype) {
   if (input_dtype < 0 || input_dtype > 2 || output_dtype < 0 || output_dtype > 1)
     return fail(HDRNET_INVALID_ARGUMENT, "unknown dtype code (input %d, output %d)", input_dtype, output_dtype);
   if (!(input_white_level > 0.0f)) return fail(HDRNET_INVALID_ARGUMENT, "input_white_level must be positive");
+  return HDRNET_OK;
+}
+
+int check_frame_values(int Cin, int Cout, int input_dtype, float input_white_level, int output_dtype) {
+  if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
+  return check_io_format(input_dtype, input_white_level, output_dtype);
+}
+
+// the one integer frame in, float32 out that the pyramid's resize and the low-res gather read
+int check_input_dtype(const char* what, int dtype) {
+  if (dtype < 0 || dtype > 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", what, dtype);
   return HDRNET_OK;
 }
 
@@ -195,6 +229,111 @@ int check_pixel_buffers(const char* what, int pixel_format, int Cin, int Cout, i
                 mask == 15u ? "4-channel frames (RGBA / BGRA) must be 16-B aligned (one 16-byte access per lane)"
                             : "3-channel integer frames must be 4-B aligned");
   return HDRNET_OK;
+}
+
+// Pixel side, a semi-planar YUV 4:2:0 surface (include/hdrnet_amd_yuv.h).  The rules of one surface (`which`: "input" /
+// "output"), checked before any HIP call:
+int check_yuv_extents(const char* what, int B, int H, int W) {
+  if (B < 0 || H < 0 || W < 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: negative image extent (B=%d, H=%d, W=%d)", what, B, H, W);
+  if (H % 2 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: H %% 2 != 0 (H=%d): a chroma row serves two image rows", what, H);
+  if (W % 4 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: W %% 4 != 0 (W=%d): a lane owns 4 pixels", what, W);
+  if (B > 65535 || H > 65535 || (long long)W * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large (B, H <= 65535)", what);
+  return HDRNET_OK;
+}
+
+int check_yuv_surface(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvSurface& s, int B, int H,
+                      int W) {
+  if (sample_dtype != 1 && sample_dtype != 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
+                sample_dtype);
+  const long long row = (long long)W * sample_dtype;
+  if (s.pitch_y < row || s.pitch_uv < row)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a pitch of the %s surface is below the row's %lld bytes (pitch_y=%d, "
+                "pitch_uv=%d)", what, which, row, s.pitch_y, s.pitch_uv);
+  if ((s.pitch_y | s.pitch_uv) & 3)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitches of the %s surface must be multiples of 4 (pitch_y=%d, pitch_uv=%d)",
+                what, which, s.pitch_y, s.pitch_uv);
+  if (s.image_y < 0 || s.image_uv < 0 || ((s.image_y | s.image_uv) & 3))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4", what,
+                which);
+  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_uv < (long long)s.pitch_uv * (H / 2)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
+  return HDRNET_OK;
+}
+
+int check_yuv_pointers(const char* what, const char* which, const hdrnet_amd::YuvSurface& s, const float* coef) {
+  if (!s.y || !s.uv) return fail(HDRNET_INVALID_ARGUMENT, "%s: null plane of the %s surface", what, which);
+  if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
+  if (((uintptr_t)s.y | (uintptr_t)s.uv | (uintptr_t)coef) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the planes and constants of the %s surface must be 4-B aligned", what, which);
+  return HDRNET_OK;
+}
+
+// ... and of a fused forward's surfaces and output.  `io`: the call's arguments as given; io.out.y is `out` whatever the
+// output kind.
+int check_yuv_io_values(const char* what, const hdrnet_amd::YuvIo& io, int sample_dtype, int B, int H, int W, int Cin, int Cout,
+                        int has_offset) {
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
+  if (io.out_kind < HDRNET_YUV_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_OUT_NV12)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 NV12)", what, io.out_kind);
+  if (Cin != 3 || Cout != 3 || !has_offset)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
+  if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_surface(what, "output", 1, io.out, B, H, W);
+  return HDRNET_OK;
+}
+
+int check_yuv_io_pointers(const char* what, const hdrnet_amd::YuvIo& io) {
+  if (int rc = check_yuv_pointers(what, "input", io.in, io.to_rgb)) return rc;
+  if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_pointers(what, "output", io.out, io.from_rgb);
+  if (!io.out.y || ((uintptr_t)io.out.y & (io.out_kind == HDRNET_YUV_OUT_RGB_F32 ? 15u : 3u)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
+  return HDRNET_OK;
+}
+
+// Guide side, a map or the network.  Here the map wins over a network given beside it (the up-add entry points refuse
+// that: check_upadd_values), so with a map there is nothing to prescale: the refusal's Cin is then 0.
+int check_guide_given(const char* prefix, const float* guide, const float* conv1, const float* conv2, int n_feats) {
+  if (!guide && (!conv1 || !conv2 || n_feats <= 0 || n_feats > 4096))
+    return fail(HDRNET_INVALID_ARGUMENT, "%seither a guide map or the guide network must be given", prefix);
+  return HDRNET_OK;
+}
+
+int set_io_guide_flags(hdrnet_amd::ApplyIoArgs& a, unsigned flags) {
+  const bool network = !a.guide;
+  return set_guide_flags(a, flags, network ? a.Cin : 0, network ? a.guide_conv1 : nullptr, network ? a.guide_conv2 : nullptr);
+}
+
+// Guide side, the curves: the knots, and the cell tables of hdrnet_curves_guide_prepare_f32 where given.  One rule with
+// two texts: a YUV surface has refused Cin != 3 by then, so its text does not name it.
+int check_curves_knots(const char* prefix, int npts) {
+  if (npts <= 0 || npts > 4096) return fail(HDRNET_INVALID_ARGUMENT, "%sbad number of curve knots (%d)", prefix, npts);
+  return HDRNET_OK;
+}
+
+int set_curves_prepared(hdrnet_amd::ApplyIoArgs& a, const void* prepared, const char* prefix, const char* needs) {
+  if (!prepared) return HDRNET_OK;
+  if (((uintptr_t)prepared & 15u) || a.Cin != 3 || a.n_feats > 16)
+    return fail(HDRNET_INVALID_ARGUMENT, "%sprepared curves tables need %s and the 16-B aligned buffer "
+                                         "hdrnet_curves_guide_prepare_f32 wrote (and reported usable)", prefix, needs);
+  a.guide_prepared = static_cast<const float*>(prepared);
+  return HDRNET_OK;
+}
+
+// The tail: the kernel family is the pixel source's (a.yuv, or `coarse` for the pyramid's up-add), `otherwise` what the
+// entry point supports, `op` its name in a runtime failure.
+int launch_io(const hdrnet_amd::ApplyIoArgs& a, const float* coarse, int Hc, int Wc, const char* op, const char* otherwise,
+              void* stream) {
+  using namespace hdrnet_amd;
+  if (!(a.yuv ? apply_fwd_io_yuv_supported(a) : coarse ? apply_fwd_io_upadd_supported(a, coarse) : apply_fwd_io_supported(a)))
+    return refuse_fused(a.B, a.H, a.W, a.GW, a.GD, a.Cout, rows::kSegLimits, otherwise);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* name = "";
+  const hipError_t e = a.yuv    ? launch_apply_fwd_io_yuv(a, s, &name)
+                       : coarse ? launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name)
+                                : launch_apply_fwd_io(a, s, &name);
+  return finish_launch(e, op, name);
 }
 
 // any parameter the coefficient network reads (and, for the gradient, any it writes) missing?
@@ -318,22 +457,6 @@ int grad_dispatch(const hdrnet_amd::ApplyGradArgs& a, unsigned family, hipStream
 }
 
 }  // namespace
-
-// the wire-format forwards for a frame in any pixel format (defined beside their entry points below)
-static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
-                         int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
-                         float* guide_out, unsigned flags, int pixel_format, void* stream);
-static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
-                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
-                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
-                                float* guide_out, int pixel_format, void* stream);
-static int prepare_impl(const char* what, const void* src_input, int input_dtype, float input_white_level,
-                        const void* src_target, int target_dtype, float target_white_level, int N, int Hs, int Ws,
-                        const int* ops, int B, float* image_input, float* image_target, int H, int W,
-                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged = false,
-                        long long n_samples = 0, const int* images = nullptr, int pixel_format = 0);
 
 extern "C" {
 
@@ -465,11 +588,9 @@ int hdrnet_bilateral_slice_apply_nnguide_f32_ex(const float* grid, const float* 
   if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !guide_conv1 || !guide_conv2)
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
   ApplyArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout,
               Cin + (has_offset ? 1 : 0), has_offset != 0, 0};
-  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
-  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
+  if (int rc = set_guide_flags(a, flags, Cin, guide_conv1, guide_conv2)) return rc;
   if (!apply_fwd_nnguide_supported(a, guide_out))
     return refuse_fused(B, H, W, GW, GD, Cin > Cout ? Cin : Cout, rows::kNeedVec4 | rows::kRowsLimits,
                         "fused guide + slice-apply needs (Cin, Cout) in {(3,3), (1,1)}, W % 4 == 0 and 16-B "
@@ -499,18 +620,12 @@ int hdrnet_bilateral_slice_apply_upadd_f32_ex(const float* grid, const float* gu
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
   if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (Hc <= 0 || Wc <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad coarse extents (%d x %d)", Hc, Wc);
-  if ((guide != nullptr) == (guide_conv1 != nullptr))
-    return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
-  if (guide_conv1 && (!guide_conv2 || n_feats <= 0 || n_feats > 4096))
-    return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
+  if (int rc = check_upadd_values(Hc, Wc, guide, guide_conv1, guide_conv2, n_feats)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !coarse) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
   ApplyArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout,
               Cin + (has_offset ? 1 : 0), has_offset != 0, 0};
-  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
-  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
+  if (int rc = set_guide_flags(a, flags, Cin, guide_conv1, guide_conv2)) return rc;
   if (!apply_fwd_upadd_supported(a, coarse, guide_conv1 != nullptr))
     return refuse_fused(B, H, W, GW, GD, Cin > Cout ? Cin : Cout, rows::kNeedVec4 | rows::kRowsLimits,
                         "slice-apply + up-add needs Cin = Cout = 3 with offset, W % 4 == 0 and 16-B aligned "
@@ -884,15 +999,30 @@ int hdrnet_coefficients_bn_grad_wide_f32(const float* lowres, const hdrnet_coeff
                                     workspace, workspace_bytes, stream);
 }
 
-int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,
-                                    void* out, int B, int H, int W, int GH, int GW, int GD, int Cin,
-                                    int Cout, int has_offset, int input_dtype,
-                                    float input_white_level, int output_dtype,
-                                    const float* guide_conv1, const float* guide_conv2, int n_feats,
-                                    float* guide_out, void* stream) {
-  return hdrnet_bilateral_slice_apply_io_ex(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset,
-                                            input_dtype, input_white_level, output_dtype, guide_conv1, guide_conv2,
-                                            n_feats, guide_out, 0u, stream);
+// ---- include/hdrnet_amd.h: the wire formats (uint8 / uint16 / float32 frames in, float32 / uint8 out) --------------------
+// with a guide map or the guide network, for a frame in `pixel_format` (io_ex: HDRNET_PX_RGB)
+static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
+                         int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
+                         float* guide_out, unsigned flags, int pixel_format, void* stream) {
+  using namespace hdrnet_amd;
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_guide_flags(flags)) return rc;
+  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (!grid || !input || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  if (int rc = check_guide_given("", guide, guide_conv1, guide_conv2, n_feats)) return rc;
+  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset, W, input,
+                                   output_dtype == 1 ? out : nullptr))
+    return rc;
+  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
+                input_dtype, output_dtype, input_white_level, guide_conv1, guide_conv2, n_feats,
+                guide_out};
+  a.pixel_format = pixel_format;
+  if (int rc = set_io_guide_flags(a, flags)) return rc;
+  return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIO",
+                   "the wire-format forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                   "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32", stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, const void* input,
@@ -906,7 +1036,100 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
                        HDRNET_PX_RGB, stream);
 }
 
+int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,
+                                    void* out, int B, int H, int W, int GH, int GW, int GD, int Cin,
+                                    int Cout, int has_offset, int input_dtype,
+                                    float input_white_level, int output_dtype,
+                                    const float* guide_conv1, const float* guide_conv2, int n_feats,
+                                    float* guide_out, void* stream) {
+  return hdrnet_bilateral_slice_apply_io_ex(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset,
+                                            input_dtype, input_white_level, output_dtype, guide_conv1, guide_conv2,
+                                            n_feats, guide_out, 0u, stream);
+}
+
+// ... and with the curves guide (..._io_curves_prepared: HDRNET_PX_RGB)
+static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
+                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
+                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
+                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
+                                float* guide_out, int pixel_format, void* stream) {
+  using namespace hdrnet_amd;
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype)) return rc;
+  if (int rc = check_curves_knots("", npts)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (!grid || !input || !out || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
+    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout, has_offset, W,
+                                   input, output_dtype == 1 ? out : nullptr))
+    return rc;
+  ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
+                input_dtype, output_dtype, input_white_level, guide_ccm, guide_mix, npts,
+                guide_out, guide_shifts, guide_slopes};
+  a.pixel_format = pixel_format;
+  if (int rc = set_curves_prepared(a, prepared, "", "Cin = 3, npts <= 16")) return rc;
+  return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIOCurves",
+                   "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                   "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32", stream);
+}
+
+size_t hdrnet_curves_guide_prepared_bytes(int Cin) { return hdrnet_amd::curves_guide_prepared_bytes(Cin); }
+
+int hdrnet_curves_guide_prepare_f32(const float* guide_shifts, const float* guide_slopes, int npts, int Cin,
+                                    void* prepared, size_t prepared_bytes, int* usable, void* stream) {
+  using namespace hdrnet_amd;
+  const size_t need = curves_guide_prepared_bytes(Cin);
+  if (need == 0 || npts <= 0 || npts > 16)
+    return fail(HDRNET_INVALID_ARGUMENT, "curves prepare needs Cin = 3 and 1 .. 16 knots per channel (Cin=%d, npts=%d)", Cin,
+                npts);
+  if (!guide_shifts || !guide_slopes || !prepared) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  if (((uintptr_t)prepared & 15u) || prepared_bytes < need)
+    return fail(HDRNET_INVALID_ARGUMENT, "curves prepare needs a 16-B aligned buffer of hdrnet_curves_guide_prepared_bytes()");
+  if (!usable) return fail(HDRNET_INVALID_ARGUMENT, "curves prepare: `usable` must point to an int");
+  *usable = 0;
+  const int rc = finish_launch(launch_curves_guide_prepare(guide_shifts, guide_slopes, npts, Cin,
+                                                           static_cast<float*>(prepared), static_cast<hipStream_t>(stream)),
+                                "CurvesGuidePrepare", "curves_prepare");
+  if (rc != HDRNET_OK) return rc;
+  // a SET-UP call, once per parameter set: the table's `ok` word comes back to the host (this waits for `stream`), because
+  // which forward kernel a prepared buffer selects is decided on the host
+  float ok = 0.0f;
+  hipError_t e = hipMemcpyAsync(&ok, static_cast<const float*>(prepared) + curves_guide_prepared_ok_offset(Cin),
+                                sizeof(float), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+  if (e != hipSuccess)
+    return fail(HDRNET_RUNTIME_FAILURE, "curves prepare: reading the table's ok word back: %s", hipGetErrorString(e));
+  *usable = ok != 0.0f ? 1 : 0;
+  return HDRNET_OK;
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const void* input, void* out, int B, int H,
+                                                    int W, int GH, int GW, int GD, int Cin, int Cout,
+                                                    int has_offset, int input_dtype, float input_white_level,
+                                                    int output_dtype, const float* guide_ccm,
+                                                    const float* guide_shifts, const float* guide_slopes,
+                                                    const float* guide_mix, int npts, const void* prepared,
+                                                    float* guide_out, void* stream) {
+  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
+                              prepared, guide_out, HDRNET_PX_RGB, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves(const float* grid, const void* input, void* out, int B, int H,
+                                           int W, int GH, int GW, int GD, int Cin, int Cout,
+                                           int has_offset, int input_dtype, float input_white_level,
+                                           int output_dtype, const float* guide_ccm,
+                                           const float* guide_shifts, const float* guide_slopes,
+                                           const float* guide_mix, int npts, float* guide_out,
+                                           void* stream) {
+  return hdrnet_bilateral_slice_apply_io_curves_prepared(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset,
+                                                         input_dtype, input_white_level, output_dtype, guide_ccm,
+                                                         guide_shifts, guide_slopes, guide_mix, npts, nullptr, guide_out,
+                                                         stream);
+}
+
 // ---- include/hdrnet_amd_pixel_formats.h: frames in BGR / RGBA / BGRA order -----------------------------------------
+// (the format codes answer before anything else; hdrnet_lowres_input_px: sample preparation, below)
 int hdrnet_bilateral_slice_apply_io_px(const float* grid, const float* guide, const void* input, void* out, int B, int H,
                                        int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype,
                                        float input_white_level, int output_dtype, const float* guide_conv1,
@@ -935,147 +1158,33 @@ int hdrnet_bilateral_slice_apply_io_curves_px(const float* grid, const void* inp
                               prepared, guide_out, input_format, stream);
 }
 
-int hdrnet_lowres_input_px(const void* frames, int dtype, float white_level, int B, int H, int W, float* lowres,
-                           int net_input_size, int pixel_format, void* stream) {
-  const char* what = "hdrnet_lowres_input_px";
-  if (pixel_format == HDRNET_PX_RGB) return hdrnet_lowres_input(frames, dtype, white_level, B, H, W, lowres, net_input_size, stream);
-  if (dtype < 0 || dtype > 2)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", what, dtype);
-  if (int rc = check_pixel_formats(what, dtype, 0, pixel_format, HDRNET_PX_RGB)) return rc;
-  if (B > 0 && !lowres) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (lowres)", what);
-  if (B > 0 && pixel_format >= HDRNET_PX_RGBA && ((uintptr_t)frames & 15u))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: 4-channel frames (RGBA / BGRA) must be 16-B aligned", what);
-  return prepare_impl(what, frames, dtype, white_level, nullptr, 0, 1.0f, B > 0 ? B : 1, H, W, nullptr, B, nullptr, nullptr,
-                      H, W, lowres, net_input_size, 0u, stream, false, 0, nullptr, pixel_format);
-}
-
-
-// ---- include/hdrnet_amd_yuv.h: semi-planar YUV 4:2:0 surfaces ------------------------------------------------------------
-// The rules of a surface (`which`: "input" / "output"), checked before any HIP call; `bytes`: per sample.
-static int check_yuv_extents(const char* what, int B, int H, int W) {
-  if (B < 0 || H < 0 || W < 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: negative image extent (B=%d, H=%d, W=%d)", what, B, H, W);
-  if (H % 2 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: H %% 2 != 0 (H=%d): a chroma row serves two image rows", what, H);
-  if (W % 4 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: W %% 4 != 0 (W=%d): a lane owns 4 pixels", what, W);
-  if (B > 65535 || H > 65535 || (long long)W * 12 >= (1LL << 31))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large (B, H <= 65535)", what);
-  return HDRNET_OK;
-}
-
-static int check_yuv_surface(const char* what, const char* which, int sample_dtype, int pitch_y, int pitch_uv,
-                             long long image_stride_y, long long image_stride_uv, int B, int H, int W) {
-  if (sample_dtype != 1 && sample_dtype != 2)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
-                sample_dtype);
-  const long long row = (long long)W * sample_dtype;
-  if (pitch_y < row || pitch_uv < row)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: a pitch of the %s surface is below the row's %lld bytes (pitch_y=%d, "
-                "pitch_uv=%d)", what, which, row, pitch_y, pitch_uv);
-  if ((pitch_y | pitch_uv) & 3)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitches of the %s surface must be multiples of 4 (pitch_y=%d, pitch_uv=%d)",
-                what, which, pitch_y, pitch_uv);
-  if (image_stride_y < 0 || image_stride_uv < 0 || ((image_stride_y | image_stride_uv) & 3))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4", what,
-                which);
-  if (B > 1 && (image_stride_y < (long long)pitch_y * H || image_stride_uv < (long long)pitch_uv * (H / 2)))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
-  return HDRNET_OK;
-}
-
-static int check_yuv_pointers(const char* what, const char* which, const void* y, const void* uv, const float* coef) {
-  if (!y || !uv) return fail(HDRNET_INVALID_ARGUMENT, "%s: null plane of the %s surface", what, which);
-  if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
-  if (((uintptr_t)y | (uintptr_t)uv | (uintptr_t)coef) & 3u)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: the planes and constants of the %s surface must be 4-B aligned", what, which);
-  return HDRNET_OK;
-}
-
+// ---- include/hdrnet_amd_yuv.h: semi-planar YUV 4:2:0 surfaces (hdrnet_lowres_input_yuv: sample preparation, below) --------
 int hdrnet_yuv_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
                           long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
                           float* rgb, void* stream) {
   using namespace hdrnet_amd;
   const char* what = "hdrnet_yuv_to_rgb_f32";
-  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
-  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
-    return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
-  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
   const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", in, to_rgb)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
   return finish_launch(launch_yuv_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, static_cast<hipStream_t>(stream)), what,
                        "yuv_to_rgb");
 }
 
-int hdrnet_lowres_input_yuv(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
-                            long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
-                            float* lowres, int net_input_size, void* stream) {
+// both fused entry points, once surfaces and guide are checked: `a` reads the surfaces of `io` (an RGB `out` is a.out)
+static int yuv_io_launch(const char* op, hdrnet_amd::ApplyIoArgs& a, hdrnet_amd::YuvIo& io, void* out, void* stream) {
   using namespace hdrnet_amd;
-  const char* what = "hdrnet_lowres_input_yuv";
-  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
-  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
-    return rc;
-  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
-  if (B == 0) return finish_noop();
-  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
-  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
-  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
-  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
-                   false};
-  a.yuv = &in;
-  a.yuv_to_rgb = to_rgb;
-  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
-}
-
-// what both fused entry points check of their surfaces and output, and the bundle they launch with
-static int yuv_io_args(const char* what, const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
-                       long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb, int Cin,
-                       int Cout, int has_offset, int output_kind, void* out, void* out_uv, int out_pitch_y, int out_pitch_uv,
-                       long long out_image_stride_y, long long out_image_stride_uv, const float* from_rgb, bool* noop,
-                       hdrnet_amd::YuvIo* io) {
-  using namespace hdrnet_amd;
-  *noop = false;
-  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
-  if (int rc = check_yuv_surface(what, "input", sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W))
-    return rc;
-  if (output_kind < HDRNET_YUV_OUT_RGB_F32 || output_kind > HDRNET_YUV_OUT_NV12)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 NV12)", what, output_kind);
-  if (Cin != 3 || Cout != 3 || !has_offset)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
-  if (output_kind == HDRNET_YUV_OUT_NV12)
-    if (int rc = check_yuv_surface(what, "output", 1, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv, B, H, W))
-      return rc;
-  if ((long long)B * H * W == 0) {
-    *noop = true;
-    return HDRNET_OK;
+  if (io.out_kind != HDRNET_YUV_OUT_NV12) {
+    a.out = out;
+    io.out = YuvSurface{};
+    io.from_rgb = nullptr;
   }
-  if (int rc = check_yuv_pointers(what, "input", y, uv, to_rgb)) return rc;
-  if (output_kind == HDRNET_YUV_OUT_NV12) {
-    if (int rc = check_yuv_pointers(what, "output", out, out_uv, from_rgb)) return rc;
-  } else if (!out || ((uintptr_t)out & (output_kind == HDRNET_YUV_OUT_RGB_F32 ? 15u : 3u))) {
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
-  }
-  io->in = YuvSurface{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
-  io->to_rgb = to_rgb;
-  io->out_kind = output_kind;
-  io->out = output_kind == HDRNET_YUV_OUT_NV12
-                ? YuvSurface{out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}
-                : YuvSurface{};
-  io->from_rgb = output_kind == HDRNET_YUV_OUT_NV12 ? from_rgb : nullptr;
-  return HDRNET_OK;
-}
-
-static int yuv_io_launch(const char* what, hdrnet_amd::ApplyIoArgs& a, const hdrnet_amd::YuvIo& io, void* out, void* stream) {
-  using namespace hdrnet_amd;
-  a.pixel_format = 0;
   a.yuv = &io;
-  a.input = nullptr;
-  a.out = io.out_kind == HDRNET_YUV_OUT_NV12 ? nullptr : out;
-  if (!apply_fwd_io_yuv_supported(a))
-    return refuse_fused(a.B, a.H, a.W, a.GW, a.GD, a.Cout, rows::kSegLimits,
-                        "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers");
-  const char* name = "";
-  const hipError_t e = launch_apply_fwd_io_yuv(a, static_cast<hipStream_t>(stream), &name);
-  return finish_launch(e, what, name);
+  return launch_io(a, nullptr, 0, 0, op,
+                   "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers", stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_yuv(const float* grid, const float* guide, const void* y, const void* uv,
@@ -1088,23 +1197,18 @@ int hdrnet_bilateral_slice_apply_io_yuv(const float* grid, const float* guide, c
                                         const float* from_rgb, void* stream) {
   using namespace hdrnet_amd;
   const char* what = "hdrnet_bilateral_slice_apply_io_yuv";
+  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+           {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
-  bool noop = false;
-  YuvIo io{};
-  if (int rc = yuv_io_args(what, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb, Cin,
-                           Cout, has_offset, output_kind, out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y,
-                           out_image_stride_uv, from_rgb, &noop, &io))
-    return rc;
-  if (noop) return finish_noop();
+  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_io_pointers(what, io)) return rc;
   if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
-  if (!guide && (!guide_conv1 || !guide_conv2 || n_feats <= 0 || n_feats > 4096))
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: either a guide map or the guide network must be given", what);
+  if (int rc = check_guide_given("hdrnet_bilateral_slice_apply_io_yuv: ", guide, guide_conv1, guide_conv2, n_feats)) return rc;
   ApplyIoArgs a{grid, guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
                 sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_conv1, guide_conv2, n_feats, guide_out};
-  if (int rc = check_guide_prescaled(flags, guide ? 0 : Cin, guide ? nullptr : guide_conv1, guide ? nullptr : guide_conv2)) return rc;
-  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
-  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
+  if (int rc = set_io_guide_flags(a, flags)) return rc;
   return yuv_io_launch("BilateralSliceApplyIOYuv", a, io, out, stream);
 }
 
@@ -1119,60 +1223,21 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv(const float* grid, const void* y,
                                                long long out_image_stride_uv, const float* from_rgb, void* stream) {
   using namespace hdrnet_amd;
   const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv";
+  const char* prefix = "hdrnet_bilateral_slice_apply_io_curves_yuv: ";
+  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+           {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (npts <= 0 || npts > 4096) return fail(HDRNET_INVALID_ARGUMENT, "%s: bad number of curve knots (%d)", what, npts);
-  bool noop = false;
-  YuvIo io{};
-  if (int rc = yuv_io_args(what, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb, Cin,
-                           Cout, has_offset, output_kind, out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y,
-                           out_image_stride_uv, from_rgb, &noop, &io))
-    return rc;
-  if (noop) return finish_noop();
+  if (int rc = check_curves_knots(prefix, npts)) return rc;
+  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_io_pointers(what, io)) return rc;
   if (!grid || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
   ApplyIoArgs a{grid, nullptr, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
                 sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_ccm, guide_mix, npts,
                 guide_out, guide_shifts, guide_slopes};
-  if (prepared) {
-    if (((uintptr_t)prepared & 15u) || npts > 16)
-      return fail(HDRNET_INVALID_ARGUMENT, "%s: prepared curves tables need npts <= 16 and the 16-B aligned buffer "
-                                           "hdrnet_curves_guide_prepare_f32 wrote (and reported usable)", what);
-    a.guide_prepared = static_cast<const float*>(prepared);
-  }
+  if (int rc = set_curves_prepared(a, prepared, prefix, "npts <= 16")) return rc;
   return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, out, stream);
-}
-
-// the wire-format forward with a guide map or the guide network, for a frame in `pixel_format` (io_ex: HDRNET_PX_RGB)
-static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
-                         int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
-                         float* guide_out, unsigned flags, int pixel_format, void* stream) {
-  using namespace hdrnet_amd;
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_guide_flags(flags)) return rc;
-  if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (!grid || !input || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (!guide && (!guide_conv1 || !guide_conv2 || n_feats <= 0 || n_feats > 4096))
-    return fail(HDRNET_INVALID_ARGUMENT, "either a guide map or the guide network must be given");
-  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
-                input_dtype, output_dtype, input_white_level, guide_conv1, guide_conv2, n_feats,
-                guide_out};
-  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset, W, input,
-                                   output_dtype == 1 ? out : nullptr))
-    return rc;
-  a.pixel_format = pixel_format;
-  if (int rc = check_guide_prescaled(flags, guide ? 0 : Cin, guide ? nullptr : guide_conv1, guide ? nullptr : guide_conv2)) return rc;
-  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
-  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
-  if (!apply_fwd_io_supported(a))
-    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
-                        "the wire-format forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
-                        "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32");
-  const char* name = "";
-  const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
-  return finish_launch(e, "BilateralSliceApplyIO", name);
 }
 
 // ---- include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats ---------------------------------------------
@@ -1183,8 +1248,7 @@ int hdrnet_resize_bilinear_io(const void* input, int input_dtype, float white_le
   if (B < 0 || Hin <= 0 || Win <= 0 || Hout < 0 || Wout < 0)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: bad extents (B=%d, in %dx%d, out %dx%d)", what, B, Hin, Win, Hout, Wout);
   if (C != 3) return fail(HDRNET_INVALID_ARGUMENT, "%s: C must be 3 (RGB frames), got C=%d", what, C);
-  if (input_dtype < 0 || input_dtype > 2)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", what, input_dtype);
+  if (int rc = check_input_dtype(what, input_dtype)) return rc;
   if (!(white_level > 0.0f) || !(white_level <= 3.4028234e38f))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: white_level must be positive and finite", what);
   if ((long long)B * Hin * Win * 12 >= (1LL << 40))
@@ -1208,44 +1272,34 @@ int hdrnet_bilateral_slice_apply_upadd_io_ex(const float* grid, const float* gui
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
-  if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (int rc = check_io_format(input_dtype, white_level, output_dtype)) return rc;
-  if (Hc <= 0 || Wc <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad coarse extents (%d x %d)", Hc, Wc);
-  if ((guide != nullptr) == (guide_conv1 != nullptr))
-    return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
-  if (guide_conv1 && (!guide_conv2 || n_feats <= 0 || n_feats > 4096))
-    return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
+  if (int rc = check_frame_values(Cin, Cout, input_dtype, white_level, output_dtype)) return rc;
+  if (int rc = check_upadd_values(Hc, Wc, guide, guide_conv1, guide_conv2, n_feats)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !coarse) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_guide_prescaled(flags, Cin, guide_conv1, guide_conv2)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* name = "";
+  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
+                input_dtype, output_dtype, white_level, guide_conv1, guide_conv2, n_feats, nullptr};
+  if (int rc = set_guide_flags(a, flags, Cin, guide_conv1, guide_conv2)) return rc;
   if (input_dtype == 0 && output_dtype == 0) {
     // float32 both ways: the float op itself (its kernel, its bits)
     return hdrnet_bilateral_slice_apply_upadd_f32_ex(grid, guide, static_cast<const float*>(input), coarse, Hc, Wc,
                                                      static_cast<float*>(out), B, H, W, GH, GW, GD, Cin, Cout, has_offset,
                                                      guide_conv1, guide_conv2, n_feats, flags, stream);
   }
-  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
-                input_dtype, output_dtype, white_level, guide_conv1, guide_conv2, n_feats, nullptr};
-  a.fast_sigmoid = (flags & HDRNET_GUIDE_SIGMOID_FAST) != 0;
-  a.guide_prescaled = (flags & HDRNET_GUIDE_RELU_PRESCALED) != 0;
-  if (!apply_fwd_io_upadd_supported(a, coarse))
-    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
-                        "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
-                        "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32");
-  const hipError_t e = launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name);
-  return finish_launch(e, "BilateralSliceApplyUpAddIO", name);
+  return launch_io(a, coarse, Hc, Wc, "BilateralSliceApplyUpAddIO",
+                   "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                   "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32", stream);
 }
 
+// ---- sample preparation (sample_prep.hip): hdrnet_prepare_batch* of include/hdrnet_amd_train.h, and the low-res network
+// input from frames in each of the wire formats above -------------------------------------------------------------------
 // Sample preparation (sample_prep.hip).  Everything is checked before any HIP call.  `ragged`: the sources are flat
 // buffers of n_samples samples with the descriptor table `images` (hdrnet_prepare_batch_ragged); Hs / Ws are then unused
 // and the fit of the crop is a matter of the table (the device clamps).
 static int prepare_impl(const char* what, const void* src_input, int input_dtype, float input_white_level,
                         const void* src_target, int target_dtype, float target_white_level, int N, int Hs, int Ws,
                         const int* ops, int B, float* image_input, float* image_target, int H, int W,
-                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged,
-                        long long n_samples, const int* images, int pixel_format) {
+                        float* lowres_input, int net_input_size, unsigned flags, void* stream, bool ragged = false,
+                        long long n_samples = 0, const int* images = nullptr, int pixel_format = 0) {
   using namespace hdrnet_amd;
   if (ragged) Hs = Ws = 1;  // unused
   if (flags & ~HDRNET_SAMPLE_EVEN_TURNS_ONLY)
@@ -1327,95 +1381,37 @@ int hdrnet_lowres_input(const void* frames, int dtype, float white_level, int B,
                       B, nullptr, nullptr, H, W, lowres, net_input_size, 0u, stream);
 }
 
-int hdrnet_bilateral_slice_apply_io_curves(const float* grid, const void* input, void* out, int B, int H,
-                                           int W, int GH, int GW, int GD, int Cin, int Cout,
-                                           int has_offset, int input_dtype, float input_white_level,
-                                           int output_dtype, const float* guide_ccm,
-                                           const float* guide_shifts, const float* guide_slopes,
-                                           const float* guide_mix, int npts, float* guide_out,
-                                           void* stream) {
-  return hdrnet_bilateral_slice_apply_io_curves_prepared(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset,
-                                                         input_dtype, input_white_level, output_dtype, guide_ccm,
-                                                         guide_shifts, guide_slopes, guide_mix, npts, nullptr, guide_out,
-                                                         stream);
+int hdrnet_lowres_input_px(const void* frames, int dtype, float white_level, int B, int H, int W, float* lowres,
+                           int net_input_size, int pixel_format, void* stream) {
+  const char* what = "hdrnet_lowres_input_px";
+  if (pixel_format == HDRNET_PX_RGB) return hdrnet_lowres_input(frames, dtype, white_level, B, H, W, lowres, net_input_size, stream);
+  if (int rc = check_input_dtype(what, dtype)) return rc;
+  if (int rc = check_pixel_formats(what, dtype, 0, pixel_format, HDRNET_PX_RGB)) return rc;
+  if (B > 0 && !lowres) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (lowres)", what);
+  if (B > 0 && pixel_format >= HDRNET_PX_RGBA && ((uintptr_t)frames & 15u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: 4-channel frames (RGBA / BGRA) must be 16-B aligned", what);
+  return prepare_impl(what, frames, dtype, white_level, nullptr, 0, 1.0f, B > 0 ? B : 1, H, W, nullptr, B, nullptr, nullptr,
+                      H, W, lowres, net_input_size, 0u, stream, false, 0, nullptr, pixel_format);
 }
 
-size_t hdrnet_curves_guide_prepared_bytes(int Cin) { return hdrnet_amd::curves_guide_prepared_bytes(Cin); }
-
-int hdrnet_curves_guide_prepare_f32(const float* guide_shifts, const float* guide_slopes, int npts, int Cin,
-                                    void* prepared, size_t prepared_bytes, int* usable, void* stream) {
+int hdrnet_lowres_input_yuv(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                            long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                            float* lowres, int net_input_size, void* stream) {
   using namespace hdrnet_amd;
-  const size_t need = curves_guide_prepared_bytes(Cin);
-  if (need == 0 || npts <= 0 || npts > 16)
-    return fail(HDRNET_INVALID_ARGUMENT, "curves prepare needs Cin = 3 and 1 .. 16 knots per channel (Cin=%d, npts=%d)", Cin,
-                npts);
-  if (!guide_shifts || !guide_slopes || !prepared) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (((uintptr_t)prepared & 15u) || prepared_bytes < need)
-    return fail(HDRNET_INVALID_ARGUMENT, "curves prepare needs a 16-B aligned buffer of hdrnet_curves_guide_prepared_bytes()");
-  if (!usable) return fail(HDRNET_INVALID_ARGUMENT, "curves prepare: `usable` must point to an int");
-  *usable = 0;
-  const int rc = finish_launch(launch_curves_guide_prepare(guide_shifts, guide_slopes, npts, Cin,
-                                                           static_cast<float*>(prepared), static_cast<hipStream_t>(stream)),
-                                "CurvesGuidePrepare", "curves_prepare");
-  if (rc != HDRNET_OK) return rc;
-  // a SET-UP call, once per parameter set: the table's `ok` word comes back to the host (this waits for `stream`), because
-  // which forward kernel a prepared buffer selects is decided on the host
-  float ok = 0.0f;
-  hipError_t e = hipMemcpyAsync(&ok, static_cast<const float*>(prepared) + curves_guide_prepared_ok_offset(Cin),
-                                sizeof(float), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream));
-  if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-  if (e != hipSuccess)
-    return fail(HDRNET_RUNTIME_FAILURE, "curves prepare: reading the table's ok word back: %s", hipGetErrorString(e));
-  *usable = ok != 0.0f ? 1 : 0;
-  return HDRNET_OK;
-}
-
-int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const void* input, void* out, int B, int H,
-                                                    int W, int GH, int GW, int GD, int Cin, int Cout,
-                                                    int has_offset, int input_dtype, float input_white_level,
-                                                    int output_dtype, const float* guide_ccm,
-                                                    const float* guide_shifts, const float* guide_slopes,
-                                                    const float* guide_mix, int npts, const void* prepared,
-                                                    float* guide_out, void* stream) {
-  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
-                              prepared, guide_out, HDRNET_PX_RGB, stream);
-}
-
-// ... and with the curves guide (..._io_curves_prepared: HDRNET_PX_RGB)
-static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
-                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
-                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
-                                float* guide_out, int pixel_format, void* stream) {
-  using namespace hdrnet_amd;
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
-  if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
-  if (npts <= 0 || npts > 4096) return fail(HDRNET_INVALID_ARGUMENT, "bad number of curve knots (%d)", npts);
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (!grid || !input || !out || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
-    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
-                input_dtype, output_dtype, input_white_level, guide_ccm, guide_mix, npts,
-                guide_out, guide_shifts, guide_slopes};
-  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout, has_offset, W,
-                                   input, output_dtype == 1 ? out : nullptr))
-    return rc;
-  a.pixel_format = pixel_format;
-  if (prepared) {
-    if (((uintptr_t)prepared & 15u) || Cin != 3 || npts > 16)
-      return fail(HDRNET_INVALID_ARGUMENT, "prepared curves tables need Cin = 3, npts <= 16 and the 16-B aligned buffer "
-                                           "hdrnet_curves_guide_prepare_f32 wrote (and reported usable)");
-    a.guide_prepared = static_cast<const float*>(prepared);
-  }
-  if (!apply_fwd_io_supported(a))
-    return refuse_fused(B, H, W, GW, GD, Cout, rows::kSegLimits,
-                        "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
-                        "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32");
-  const char* name = "";
-  const hipError_t e = launch_apply_fwd_io(a, static_cast<hipStream_t>(stream), &name);
-  return finish_launch(e, "BilateralSliceApplyIOCurves", name);
+  const char* what = "hdrnet_lowres_input_yuv";
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", in, to_rgb)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
+                   false};
+  a.yuv = &in;
+  a.yuv_to_rgb = to_rgb;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
 }
 
 size_t hdrnet_bilateral_slice_apply_grad_workspace_bytes(int B, int H, int W, int GH, int GW,

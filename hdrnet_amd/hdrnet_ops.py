@@ -474,8 +474,8 @@ class _BilateralSliceApplyCurves(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, grid, inp, ccm, shifts, slopes, mix, has_offset):
-        out, guide = _apply_io_curves(grid, inp, (ccm, shifts, slopes, mix), None, torch.float32,
-                                      bool(has_offset), True)
+        out, guide = bilateral_slice_apply_io(grid, inp, guide_curves=(ccm, shifts, slopes, mix),
+                                              has_offset=bool(has_offset), return_guide=True)
         ctx.save_for_backward(grid, inp, ccm, shifts, slopes, mix, guide)
         ctx.has_offset = bool(has_offset)
         ctx.flags = _flags()
@@ -522,7 +522,8 @@ def bilateral_slice_apply_curves(grid: torch.Tensor, input: torch.Tensor, ccm: t
         if input.dim() != 4 or input.shape[3] != 3 or shifts.dim() != 2 or shifts.shape[0] != 16:
             raise ValueError("the differentiable curves-guide op needs Cin = 3 and 16 knots per channel")
         return _BilateralSliceApplyCurves.apply(grid, input, ccm, shifts, slopes, mix, has_offset)
-    return _apply_io_curves(grid, input, (ccm, shifts, slopes, mix), None, torch.float32, has_offset, False, prepared)
+    return bilateral_slice_apply_io(grid, input, guide_curves=(ccm, shifts, slopes, mix), has_offset=has_offset,
+                                    curves_prepared=prepared)
 
 
 def input_moments(input: torch.Tensor):  # noqa: A002
@@ -1025,18 +1026,29 @@ _DTYPE_CODE = {torch.float32: 0, torch.uint8: 1, torch.uint16: 2}
 _DEFAULT_WHITE = {torch.float32: 1.0, torch.uint8: 255.0, torch.uint16: 65535.0}
 
 
-def _check_io(grid, input, has_offset):  # noqa: A002
-    """Rank / batch / channel / dtype rules shared by the wire-format entry points (the OP_REQUIRES of
-    bilateral_slice_apply_op.cc:147-193 on an input that may be uint8 / uint16).  Returns
-    (B, H, W, GH, GW, GD, Cin, Cout)."""
+def _frame_head(input, white_level, out_dtype=torch.float32, rank_text=None):  # noqa: A002
+    """What every op on a wire-format frame asks first: rank 4, float32 / uint8 / uint16, ``out_dtype`` float32 or
+    uint8.  Returns the white level: the dtype's default where None."""
     if not isinstance(input, torch.Tensor) or input.dim() != 4:
-        raise ValueError("Input image should be 4D (batch_size, height, width, input_channels)")
+        raise ValueError(rank_text or "Input image should be 4D (batch_size, height, width, input_channels), got "
+                         f"{tuple(input.shape) if isinstance(input, torch.Tensor) else type(input).__name__}")
     if input.dtype not in _DTYPE_CODE:
         raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+    return _DEFAULT_WHITE[input.dtype] if white_level is None else white_level
+
+
+def _check_io(grid, input, has_offset, pixel_format="rgb"):  # noqa: A002
+    """Batch / channel rules shared by the wire-format entry points (the OP_REQUIRES of
+    bilateral_slice_apply_op.cc:147-193 on an input that ``_frame_head`` has passed), for a frame in ``pixel_format``: the
+    op sees three channels whatever another format than RGB stores.  Returns (B, H, W, GH, GW, GD, Cin, Cout)."""
     _require_f32("grid", grid)
     if grid.dim() != 5:
         raise ValueError(f"Input grid should be 5D, got {tuple(grid.shape)}")
     B, H, W, Cin = input.shape
+    if pixel_format != "rgb":
+        Cin = min(Cin, 3)
     if grid.shape[0] != B:
         raise ValueError("Batch sizes should match.")
     GH, GW, GD, C = grid.shape[1:]
@@ -1046,24 +1058,64 @@ def _check_io(grid, input, has_offset):  # noqa: A002
             "Slicing with affine offset, grid should have output_channels * (input_channels + 1) channels."
             if has_offset else
             "Slicing without affine offset, grid should have output_channels * input_channels channels.")
+    if pixel_format != "rgb" and ((Cin, C // Cj) != (3, 3) or not has_offset):
+        raise ValueError(f"pixel_format={pixel_format!r} needs the 3 -> 3 op with offset (a [.., 12] grid), got Cout = {C // Cj}, "
+                         f"has_offset = {bool(has_offset)}")
     return B, H, W, GH, GW, GD, Cin, C // Cj
 
 
-def _io_guide(guide, guide_conv1, guide_conv2, bhw, Cin):
-    """The guide of a wire-format entry point, checked: ``(guide map, None, None, 0)`` or ``(None, guide_conv1,
-    guide_conv2, n)``, detached and contiguous.  The caller has made sure that exactly one of the two is given."""
+_ONE_GUIDE = "give exactly one of guide, (guide_conv1, guide_conv2), guide_curves"
+_MAP_OR_NETWORK = "give either a guide map or both guide_conv1 and guide_conv2"
+
+
+def _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, bhw, Cin,
+                  map_or_network=_MAP_OR_NETWORK, lone_conv_ok=True, prepared_name="prepared"):
+    """The guide of a wire-format forward: exactly one of a ``guide`` map, the guide network (``guide_conv1``,
+    ``guide_conv2``) and ``guide_curves`` (with ``curves_prepared``), checked against the frame's ``bhw`` and ``Cin``.
+    Returns ``(False, (guide map, None, None), 0)``, ``(False, (None, guide_conv1, guide_conv2), n)`` or ``(True, (ccm,
+    shifts, slopes, mix, curves_prepared), npts)`` -- whether to call the curves entry points, the tensors detached and
+    contiguous in the order those take them, and the feature / knot count.  ``map_or_network``: the caller's wording for
+    neither or both of the first two; ``lone_conv_ok``: half a network beside a map is ignored (the map wins, as in the C
+    ABI) rather than refused; ``prepared_name``: what the caller calls ``curves_prepared``."""
+    half = (guide_conv1 is None) != (guide_conv2 is None)
+    n_given = sum(x is not None for x in (guide, guide_curves)) + int(guide_conv1 is not None and guide_conv2 is not None)
+    if guide_curves is not None and (n_given != 1 or half):
+        raise ValueError(_ONE_GUIDE)
+    if n_given != 1 or (half and not lone_conv_ok):
+        raise ValueError(map_or_network)
+    if return_guide and guide is not None:
+        raise ValueError("return_guide needs a guide computed by the kernel (guide network or guide_curves)")
     if guide is not None:
         _require_f32("guide", guide)
         if tuple(guide.shape) != tuple(bhw):
             raise ValueError("Input and guide size should match.")
         _require_gpu("guide", guide)
-        return guide.detach().contiguous(), None, None, 0
-    _require_f32("guide_conv1", guide_conv1)
-    _require_f32("guide_conv2", guide_conv2)
-    n = guide_conv1.shape[0]
-    if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
-        raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
-    return None, guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous(), n
+        return False, (guide.detach().contiguous(), None, None), 0
+    if guide_curves is None:
+        _require_f32("guide_conv1", guide_conv1)
+        _require_f32("guide_conv2", guide_conv2)
+        n = guide_conv1.shape[0]
+        if guide_conv1.dim() != 2 or guide_conv1.shape[1] != Cin + 1 or tuple(guide_conv2.shape) != (n + 1,):
+            raise ValueError("guide_conv1 should be [n, Cin + 1] and guide_conv2 [n + 1]")
+        return False, (None, guide_conv1.detach().contiguous(), guide_conv2.detach().contiguous()), n
+    if len(guide_curves) != 4:
+        raise ValueError("guide_curves should be (ccm, shifts, slopes, mix)")
+    shifts = guide_curves[1]
+    npts = shifts.shape[0] if shifts.dim() == 2 else -1
+    for nm, t, shape in zip(("ccm", "shifts", "slopes", "mix"), guide_curves,
+                            ((Cin, Cin + 1), (npts, Cin), (npts, Cin), (Cin + 1,))):
+        _require_f32(f"guide_curves.{nm}", t)
+        if tuple(t.shape) != shape or npts <= 0:
+            raise ValueError(f"guide_curves.{nm} should be {list(shape)}, got {list(t.shape)}")
+    for nm, t in zip(("ccm", "shifts", "slopes", "mix"), guide_curves):
+        _require_gpu(f"guide_curves.{nm}", t)
+    if curves_prepared is not None:
+        _require_f32(prepared_name, curves_prepared)
+        _require_gpu(prepared_name, curves_prepared)
+        if (not curves_prepared.is_contiguous()
+                or curves_prepared.numel() * 4 < _lib.load().hdrnet_curves_guide_prepared_bytes(Cin)):
+            raise ValueError(f"{prepared_name} should be the tensor curves_guide_prepare returned")
+    return True, (*(t.detach().contiguous() for t in guide_curves), curves_prepared), npts
 
 
 def curves_guide_prepare(shifts: torch.Tensor, slopes: torch.Tensor) -> Optional[torch.Tensor]:
@@ -1107,60 +1159,6 @@ def _px_codes(pixel_format: str, out_dtype):
     return code, (code if out_dtype == torch.uint8 else _lib.PIXEL_FORMATS["rgb"])
 
 
-def _check_io_px(grid, input, has_offset, pixel_format):  # noqa: A002
-    """``_check_io`` for a frame in another pixel format than RGB: the op sees three channels whatever the frame stores."""
-    if not isinstance(input, torch.Tensor) or input.dim() != 4:
-        raise ValueError("Input image should be 4D (batch_size, height, width, input_channels)")
-    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input[..., :3], has_offset)
-    if (Cin, Cout) != (3, 3) or not has_offset:
-        raise ValueError(f"pixel_format={pixel_format!r} needs the 3 -> 3 op with offset (a [.., 12] grid), got Cout = {Cout}, "
-                         f"has_offset = {bool(has_offset)}")
-    return B, H, W, GH, GW, GD, Cin, Cout
-
-
-def _apply_io_curves(grid, input, curves, input_white_level, out_dtype, has_offset, return_guide,  # noqa: A002
-                     prepared=None, pixel_format="rgb"):
-    if len(curves) != 4:
-        raise ValueError("guide_curves should be (ccm, shifts, slopes, mix)")
-    ccm, shifts, slopes, mix = curves
-    if pixel_format == "rgb":
-        B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
-    else:
-        B, H, W, GH, GW, GD, Cin, Cout = _check_io_px(grid, input, has_offset, pixel_format)
-    npts = shifts.shape[0] if shifts.dim() == 2 else -1
-    for nm, t, shape in (("ccm", ccm, (Cin, Cin + 1)), ("shifts", shifts, (npts, Cin)),
-                         ("slopes", slopes, (npts, Cin)), ("mix", mix, (Cin + 1,))):
-        _require_f32(f"guide_curves.{nm}", t)
-        if tuple(t.shape) != shape or npts <= 0:
-            raise ValueError(f"guide_curves.{nm} should be {list(shape)}, got {list(t.shape)}")
-    if input_white_level is None:
-        input_white_level = _DEFAULT_WHITE[input.dtype]
-    for nm, t in (("grid", grid), ("input", input), ("guide_curves.ccm", ccm), ("guide_curves.shifts", shifts),
-                  ("guide_curves.slopes", slopes), ("guide_curves.mix", mix)):
-        _require_gpu(nm, t)
-    grid, inp = grid.detach().contiguous(), input.detach().contiguous()
-    ccm, shifts, slopes, mix = (t.detach().contiguous() for t in (ccm, shifts, slopes, mix))
-    dev = inp.device
-    lib = _lib.load()
-    if prepared is not None:
-        _require_f32("prepared", prepared)
-        _require_gpu("prepared", prepared)
-        if not prepared.is_contiguous() or prepared.numel() * 4 < lib.hdrnet_curves_guide_prepared_bytes(Cin):
-            raise ValueError("prepared should be the tensor curves_guide_prepare returned")
-    out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
-    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    with torch.cuda.device(dev):
-        args = (grid.data_ptr(), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
-                int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
-                ccm.data_ptr(), shifts.data_ptr(), slopes.data_ptr(), mix.data_ptr(), npts, _ptr(prepared), _ptr(gout))
-        if pixel_format == "rgb":
-            rc = lib.hdrnet_bilateral_slice_apply_io_curves_prepared(*args, _stream(dev))
-        else:
-            rc = lib.hdrnet_bilateral_slice_apply_io_curves_px(*args, *_px_codes(pixel_format, out_dtype), _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOCurves")
-    return (out, gout) if return_guide else out
-
-
 def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A002
                              guide: Optional[torch.Tensor] = None,
                              guide_conv1: Optional[torch.Tensor] = None,
@@ -1192,47 +1190,31 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     only.  A uint8 output has the input's format, with alpha carried over (the byte of a uint8 frame, ``alpha >> 8`` of a
     uint16 one: alpha is never divided by the white level or quantised); a float32 output is ``[B, H, W, 3]`` RGB.
     4-channel frames must be 16-byte aligned.  Out of scope: float32 frames in other orders, uint16 output."""
-    if input.dim() != 4:
-        raise ValueError(f"Input image should be 4D (batch_size, height, width, input_channels), got {tuple(input.shape)}")
-    if input.dtype not in _DTYPE_CODE:
-        raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
-    if pixel_format != "rgb":  # "rgb": every rule below is the one it always was
+    input_white_level = _frame_head(input, input_white_level, out_dtype)
+    rgb = pixel_format == "rgb"
+    if not rgb:  # "rgb": every rule below is the one it always was
         pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32,
                                          "bilateral_slice_apply_io")
-    if guide_curves is not None:
-        if guide is not None or guide_conv1 is not None or guide_conv2 is not None:
-            raise ValueError("give exactly one of guide, (guide_conv1, guide_conv2), guide_curves")
-        return _apply_io_curves(grid, input, guide_curves, input_white_level, out_dtype, has_offset, return_guide,
-                                curves_prepared, pixel_format)
-    if return_guide and guide is not None:
-        raise ValueError("return_guide needs a guide computed by the kernel (guide network or guide_curves)")
-    if (guide is None) == (guide_conv1 is None or guide_conv2 is None):
-        raise ValueError("give either a guide map or both guide_conv1 and guide_conv2")
-    if input_white_level is None:
-        input_white_level = _DEFAULT_WHITE[input.dtype]
-    if pixel_format == "rgb":
-        B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
-    else:
-        B, H, W, GH, GW, GD, Cin, Cout = _check_io_px(grid, input, has_offset, pixel_format)
-    guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), Cin)
+    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset, pixel_format)
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), Cin)
     _require_gpu("grid", grid)
     _require_gpu("input", input)
     grid, inp = grid.detach().contiguous(), input.detach().contiguous()
     dev = inp.device
     out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    lib = _lib.load()
+    frame = (inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, int(bool(has_offset)),
+             _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype])
+    if curves:
+        fn = "hdrnet_bilateral_slice_apply_io_curves" + ("_prepared" if rgb else "_px")
+        args = (grid.data_ptr(), *frame, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
+    else:
+        fn = "hdrnet_bilateral_slice_apply_io" + ("_ex" if rgb else "_px")
+        args = (grid.data_ptr(), _ptr(g[0]), *frame, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
-        args = (grid.data_ptr(), _ptr(guide), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout,
-                int(bool(has_offset)), _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype],
-                _ptr(c1), _ptr(c2), n, _ptr(gout), _guide_flags(fast_sigmoid, prescaled and guide is None))
-        if pixel_format == "rgb":
-            rc = lib.hdrnet_bilateral_slice_apply_io_ex(*args, _stream(dev))
-        else:
-            rc = lib.hdrnet_bilateral_slice_apply_io_px(*args, *_px_codes(pixel_format, out_dtype), _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIO")
+        rc = getattr(_lib.load(), fn)(*args, *(() if rgb else _px_codes(pixel_format, out_dtype)), _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
     return (out, gout) if return_guide else out
 
 
@@ -1337,11 +1319,6 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
         raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
                          f"{tuple(grid.shape)}")
     GH, GW, GD = grid.shape[1:4]
-    n_given = sum(x is not None for x in (guide, guide_curves)) + int(guide_conv1 is not None or guide_conv2 is not None)
-    if n_given != 1 or (guide_conv1 is None) != (guide_conv2 is None):
-        raise ValueError("give exactly one of guide, (guide_conv1, guide_conv2), guide_curves")
-    if return_guide and guide is not None:
-        raise ValueError("return_guide needs a guide computed by the kernel (guide network or guide_curves)")
     tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb)]
     oy = ouv = None
     if out == "nv12":
@@ -1352,19 +1329,8 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
             if (oB, oH, oW) != (B, H, W) or oy.dtype != torch.uint8:
                 raise ValueError(f"{what}: out_planes should be a uint8 surface of {[B, H, W]}, got {oy.dtype} {[oB, oH, oW]}")
             tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
-    if guide_curves is not None:
-        if len(guide_curves) != 4:
-            raise ValueError("guide_curves should be (ccm, shifts, slopes, mix)")
-        ccm, shifts, slopes, mix = guide_curves
-        npts = shifts.shape[0] if shifts.dim() == 2 else -1
-        for nm, t, shape in (("ccm", ccm, (3, 4)), ("shifts", shifts, (npts, 3)), ("slopes", slopes, (npts, 3)),
-                             ("mix", mix, (4,))):
-            _require_f32(f"guide_curves.{nm}", t)
-            if tuple(t.shape) != shape or npts <= 0:
-                raise ValueError(f"guide_curves.{nm} should be {list(shape)}, got {list(t.shape)}")
-            tensors.append((f"guide_curves.{nm}", t))
-    else:
-        guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), 3)
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
+                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
     for nm, t in tensors:
         _require_gpu(nm, t)
     dev = y.device
@@ -1386,20 +1352,13 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
     head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
     with torch.cuda.device(dev):
-        if guide_curves is not None:
-            if curves_prepared is not None:
-                _require_f32("curves_prepared", curves_prepared)
-                _require_gpu("curves_prepared", curves_prepared)
-                if not curves_prepared.is_contiguous() or curves_prepared.numel() * 4 < lib.hdrnet_curves_guide_prepared_bytes(3):
-                    raise ValueError("curves_prepared should be the tensor curves_guide_prepare returned")
-            ccm, shifts, slopes, mix = (t.detach().contiguous() for t in guide_curves)
+        if curves:
             rc = lib.hdrnet_bilateral_slice_apply_io_curves_yuv(
-                grid.data_ptr(), *head, ccm.data_ptr(), shifts.data_ptr(), slopes.data_ptr(), mix.data_ptr(), npts,
-                _ptr(curves_prepared), _ptr(gout), *output, _stream(dev))
+                grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), *output, _stream(dev))
         else:
             rc = lib.hdrnet_bilateral_slice_apply_io_yuv(
-                grid.data_ptr(), _ptr(guide), *head, _ptr(c1), _ptr(c2), n, _ptr(gout),
-                _guide_flags(fast_sigmoid, prescaled and guide is None), *output, _stream(dev))
+                grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOYuv")
     return (result, gout) if return_guide else result
 
@@ -1411,17 +1370,12 @@ def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A0
     float32 ``[B, height, width, 3]`` out -- level 1 of ``HDRNetGaussianPyrNN``'s input pyramid without a float32 copy of
     the frame (``hdrnet_resize_bilinear_io``, include/hdrnet_amd_pyramid_io.h).  Same taps and lerp as
     ``resize_bilinear``; the division is the wire-format forward's IEEE-rounded one.  No autograd."""
-    if not isinstance(input, torch.Tensor) or input.dim() != 4:
-        raise ValueError("input should be 4D (batch, height, width, channels)")
-    if input.dtype not in _DTYPE_CODE:
-        raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
+    white_level = _frame_head(input, white_level, rank_text="input should be 4D (batch, height, width, channels)")
     if input.shape[3] != 3:
         raise ValueError(f"resize_bilinear_io takes RGB frames (C = 3), got C = {input.shape[3]}")
     if min(input.shape[1], input.shape[2]) < 1 or int(height) < 0 or int(width) < 0:
         raise ValueError(f"bad extents: in {tuple(input.shape)}, out {height} x {width}")
     _require_gpu("input", input)
-    if white_level is None:
-        white_level = _DEFAULT_WHITE[input.dtype]
     inp = input.detach().contiguous()
     B, Hin, Win, C = inp.shape
     out = torch.empty((B, int(height), int(width), C), dtype=torch.float32, device=inp.device)
@@ -1448,19 +1402,10 @@ def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coar
     the folded guide network (``guide_conv1``, ``guide_conv2``; ``fast_sigmoid`` / ``prescaled`` as in
     ``bilateral_slice_apply_io``); the curves guide belongs to the single-level models and is refused.  Cin = Cout = 3 with
     offset.  float32 in with float32 out is ``bilateral_slice_apply_upadd`` itself.  No autograd."""
-    if input.dim() != 4:
-        raise ValueError(f"Input image should be 4D (batch_size, height, width, input_channels), got {tuple(input.shape)}")
-    if input.dtype not in _DTYPE_CODE:
-        raise TypeError(f"input must be float32, uint8 or uint16, got {input.dtype}")
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+    input_white_level = _frame_head(input, input_white_level, out_dtype)
     if guide_curves is not None:
         raise ValueError("bilateral_slice_apply_upadd_io takes a guide map or the guide network: the curves guide has no "
                          "up-add form")
-    if (guide is None) == (guide_conv1 is None or guide_conv2 is None):
-        raise ValueError("give either a guide map or both guide_conv1 and guide_conv2")
-    if input_white_level is None:
-        input_white_level = _DEFAULT_WHITE[input.dtype]
     B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset)
     if (Cin, Cout) != (3, 3) or not has_offset:
         raise ValueError(f"bilateral_slice_apply_upadd_io supports Cin = Cout = 3 with offset, got Cin = {Cin}, "
@@ -1468,7 +1413,7 @@ def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coar
     _require_f32("coarse", coarse)
     if coarse.dim() != 4 or coarse.shape[0] != B or coarse.shape[3] != Cout or min(coarse.shape[1], coarse.shape[2]) < 1:
         raise ValueError(f"coarse should be [B, Hc, Wc, Cout] = [{B}, >= 1, >= 1, {Cout}], got {tuple(coarse.shape)}")
-    guide, c1, c2, n = _io_guide(guide, guide_conv1, guide_conv2, (B, H, W), Cin)
+    (guide, c1, c2), n = _guide_source(guide, guide_conv1, guide_conv2, None, None, False, (B, H, W), Cin)[1:]
     for nm, t in (("grid", grid), ("input", input), ("coarse", coarse)):
         _require_gpu(nm, t)
     grid, inp, coarse = grid.detach().contiguous(), input.detach().contiguous(), coarse.detach().contiguous()

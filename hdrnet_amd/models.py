@@ -582,6 +582,13 @@ class HDRNetCurves(nn.Module):
         arrays = self.guide.exported()
         return {"guide_curves": arrays, "curves_prepared": self.guide.prepared() if self.prepare_curves else None}
 
+    def _slice_apply_wire(self, op, lowres: torch.Tensor, *pixels, **kwargs):
+        """The tail of ``process`` / ``process_yuv``: the coefficient network on ``lowres``, its grid in the op's 5-D form,
+        then ``op(grid, *pixels, **kwargs)`` with this model's guide arguments."""
+        coeffs = self.coefficients(lowres)
+        gs = coeffs.shape
+        return op(coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), *pixels, **kwargs, **self._process_guide_args())
+
     def process(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
                 white_level: Optional[float] = None, pixel_format: Optional[str] = None) -> torch.Tensor:
         """Frame in, frame out (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on the device ->
@@ -617,11 +624,8 @@ class HDRNetCurves(nn.Module):
             lowres = data.lowres_input(frame, self.params["net_input_size"], white_level, pixel_format=pixel_format)
             if frame.dtype == torch.float32 and out_dtype == torch.float32:  # float32 is never scaled
                 return self.forward(lowres, frame)
-            coeffs = self.coefficients(lowres)
-            gs = coeffs.shape
-            return hdrnet_ops.bilateral_slice_apply_io(
-                coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), frame, input_white_level=white_level,
-                out_dtype=out_dtype, has_offset=True, pixel_format=pixel_format, **self._process_guide_args())
+            return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io, lowres, frame, input_white_level=white_level,
+                                          out_dtype=out_dtype, has_offset=True, pixel_format=pixel_format)
 
 
     # ---- YUV surface in, frame or NV12 surface out ------------------------------------------------------------------------
@@ -667,11 +671,9 @@ class HDRNetCurves(nn.Module):
         with torch.no_grad():
             to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, y.device)
             lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"])
-            coeffs = self.coefficients(lowres)
-            gs = coeffs.shape
-            return hdrnet_ops.bilateral_slice_apply_io_yuv(
-                coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), y, uv, to_rgb, out=out, out_dtype=out_dtype,
-                from_rgb=from_rgb if out == "nv12" else None, out_planes=out_planes, **self._process_guide_args())
+            return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv, lowres, y, uv, to_rgb, out=out,
+                                          out_dtype=out_dtype, from_rgb=from_rgb if out == "nv12" else None,
+                                          out_planes=out_planes)
 
 
 class HDRNetPointwiseNNGuide(HDRNetCurves):

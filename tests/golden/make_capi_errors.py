@@ -104,6 +104,71 @@ SEG_EXTENT_ROWS = [("H beyond 65535", dict(H=65536)), ("B beyond 65535", dict(B=
 PREP_EXTENT_ROWS = [("image too large", dict(Hs=16384, Ws=16384, H=16384, W=16384))]
 ADAM_ROWS = [("wrong extents", dict(n=0)), ("null buffer", dict(step=None)), ("misaligned pointer", dict(grad=Q))]
 
+# ---- the wire formats' other front ends: pixel formats, YUV surfaces, the pyramid model (their own headers)
+IO_PX = dict(IO, flags=0, input_format=1, output_format=1)          # uint8 BGR both ways
+CURVES_PX = dict(CURVES, input_dtype=1, input_white_level=255.0, output_dtype=1, input_format=3, output_format=3)  # BGRA
+LOWRES_PX = dict(frames=P, dtype=1, white_level=255.0, B=1, H=64, W=64, lowres=P, net_input_size=16, pixel_format=3)
+UPADD_IO = dict(UPADD, input_dtype=1, white_level=255.0, output_dtype=1, flags=0)
+RESIZE_IO = dict(input=P, input_dtype=1, white_level=255.0, out=P, B=1, Hin=2, Win=2, Hout=4, Wout=4, C=3)
+SURFACE = dict(y=P, uv=P, sample_dtype=1, pitch_y=8, pitch_uv=8, image_stride_y=32, image_stride_uv=16, B=1, H=4, W=8, to_rgb=P)
+RGB_OUT = dict(output_kind=1, out=P, out_uv=None, out_pitch_y=0, out_pitch_uv=0, out_image_stride_y=0, out_image_stride_uv=0,
+               from_rgb=None)
+NV12_OUT = dict(output_kind=2, out=P, out_uv=P, out_pitch_y=8, out_pitch_uv=8, out_image_stride_y=32, out_image_stride_uv=16,
+                from_rgb=P)
+IO_YUV = dict(SURFACE, grid=P, guide=P, GH=2, GW=2, GD=2, Cin=3, Cout=3, has_offset=1, guide_conv1=None, guide_conv2=None,
+              n_feats=0, guide_out=None, flags=0, **RGB_OUT)
+CURVES_YUV = dict(SURFACE, grid=P, GH=2, GW=2, GD=2, Cin=3, Cout=3, has_offset=1, guide_ccm=P, guide_shifts=P, guide_slopes=P,
+                  guide_mix=P, npts=16, prepared=None, guide_out=None, **RGB_OUT)
+NETWORK = dict(guide=None, guide_conv1=P, guide_conv2=P, n_feats=16)
+PRESCALED_ROWS = [("prescaled with a guide map", dict(flags=0x20000)),
+                  ("prescaled misaligned", dict(NETWORK, guide_conv1=Q, flags=0x30000))]
+# rows that break two rules which live in different steps of the front end: the text pins which one answers
+IO_TWO_RULES = [("unknown flags and dtype code", dict(flags=0x40000, input_dtype=3)),
+                ("null grid and missing guide", dict(grid=None, guide=None)),
+                ("channel counts and white level", dict(Cin=0, input_white_level=0.0)),
+                ("zero size with null buffers", dict(B=0, grid=None, guide=None, input=None, out=None)),
+                ("zero size and unknown flags", dict(B=0, flags=0x40000))]
+CURVES_TWO_RULES = [("knots and dtype code", dict(npts=0, input_dtype=5)), ("null buffer and misaligned tables", dict(grid=None, prepared=Q)),
+                    ("tables need Cin = 3", dict(Cin=1, Cout=1, input_format=0, output_format=0)),
+                    ("zero size and knots", dict(W=0, npts=0))]
+PX_FORMAT_ROWS = [("unknown pixel format", dict(input_format=4, output_format=4)), ("negative pixel format", dict(input_format=-1, output_format=-1)),
+                  ("unknown output format", dict(input_format=0, output_format=7, output_dtype=0)),
+                  ("float32 with BGR", dict(input_dtype=0, input_white_level=1.0)),
+                  ("float32 both ways with BGRA", dict(input_dtype=0, input_white_level=1.0, output_dtype=0, input_format=3, output_format=0)),
+                  ("u8 output format differs", dict(output_format=0)), ("u8 output format differs from RGB", dict(input_format=0)),
+                  ("f32 output not RGB", dict(output_dtype=0)),
+                  ("unknown pixel format and wrong extents", dict(input_format=4, GH=0)),
+                  ("unknown pixel format and W % 4", dict(input_format=4, W=6)),
+                  ("unknown pixel format and dtype code", dict(input_format=4, input_dtype=3)),
+                  ("zero size and unknown pixel format", dict(B=0, output_format=9))]
+PX_BUFFER_ROWS = [("W not a multiple of 4", dict(W=6)), ("W % 4 with RGB passes the format step", dict(W=6, H=65536, input_format=0, output_format=0)),
+                  ("4-channel alignment", dict(input_format=3, output_format=3, input=Q)),
+                  ("4-channel alignment of out", dict(input_format=2, output_format=2, out=0x1008)),
+                  ("4-channel u16 alignment", dict(input_format=3, output_format=3, input_dtype=2, input_white_level=65535.0, input=Q)),
+                  ("3-channel alignment", dict(input_format=1, output_format=1, input=0x1002)),
+                  ("not 3 -> 3", dict(Cin=4, Cout=4)), ("no offset", dict(has_offset=0)),
+                  ("null input and W % 4", dict(input=None, W=6))]
+SURFACE_ROWS = [("wrong extents", dict(B=-1)), ("null buffer", dict(y=None)), ("null uv plane", dict(uv=None)),
+                ("null constants", dict(to_rgb=None)), ("misaligned plane", dict(y=0x1002)), ("odd H", dict(H=5)),
+                ("W not a multiple of 4", dict(W=6)), ("pitch below row", dict(pitch_y=4)), ("uv pitch below row", dict(pitch_uv=4)),
+                ("u16 pitch below row", dict(sample_dtype=2, image_stride_y=64, image_stride_uv=32)),
+                ("pitch not a multiple of 4", dict(pitch_y=10)), ("uv pitch not a multiple of 4", dict(pitch_uv=14)),
+                ("image stride", dict(image_stride_y=30)), ("image stride below plane", dict(B=2, image_stride_y=16)),
+                ("sample dtype", dict(sample_dtype=0)), ("sample dtype 3", dict(sample_dtype=3)),
+                ("H beyond 65535", dict(H=65536)), ("B beyond 65535", dict(B=65536, H=2)), ("row beyond 2^31 bytes", dict(H=2, W=ROW_2G)),
+                ("odd H and sample dtype", dict(H=5, sample_dtype=0)), ("zero size", dict(B=0)),
+                ("zero size with null buffers", dict(B=0, y=None, uv=None, to_rgb=None))]
+YUV_IO_ROWS = SURFACE_ROWS + [
+    ("output kind", dict(output_kind=3)), ("negative output kind", dict(output_kind=-1)), ("channel counts", dict(Cin=4, Cout=4)),
+    ("output channel count", dict(Cout=4)), ("no offset", dict(has_offset=0)), ("null out", dict(out=None)),
+    ("misaligned f32 out", dict(output_kind=0, out=Q)), ("output pitch below row", dict(NV12_OUT, out_pitch_y=4)),
+    ("output pitch not a multiple of 4", dict(NV12_OUT, out_pitch_uv=10)), ("null output plane", dict(NV12_OUT, out_uv=None)),
+    ("null output constants", dict(NV12_OUT, from_rgb=None)), ("null grid", dict(grid=None)),
+    ("grid extents and odd H", dict(GH=0, H=5)), ("output kind and pitch", dict(output_kind=3, pitch_y=10)),
+    ("output kind and channel counts", dict(output_kind=3, Cin=4, Cout=4)), ("null out and null grid", dict(out=None, grid=None)),
+    ("zero size with a null NV12 output", dict(NV12_OUT, B=0, out=None, out_uv=None, from_rgb=None)),
+    ("W beyond 2^23", dict(H=2, W=WIDE, pitch_y=WIDE, pitch_uv=WIDE))]
+
 # function -> (base arguments by name, [(case, overrides)])
 TABLE = {
     "hdrnet_bilateral_slice_apply_f32": (APPLY, APPLY_ROWS + GENERIC_EXTENT_ROWS),
@@ -113,17 +178,25 @@ TABLE = {
     "hdrnet_bilateral_slice_apply_nnguide_f32": (NNG, NNG_ROWS + ROWS_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_nnguide_f32_ex": (NNG, NNG_ROWS + GUIDE_FLAG_ROWS + [
         ("prescaled needs Cin = 3", dict(flags=0x20000, Cin=1, Cout=1)), ("prescaled misaligned", dict(flags=0x30000, guide_conv1=Q))]
-        + ROWS_EXTENT_ROWS),
+        + ROWS_EXTENT_ROWS + [("unknown flags and feature count", dict(flags=0x40000, n_feats=0)),
+                              ("null buffer and prescaled misaligned", dict(grid=None, flags=0x20000, guide_conv2=Q))]),
     "hdrnet_bilateral_slice_apply_io_curves": (CURVES, CURVES_ROWS + SEG_EXTENT_ROWS),
     "hdrnet_curves_guide_prepare_f32": (
         dict(guide_shifts=P, guide_slopes=P, npts=16, Cin=3, prepared=P, prepared_bytes=1 << 20, usable={"int": 7}),
         [("wrong extents", dict(npts=17)), ("channel count", dict(Cin=1)), ("null buffer", dict(guide_slopes=None)),
          ("buffer too small", dict(prepared_bytes=64)), ("misaligned pointer", dict(prepared=Q)), ("nowhere to report", dict(usable=None))]),
     "hdrnet_bilateral_slice_apply_io_curves_prepared": (CURVES, CURVES_ROWS + [
-        ("misaligned tables", dict(prepared=Q)), ("too many knots for tables", dict(npts=20))] + SEG_EXTENT_ROWS),
+        ("misaligned tables", dict(prepared=Q)), ("too many knots for tables", dict(npts=20))] + SEG_EXTENT_ROWS + [
+        ("knots and dtype code", dict(npts=0, input_dtype=5)), ("null buffer and misaligned tables", dict(grid=None, prepared=Q)),
+        ("tables need Cin = 3", dict(Cin=1, Cout=1)), ("zero size and knots", dict(W=0, npts=0))]),
     "hdrnet_bilateral_slice_apply_upadd_f32": (UPADD, UPADD_ROWS + ROWS_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_upadd_f32_ex": (UPADD, UPADD_ROWS + GUIDE_FLAG_ROWS + [
-        ("prescaled with a guide map", dict(flags=0x20000))] + ROWS_EXTENT_ROWS),
+        ("prescaled with a guide map", dict(flags=0x20000))] + ROWS_EXTENT_ROWS + [
+        ("prescaled misaligned", dict(NETWORK, guide_conv1=Q, flags=0x30000)),
+        ("network without features", dict(NETWORK, n_feats=0)), ("unknown flags and coarse extents", dict(flags=0x40000, Hc=0)),
+        ("coarse extents and guide and network both", dict(Hc=0, guide_conv1=P)),
+        ("null buffer and prescaled with a guide map", dict(coarse=None, flags=0x20000)),
+        ("zero size and guide and network neither", dict(H=0, guide=None))]),
     "hdrnet_resize_bilinear_f32": (dict({"in": P}, out=P, B=1, Hin=4, Win=4, Hout=8, Wout=8, C=3),
                                    [("wrong extents", dict(Hin=0)), ("null buffer", dict(out=None)), ("channel count", dict(C=0)),
                                     ("zero size", dict(Hout=0))]),
@@ -173,7 +246,9 @@ TABLE = {
          ("misaligned workspace", dict(workspace=Q))]),
     "hdrnet_bilateral_slice_apply_io": (IO, IO_ROWS + SEG_EXTENT_ROWS),
     "hdrnet_bilateral_slice_apply_io_ex": (IO, IO_ROWS + GUIDE_FLAG_ROWS + [("prescaled with a guide map", dict(flags=0x20000))]
-                                           + SEG_EXTENT_ROWS),
+                                           + SEG_EXTENT_ROWS + [("prescaled misaligned", dict(NETWORK, guide_conv1=Q, flags=0x30000)),
+                                                                ("guide map and network both", dict(guide_conv1=P, guide_conv2=P, n_feats=16, H=65536))]
+                                           + IO_TWO_RULES),
     "hdrnet_bilateral_slice_apply_grad_f32": (GRAD, GRAD_ROWS),
     "hdrnet_bilateral_slice_apply_grad_f32_ex": (GRAD, GRAD_ROWS + FLAG_ROWS),
     "hdrnet_bilateral_slice_f32": (SLICE, SLICE_ROWS + GENERIC_EXTENT_ROWS),
@@ -204,6 +279,56 @@ TABLE = {
                                                    ("input too large", dict(batch=65535, in_height=65535, in_width=65535))]),
     "hdrnet_adam_step_f32": (ADAM, ADAM_ROWS),
     "hdrnet_adam_step_tf_f32": (ADAM, ADAM_ROWS),
+    # include/hdrnet_amd_pixel_formats.h
+    "hdrnet_bilateral_slice_apply_io_px": (IO_PX, IO_ROWS + GUIDE_FLAG_ROWS + PRESCALED_ROWS + PX_FORMAT_ROWS + PX_BUFFER_ROWS + [
+        ("missing guide and W % 4", dict(guide=None, W=6)),
+        ("W % 4 and prescaled misaligned", dict(NETWORK, W=6, guide_conv1=Q, flags=0x30000))] + IO_TWO_RULES + SEG_EXTENT_ROWS),
+    "hdrnet_bilateral_slice_apply_io_curves_px": (CURVES_PX, CURVES_ROWS + [
+        ("misaligned tables", dict(prepared=Q)), ("too many knots for tables", dict(npts=20))] + PX_FORMAT_ROWS + PX_BUFFER_ROWS + [
+        ("knots and unknown pixel format", dict(npts=0, input_format=4)), ("W % 4 and misaligned tables", dict(W=6, prepared=Q))]
+        + CURVES_TWO_RULES + SEG_EXTENT_ROWS),
+    "hdrnet_lowres_input_px": (LOWRES_PX, [
+        ("wrong extents", dict(H=0)), ("null buffer", dict(lowres=None)), ("null frames", dict(frames=None)),
+        ("dtype code", dict(dtype=7)), ("white level", dict(white_level=0.0)), ("misaligned pointer", dict(lowres=Q)),
+        ("zero size", dict(B=0)), ("batch too large", dict(B=65536)), ("image too large", dict(H=16384, W=16384)),
+        ("net input size", dict(net_input_size=0)), ("unknown pixel format", dict(pixel_format=4)),
+        ("negative pixel format", dict(pixel_format=-2)), ("float32 with BGR", dict(dtype=0, white_level=1.0, pixel_format=1)),
+        ("4-channel alignment", dict(frames=Q)), ("3-channel alignment", dict(frames=0x1002, pixel_format=1)),
+        ("RGB is hdrnet_lowres_input", dict(pixel_format=0, lowres=None)),
+        ("unknown pixel format and dtype code", dict(pixel_format=4, dtype=7)),
+        ("unknown pixel format and null buffer", dict(pixel_format=4, lowres=None)),
+        ("null buffer and white level", dict(lowres=None, white_level=0.0)),
+        ("zero size with null buffers", dict(B=0, frames=None, lowres=None))]),
+    # include/hdrnet_amd_yuv.h
+    "hdrnet_yuv_to_rgb_f32": (dict(SURFACE, rgb=P), SURFACE_ROWS + [("null rgb", dict(rgb=None)), ("misaligned rgb", dict(rgb=Q)),
+                                                                   ("null plane and null rgb", dict(uv=None, rgb=None))]),
+    "hdrnet_lowres_input_yuv": (dict(SURFACE, lowres=P, net_input_size=4), SURFACE_ROWS + [
+        ("null lowres", dict(lowres=None)), ("misaligned lowres", dict(lowres=Q)), ("net input size", dict(net_input_size=0)),
+        ("empty frame", dict(H=0)), ("net input size and null plane", dict(net_input_size=0, y=None))]),
+    "hdrnet_bilateral_slice_apply_io_yuv": (IO_YUV, YUV_IO_ROWS + GUIDE_FLAG_ROWS + PRESCALED_ROWS + [
+        ("neither guide nor network", dict(guide=None)), ("network without features", dict(NETWORK, n_feats=0)),
+        ("unknown flags and odd H", dict(flags=0x40000, H=5)), ("unknown flags and sample dtype", dict(flags=0x40000, sample_dtype=0)),
+        ("null grid and missing guide", dict(grid=None, guide=None)), ("missing guide and null out", dict(guide=None, out=None)),
+        ("zero size and unknown flags", dict(B=0, flags=0x40000))]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv": (CURVES_YUV, YUV_IO_ROWS + [
+        ("knots", dict(npts=0)), ("knots and odd H", dict(npts=0, H=5)), ("knots and wrong extents", dict(npts=0, GD=0)),
+        ("null curves parameter", dict(guide_mix=None)), ("misaligned tables", dict(prepared=Q)),
+        ("too many knots for tables", dict(prepared=P, npts=20)), ("null grid and misaligned tables", dict(grid=None, prepared=Q)),
+        ("null out and misaligned tables", dict(out=None, prepared=Q)), ("zero size and knots", dict(B=0, npts=0))]),
+    # include/hdrnet_amd_pyramid_io.h
+    "hdrnet_resize_bilinear_io": (RESIZE_IO, [
+        ("wrong extents", dict(Hin=0)), ("null buffer", dict(out=None)), ("null input", dict(input=None)), ("channel count", dict(C=4)),
+        ("dtype code", dict(input_dtype=3)), ("white level", dict(white_level=0.0)), ("white level not finite", dict(white_level=INF)),
+        ("input too large", dict(B=65535, Hin=65535, Win=65535)), ("misaligned input", dict(input=ODD)),
+        ("misaligned out", dict(out=0x1002)), ("zero size", dict(Hout=0)), ("channel count and dtype code", dict(C=1, input_dtype=-1))]),
+    "hdrnet_bilateral_slice_apply_upadd_io_ex": (UPADD_IO, UPADD_ROWS + GUIDE_FLAG_ROWS + PRESCALED_ROWS + [
+        ("dtype code", dict(input_dtype=3)), ("output dtype code", dict(output_dtype=2)), ("white level", dict(white_level=0.0)),
+        ("channel counts", dict(Cin=0)), ("network without features", dict(NETWORK, n_feats=0)),
+        ("unknown flags and dtype code", dict(flags=0x40000, input_dtype=3)), ("dtype code and coarse extents", dict(output_dtype=2, Wc=-2)),
+        ("coarse extents and guide and network both", dict(Hc=0, guide_conv1=P)),
+        ("null buffer and prescaled with a guide map", dict(coarse=None, flags=0x20000)),
+        ("zero size and guide and network neither", dict(H=0, guide=None)),
+        ("float32 both ways is the float op", dict(input_dtype=0, white_level=1.0, output_dtype=0, H=1, W=WIDE))] + SEG_EXTENT_ROWS),
     "hdrnet_prepare_batch": (PREP, PREP_COMMON + [
         ("crop does not fit", dict(H=16)), ("crop does not fit turned", dict(Ws=16, W=12)),
         ("identity needs the whole image", dict(ops=None)), ("misaligned ops", dict(ops=ODD))] + PREP_EXTENT_ROWS),
@@ -218,7 +343,7 @@ NO_TEXT = ("hdrnet_l2_loss_with_grad_f32", "hdrnet_l2_loss_grad_scale_f32", "hdr
 
 def parameter_names():
     src = ""
-    for h in ("hdrnet_amd.h", "hdrnet_amd_train.h"):
+    for h in ("hdrnet_amd.h", "hdrnet_amd_train.h", "hdrnet_amd_pixel_formats.h", "hdrnet_amd_yuv.h", "hdrnet_amd_pyramid_io.h"):
         src += re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
     src = re.sub(r"//[^\n]*", "", src)
     out = {}
@@ -252,7 +377,8 @@ def call(lib, fn, args):
     """(rc, error text, kernel name) of one fixture row on `lib` (argtypes as hdrnet_amd._lib declares them)."""
     from hdrnet_amd import _lib
     table = dict(_lib.SIGNATURES)
-    table.update(_lib.TRAIN_SIGNATURES)
+    for more in (_lib.TRAIN_SIGNATURES, _lib.PIXEL_FORMAT_SIGNATURES, _lib.YUV_SIGNATURES, _lib.PYRAMID_IO_SIGNATURES):
+        table.update(more)
     f = getattr(lib, fn)
     f.restype, f.argtypes = table[fn]
     lib.hdrnet_last_error.restype = lib.hdrnet_last_kernel.restype = ctypes.c_char_p

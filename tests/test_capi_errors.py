@@ -1,7 +1,8 @@
 """Argument validation of the C-ABI, row by row: every entry point that returns a status answers a table of
 deliberately wrong and deliberately empty calls with the return code and the complete hdrnet_last_error() text
 recorded in tests/golden/capi_errors.json (tests/golden/make_capi_errors.py: recorded from the library before the
-front-end's tails were folded into shared helpers), and a legal no-op names the kernel "noop".
+front-end's tails, and later the wire-format forwards' argument rules, were folded into shared helpers), and a legal
+no-op names the kernel "noop".
 
 Validation happens before any HIP call, so this runs without a GPU; no row validates fully (the generator refuses
 to record one that does), so none reaches one where there is a GPU."""
@@ -30,11 +31,13 @@ def lib():
 
 
 def test_table_covers_every_status_entry_point():
-    """>= 3 rows per function of the two binding tables that returns a status: wrong extents, a null buffer and a
-    case of its own; the fixture is the generator's table, row for row."""
+    """>= 3 rows per function of the five binding tables (the coefficient network's training tables have tests of their
+    own) that returns a status: wrong extents, a null buffer and a case of its own; the fixture is the generator's
+    table, row for row."""
     from hdrnet_amd import _lib
     table = dict(_lib.SIGNATURES)
-    table.update(_lib.TRAIN_SIGNATURES)
+    for more in (_lib.TRAIN_SIGNATURES, _lib.PIXEL_FORMAT_SIGNATURES, _lib.YUV_SIGNATURES, _lib.PYRAMID_IO_SIGNATURES):
+        table.update(more)
     status = sorted(n for n, (res, _) in table.items() if res is ctypes.c_int and n != "hdrnet_version")
     assert sorted(gen.TABLE) == status
     assert [(r["fn"], r["case"]) for r in ROWS] == [(fn, case) for fn, (_, cases) in gen.TABLE.items() for case, _ in cases]
