@@ -405,6 +405,13 @@ int variant(unsigned flags) { return (int)((flags >> 8) & 0xffu); }
 int grad_dispatch(const hdrnet_amd::ApplyGradArgs& a, unsigned family, hipStream_t s) {
   using namespace hdrnet_amd;
   const char* what = a.slice ? "BilateralSliceGrad" : "BilateralSliceApplyGrad";
+#ifdef HDRNET_TOOLS_BUILD
+  // an A/B script must not time the product pass against itself under a number whose kernel is gone
+  if (a.variant != 0 && a.variant != 3 && a.variant != 11)
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "gradient kernel variant %d is not in this library: variants 2 and 4..10 were retired with their "
+                "kernels, 0, 3 and 11 remain (include/hdrnet_amd_tools.h)", a.variant);
+#endif
   if (!a.dgrid && !a.dguide && !a.dinput) return finish_noop();
   const long long npix = (long long)a.B * a.H * a.W;
   if (npix == 0) {
@@ -490,10 +497,7 @@ void hdrnet_enable_kernel_names(int on) { g_kernel_names.store(on ? 1 : 0, std::
 // tools build only (include/hdrnet_amd_tools.h)
 void hdrnet_tools_set_knob(int idx, int value) { hdrnet_amd::tools_set_knob(idx, value); }
 
-void hdrnet_tools_set_trace(void* device_buf) {
-  hdrnet_amd::grid_grad_set_trace(static_cast<long long*>(device_buf));
-  hdrnet_amd::coeff_net_set_trace(static_cast<long long*>(device_buf));
-}
+void hdrnet_tools_set_trace(void* device_buf) { hdrnet_amd::coeff_net_set_trace(static_cast<long long*>(device_buf)); }
 #endif
 
 // Forward, whole frames (H_total = rows, y0 = 0) or one row band of every frame.

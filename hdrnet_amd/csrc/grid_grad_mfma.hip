@@ -57,50 +57,8 @@ using rows::vjp_blend;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// SPLIT operands (tools variant 2): an f32 value x travels as ONE dword {hi, lo} of two bf16.  Two values at once
-// (round 5; round 2's form took 4 instructions per value): hi = the upper 16 bits (truncation, so the remainder x - hi
-// is exact), lo = the remainder ROUNDED to bf16 (v_cvt_pk_bf16_f32, both values in one instruction): x = hi + lo to
-// 2^-17 relative, unbiased (a truncated lo -- 3 instructions per value, another 2-5 % faster -- biases every product by
-// ~-1e-5).  Per pair: 2 v_and, 1 v_pk_add (negated), 1 cvt, 2 v_perm.
-typedef float f32x2_sp __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_sp __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2_sp split_pack2(f32x2_sp x) {
-  const unsigned u0 = __float_as_uint(x.x), u1 = __float_as_uint(x.y);
-  const f32x2_sp hi = {__uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 & 0xffff0000u)};
-  const f32x2_sp lo = x - hi;
-  const unsigned lp = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2_sp));  // {bf16(lo0), bf16(lo1)}
-  return f32x2_sp{__uint_as_float(__builtin_amdgcn_perm(lp, u0, 0x05040302u)),   // {u0[31:16], lp[15:0]}
-                  __uint_as_float(__builtin_amdgcn_perm(lp, u1, 0x07060302u))};  // {u1[31:16], lp[31:16]}
-}
-
-__device__ __forceinline__ float split_pack(float x) { return split_pack2(f32x2_sp{x, x}).x; }
-
-// SPLIT = 2 (tools variant 10, round 6): the f16 form with fp32-grade products.  x travels as one dword {hi, lo'} of two
-// f16: hi = f16(x) (round to nearest: the remainder x - hi is exact in f32), lo' = f16((x - hi) * 2^11) -- the remainder
-// re-scaled into f16's normal range, so hi + 2^-11 lo' carries ~22 bits.  [a_hi, 0] x [v_hi, v_lo'] accumulates hi hi into
-// one tile, [a_hi, a_lo'] x [v_lo', v_hi] (the dword rotated) the two cross terms hi lo' + lo' hi into a second; the row
-// fold combines them as acc0 + 2^-11 acc1.  The dropped lo' lo' term is 2^-22 relative.  Per pair: 2 cvt_pk, 2 cvt back,
-// 1 v_pk_add, 1 v_pk_mul, 2 v_perm = 4 per value.  RANGE: f16 holds 6e-8 .. 65504 -- V = dout x [in; 1] of a real
-// training step (dout ~ 1 / pixels ~ 1e-7) sits in f16's denormals, where hi keeps a few bits and only lo' is normal:
-// ~12 bits in all (measured: profiles/r06/bwd_steps.md).  An experiment, not a product path.
-typedef _Float16 f16x2_sp __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x2_sp split_pack2_f16(f32x2_sp x) {
-  const f16x2_sp h = __builtin_convertvector(x, f16x2_sp);
-  const f32x2_sp hf = __builtin_convertvector(h, f32x2_sp);
-  const f32x2_sp r = (x - hf) * f32x2_sp{2048.0f, 2048.0f};
-  const f16x2_sp l = __builtin_convertvector(r, f16x2_sp);
-  const unsigned hp = __builtin_bit_cast(unsigned, h), lp = __builtin_bit_cast(unsigned, l);
-  return f32x2_sp{__uint_as_float(__builtin_amdgcn_perm(lp, hp, 0x05040100u)),   // {lp[15:0], hp[15:0]}: hi in the low half
-                  __uint_as_float(__builtin_amdgcn_perm(lp, hp, 0x07060302u))};  // {lp[31:16], hp[31:16]}
-}
-
 constexpr int kWaves = 4;      // waves per workgroup; they share ONE task and split its rows
 constexpr int kTileFloats = 3 * 16 * 16;  // partial tile: [rel 3][k 16][c 16]
-constexpr int kTraceChunks = 16;          // tools phase trace: chunks recorded per workgroup
 
 struct GGParams {
   const float* guide;
@@ -114,7 +72,6 @@ struct GGParams {
   int rg, nyg;
   long long ntasks;
   float scale_x, scale_y;  // GW / W, GH / H  (forward's expressions)
-  long long* trace;        // tools variant 9 (ABL 6): per-chunk phase stamps of wave 0, [task][kTraceChunks][5]
 };
 
 // LDS traffic of ONE wave needs no fence: the LDS executes a wave's instructions in order, so
@@ -187,15 +144,6 @@ __device__ __forceinline__ void buf_load(__amdgpu_buffer_rsrc_t rs, unsigned byt
 
 constexpr int kTStride = 68;  // floats per operand row: 64 pixels + 4 (16-B aligned, 4-bank skew)
 
-// SPLIT = true (tools variant 2): the contraction runs on the bf16 matrix pipe (v_mfma_f32_16x16x32_bf16, 16x the
-// f32-input rate) with every f32 operand split into two bf16 terms (split_pack2 above).  A K-slot pair is one pixel's
-// {hi, lo}: [a_hi, a_lo] x [v_hi, v_lo] gives hi hi + lo lo, the same A against the dword ROTATED by 16 bits gives the
-// two cross terms -- all four products, f32 accumulate.  Per 64-pixel chunk 8 MFMAs of ~17 cycles instead of 16 of 32,
-// for 3.5 VALU per staged value + one rotate per B dword (72 per chunk; round 2's form: 96, and no gain).  Measured in
-// round 5 (profiles/r05/bwd_steps.md): dgrid -8 %, dgrid + dguide -4 %, all three -2 % at 4K -- and 6e-6 of dgrid's
-// scale away from the exact-f32 contraction, as much as the summation-order noise the parity bar (1e-5 x scale) is set
-// against.  Not the product for that reason; the product's contraction is bit-equal to an fmaf chain.
-//
 // WG / WI (FUSED BACKWARD): the same pass also produces the per-pixel VJPs -- dguide (WG) and dinput
 // (WI), bilateral_slice_apply.cc:140-259 -- from the pixel data it has loaded anyway (guide, input,
 // dout are read ONCE for all three gradients: 28 B/px in, 16 B/px out, instead of two kernels reading
@@ -216,17 +164,16 @@ constexpr int kTStride = 68;  // floats per operand row: 64 pixels + 4 (16-B ali
 // tiles; stage 2 runs once per window.  Each launch re-reads the pixels (2 x 28 B/px): a shape outside the reference's
 // configurations, kept off the ~100 x slower generic gather rather than tuned.  dgrid only (the fused VJPs read whole
 // coefficient vectors).
-template <int CIN, int COUT, bool OFFSET, bool APPLY, int SPLIT, bool WG = false, bool WI = false, int ABL = 0, int NH = 1, int CW = 0>
+template <int CIN, int COUT, bool OFFSET, bool APPLY, bool WG = false, bool WI = false, int NH = 1, int CW = 0>
 __global__ __launch_bounds__(kWaves * 64)
-__attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET ? 1 : 0) : 1) <= 12) ? ((NH == 1 && SPLIT == 0) ? 4 : 3) : 1))) void grid_grad_stage1(GGParams p) {
+__attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET ? 1 : 0) : 1) <= 12) ? (NH == 1 ? 4 : 3) : 1))) void grid_grad_stage1(GGParams p) {
   constexpr int CJ = APPLY ? CIN + (OFFSET ? 1 : 0) : 1;
   constexpr int CFULL = COUT * CJ;
   constexpr int C0 = 16 * CW;                                  // first grid channel of this window
   constexpr int C = CFULL - C0 < 16 ? CFULL - C0 : 16;         // columns of this window's tile
   static_assert(C >= 1 && C <= 16 && CFULL <= 32, "one 16-column MFMA tile per window, two windows");
-  static_assert(CFULL <= 16 || (!WG && !WI && SPLIT == 0 && ABL == 0 && APPLY), "channel windows: apply dgrid only");
+  static_assert(CFULL <= 16 || (!WG && !WI && APPLY), "channel windows: apply dgrid only");
   static_assert(NH == 1 || NH == 2, "8 or 16 planes");
-  static_assert(NH == 1 || (!SPLIT && ABL == 0), "the tools variants exist for GD <= 8 only");
   constexpr bool FUSED = WG || WI;
   static_assert(!FUSED || C % 4 == 0, "fused backward: float4 coefficient vectors");
   static_assert(!WI || (APPLY && CIN > 0), "dinput needs an input");
@@ -243,7 +190,6 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
   constexpr int kSlabOps = (16 + C) * kTStride + kImg;  // floats per wave: A^T [16][68], V^T [C][68], image
   constexpr int kSlab = kSlabOps >= NH * kTileFloats ? kSlabOps : NH * kTileFloats;  // the final reduction reuses the slabs
   __shared__ __attribute__((aligned(16))) float lds[kWaves * kSlab];
-  if constexpr (ABL == 5) return;  // tools ablation: the launch alone
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   float* at = lds + wave * kSlab;    // A^T[k][px]
@@ -321,7 +267,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
     float g[kBatch], in[kBatch][CIN_Q], d[kBatch][COUT];
   };
   const int nrows = (y_end - (y_first + wave) + kWaves - 1) / kWaves;
-  const int nbt = (ABL != 3 && span > 0 && nrows > 0) ? nrows * nbr : 0;  // ABL 3: prologue + epilogue only
+  const int nbt = (span > 0 && nrows > 0) ? nrows * nbr : 0;
   // (row, batch in row) of the next batch to load / to contract: advanced incrementally -- `t / nbr` is an
   // integer division by a run-time value, ~20 instructions each on this target
   int ld_y = y_first + wave, ld_bi = 0;
@@ -359,12 +305,12 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
 
   // kAhead batches are in flight beyond the one being contracted (a ring of kAhead + 1 register sets, the
   // loop unrolled over it).  Two ahead in the fused pass measured the same as one (118.5 vs 120 us all
-  // three, 101 vs 101 us dgrid + dguide at 4K; profiles/r02/exp21): what tools variant 4 removes is the
-  // exposed first load of every wave, not a too-short steady-state distance.
+  // three, 101 vs 101 us dgrid + dguide at 4K; profiles/r02/exp21): what the load-once ablation removed (DESIGN.md
+  // section 4.2) was the exposed first load of every wave, not a too-short steady-state distance.
   constexpr int kAhead = 1;
   Batch ring[kAhead + 1];
   load_batch(ring[0], nbt > 0);  // issued first: the rest of the prologue runs under its latency
-  if constexpr (kAhead > 1 && ABL != 1 && ABL != 4) load_batch(ring[1], nbt > 1);
+  if constexpr (kAhead > 1) load_batch(ring[1], nbt > 1);
   // fused: this lane's element of the two grid rows the coefficient image blends.  They change only when
   // gy0 does (once per cell height), so they stay in registers across the wave's rows.
   f32x4 sa[NSLOT], sb[NSLOT];
@@ -402,9 +348,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
   int row_gy0 = 0;
   float row_wy0 = 0.0f, row_wy1 = 0.0f;
   auto process = [&](int t, const Batch& cur, Batch& refill) {
-    if constexpr (ABL != 1 && ABL != 4) {  // (tools ablation 1 / 4: the first batch is all a wave ever loads)
-      load_batch(refill, t + kAhead < nbt);  // always issued (see load_batch)
-    }
+    load_batch(refill, t + kAhead < nbt);  // always issued (see load_batch)
     if (t >= nbt) return;  // a padding step of the unrolled ring: it only keeps the VMEM count uniform
     const int y = pr_y, bi = pr_bi;
     if (++pr_bi == nbr) {
@@ -488,8 +432,6 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
     for (int cb = 0; cb < kBatch; ++cb) {
       const int x0 = xb + 64 * cb;
       if (x0 < x_hi) {  // wave-uniform
-        [[maybe_unused]] long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0;
-        if constexpr (ABL == 6) ts0 = clock64();
         const int ci = bi * kBatch + cb;  // chunk in row, wave-uniform
         float dx;
         if (ci == 0) dx = dxc[0];
@@ -670,9 +612,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
         // (NH = 2: plane z lives in row z & 7 of half z >> 3's tile; the scatter itself happens per live half, below)
         float* aP = at + __umul24((unsigned)(NH == 1 ? zP : (zP & 7)), (unsigned)kTStride) + lane;
         float* aQ = at + __umul24((unsigned)(NH == 1 ? zQ : (zQ & 7)), (unsigned)kTStride) + lane;
-        auto enc2 = [](f32x2 v) { return SPLIT == 1 ? f32x2(split_pack2(v)) : SPLIT == 2 ? f32x2(split_pack2_f16(v)) : v; };
-        auto enc = [&](float v) { return SPLIT ? enc2(f32x2{v, v}).x : v; };
-        const f32x2 q2 = enc2(f32x2{w0, w1} * f32x2{wQ, wQ}), p2 = enc2(f32x2{w0, w1} * f32x2{wP, wP});
+        const f32x2 q2 = f32x2{w0, w1} * f32x2{wQ, wQ}, p2 = f32x2{w0, w1} * f32x2{wP, wP};
         if constexpr (NH == 1) {
           aQ[0] = q2.x;
           aQ[8 * kTStride] = q2.y;
@@ -683,7 +623,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
         if constexpr (UPAIRS) {
 #pragma unroll
           for (int i = 0; i < COUT; ++i) {
-            const f32x2 e01 = enc2(U01[i]), e23 = enc2(U23[i]);
+            const f32x2 e01 = U01[i], e23 = U23[i];
             vt[(i * CJ + 0) * kTStride + lane] = e01.x;
             vt[(i * CJ + 1) * kTStride + lane] = e01.y;
             vt[(i * CJ + 2) * kTStride + lane] = e23.x;
@@ -697,12 +637,12 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
               const int c = i * CJ + j;  // (compile-time after unrolling: only this window's channels are staged)
               if (c >= C0 && c < C0 + C)
                 vt[(c - C0) * kTStride + lane] =
-                    enc((j < CIN) ? cur.d[cb][i] * cur.in[cb][j < CIN ? j : 0] : cur.d[cb][i]);
+                    (j < CIN) ? cur.d[cb][i] * cur.in[cb][j < CIN ? j : 0] : cur.d[cb][i];
             }
           }
         } else {
 #pragma unroll
-          for (int c = 0; c < C; ++c) vt[c * kTStride + lane] = enc(cur.d[cb][c]);
+          for (int c = 0; c < C; ++c) vt[c * kTStride + lane] = cur.d[cb][c];
         }
         wave_lds_order();
         // D[k, c] += sum_px A[k, px] * V[px, c]; two accumulators break the dependent-issue chain.
@@ -723,51 +663,16 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
 #define HDRNET_GG_OUT(x) "=&v"(x)
 #define HDRNET_GG_INOUT(x) "+v"(x)
         auto contract = [&](f32x4& dacc, f32x4& dacc2) {
-          if constexpr (SPLIT != 0) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-              const f32x4 a4 = {av[2 * q][0], av[2 * q][1], av[2 * q + 1][0], av[2 * q + 1][1]};
-              const f32x4 b4 = {bv[2 * q][0], bv[2 * q][1], bv[2 * q + 1][0], bv[2 * q + 1][1]};
-              const u32x4_t vb = __builtin_bit_cast(u32x4_t, b4);
-              // [a_hi, a_lo] x [v_hi, v_lo] = hi hi + lo lo, then x the ROTATED dword [v_lo, v_hi] = the two cross terms:
-              // all four products, one v_alignbit per B dword (round 2: three products, a perm and a shift per dword)
-              u32x4_t br;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) br[e] = __builtin_amdgcn_alignbit(vb[e], vb[e], 16);
-              if constexpr (SPLIT == 1) {
-                const bf16x8 a8 = __builtin_bit_cast(bf16x8, a4);
-                dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8, __builtin_bit_cast(bf16x8, vb), dacc, 0, 0, 0);
-                dacc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8, __builtin_bit_cast(bf16x8, br), dacc2, 0, 0, 0);
-              } else {
-                // f16 hi / lo': dacc takes hi hi alone ([a_hi, 0]: the lo' lo' product has the wrong scale), dacc2 the
-                // cross terms (scale 2^-11, applied at the row fold)
-                const u32x4_t ua = __builtin_bit_cast(u32x4_t, a4);
-                const u32x4_t ah = {ua[0] & 0xffffu, ua[1] & 0xffffu, ua[2] & 0xffffu, ua[3] & 0xffffu};
-                dacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, vb), dacc, 0, 0, 0);
-                dacc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ua), __builtin_bit_cast(f16x8, br), dacc2, 0, 0, 0);
-              }
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if constexpr (ABL == 2 || ABL == 4) {  // tools ablation: no MFMAs
-                dacc[0] += av[e][0] * bv[e][0];
-                dacc2[0] += av[e][1] * bv[e][1];
-                continue;
-              }
-              dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e][0], bv[e][0], dacc, 0, 0, 0);
-              dacc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e][1], bv[e][1], dacc2, 0, 0, 0);
-            }
+          for (int e = 0; e < 4; ++e) {
+            dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e][0], bv[e][0], dacc, 0, 0, 0);
+            dacc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e][1], bv[e][1], dacc2, 0, 0, 0);
           }
         };
-        if constexpr (ABL == 6) ts1 = clock64();  // VALU phase + staging writes issued
         if constexpr (NH == 1) {
           HDRNET_GG_READS(0, HDRNET_GG_OUT);
-          if constexpr (ABL == 6) ts2 = clock64();  // first half's operands have arrived
           contract(dacc[0], dacc2[0]);
           HDRNET_GG_READS(64, HDRNET_GG_INOUT);
-          if constexpr (ABL == 6) ts3 = clock64();  // first half's MFMAs issued, second half's operands arrived
           contract(dacc[0], dacc2[0]);
           wave_lds_order();
           aQ[0] = 0.0f;
@@ -803,13 +708,6 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
 #undef HDRNET_GG_READS
 #undef HDRNET_GG_OUT
 #undef HDRNET_GG_INOUT
-        if constexpr (ABL == 6) {
-          const int nch = t * kBatch + cb;  // chunk ordinal of this wave
-          if (wave == 0 && lane == 0 && nch < kTraceChunks) {
-            long long* tr = p.trace + ((size_t)task * kTraceChunks + nch) * 5;
-            tr[0] = ts0; tr[1] = ts1; tr[2] = ts2; tr[3] = ts3; tr[4] = clock64();
-          }
-        }
         if constexpr (WI) __builtin_amdgcn_sched_barrier(0);  // chunk by chunk: keeps the live set of one
       }
     }
@@ -823,8 +721,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
       const int rel1 = clamp_index(gy0 + 1, 0, p.GH - 1) - gy_base;
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        if constexpr (SPLIT == 2) dacc[h] += 0x1p-11f * dacc2[h];  // hi hi + 2^-11 (hi lo' + lo' hi)
-        else dacc[h] += dacc2[h];
+        dacc[h] += dacc2[h];
 #pragma unroll
         for (int rr = 0; rr < 3; ++rr) {
           const float sr = (rel0 == rr ? wy0 : 0.0f) + (rel1 == rr ? wy1 : 0.0f);
@@ -835,9 +732,7 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
       }
     }
   };
-  if constexpr (ABL == 1 || ABL == 4) {
-    for (int t = 0; t < nbt; ++t) process(t, ring[0], ring[0]);
-  } else if constexpr (kAhead == 1) {
+  if constexpr (kAhead == 1) {
     for (int t = 0; t < nbt; t += 2) {
       process(t, ring[0], ring[1]);
       process(t + 1, ring[1], ring[0]);
@@ -1044,21 +939,18 @@ void warn_small_workspace(size_t have, size_t need) {
           "grid-gradient kernel, which is ~100x slower\n", have, need);
 }
 
-long long* g_gg_trace = nullptr;  // tools: phase-trace buffer (grid_grad_set_trace)
-
 // Workgroups of `kfn` resident on the device at once (occupancy x CUs).  Queried once per kernel.
 typedef void (*Stage1Fn)(GGParams);
 
-long long resident_slots(Stage1Fn kfn, std::atomic<int>* cache, size_t dyn_lds = 0) {
-  if (dyn_lds) cache = nullptr;  // (tools: an occupancy experiment -- never cached)
-  int occ = cache ? cache->load(std::memory_order_relaxed) : 0;
+long long resident_slots(Stage1Fn kfn, std::atomic<int>* cache) {
+  int occ = cache->load(std::memory_order_relaxed);
   if (occ <= 0) {
     occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kfn), kWaves * 64, dyn_lds) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kfn), kWaves * 64, 0) !=
             hipSuccess || occ <= 0)
       occ = 1;
     if (occ > kMaxOcc) occ = kMaxOcc;  // the workspace bound (gg_ws_bound) covers 1 .. kMaxOcc
-    if (cache) cache->store(occ, std::memory_order_relaxed);
+    cache->store(occ, std::memory_order_relaxed);
   }
   return (long long)occ * rows::num_cus();  // CU count of the CURRENT device (cached per ordinal)
 }
@@ -1068,84 +960,49 @@ struct GGPtrs {
   float *dgrid, *dguide, *dinput;
 };
 
+// Stage 1 into p.partial, then stage 2 from it into channels c0 .. c0 + cw - 1 of the grid's C: the whole tile
+// (c0 = 0, cw = 16) or one channel window of two.  NH: the plane halves `kfn` was instantiated for.
+template <int NH>
+hipError_t gg_run(Stage1Fn kfn, const GGParams& p, int B, float* dgrid, int C, int c0, int cw, hipStream_t s) {
+  const dim3 nblocks((unsigned)(p.GW + 1), (unsigned)p.nyg, (unsigned)B);
+  kfn<<<nblocks, kWaves * 64, 0, s>>>(p);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 ncols((unsigned)p.GW, (unsigned)p.GH, (unsigned)B);
+  grid_grad_stage2<NH><<<ncols, 512, 0, s>>>(p.partial, dgrid, p.GH, p.GW, p.GD, C, p.rg, p.nyg, p.scale_y, c0, cw);
+  return hipGetLastError();
+}
+
 template <int CIN, int COUT, bool OFFSET, bool APPLY>
 hipError_t gg_launch(const GGPtrs& q, int B, int H, int W, int GH, int GW, int GD, void* ws, size_t ws_bytes,
-                     hipStream_t s, int split, int ablate = 0) {
+                     hipStream_t s) {
   constexpr int C = APPLY ? COUT * (CIN + (OFFSET ? 1 : 0)) : COUT;
   const bool wg = q.dguide != nullptr, wi = q.dinput != nullptr;
-  Stage1Fn kfn = nullptr;
-  std::atomic<int>* occ = nullptr;
-  static std::atomic<int> occ_cache[16];  // per (plane halves, split, dguide, dinput) of this shape
-#ifdef HDRNET_TOOLS_BUILD
-  if constexpr (APPLY && CIN == 3 && COUT == 3 && OFFSET) {  // ablations (tools variants 4 .. 8): timing only
-    if (ablate >= 1 && ablate <= 6) {
-      if (ablate == 6 && !g_gg_trace) return hipErrorInvalidValue;
-#define GG_ABL(A)                                                                              \
-  (wg && wi ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0, true, true, A>       \
-            : wg ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0, true, false, A> \
-                 : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0, false, false, A>)
-      kfn = ablate == 1 ? GG_ABL(1) : ablate == 2 ? GG_ABL(2) : ablate == 3 ? GG_ABL(3) : ablate == 4 ? GG_ABL(4) : ablate == 5 ? GG_ABL(5) : GG_ABL(6);
-#undef GG_ABL
-    }
-  }
-#endif
   const bool two = GD > 8;  // NH = 2: planes 8 .. 15 in a second tile per task
-  if (two && (split || kfn)) return hipErrorNotSupported;  // the tools variants exist for GD <= 8 only
-  if (!kfn) {
-    occ = &occ_cache[(two ? 12 : 4 * split) + (wg ? 2 : 0) + (wi ? 1 : 0)];
-    if constexpr (C % 4 == 0) {
-      constexpr bool CAN_WI = APPLY && CIN > 0;
-      if (wi && !CAN_WI) return hipErrorInvalidValue;
-#define GG_PICK(SPL, NH)                                                                              \
-  (wg && wi ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, SPL, true, CAN_WI, 0, NH>          \
-            : wg ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, SPL, true, false, 0, NH>      \
-                 : wi ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, SPL, false, CAN_WI, 0, NH> \
-                      : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, SPL, false, false, 0, NH>)
-#ifdef HDRNET_TOOLS_BUILD  // the split contractions are experiments: not in the product library
-      kfn = two ? GG_PICK(0, 2) : split == 1 ? GG_PICK(1, 1) : split == 2 ? GG_PICK(2, 1) : GG_PICK(0, 1);
-#else
-      if (split) return hipErrorNotSupported;
-      kfn = two ? GG_PICK(0, 2) : GG_PICK(0, 1);
-#endif
+  Stage1Fn kfn = nullptr;
+  static std::atomic<int> occ_cache[8];  // per (plane halves, dguide, dinput) of this shape
+  if constexpr (C % 4 == 0) {
+    constexpr bool CAN_WI = APPLY && CIN > 0;
+    if (wi && !CAN_WI) return hipErrorInvalidValue;
+#define GG_PICK(NH)                                                                           \
+  (wg && wi ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, true, CAN_WI, NH>          \
+            : wg ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, true, false, NH>      \
+                 : wi ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, false, CAN_WI, NH> \
+                      : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, false, false, NH>)
+    kfn = two ? GG_PICK(2) : GG_PICK(1);
 #undef GG_PICK
-    } else {
-      if (wg || wi) return hipErrorInvalidValue;  // fused VJPs read the coefficient image as float4
-#ifdef HDRNET_TOOLS_BUILD
-      kfn = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0, false, false, 0, 2>
-                : split == 1 ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 1>
-                : split == 2 ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 2>
-                             : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0>;
-#else
-      if (split) return hipErrorNotSupported;
-      kfn = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0, false, false, 0, 2>
-                : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, 0>;
-#endif
-    }
+  } else {
+    if (wg || wi) return hipErrorInvalidValue;  // fused VJPs read the coefficient image as float4
+    kfn = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY, false, false, 2>
+              : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, APPLY>;
   }
-#ifdef HDRNET_TOOLS_BUILD
-  // tools knob 1: bytes of UNUSED dynamic LDS per workgroup -- lowers the resident workgroups per CU (and re-fits the
-  // row groups to the new round size) to measure what a resident wave is worth (profiles/r05/bwd_steps.md)
-  const size_t dyn_lds = (size_t)(tools_knob(1) > 0 ? tools_knob(1) : 0);
-#else
-  const size_t dyn_lds = 0;
-#endif
   GGPlan pl;
-  if (!gg_plan(B, H, W, GH, GW, GD, C, resident_slots(kfn, occ, dyn_lds), &pl) || pl.ws_bytes > ws_bytes)
+  if (!gg_plan(B, H, W, GH, GW, GD, C, resident_slots(kfn, &occ_cache[(two ? 4 : 0) + (wg ? 2 : 0) + (wi ? 1 : 0)]), &pl) ||
+      pl.ws_bytes > ws_bytes)
     return hipErrorInvalidValue;
-  GGParams p{q.guide, q.input, q.dout, q.grid, q.dguide, q.dinput, static_cast<float*>(ws), H, W, GH, GW, GD,
-             pl.rg, pl.nyg, pl.ntasks, (float)GW / W, (float)GH / H, g_gg_trace};
-  const dim3 nblocks((unsigned)(GW + 1), (unsigned)pl.nyg, (unsigned)B);
-  kfn<<<nblocks, kWaves * 64, dyn_lds, s>>>(p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const dim3 ncols((unsigned)GW, (unsigned)GH, (unsigned)B);
-  if (two)
-    grid_grad_stage2<2><<<ncols, 512, 0, s>>>(static_cast<const float*>(ws), q.dgrid, GH, GW, GD, C, pl.rg, pl.nyg,
-                                              (float)GH / H);
-  else
-    grid_grad_stage2<1><<<ncols, 512, 0, s>>>(static_cast<const float*>(ws), q.dgrid, GH, GW, GD, C, pl.rg, pl.nyg,
-                                              (float)GH / H);
-  return hipGetLastError();
+  const GGParams p{q.guide, q.input, q.dout, q.grid, q.dguide, q.dinput, static_cast<float*>(ws), H, W, GH, GW, GD,
+                   pl.rg, pl.nyg, pl.ntasks, (float)GW / W, (float)GH / H};
+  return two ? gg_run<2>(kfn, p, B, q.dgrid, C, 0, 16, s) : gg_run<1>(kfn, p, B, q.dgrid, C, 0, 16, s);
 }
 
 // 17 .. 32 grid channels (4 -> 4 with offset): dgrid as two channel windows of 16 columns (grid_grad_stage1's CW) --
@@ -1158,39 +1015,26 @@ hipError_t gg_launch_windows(const GGPtrs& q, int B, int H, int W, int GH, int G
   if (q.dguide || q.dinput) return hipErrorInvalidValue;  // the per-pixel VJPs of these shapes run in apply_vjp_seg
   const bool two = GD > 8;
   static std::atomic<int> occ_cache[2];
-  const Stage1Fn k0 = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, 0, false, false, 0, 2, 0>
-                          : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, 0, false, false, 0, 1, 0>;
-  const Stage1Fn k1 = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, 0, false, false, 0, 2, 1>
-                          : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, 0, false, false, 0, 1, 1>;
+  const Stage1Fn k0 = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, false, false, 2, 0>
+                          : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, false, false, 1, 0>;
+  const Stage1Fn k1 = two ? (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, false, false, 2, 1>
+                          : (Stage1Fn)grid_grad_stage1<CIN, COUT, OFFSET, true, false, false, 1, 1>;
   GGPlan pl;
   if (!gg_plan(B, H, W, GH, GW, GD, C, resident_slots(k0, &occ_cache[two ? 1 : 0]), &pl) || pl.ws_bytes > ws_bytes)
     return hipErrorInvalidValue;
   const size_t window_floats = (size_t)pl.ntasks * (two ? 2 : 1) * kTileFloats;
-  const dim3 nblocks((unsigned)(GW + 1), (unsigned)pl.nyg, (unsigned)B);
-  const dim3 ncols((unsigned)GW, (unsigned)GH, (unsigned)B);
   for (int w = 0; w < 2; ++w) {
-    float* part = static_cast<float*>(ws) + w * window_floats;
-    GGParams p{q.guide, q.input, q.dout, q.grid, nullptr, nullptr, part, H, W, GH, GW, GD,
-               pl.rg, pl.nyg, pl.ntasks, (float)GW / W, (float)GH / H, nullptr};
-    (w == 0 ? k0 : k1)<<<nblocks, kWaves * 64, 0, s>>>(p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    const GGParams p{q.guide, q.input, q.dout, q.grid, nullptr, nullptr, static_cast<float*>(ws) + w * window_floats,
+                     H, W, GH, GW, GD, pl.rg, pl.nyg, pl.ntasks, (float)GW / W, (float)GH / H};
+    const Stage1Fn kfn = w == 0 ? k0 : k1;
     const int c0 = 16 * w, cw = w == 0 ? 16 : C - 16;
-    if (two)
-      grid_grad_stage2<2><<<ncols, 512, 0, s>>>(part, q.dgrid, GH, GW, GD, C, pl.rg, pl.nyg, (float)GH / H, c0, cw);
-    else
-      grid_grad_stage2<1><<<ncols, 512, 0, s>>>(part, q.dgrid, GH, GW, GD, C, pl.rg, pl.nyg, (float)GH / H, c0, cw);
-    e = hipGetLastError();
+    const hipError_t e = two ? gg_run<2>(kfn, p, B, q.dgrid, C, c0, cw, s) : gg_run<1>(kfn, p, B, q.dgrid, C, c0, cw, s);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
 }  // namespace
-
-#ifdef HDRNET_TOOLS_BUILD
-void grid_grad_set_trace(long long* device_buf) { g_gg_trace = device_buf; }
-#endif
 
 size_t grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C) {
   size_t bytes = 0;
@@ -1206,22 +1050,18 @@ bool grid_grad_mfma_supported(const ApplyGradArgs& a) {
   return false;
 }
 
-// variant (tools A/B): 2 = bf16-split contraction, 10 = f16 hi-lo' split.  fused: also write a.dguide / a.dinput.
+// fused: also write a.dguide / a.dinput.
 static hipError_t gg_dispatch(const ApplyGradArgs& a, bool fused, hipStream_t s) {
   const GGPtrs q{a.guide, a.input, a.dout, a.grid, a.dgrid, fused ? a.dguide : nullptr,
                  fused ? a.dinput : nullptr};
-  const int split = a.variant == 2 ? 1 : a.variant == 10 ? 2 : 0;
   if (!a.slice) {
 #define HDRNET_CASE(CI, CO, OFF)                                                                  \
   if constexpr (CO * (CI + (OFF ? 1 : 0)) <= 16) {                                                \
     if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF)                                       \
-      return gg_launch<CI, CO, OFF, true>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s, \
-                                          split, (a.variant >= 4 && a.variant <= 9) ? a.variant - 3 : 0); \
+      return gg_launch<CI, CO, OFF, true>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s); \
   } else if constexpr (CO * (CI + (OFF ? 1 : 0)) <= 32) {                                         \
-    if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF) {                                     \
-      if (a.variant != 0 && a.variant != 3) return hipErrorNotSupported;                          \
+    if (a.Cin == CI && a.Cout == CO && a.has_offset == OFF)                                       \
       return gg_launch_windows<CI, CO, OFF>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s); \
-    }                                                                                             \
   }
     HDRNET_APPLY_FAST_SHAPES(HDRNET_CASE)
 #undef HDRNET_CASE
@@ -1229,14 +1069,14 @@ static hipError_t gg_dispatch(const ApplyGradArgs& a, bool fused, hipStream_t s)
   }
 #define HDRNET_CASE(CC)                                                                            \
   if (a.Cout == CC)                                                                                \
-    return gg_launch<0, CC, false, false>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s, split);
+    return gg_launch<0, CC, false, false>(q, a.B, a.H, a.W, a.GH, a.GW, a.GD, a.workspace, a.workspace_bytes, s);
   HDRNET_SLICE_FAST_CHANNELS(HDRNET_CASE)
 #undef HDRNET_CASE
   return hipErrorInvalidValue;
 }
 
 hipError_t launch_grid_grad_mfma(const ApplyGradArgs& a, hipStream_t s, const char** name) {
-  *name = a.variant == 2 ? "grid_grad_mfma/bf16x2" : (a.variant == 10 && !a.slice) ? "grid_grad_mfma/f16hilo" : "grid_grad_mfma";
+  *name = "grid_grad_mfma";
   return gg_dispatch(a, false, s);
 }
 
@@ -1249,8 +1089,7 @@ bool bwd_fused_supported(const ApplyGradArgs& a) {
 }
 
 hipError_t launch_bwd_fused(const ApplyGradArgs& a, hipStream_t s, const char** name) {
-  *name = a.slice ? "slice_bwd_fused/mfma"
-                  : a.variant == 2 ? "apply_bwd_fused/mfma-bf16x2" : a.variant == 10 ? "apply_bwd_fused/mfma-f16hilo" : "apply_bwd_fused/mfma";
+  *name = a.slice ? "slice_bwd_fused/mfma" : "apply_bwd_fused/mfma";
   return gg_dispatch(a, true, s);
 }
 

@@ -85,7 +85,7 @@ struct ApplyGradArgs {
   bool has_offset;
   void* workspace;
   size_t workspace_bytes;
-  int variant = 0;  // tools build A/B: 2 = bf16-split dgrid contraction, 3 = separate (un-fused) kernels
+  int variant = 0;  // tools build A/B: 3 = separate (un-fused) kernels, 11 = apply_vjp_rows (include/hdrnet_amd_tools.h)
   bool slice = false;
 };
 
@@ -190,7 +190,6 @@ hipError_t launch_apply_fwd_seg_upadd(const ApplyArgs& a, const float* coarse, i
 #ifdef HDRNET_TOOLS_BUILD
 void tools_set_knob(int idx, int value);  // apply_fwd_variants.hip: experiment knobs (include/hdrnet_amd_tools.h)
 int tools_knob(int idx);
-void grid_grad_set_trace(long long* device_buf);
 void coeff_net_set_trace(long long* device_buf);
 #endif
 

@@ -17,15 +17,14 @@
  *                108 skeleton 106 on flat 1024-pixel tasks
  *   - kernel variants of the GRADIENT entry points (HDRNET_VARIANT(n) in the flags of
  *     hdrnet_bilateral_slice{,_apply}_grad_f32_ex; tools/bwd_ab.py times them interleaved):
- *       2  bf16-split contraction (two v_mfma_f32_16x16x32_bf16 per 16 pixels)   3  un-fused kernels
- *       4..8  ABLATIONS of the fused pass (timing only, results are garbage): 4 pixels loaded once per
- *             wave, 5 no MFMAs, 6 prologue + epilogue only, 7 = 4 + 5, 8 the launch alone; 9 = the product
- *             pass with per-chunk phase stamps of wave 0 ([task][16][5] clock64 values in the buffer
- *             given to hdrnet_tools_set_trace; tools/exp/r02_exp29.py)
+ *       3     un-fused kernels (per-pixel VJPs and the dgrid contraction as separate launches)
  *       11    (dgrid == NULL) the round-1 per-pixel VJP kernel (apply_vjp_rows) instead of apply_vjp_seg
+ *       (2 and 4..10: the bf16-split and f16 hi/lo' contractions, the timing ablations of the fused pass and its
+ *                phase trace.  Removed -- grid_grad_mfma.hip holds the product's configurations only; measurements in
+ *                DESIGN.md section 4.2, docs/EXPERIMENTS.md and profiles/, code in the history, last at 6d87df0.)
+ *       Any other number is refused with HDRNET_INVALID_ARGUMENT: no variant runs the product pass under its name.
  *       knob 3 (hdrnet_tools_set_knob): rows per workgroup task of the fast gradient pass, forced
- *   - hdrnet_tools_set_trace: device buffer for the phase trace of gradient variant 9 and the coefficient network's
- *     per-workgroup timeline (tools/coeff_trace.py).
+ *   - hdrnet_tools_set_trace: device buffer for the coefficient network's per-workgroup timeline (tools/coeff_trace.py).
  *
  * Nothing in the product path links or loads this library.
  */
@@ -38,12 +37,11 @@
 extern "C" {
 #endif
 
-/* device_buf: sized by the tracing tool (tools/coeff_trace.py, tools/exp/r02_exp29.py); NULL disables. */
+/* device_buf: sized by the tracing tool (tools/coeff_trace.py); NULL disables. */
 void hdrnet_tools_set_trace(void* device_buf);
 
-/* Experiment knobs read at launch (knobs 0, 2 and 7 drove the product kernel's removed flavours):
- *   1  gradient pass (grid_grad_mfma.hip): bytes of unused dynamic LDS per stage-1 workgroup -- fewer resident workgroups
- *      per CU, the row groups re-fitted to them (tools/bwd_ab.py)
+/* Experiment knobs read at launch (knobs 0, 2 and 7 drove the product kernel's removed flavours, knob 1 padded the
+ * gradient pass's LDS to lower its occupancy: removed with them, nothing reads those numbers):
  *   3  gradient pass: rg, the rows per workgroup task, FORCED instead of fitted to the device (gg_plan); 0 = fitted.
  *      Accepted: 1 .. cell, cell = max(H / GH, 1) -- a task's rows may span at most three clamped grid rows.  With any
  *      other value the pass refuses the shape: hdrnet_bilateral_slice{,_apply}_grad_workspace_bytes returns 0 and the

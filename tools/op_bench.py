@@ -19,8 +19,8 @@ of the chain a caller wrote before it (index-select to RGB -> process -> flip + 
 fused kernel alone, BGRA u8 -> u8 against RGB u8 -> u8; `yuv` = HDRNetPointwiseNNGuide on NV12 surfaces at 4K and 1080p: a
 hipGraph of process_yuv(..., out="nv12") against a hipGraph of the stock chain (planes -> repeat_interleave -> affine + clamp
 -> process -> affine -> 2 x 2 mean -> quantise), alternating, and beside it the fused kernel alone, NV12 -> NV12 and NV12 ->
-u8 RGB against RGB u8 -> u8.  --tools loads the tools build and adds the round-1
-kernels (variant 1 of the gradient entry points: dense-tile dgrid) for A/B.
+u8 RGB against RGB u8 -> u8.  --tools loads the tools build and adds the un-fused
+gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
   apply fwd   4*[HW(1+Cin+Cout) + grid]
@@ -287,12 +287,6 @@ def main():
     if args.tools:
         run("apply bwd (all three), un-fused kernels", lambda k: apply_bwd(k, variant=3),
             4 * npx * (1 + Cin + Cout) + 4 * npx * (1 + Cin) + 2 * gridb)
-        run("apply bwd (all three), bf16-split MFMA", lambda k: apply_bwd(k, variant=2),
-            4 * npx * (1 + Cin + Cout) + 4 * npx * (1 + Cin) + 2 * gridb)
-        run("apply bwd dgrid+dguide, bf16-split MFMA", lambda k: apply_bwd(k, di=False, variant=2),
-            4 * npx * (1 + Cin + Cout) + 4 * npx + 2 * gridb)
-        run("apply bwd dgrid only (bf16-split MFMA)", lambda k: apply_bwd(k, dgu=False, di=False, variant=2),
-            4 * npx * (1 + Cin + Cout) + gridb)
     run("slice fwd", slice_fwd, 4 * npx * (1 + C) + gridb)
     run("slice bwd (both)", slice_bwd, 4 * npx * (1 + C) + 4 * npx + 2 * gridb)
     if args.json:
