@@ -58,8 +58,7 @@ SOURCES = [
     ("sample_prep.hip", []),
 ]
 TOOLS_ONLY_SOURCES = [
-    ("apply_fwd_variants.hip", ["-fno-slp-vectorize"]),
-    ("pyramid_onepass.hip", ["-fno-slp-vectorize"]),
+    ("apply_fwd_skeletons.hip", ["-fno-slp-vectorize"]),
 ]
 
 

@@ -12,10 +12,10 @@ bool apply_fwd_io_supported(const ApplyIoArgs& a) {
     // pixels with alpha: one 16-byte access per lane, each way
     if (px_stored(a.pixel_format) == 4 && (((uintptr_t)a.input | (a.output_dtype == 1 ? (uintptr_t)a.out : 0)) & 15u)) return false;
   }
-  return io_geom(a, 0).ok;
+  return io_geom(a).ok;
 }
 
-rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a) { return io_geom(a, 0); }
+rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a) { return io_geom(a); }
 
 size_t curves_guide_prepared_bytes(int Cin) { return Cin == 3 ? CurveCells<3>::kFloats * sizeof(float) : 0; }
 size_t curves_guide_prepared_ok_offset(int Cin) { return Cin == 3 ? (size_t)CurveCells<3>::kOk : 0; }

@@ -402,160 +402,6 @@ __device__ __forceinline__ void guide_curves_quad_cells(const float* __restrict_
   }
 }
 
-// ---- TOOLS BUILD ONLY (knob 5): the point-wise guide network's hidden layer on the bf16 matrix cores, uint8 input ----
-// Round 4 experiment, bit-level parity green (guide within 1e-6 of the oracle), REJECTED on time:
-// u8 -> guide network -> u8 at 4K 39.5 us on the VALU, 47.2 us with 48 of these matrix instructions per wave (max + fma
-// on the VALU), 53.4 us with 60 (the |h| form below) -- a v_mfma_f32_4x4x4_16B_bf16 costs its SIMD ~25 cycles for 1024
-// multiply-adds, and an f32-accurate product needs three of them (hi / mid / lo of the weight): no faster than the 3
-// VALU FMAs it replaces.  The 16 x 16 x 16 form does 96 useful multiply-adds per cycle, / 3 parts = the VALU's own 32, and
-// needs every pixel's bytes in four lanes (an LDS round trip).  A K = 4 contraction is too small for the matrix cores at
-// f32 accuracy.  profiles/r04/guide_nn_mfma.md.  The product evaluates the network with guide_nn_quad (rows_common.hip.h).
-// h[f] = conv1[f][3] + sum_j conv1[f][j] * (v_j / white) is a 16 x 4 by 4 x pixels contraction.  For UINT8 samples the
-// pixel side is exact in bf16 (integers <= 255; the 1 of the bias column too), so the only thing to split is the
-// weight side: w' = w / white (f32) = hi + mid + lo, three bf16 that carry its 24 significant bits, every product exact in
-// the matrix core's f32 accumulator.  v_mfma_f32_4x4x4_16B_bf16 multiplies sixteen independent 4 x 4 blocks: in block b
-// (lanes 4b .. 4b + 3) lane 4b + i supplies row i of A (feature 4 fg + i: its three weights and its bias, one of the three
-// parts), lane 4b + j supplies column j of B -- ITS OWN pixel's (r, g, b, 1) -- and receives column j of D: the four
-// features of its own pixel.  No cross-lane traffic on the pixel side at all; 3 parts x (n / 4) feature groups
-// matrix instructions per pixel quad-slot replace 3 n VALU FMAs per pixel, and the bf16 pipe runs beside the VALU
-// (the f32 matrix instructions do not: profiles/r01/f_ubench_mfma_valu_overlap.txt).  ReLU, the mixing layer and the
-// sigmoid stay on the VALU.  A operands: prepared once per workgroup by wave 0 in LDS (NnTab), re-read per feature group.
-// Requires n % 4 == 0, n <= 16; other sizes / input types take guide_nn_quad.
-#ifdef HDRNET_TOOLS_BUILD
-constexpr bool kToolsBuild = true;
-#else
-constexpr bool kToolsBuild = false;
-#endif
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-struct NnTab {
-  // [feature group 0 .. 3, 4 = the linear row][part][row i][2 dwords = 4 bf16]
-  static constexpr int kWords = 5 * 3 * 4 * 2 + 4;  // + 4 floats of scratch for the linear row; 16-B multiple
-};
-
-__device__ __forceinline__ unsigned bf16_rne_bits(float x) {  // round-to-nearest-even truncation to bf16 (finite x)
-  const unsigned u = __float_as_uint(x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-// w[0 .. 3] -> its three bf16 parts, packed as the A operand's two dwords, at tab[((group * 3 + part) * 4 + row) * 2].
-__device__ __forceinline__ void nn_store_row(unsigned* __restrict__ tab, int group, int row, const float (&w)[4]) {
-  unsigned part[3][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float r = w[k];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const unsigned b = bf16_rne_bits(r);
-      part[q][k] = b;
-      r -= __uint_as_float(b << 16);  // exact: the remainder of a bf16 rounding fits a float
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    unsigned* d = tab + ((group * 3 + q) * 4 + row) * 2;
-    d[0] = part[q][0] | (part[q][1] << 16);
-    d[1] = part[q][2] | (part[q][3] << 16);
-  }
-}
-
-// relu(h) = (h + |h|) / 2:  bias2 + sum_f m_f relu(h_f) = [bias2 + sum_f (m_f / 2) h_f] + sum_f (m_f / 2) |h_f|.  The
-// bracket is affine in the pixel -- ONE more row for the matrix cores (group 4, row 0: L_j = sum_f (m_f / 2) w'_fj,
-// L_3 = bias2 + sum_f (m_f / 2) b_f, summed in float64) -- and the rest is one FMA with the |.| source modifier per
-// feature and pixel: no max, no second accumulation.
-// Run by lanes 0 .. 19 of wave 0: lane < 16 = a feature row, lanes 16 .. 19 = the linear row's four entries.
-__device__ __forceinline__ void nn_build_tables(unsigned* __restrict__ tab, float* __restrict__ lin, const GuideNet& gn,
-                                                float white, int lane) {
-  if (lane < 16) {
-    float w[4] = {0.f, 0.f, 0.f, 0.f};
-    if (lane < gn.n) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) w[j] = gn.conv1[lane * 4 + j] / white;  // (w / white) * v == w * (v / white) to an ulp
-      w[3] = gn.conv1[lane * 4 + 3];
-    }
-    nn_store_row(tab, lane >> 2, lane & 3, w);
-    if (lane >= 1 && lane < 4) {  // rows 1 .. 3 of the linear group: zero
-      const float z[4] = {0.f, 0.f, 0.f, 0.f};
-      nn_store_row(tab, 4, lane, z);
-    }
-  } else if (lane < 20) {
-    const int j = lane - 16;
-    double acc = j == 3 ? (double)gn.conv2[gn.n] : 0.0;
-    for (int f = 0; f < gn.n; ++f) {
-      const float w = j == 3 ? gn.conv1[f * 4 + 3] : gn.conv1[f * 4 + j] / white;
-      acc += 0.5 * (double)gn.conv2[f] * (double)w;
-    }
-    lin[j] = (float)acc;
-  }
-  wave_lds_sync();
-  if (lane == 0) {
-    const float w[4] = {lin[0], lin[1], lin[2], lin[3]};
-    nn_store_row(tab, 4, 0, w);
-  }
-}
-
-// raw: the lane's 12 bytes (4 RGB pixels).  g[q] = the guide of pixel q.
-__device__ __forceinline__ void guide_nn_quad_mfma_u8(const unsigned* __restrict__ tab, const GuideNet& gn,
-                                                      const uint32_t (&raw)[3], int lane, float (&g)[kPxPerThread]) {
-  cfloat* c2 = (cfloat*)gn.conv2;
-  // B operands: bf16(v) is the upper half of float(v) for an integer v <= 255
-  bf16x4_t bq[kPxPerThread];
-#pragma unroll
-  for (int q = 0; q < kPxPerThread; ++q) {
-    float ch[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int byte = 3 * q + c;
-      ch[c] = (float)((raw[byte >> 2] >> (8 * (byte & 3))) & 0xffu);  // v_cvt_f32_ubyteN
-    }
-    const unsigned lo = (__float_as_uint(ch[0]) >> 16) | (__float_as_uint(ch[1]) & 0xffff0000u);
-    const unsigned hi = (__float_as_uint(ch[2]) >> 16) | 0x3f800000u;  // (b, 1.0)
-    bq[q] = __builtin_bit_cast(bf16x4_t, uint2{lo, hi});
-  }
-  const unsigned* arow = tab + (lane & 3) * 2;
-  float acc[kPxPerThread];
-  {  // the affine part: group 4, row 0
-    bf16x4_t a[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(bf16x4_t, *reinterpret_cast<const uint2*>(arow + (4 * 3 + q) * 8));
-#pragma unroll
-    for (int q = 0; q < kPxPerThread; ++q) {
-      f32x4 h = {0.f, 0.f, 0.f, 0.f};
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[2], bq[q], h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[1], bq[q], h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[0], bq[q], h, 0, 0, 0);
-      acc[q] = h[0];
-    }
-  }
-  const int ngroups = gn.n >> 2;
-#pragma unroll 1
-  for (int fg = 0; fg < ngroups; ++fg) {
-    bf16x4_t a[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) a[q] = __builtin_bit_cast(bf16x4_t, *reinterpret_cast<const uint2*>(arow + (fg * 3 + q) * 8));
-    float m[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) m[i] = 0.5f * c2[fg * 4 + i];
-#pragma unroll
-    for (int q = 0; q < kPxPerThread; ++q) {
-      f32x4 h = {0.f, 0.f, 0.f, 0.f};
-      // small terms first: lo, mid, hi
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[2], bq[q], h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[1], bq[q], h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a[0], bq[q], h, 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[q] = fmaf(m[i], __builtin_fabsf(h[i]), acc[q]);
-    }
-  }
-  if (!gn.fast_sigmoid) {  // the reference's sigmoid (rows_common.hip.h: GuideNN::fast_sigmoid)
-#pragma unroll
-    for (int q = 0; q < kPxPerThread; ++q) g[q] = 1.0f / (1.0f + expf(-acc[q]));
-  } else {
-#pragma unroll
-    for (int q = 0; q < kPxPerThread; ++q)
-      g[q] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * acc[q]));
-  }
-}
-
 // div_white / WhiteLevel / io_white_level (tf.to_float(im) / white_level in three instructions) and load_pixels: white_level.hip.h
 
 struct IoParams {
@@ -570,7 +416,6 @@ struct IoParams {
   int grid_image;  // floats per image of the grid
   SegTab tab;      // (cmin, ncols) per segment, from the host (seg_common.hip.h)
   GuideNet gn;
-  int nn_mfma;     // tools build, knob 5: the guide network's hidden layer on the matrix cores (uint8 input)
   // YUV surfaces (PX == kPxYuv / OUT == kOutNV12; unused by every other instantiation)
   YuvSurface yin, yout;
   const float* to_rgb;    // 12 floats each (yuv_convert.hip.h)
@@ -590,23 +435,16 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   constexpr int CB = C * (int)sizeof(float);
   constexpr int NI = CIN * kPxPerThread, NO = COUT * kPxPerThread;
-  extern __shared__ __attribute__((aligned(16))) float lds_all[];
+  extern __shared__ __attribute__((aligned(16))) float lds[];
   // curves guide: its lookup tables first (compile-time LDS addresses), the coefficient image behind them
   // Integer samples with a guide MAP: the input is used by the affine only, so the white level goes into the staged
   // coefficients (coef / wl) * v, and the 12 divisions per lane (3 instructions each) disappear: u8 -> u8 26.7 -> ... us.
   // (With a guide NETWORK the guide's own input stays v / wl, IEEE-rounded as TensorFlow's division.)
   // (A YUV surface's conversion clamps: its pixels enter as the converted floats, nothing to fold.)
   constexpr bool FOLD_WL = GUIDE == kGuideMap && sizeof(TI) < 4 && C == 12 && !YUV;
-#ifdef HDRNET_TOOLS_BUILD
-  constexpr bool NN_MFMA = GUIDE == kGuideNN && sizeof(TI) == 1 && CIN == 3 && PX == kPxRGB;  // experiment: hidden layer on the bf16 matrix cores
-#else
-  constexpr bool NN_MFMA = false;
-#endif
   // The curves guide's lookup tables are STATIC LDS: their addresses are compile-time constants, so a table walk's
   // ds_read takes the walked byte offset as its address register and the table's base as its immediate (behind the
   // dynamic array's link-time base every step paid a v_add).  The coefficient image and the slabs stay dynamic.
-  constexpr int kTabFloats = NN_MFMA ? NnTab::kWords : 0;
-  float* const lds = lds_all + kTabFloats;
   // (static LDS costs resident workgroups here: 3 KB more measured 8 %, and a kernel carrying BOTH table forms behind a
   //  run-time switch took 70-74 VGPRs instead of 54-64 -- profiles/r05/f2_prepared_guides.md -- so the two forms are two
   //  instantiations, chosen on the host by whether the caller passed a prepared buffer)
@@ -642,7 +480,6 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
 
     float gs[kPxPerThread] = {0.f, 0.f, 0.f, 0.f};
     float inf[NI];
-    [[maybe_unused]] uint32_t raw[3] = {};
     [[maybe_unused]] uint32_t alpha[kPxPerThread] = {};  // RGBA / BGRA: the 4 pixels' alpha samples as stored
 #pragma unroll
     for (int q = 0; q < NI; ++q) inf[q] = 0.0f;
@@ -652,13 +489,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
         gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
       }
       if constexpr (YUV) yuv_load_quad<TI>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
-      else if constexpr (NN_MFMA) load_pixels<TI, NI>(input, px * CIN, p.white, inf, raw);
       else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
-    }
-    const bool nn_mfma = NN_MFMA && p.nn_mfma && p.gn.n <= 16 && (p.gn.n & 3) == 0;  // uniform
-    if constexpr (NN_MFMA) {
-      if (nn_mfma && wave == 0)
-        nn_build_tables(reinterpret_cast<unsigned*>(lds_all), lds_all + NnTab::kWords - 4, p.gn, p.white.wl, lane);
     }
 
     // (the guide's tables depend on the parameters only: built for the first row, read for both)
@@ -688,16 +519,8 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
     float of[NO];
     if (active) {
       if constexpr (GUIDE != kGuideMap) {
-        if constexpr (GUIDE == kGuideNN) {
-          bool done = false;
-          if constexpr (NN_MFMA) {
-            if (nn_mfma) {
-              guide_nn_quad_mfma_u8(reinterpret_cast<const unsigned*>(lds_all), p.gn, raw, lane, gs);
-              done = true;
-            }
-          }
-          if (!done) guide_nn_quad<CIN>(GuideNN{p.gn.conv1, p.gn.conv2, p.gn.guide_out, p.gn.n, p.gn.fast_sigmoid, p.gn.prescaled}, inf, gs);  // (writes nothing itself)
-        }
+        if constexpr (GUIDE == kGuideNN)
+          guide_nn_quad<CIN>(GuideNN{p.gn.conv1, p.gn.conv2, p.gn.guide_out, p.gn.n, p.gn.fast_sigmoid, p.gn.prescaled}, inf, gs);  // (writes nothing itself)
         else if constexpr (GUIDE == kGuideCurves)
           guide_curves_quad<CIN>(ctab, p.gn, inf, gs);
         else if constexpr (GUIDE == kGuideCurvesCells)
@@ -816,10 +639,9 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
 constexpr int kStaticTabFloats = CurveTab<3>::kFloats > 3 * kCurveCells * 4 ? CurveTab<3>::kFloats : 3 * kCurveCells * 4;
 static_assert(kStaticTabFloats == 768, "tests/test_row_geom.py and io_fits of tests/row_plan.py budget 768 floats of static tables");
 
-// Launch geometry (row_geom.h).  `tab_floats`: dynamic LDS in front of the image -- the tables of the tools build's
-// matrix-core guide network, known to its instantiation alone (launch_io), so the predicate passes 0.
-RowGeom io_geom(const ApplyIoArgs& a, int tab_floats) {
-  return io_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cout * (a.Cin + (a.has_offset ? 1 : 0)), a.Cout, tab_floats,
+// Launch geometry (row_geom.h): no dynamic tables in front of the image.
+RowGeom io_geom(const ApplyIoArgs& a) {
+  return io_fwd_geom(Frame{a.B, a.H, a.W, a.GW, a.GD}, a.Cout * (a.Cin + (a.has_offset ? 1 : 0)), a.Cout, 0,
                      kStaticTabFloats,
                      ptr_bits(a.grid, a.guide, a.guide_out, a.output_dtype == 0 ? a.out : nullptr,
                               a.input_dtype == 0 ? a.input : nullptr));
@@ -828,7 +650,7 @@ RowGeom io_geom(const ApplyIoArgs& a, int tab_floats) {
 template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
 hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
-  const RowGeom g = io_geom(a, (kToolsBuild && GUIDE == kGuideNN) ? NnTab::kWords : 0);
+  const RowGeom g = io_geom(a);
   IoParams p;
   p.grid = a.grid;
   p.guide = a.guide;
@@ -845,11 +667,6 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   p.tab = make_seg_tab(a.W, g.pl.seg, g.pl.nseg, p.scale_x);
   p.gn = GuideNet{a.guide_conv1, a.guide_conv2, a.guide_shifts, a.guide_slopes, a.guide_out, a.n_feats, a.fast_sigmoid, a.guide_prescaled,
                      (a.guide_shifts && a.n_feats <= kCurveMaxKnots) ? a.guide_prepared : nullptr};
-#ifdef HDRNET_TOOLS_BUILD
-  p.nn_mfma = tools_knob(5);
-#else
-  p.nn_mfma = 0;
-#endif
   p.yin = p.yout = YuvSurface{};
   p.to_rgb = p.from_rgb = nullptr;
   if constexpr (PX == kPxYuv) {

@@ -45,7 +45,7 @@ bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a) {
   if (!a.yuv || !(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
   if (a.input_dtype != 1 && a.input_dtype != 2) return false;
   if (a.H % 2 != 0 || a.W % 4 != 0) return false;
-  return io_geom(a, 0).ok;
+  return io_geom(a).ok;
 }
 
 hipError_t launch_apply_fwd_io_yuv(const ApplyIoArgs& a, hipStream_t s, const char** name) {

@@ -30,8 +30,19 @@
 // 1e-7 relative level (tests/test_gpu_parity.py holds rtol=atol=1e-5 and reports
 // the reference's own 1e-6 bar).
 //
-// Benchmark-only alternatives (one wave per tile, persistent stream, memory skeletons) live
-// in apply_fwd_variants.hip; DESIGN.md section 4 records why they lost.
+// The alternatives that were measured and rejected (one wave per tile, persistent stream, per-lane stores,
+// nontemporal lane-contiguous loads) are not in the tree: DESIGN.md section 4 records why they lost.  The tools
+// build keeps two memory skeletons (apply_fwd_skeletons.hip) and can select this file's vec4 kernel as variant 19.
+//
+// Is the plain apply_fwd_rows_vec4 still reachable in the product once apply_fwd_seg has refused?  Yes.  Both
+// predicates ask for a fast shape and read the same Plan (geom_for here, seg_geom there: the same pointers, so the same
+// Plan::vec4), but their limits differ (row_geom.h: kSegLimits against kRowsLimits):
+//   * LDS.  seg_fwd_geom budgets the PADDED image (seg_cols_for columns, unclamped, of GD + 2 planes) and a slab of
+//     guide + input per wave; rows_fwd_geom the clamped one (at most GW columns of GD planes) and a slab without the
+//     guide.  3 -> 3 with offset at W = 1024, GW = 64, GD = 16 (one segment of 256 threads): 67 x 18 x 48 B + 16 KB of
+//     slabs = 74 272 B, refused against the 64 KB budget; here 64 x 16 x 48 B + 16 B + 12 KB = 61 456 B, served.
+//   * the 3-D launch grid.  B or H above 65535 (kLimBH) is refused there; the 1-D grid here takes it (kLimBlocks).
+// So the kernel is the product's for deep grids under wide segments and for very tall frames, not only variant 19.
 #include <hip/hip_runtime.h>
 
 #include "launch.hip.h"
@@ -44,11 +55,7 @@ using namespace rows;
 
 // ---- 4 consecutive pixels per thread, 16-byte global accesses -----------------------
 // Requires W % 4 == 0, seg % 4 == 0 and 16-B aligned guide / input / out.
-//
-// LDS_STORES = false keeps the naive per-lane stores (16 B at a 16*COUT-byte lane stride); it
-// exists only to document the 6.5 us per 4K frame they cost (tools/ab_bench.py, variant 7).
-template <int CIN, int COUT, bool OFFSET, bool GUIDE_NN = false, bool LDS_STORES = true, bool UPADD = false,
-          bool NT_LOADS = false>
+template <int CIN, int COUT, bool OFFSET, bool GUIDE_NN = false, bool UPADD = false>
 __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
     const float* __restrict__ grid, const float* __restrict__ guide,
     const float* __restrict__ input, float* __restrict__ out, int H, int W, int GH, int GW,
@@ -71,13 +78,6 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
 
   // Issue this thread's streaming loads before the staging pass so their HBM
   // latency overlaps the (L2-resident) grid reads and the barrier.
-  // NT_LOADS (benchmark variant 8): nontemporal, LANE-CONTIGUOUS loads (lane l takes float4 number
-  // l + 64k of the wave's input run) + an LDS transpose.  Nontemporal loads lower the no-compute
-  // floor of this geometry from 41.2 to 39.0 us (36.2 us stand-alone), but only lane-contiguous:
-  // an nt line is not kept for the next instruction, so the per-pixel pattern (three loads that
-  // each touch every line of the run) re-fetches and loses 5 us.  The full kernel does not
-  // cash it in (44.5 vs 43.6 us): it is bound by bytes in flight -- 10 workgroups per CU cover
-  // latency + compute -- not by the memory system's peak.  DESIGN.md section 4.
   const int lane = threadIdx.x & 63;
   const int wave_x0 = xs + kPxPerThread * (int)(threadIdx.x & ~63u);
   const int wave_px = min(xe, wave_x0 + 64 * kPxPerThread) - wave_x0;  // <= 0 for an idle wave
@@ -85,17 +85,7 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
                  (threadIdx.x >> 6) * (64 * (CIN > COUT ? CIN : COUT));
   float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 iv[(CIN * kPxPerThread) / 4];
-  if constexpr (LDS_STORES && NT_LOADS) {
-    if constexpr (!GUIDE_NN) {
-      if (active) g4 = load_stream4(guide + p);
-    }
-    const float* ibase = input + ((size_t)row * W + wave_x0) * CIN;
-#pragma unroll
-    for (int k = 0; k < CIN; ++k) {
-      const int e = lane + 64 * k;
-      if (e < wave_px * CIN / 4) iv[k] = load_stream4(ibase + 4 * e);
-    }
-  } else if (active) {
+  if (active) {
     if constexpr (!GUIDE_NN) g4 = *reinterpret_cast<const float4*>(guide + p);
     const float4* ip = reinterpret_cast<const float4*>(input + p * CIN);
 #pragma unroll
@@ -103,20 +93,6 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
   }
 
   const RowCtx r = stage_row<C, false>(colY, grid_b, y, xs, xe, GH, GW, GD, scale_x, scale_y);
-
-  if constexpr (LDS_STORES && NT_LOADS) {  // transpose the input run: lane-contiguous -> this lane's 4 pixels
-#pragma unroll
-    for (int k = 0; k < CIN; ++k) {
-      const int e = lane + 64 * k;
-      if (e < wave_px * CIN / 4) slab[e] = iv[k];
-    }
-    wave_lds_sync();
-    if (active) {
-#pragma unroll
-      for (int q = 0; q < CIN; ++q) iv[q] = slab[lane * CIN + q];
-    }
-    __builtin_amdgcn_wave_barrier();  // the slab is reused for the output below
-  }
 
   float gs[4] = {g4.x, g4.y, g4.z, g4.w};
   const float xf0 = (float)x + 0.5f;  // (x + k) + 0.5f == xf0 + k exactly: x < W <= 2^23 (row_geom.h, kMaxFloatX)
@@ -138,13 +114,6 @@ __global__ __launch_bounds__(256) void apply_fwd_rows_vec4(
       for (int i = 0; i < COUT; ++i) of[k * COUT + i] = o[i];
     }
     if constexpr (UPADD) upadd_quad<COUT>(up, b, y, x, of);
-  }
-  if constexpr (!LDS_STORES) {
-    if (!active) return;
-    float4* op = reinterpret_cast<float4*>(out + p * COUT);
-#pragma unroll
-    for (int q = 0; q < (COUT * kPxPerThread) / 4; ++q) op[q] = ov[q];
-    return;
   }
   // Store phase.  A lane's 4 pixels are 4*COUT contiguous floats, i.e. per-lane 16-B
   // stores at a 16*COUT-byte stride -- measured 6.5 us slower per 4K frame than
@@ -212,7 +181,7 @@ RowGeom geom_for(const ApplyArgs& a) {
 
 unsigned nblocks_of(const ApplyArgs& a, const RowGeom& g) { return (unsigned)((long long)a.B * a.H * g.pl.nseg); }
 
-// One launch of the vec4 kernel, whichever FLAVOUR (GUIDE_NN, LDS_STORES, UPADD, NT_LOADS): the kernel's argument list.
+// One launch of the vec4 kernel, whichever FLAVOUR (GUIDE_NN, UPADD): the kernel's argument list.
 template <int CIN, int COUT, bool OFFSET, bool... FLAVOUR>
 hipError_t launch_vec4(const ApplyArgs& a, const RowGeom& g, const float* guide, hipStream_t s,
                        const GuideNN& gn = GuideNN{nullptr, nullptr, nullptr, 0},
@@ -238,7 +207,7 @@ template <bool GUIDE_NN>
 hipError_t launch_upadd_t(const ApplyArgs& a, const GuideNN& gn, const float* coarse, int Hc, int Wc,
                           hipStream_t s) {
   const UpAdd up{coarse, Hc, Wc, resize_scale(Hc, a.H), resize_scale(Wc, a.W)};
-  return launch_vec4<3, 3, true, GUIDE_NN, true, true>(a, geom_for(a), a.guide, s, gn, up);
+  return launch_vec4<3, 3, true, GUIDE_NN, true>(a, geom_for(a), a.guide, s, gn, up);
 }
 
 // A fast shape whose geometry fits; `vec4`: ... and that the vec4 kernel serves (the fused forwards have no scalar twin).
@@ -311,10 +280,6 @@ bool apply_fwd_rows_supported(const ApplyArgs& a) { return rows_supported(a, fal
 
 hipError_t launch_apply_fwd_rows(const ApplyArgs& a, hipStream_t s, const char** name) {
 #ifdef HDRNET_TOOLS_BUILD
-  if (a.variant != 0 && a.variant != 19) {  // benchmark-only kernels (tools build), never selected by flags == 0
-    const hipError_t e = launch_apply_fwd_variant(a, s, name);
-    if (e != hipErrorNotSupported) return e;
-  }
   const bool round1_kernel = a.variant == 19;  // A/B: the round-1 product kernel below
 #else
   const bool round1_kernel = false;
@@ -328,19 +293,5 @@ hipError_t launch_apply_fwd_rows(const ApplyArgs& a, hipStream_t s, const char**
 #undef HDRNET_CASE
   return hipErrorInvalidValue;
 }
-
-#ifdef HDRNET_TOOLS_BUILD
-// The direct-store / plain-load instantiations, for tools/ab_bench.py only (apply_fwd_variants.hip
-// routes here): which = 0 per-lane stores, 1 = nontemporal lane-contiguous input loads.
-hipError_t launch_apply_fwd_rows_direct_stores(const ApplyArgs& a, hipStream_t s, const char** name, int which) {
-  if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return hipErrorInvalidValue;
-  const RowGeom g = geom_for(a);
-  if (!g.pl.vec4) return hipErrorInvalidValue;
-  *name = which == 0 ? "apply_fwd_rows/vec4-direct-stores" : "apply_fwd_rows/vec4-nt-loads";
-  if (which == 0) return launch_vec4<3, 3, true, false, false>(a, g, a.guide, s);
-  return launch_vec4<3, 3, true, false, true, false, true>(a, g, a.guide, s);
-}
-
-#endif  // HDRNET_TOOLS_BUILD
 
 }  // namespace hdrnet_amd

@@ -507,6 +507,14 @@ static int apply_fwd_impl(const float* grid, const float* guide, const float* in
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_flags(flags)) return rc;
+#ifdef HDRNET_TOOLS_BUILD
+  // an A/B script must not time the product kernel against itself under a number whose kernel is gone
+  const int v = variant(flags);
+  if (v != 0 && v != 19 && v != 106 && v != 108)
+    return fail(HDRNET_INVALID_ARGUMENT,
+                "forward kernel variant %d is not in this library: variants 2..11, 101, 103..105 and 107 were retired "
+                "with their kernels, 0, 19, 106 and 108 remain (include/hdrnet_amd_tools.h)", v);
+#endif
   if (H_total < 0 || y0 < 0 || (long long)y0 + H > H_total)
     return fail(HDRNET_INVALID_ARGUMENT, "row band [%d, %d + %d) outside the frame's %d rows", y0, y0, H, H_total);
   const bool band = y0 != 0 || H != H_total;
@@ -525,6 +533,18 @@ static int apply_fwd_impl(const float* grid, const float* guide, const float* in
   a.y0 = y0;
   a.H_total = H_total;
   hipStream_t s = static_cast<hipStream_t>(stream);
+#ifdef HDRNET_TOOLS_BUILD
+  // the memory skeletons (whatever the family): their own kernel or a refusal, never the product under their number
+  if (v == 106 || v == 108) {
+    if (!apply_fwd_skeleton_supported(a))
+      return fail(HDRNET_INVALID_ARGUMENT,
+                  "forward kernel variant %d has no kernel for this shape: the memory skeletons take 3 -> 3 with offset, "
+                  "W %% 4 == 0 and 16-byte aligned buffers (include/hdrnet_amd_tools.h)", v);
+    const char* name = "";
+    const hipError_t e = launch_apply_fwd_skeleton(a, s, &name);
+    return finish_launch(e, "BilateralSliceApply", name);
+  }
+#endif
   // a row band runs on the row-segment kernel (apply_fwd_seg.hip) or the generic one; whole frames may
   // also take the scalar row kernel (unaligned buffers, W % 4 != 0)
   const bool fast_ok = band ? apply_fwd_seg_supported(a) : apply_fwd_rows_supported(a);

@@ -1036,6 +1036,16 @@ hipError_t gg_launch_windows(const GGPtrs& q, int B, int H, int W, int GH, int G
 
 }  // namespace
 
+#ifdef HDRNET_TOOLS_BUILD
+// Experiment knobs of the tools build (hdrnet_tools_set_knob; include/hdrnet_amd_tools.h).  Knob 3 (gg_plan) is the
+// only one that is read.
+static int g_knob[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+void tools_set_knob(int idx, int value) {
+  if (idx >= 0 && idx < 8) g_knob[idx] = value;
+}
+int tools_knob(int idx) { return idx >= 0 && idx < 8 ? g_knob[idx] : 0; }
+#endif
+
 size_t grid_grad_mfma_workspace(int B, int H, int W, int GH, int GW, int GD, int C) {
   size_t bytes = 0;
   return gg_ws_bound(B, H, W, GH, GW, GD, C, &bytes) ? bytes : 0;

@@ -171,10 +171,6 @@ hipError_t launch_slice_grad_generic(const ApplyGradArgs& a, hipStream_t s);  //
 // the variant launched.
 bool apply_fwd_rows_supported(const ApplyArgs& a);
 hipError_t launch_apply_fwd_rows(const ApplyArgs& a, hipStream_t s, const char** name);
-// apply_fwd_variants.hip -- benchmark-only alternatives, reached only with a non-zero variant
-// number; hipErrorNotSupported = no such variant for the shape.
-hipError_t launch_apply_fwd_variant(const ApplyArgs& a, hipStream_t s, const char** name);
-hipError_t launch_apply_fwd_rows_direct_stores(const ApplyArgs& a, hipStream_t s, const char** name, int which);
 // apply_fwd_seg.hip -- the product forward for 16-B-aligned, W % 4 == 0 inputs: padded LDS image,
 // LDS-DMA nontemporal pixel loads, streaming (write-through / nontemporal) buffer stores.  launch_apply_fwd_rows routes here
 // when supported (else the scalar kernel of apply_fwd_rows.hip).
@@ -188,7 +184,11 @@ bool apply_fwd_seg_upadd_supported(const ApplyArgs& a, const float* coarse, bool
 hipError_t launch_apply_fwd_seg_upadd(const ApplyArgs& a, const float* coarse, int Hc, int Wc, const float* conv1,
                                       const float* conv2, int n_feats, hipStream_t s, const char** name);
 #ifdef HDRNET_TOOLS_BUILD
-void tools_set_knob(int idx, int value);  // apply_fwd_variants.hip: experiment knobs (include/hdrnet_amd_tools.h)
+// apply_fwd_skeletons.hip -- the memory skeletons (variants 106 and 108: a.variant says which).  They do not compute the
+// op; a shape or alignment without a skeleton is refused by the entry point, never served by the product kernel.
+bool apply_fwd_skeleton_supported(const ApplyArgs& a);
+hipError_t launch_apply_fwd_skeleton(const ApplyArgs& a, hipStream_t s, const char** name);
+void tools_set_knob(int idx, int value);  // grid_grad_mfma.hip: experiment knobs (include/hdrnet_amd_tools.h)
 int tools_knob(int idx);
 void coeff_net_set_trace(long long* device_buf);
 #endif

@@ -52,7 +52,7 @@ def _flags() -> int:
 @contextlib.contextmanager
 def kernel_override(which: str, variant: int = 0):
     """Force a kernel family inside the block: 'auto' | 'generic' | 'fast' (tests/bench).
-    `variant` > 0 selects a benchmark-only kernel of the TOOLS build (csrc/apply_fwd_variants.hip,
+    `variant` > 0 selects a benchmark-only kernel of the TOOLS build (include/hdrnet_amd_tools.h,
     tools/ab_bench.py); the product library these ops call has no variants and answers any non-zero
     variant with HDRNET_INVALID_ARGUMENT (raised as HdrnetInvalidArgument)."""
     table = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "fast": _lib.KERNEL_FAST}

@@ -5,16 +5,21 @@
  *
  *   - kernel VARIANTS of BilateralSliceApply forward, selected with HDRNET_VARIANT(n) in the
  *     `flags` of hdrnet_bilateral_slice_apply_f32_ex (tools/ab_bench.py times them interleaved
- *     with the product kernel).  Variants 101-106 are memory skeletons that do NOT compute the op
+ *     with the product kernel).  Variants 106 and 108 are memory skeletons that do NOT compute the op
  *     (their kernel name starts with "ABLATION"); they are the reason this is a separate library.
- *       2        one wavefront per tile            3..6   persistent software-pipelined stream
- *       7        per-lane strided stores           8      round-1 kernel + nontemporal loads
- *       9..11    2 / 3 / 4 quads per thread        19     the round-1 product kernel (apply_fwd_rows)
- *       (20..72, through round 4: the product kernel's own load / store / pixel-phase flavours, the ticketed tail, the
- *                per-workgroup timeline trace.  Removed in round 5 -- apply_fwd_seg.hip holds the product's
- *                configurations only; measurements in profiles/r02 .. r04, code in the history.)
- *       101, 103..106  memory skeletons; 107 an empty kernel with the product's launch geometry,
- *                108 skeleton 106 on flat 1024-pixel tasks
+ *       19    the round-1 product kernel (apply_fwd_rows), which the product keeps as its fallback
+ *       106   memory skeleton: the shipped kernel's accesses (nontemporal lane-contiguous loads, lane-contiguous
+ *             stores) on its row segments, no slicing -- the calibration of tools/make_traffic.py, power_probe.py
+ *       108   skeleton 106 on flat 1024-pixel tasks
+ *       The skeletons exist for 3 -> 3 with offset, W % 4 == 0 and 16-byte aligned buffers, whatever the kernel
+ *       family; any other shape is refused ("variant N has no kernel for this shape"), not served by the product kernel.
+ *       (2 one wavefront per tile, 3..6 the persistent stream, 7 per-lane stores, 8 nontemporal lane-contiguous loads,
+ *                9..11 two to four quads per thread, 101 and 103..105 the other memory skeletons, 107 the empty launch;
+ *                20..72, through round 4, the product kernel's own flavours.  Removed -- the forward's files hold the
+ *                product's configurations only; measurements in DESIGN.md section 4, docs/EXPERIMENTS.md and
+ *                profiles/, code in the history, last at 0006d48.)
+ *       Any other number is refused with HDRNET_INVALID_ARGUMENT before a pointer is looked at: no variant runs the
+ *       product kernel under its name.
  *   - kernel variants of the GRADIENT entry points (HDRNET_VARIANT(n) in the flags of
  *     hdrnet_bilateral_slice{,_apply}_grad_f32_ex; tools/bwd_ab.py times them interleaved):
  *       3     un-fused kernels (per-pixel VJPs and the dgrid contraction as separate launches)
@@ -41,27 +46,16 @@ extern "C" {
 void hdrnet_tools_set_trace(void* device_buf);
 
 /* Experiment knobs read at launch (knobs 0, 2 and 7 drove the product kernel's removed flavours, knob 1 padded the
- * gradient pass's LDS to lower its occupancy: removed with them, nothing reads those numbers):
+ * gradient pass's LDS to lower its occupancy, knob 5 put the wire-format forward's guide network on the bf16 matrix
+ * cores: removed with them, nothing reads those numbers):
  *   3  gradient pass: rg, the rows per workgroup task, FORCED instead of fitted to the device (gg_plan); 0 = fitted.
  *      Accepted: 1 .. cell, cell = max(H / GH, 1) -- a task's rows may span at most three clamped grid rows.  With any
  *      other value the pass refuses the shape: hdrnet_bilateral_slice{,_apply}_grad_workspace_bytes returns 0 and the
  *      gradient entry points take their other kernels.  While it is set the workspace query answers with exactly the
  *      forced plan's size, B * (GW + 1) * ceil(H / rg) tasks x (GD > 8 ? 2 : 1) x (C > 16 ? 2 : 1) tiles of
  *      3 x 16 x 16 floats: query after setting it.  Process-wide, like every knob: set it back to 0.  The planner
- *      itself returns min(cell, 4) .. cell; tests/test_gpu_grad_plans.py runs every such plan on small frames.
- *   5 hdrnet_bilateral_slice_apply_io, uint8 input + guide network: 1 = the hidden layer as bf16-split 4x4x4 matrix
- *      instructions (apply_fwd_io.hip; rejected on time, kept for the record) */
+ *      itself returns min(cell, 4) .. cell; tests/test_gpu_grad_plans.py runs every such plan on small frames. */
 void hdrnet_tools_set_knob(int idx, int value);
-
-/* EXPERIMENT (round 5, csrc/pyramid_onepass.hip): the multi-scale output of HDRNetGaussianPyrNN
- * (hdrnet/models.py:277-289) in ONE pass over the full-resolution frame -- a workgroup owns 4 rows of a `seg`-pixel
- * row segment and re-evaluates the coarse pixels they tap.  grids / inputs / conv1 / conv2 [0] = full resolution,
- * [1] = half, [2] = quarter (inputs as hdrnet_resize_bilinear_f32 makes them; H % 4 == 0, W % 16 == 0).  Timed against
- * the product's per-level chain by tools/pyramid_onepass_bench.py (profiles/r05/pyramid_onepass.md). */
-int hdrnet_tools_pyramid_onepass_f32(const float* const grids[3], const float* const inputs[3],
-                                     const float* const conv1[3], const float* const conv2[3], int n_feats,
-                                     float* out, int B, int H, int W, int GH, int GW, int GD, int seg,
-                                     unsigned flags, void* stream);
 
 #ifdef __cplusplus
 }

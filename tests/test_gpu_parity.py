@@ -167,14 +167,10 @@ def test_apply_forward_random(dev, ops, port, shape):
     assert worst < 4.0, (kern, worst)
 
 
-# The benchmark-only forward kernels DESIGN.md quotes timings for (tools build of the library:
-# apply_fwd_variants.hip; the product kernel's own load / store flavours, variants 20-72, were removed in round 5) must
-# compute the same op as the shipped one, or
-# those timings compare nothing.  They are reached through the TOOLS library's C-ABI only.
-@pytest.mark.parametrize("variant,expect", [(2, "apply_fwd_wave"), (3, "apply_fwd_stream"),
-                                            (5, "apply_fwd_stream"), (7, "direct-stores"),
-                                            (8, "nt-loads"), (9, "multiquad2"), (11, "multiquad4"),
-                                            (19, "apply_fwd_rows/vec4")])
+# The forward kernel that the TOOLS library selects by variant number (19: the round-1 row kernel, the product's own
+# fallback; the rejected forwards, variants 2-11, were removed with their kernels) must compute the same op as the
+# shipped one, or an A/B timing against it compares nothing.  It is reached through the TOOLS library's C-ABI only.
+@pytest.mark.parametrize("variant,expect", [(19, "apply_fwd_rows/vec4")])
 @pytest.mark.parametrize("shape", [(2, 48, 2048, 16, 16, 8, 3, 3, True, -0.2, 1.2),
                                    (1, 37, 3076, 16, 16, 8, 3, 3, True, 0.0, 1.0),
                                    (1, 21, 1920, 16, 16, 8, 3, 3, True, -0.1, 1.1)])
@@ -195,9 +191,29 @@ def test_apply_forward_benchmark_variants(dev, port, shape, variant, expect):
     assert rc == 0, tools.hdrnet_last_error().decode()
     torch.cuda.synchronize()
     kern = tools.hdrnet_last_kernel().decode()
-    # a variant without a specialisation for the shape falls back to the product kernel
-    assert expect in kern or (variant in (3, 5) and kern == "apply_fwd_seg/vec4"), kern
+    assert expect in kern, kern
     np.testing.assert_allclose(N(out), want, rtol=FWD_RTOL, atol=FWD_ATOL, err_msg=kern)
+
+
+def test_skeleton_variant_without_a_kernel_for_the_shape_is_refused(dev):
+    """Variant 106 (a memory skeleton: 3 -> 3 with offset only) on a 1 -> 1 frame is refused by number -- not served by
+    the product kernel under the skeleton's number -- and nothing is written."""
+    import torch
+    from hdrnet_amd import _lib
+    tools = _lib.load_tools()
+    B, H, W, GH, GW, GD = 1, 4, 16, 2, 2, 2
+    grid = torch.rand((B, GH, GW, GD, 2), device=dev)
+    guide = torch.rand((B, H, W), device=dev)
+    inp = torch.rand((B, H, W, 1), device=dev)
+    out = torch.full((B, H, W, 1), float("nan"), device=dev)
+    rc = tools.hdrnet_bilateral_slice_apply_f32_ex(
+        grid.data_ptr(), guide.data_ptr(), inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, 1, 1, 1,
+        _lib.KERNEL_FAST | (106 << 8), torch.cuda.current_stream(dev).cuda_stream)
+    err = tools.hdrnet_last_error().decode()
+    assert rc == _lib.HDRNET_INVALID_ARGUMENT, (rc, err)
+    assert "variant 106 has no kernel for this shape" in err, err
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())
 
 
 def test_product_library_has_no_benchmark_variants(dev):
@@ -732,57 +748,45 @@ def test_wire_format_forward(dev, ops, port, in_dtype, wl, out_dtype, nn):
 
 @pytest.mark.parametrize("n", [16, 8, 4, 12, 5])
 @pytest.mark.parametrize("out_dtype", ["uint8", "float32"])
-@pytest.mark.parametrize("mfma", [False, True])
-def test_u8_guide_network_guide_itself(dev, ops, port, n, out_dtype, mfma, monkeypatch):
+def test_u8_guide_network_guide_itself(dev, ops, port, n, out_dtype):
     """uint8 input + fused guide network: the GUIDE the kernel computes is held to 1e-6 against the numpy restatement
     of the folded network (the bar of the f32 kernel, test_nnguide_fused_matches_composed_oracle), every byte value
-    0..255 in every channel present.  mfma = True: the round-4 experiment of the TOOLS build (knob 5) -- the hidden
-    layer as bf16-split 4x4x4 matrix instructions (apply_fwd_io.hip: guide_nn_quad_mfma_u8; n % 4 == 0, n <= 16, n = 5
-    falls back to the VALU form) -- parity-green, rejected on time (profiles/r04/guide_nn_mfma.md)."""
+    0..255 in every channel present."""
     import oracle
     from hdrnet_amd import _lib
-    if mfma:
-        tools = _lib.load_tools()
-        monkeypatch.setattr(_lib, "load", lambda: tools)
-        tools.hdrnet_enable_kernel_names(1)
-        tools.hdrnet_tools_set_knob(5, 1)
-    try:
-        B, H, W, GH, GW, GD = 2, 24, 128, 16, 16, 8
-        rng = np.random.default_rng(100 + n)
-        grid6 = np.zeros((B, GH, GW, GD, 3, 4), np.float32)
-        for i in range(3):
-            grid6[..., i, i] = 1.0
-        grid = (grid6 + 0.15 * rng.standard_normal(grid6.shape)).astype(np.float32).reshape(B, GH, GW, GD, 12)
-        raw = rng.integers(0, 256, (B, H, W, 3)).astype(np.uint8)
-        raw[0, 0, :, 0] = np.arange(W) * 2 % 256          # ramps: every byte value in every channel
-        raw[0, 1, :, 1] = (np.arange(W) * 2 + 1) % 256
-        raw[0, 2, :, 2] = np.arange(W) * 2 % 256
-        raw[0, 3, :, :] = 255
-        raw[0, 4, :, :] = 0
-        inp_f = (raw.astype(np.float32) / np.float32(255.0)).astype(np.float32)
-        conv1 = (rng.standard_normal((n, 4)) * 0.8).astype(np.float32)
-        conv2 = (rng.standard_normal(n + 1) * 0.5).astype(np.float32)
-        guide = oracle.pointwise_nn_guide(inp_f, conv1, conv2)
-        want_f = port.bilateral_slice_apply(grid, guide, inp_f, True)
-        kw = dict(input_white_level=255.0, out_dtype=getattr(torch, out_dtype), guide_conv1=T(conv1, dev),
-                  guide_conv2=T(conv2, dev))
-        out, gout = ops.bilateral_slice_apply_io(T(grid, dev), torch.from_numpy(raw).to(dev), return_guide=True, **kw)
-        name = (tools if mfma else _lib.load()).hdrnet_last_kernel().decode()
-        assert name == f"apply_fwd_io/u8->{'u8' if out_dtype == 'uint8' else 'f32'}+nnguide"
-        np.testing.assert_allclose(N(gout), guide, rtol=0, atol=1e-6)
-        # inference form (HDRNET_GUIDE_SIGMOID_FAST: v_exp / v_rcp sigmoid)
-        out2 = ops.bilateral_slice_apply_io(T(grid, dev), torch.from_numpy(raw).to(dev), fast_sigmoid=True, **kw)
-        if out_dtype == "float32":
-            np.testing.assert_allclose(N(out), want_f, rtol=1e-5, atol=1e-5)
-            np.testing.assert_allclose(N(out2), want_f, rtol=1e-5, atol=1e-5)
-        else:
-            want_u8 = (np.float32(255.0) * np.clip(want_f, 0, 1)).astype(np.uint8)
-            for got in (N(out), N(out2)):
-                diff = np.abs(got.astype(np.int16) - want_u8.astype(np.int16))
-                assert diff.max() <= 1 and (diff > 0).mean() < 5e-4
-    finally:
-        if mfma:
-            tools.hdrnet_tools_set_knob(5, 0)
+    B, H, W, GH, GW, GD = 2, 24, 128, 16, 16, 8
+    rng = np.random.default_rng(100 + n)
+    grid6 = np.zeros((B, GH, GW, GD, 3, 4), np.float32)
+    for i in range(3):
+        grid6[..., i, i] = 1.0
+    grid = (grid6 + 0.15 * rng.standard_normal(grid6.shape)).astype(np.float32).reshape(B, GH, GW, GD, 12)
+    raw = rng.integers(0, 256, (B, H, W, 3)).astype(np.uint8)
+    raw[0, 0, :, 0] = np.arange(W) * 2 % 256          # ramps: every byte value in every channel
+    raw[0, 1, :, 1] = (np.arange(W) * 2 + 1) % 256
+    raw[0, 2, :, 2] = np.arange(W) * 2 % 256
+    raw[0, 3, :, :] = 255
+    raw[0, 4, :, :] = 0
+    inp_f = (raw.astype(np.float32) / np.float32(255.0)).astype(np.float32)
+    conv1 = (rng.standard_normal((n, 4)) * 0.8).astype(np.float32)
+    conv2 = (rng.standard_normal(n + 1) * 0.5).astype(np.float32)
+    guide = oracle.pointwise_nn_guide(inp_f, conv1, conv2)
+    want_f = port.bilateral_slice_apply(grid, guide, inp_f, True)
+    kw = dict(input_white_level=255.0, out_dtype=getattr(torch, out_dtype), guide_conv1=T(conv1, dev),
+              guide_conv2=T(conv2, dev))
+    out, gout = ops.bilateral_slice_apply_io(T(grid, dev), torch.from_numpy(raw).to(dev), return_guide=True, **kw)
+    name = _lib.load().hdrnet_last_kernel().decode()
+    assert name == f"apply_fwd_io/u8->{'u8' if out_dtype == 'uint8' else 'f32'}+nnguide"
+    np.testing.assert_allclose(N(gout), guide, rtol=0, atol=1e-6)
+    # inference form (HDRNET_GUIDE_SIGMOID_FAST: v_exp / v_rcp sigmoid)
+    out2 = ops.bilateral_slice_apply_io(T(grid, dev), torch.from_numpy(raw).to(dev), fast_sigmoid=True, **kw)
+    if out_dtype == "float32":
+        np.testing.assert_allclose(N(out), want_f, rtol=1e-5, atol=1e-5)
+        np.testing.assert_allclose(N(out2), want_f, rtol=1e-5, atol=1e-5)
+    else:
+        want_u8 = (np.float32(255.0) * np.clip(want_f, 0, 1)).astype(np.uint8)
+        for got in (N(out), N(out2)):
+            diff = np.abs(got.astype(np.int16) - want_u8.astype(np.int16))
+            assert diff.max() <= 1 and (diff > 0).mean() < 5e-4
 
 
 def test_nnguide_rejects_unsupported(dev, ops):
@@ -1034,68 +1038,3 @@ def test_grid_optimisation_converges(dev, ops):
         opt.step()
         first = loss.item() if first is None else first
     assert loss.item() < first / 50, (first, loss.item())
-
-
-# ---- the TOOLS kernel DESIGN.md quotes numbers for --------------------------
-# It lives in libhdrnet_amd_tools.so only.  If it drifts from what it is claimed to compute, the timings quoted
-# for it (profiles/r05/pyramid_onepass.md) compare nothing.
-def _tools_or_skip():
-    from hdrnet_amd import _lib
-    try:
-        return _lib.load_tools()
-    except (OSError, RuntimeError) as e:
-        pytest.skip(f"tools library not built: {e}")
-
-
-@pytest.mark.parametrize("B,H,W,GH,GW,GD,seg", [(1, 64, 1024, 16, 16, 8, 512), (2, 136, 1536, 8, 12, 8, 768)])
-def test_tools_pyramid_onepass_equals_the_per_level_chain_bit_for_bit(dev, B, H, W, GH, GW, GD, seg):
-    """hdrnet_tools_pyramid_onepass_f32 (csrc/pyramid_onepass.hip: the whole multi-scale output of
-    HDRNetGaussianPyrNN, hdrnet/models.py:277-289 / benchmark/assets/gpyrnn.frag:65-86, in ONE launch) against the
-    product's chain of three launches (guide network + slice-apply at 1/4; + up-add at 1/2; + up-add at 1/1)."""
-    import ctypes
-    from hdrnet_amd import _lib
-    lib = _tools_or_skip()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    gen = torch.Generator(device=dev).manual_seed(B * 1000 + W)
-    FAST = _lib.GUIDE_SIGMOID_FAST
-
-    def chk(rc):
-        assert rc == 0, lib.hdrnet_last_error().decode()
-
-    full = torch.rand((B, H, W, 3), device=dev, generator=gen)
-    half = torch.empty((B, H // 2, W // 2, 3), device=dev)
-    quarter = torch.empty((B, H // 4, W // 4, 3), device=dev)
-    chk(lib.hdrnet_resize_bilinear_f32(full.data_ptr(), half.data_ptr(), B, H, W, H // 2, W // 2, 3, stream))
-    chk(lib.hdrnet_resize_bilinear_f32(half.data_ptr(), quarter.data_ptr(), B, H // 2, W // 2, H // 4, W // 4, 3, stream))
-    ins = [full, half, quarter]
-    grids = []
-    for _l in range(3):
-        g6 = torch.zeros((B, GH, GW, GD, 3, 4), device=dev)
-        for i in range(3):
-            g6[..., i, i] = 0.4
-        grids.append((g6 + 0.15 * torch.randn(g6.shape, device=dev, generator=gen)).reshape(B, GH, GW, GD, 12).contiguous())
-    conv1 = [(torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous() for _ in range(3)]
-    conv2 = [(torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous() for _ in range(3)]
-    l2 = torch.empty((B, H // 4, W // 4, 3), device=dev)
-    l1 = torch.empty((B, H // 2, W // 2, 3), device=dev)
-    out_chain = torch.full((B, H, W, 3), float("nan"), device=dev)
-    out_one = torch.full((B, H, W, 3), float("nan"), device=dev)
-    chk(lib.hdrnet_bilateral_slice_apply_nnguide_f32_ex(
-        grids[2].data_ptr(), ins[2].data_ptr(), conv1[2].data_ptr(), conv2[2].data_ptr(), l2.data_ptr(), None,
-        B, H // 4, W // 4, GH, GW, GD, 3, 3, 1, 16, FAST, stream))
-    chk(lib.hdrnet_bilateral_slice_apply_upadd_f32_ex(
-        grids[1].data_ptr(), None, ins[1].data_ptr(), l2.data_ptr(), H // 4, W // 4, l1.data_ptr(),
-        B, H // 2, W // 2, GH, GW, GD, 3, 3, 1, conv1[1].data_ptr(), conv2[1].data_ptr(), 16, FAST, stream))
-    chk(lib.hdrnet_bilateral_slice_apply_upadd_f32_ex(
-        grids[0].data_ptr(), None, ins[0].data_ptr(), l1.data_ptr(), H // 2, W // 2, out_chain.data_ptr(),
-        B, H, W, GH, GW, GD, 3, 3, 1, conv1[0].data_ptr(), conv2[0].data_ptr(), 16, FAST, stream))
-    P3 = ctypes.c_void_p * 3
-    chk(lib.hdrnet_tools_pyramid_onepass_f32(
-        P3(*[t.data_ptr() for t in grids]), P3(*[t.data_ptr() for t in ins]), P3(*[t.data_ptr() for t in conv1]),
-        P3(*[t.data_ptr() for t in conv2]), 16, out_one.data_ptr(), B, H, W, GH, GW, GD, seg, FAST, stream))
-    torch.cuda.synchronize()
-    assert torch.isfinite(out_chain).all() and torch.isfinite(out_one).all()
-    diff = float((out_one - out_chain).abs().max())
-    print(f"pyramid one pass vs chain ({B}, {H}, {W}) seg={seg}: max|diff| = {diff:.3e} on values up to "
-          f"{float(out_chain.abs().max()):.3g}")
-    assert torch.equal(out_one, out_chain), diff

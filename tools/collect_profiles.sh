@@ -93,10 +93,9 @@ if [ -f $PREV ]; then
 fi
 # the guide forwards with the exported arrays and with the parameters prepared once per parameter set (round 5), interleaved
 for w in 4k 1080p; do python tools/guide_prepared_ab.py --workload $w 2>&1 | grep -v amdgpu.ids; done > $O/guide_prepared_ab.txt
-python tools/bwd_ab.py --rounds 5 --steps 50 --cases all,gg,g,sl,v --variants 0,2,10,3,4,5,6,7,8 > $O/bwd_ab_4k.txt 2>&1
+python tools/bwd_ab.py --rounds 5 --steps 50 --cases all,gg,g,sl,v --variants 0,3 > $O/bwd_ab_4k.txt 2>&1
 python tools/bwd_ab.py --workload 1080p --rounds 5 --steps 100 --cases all,gg,g,sl,v --variants 0,3 > $O/bwd_ab_1080p.txt 2>&1
 python tools/bwd_ab.py --smooth --rounds 5 --steps 50 --cases all,gg,g --variants 0 > $O/bwd_ab_4k_smooth_guide.txt 2>&1
-python tools/pyramid_onepass_bench.py --workload 4k --segs 512,768,1024 > $O/pyramid_onepass_4k.txt 2>&1
 python tools/e2e_bench.py > $O/e2e.txt 2>&1
 # the coefficient network's launches, per-workgroup timeline (tools build)
 python tools/coeff_trace.py > $O/coeff_trace.txt 2>&1

@@ -6,6 +6,10 @@ to the GPU box).  Box-to-box spread is ~5 %, run-to-run drift 1-2 %: a kernel ch
 only be measured like this.
 
     python tools/prev_vs_new.py --prev tools/exp/prev/libhdrnet_amd_prev.so [--workload 4k] [--rounds 7]
+                                [--cases fwd,nn,u8nn,u16nn] [--order new,prev]
+
+Per case: each build's median and min - max over the rounds, and whether the new median lies inside the previous build's
+range.  --order says which build runs first in every round; a difference that changes sign with it is the run order's.
 
 --coeff: the coefficient network's training step (forward + gradient through the C ABI, with and without batch norm,
 through the first entry points and their ..._wide twins) instead of the slice-apply entry points:
@@ -255,6 +259,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--cases", default="fwd,all,gg,g,v,slice_fwd,slice_bwd")
+    ap.add_argument("--order", default="prev,new", choices=["prev,new", "new,prev"], help="which build runs first in a round")
     ap.add_argument("--nsets", type=int, default=0, help="buffer sets to rotate over (default: enough to exceed the "
                     "Infinity Cache; 1 = cache-resident, for telling memory time from issue time)")
     ap.add_argument("--coeff", choices=["bits", "times", "trace", "report"],
@@ -299,6 +304,7 @@ def main():
     mix = torch.tensor([0.4, 0.35, 0.25, 0.02], device=dev)
     u8 = [dict(inp=torch.randint(0, 256, (B, H, W, 3), device=dev, dtype=torch.uint8),
                out=torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)) for _ in range(nsets)]
+    u16 = [torch.randint(0, 65536, (B, H, W, 3), device=dev, dtype=torch.int32).to(torch.uint16) for _ in range(nsets)]
     coarse = [torch.randn((B, H // 2, W // 2, 3), device=dev, generator=gen) for _ in range(nsets)]
     stream = torch.cuda.current_stream(dev).cuda_stream
     # The guide-network / curves-guide cases call each build the way its round's models did: a build with the round-5
@@ -387,6 +393,13 @@ def main():
                     B, H, W, GH, GW, GD, 3, 3, 1, 1, 255.0, 1, conv1.data_ptr() if nn else None,
                     conv2.data_ptr() if nn else None, 16 if nn else 0, None, stream))
             return fn
+        if case == "u16nn":  # u16 in -> guide network -> f32 out
+            def fn(k):
+                s = S[k % nsets]
+                chk(lib.hdrnet_bilateral_slice_apply_io_ex(
+                    s["grid"].data_ptr(), None, u16[k % nsets].data_ptr(), s["out"].data_ptr(), B, H, W, GH, GW, GD, 3, 3, 1,
+                    2, 65535.0, 0, nn1.data_ptr(), nn2.data_ptr(), 16, None, nnflags, stream))
+            return fn
         if case in ("curves", "u8curves"):  # curves guide fused: f32 -> f32, u8 -> u8
             u = case == "u8curves"
 
@@ -455,12 +468,14 @@ def main():
         diff = max(float((a - b).abs().max()) for a, b in zip(outs["prev"], outs["new"]))
         res = {"prev": [], "new": []}
         for _ in range(args.rounds):
-            for w in ("prev", "new"):
+            for w in args.order.split(","):
                 time_launches(fns[w], 20)
                 res[w].append(time_launches(fns[w], args.steps))
         mp, mn = statistics.median(res["prev"]), statistics.median(res["new"])
-        print(f"{case:10s} prev {mp:7.2f} us (min {min(res['prev']):7.2f})   new {mn:7.2f} us (min {min(res['new']):7.2f})   "
-              f"new / prev = {mn / mp:.3f}   max|new - prev| = {diff:.2e}")
+        lo, hi = min(res["prev"]), max(res["prev"])
+        where = "inside prev's range" if lo <= mn <= hi else f"{mn - hi:+.2f} us beyond prev's max" if mn > hi else f"{mn - lo:+.2f} us below prev's min"
+        print(f"{case:10s} prev {mp:7.2f} us ({lo:7.2f} - {hi:7.2f})   new {mn:7.2f} us ({min(res['new']):7.2f} - {max(res['new']):7.2f})   "
+              f"new / prev = {mn / mp:.3f}   new median {where}   max|new - prev| = {diff:.2e}")
 
 
 if __name__ == "__main__":
