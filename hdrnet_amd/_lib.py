@@ -200,6 +200,21 @@ YUV_SIGNATURES = {
                                                    [_I, _VP, _FP] + _YUV_OUTPUT + [_VP]),
 }
 
+# include/hdrnet_amd_u16_out.h: the same fused forwards with a 16-bit output -- a uint16 frame in the input's pixel format
+# (`output_dtype` replaced by `output_white_level`), a P010 / P016 surface (the output surface, from_rgb and `out_bits` in
+# place of the `output_kind` ... `from_rgb` tail).
+_P016_OUTPUT = [_FP, _FP, _I, _I, _LL, _LL, _FP, _I]  # out_y, out_uv, pitches, image strides, from_rgb, out_bits
+U16_OUT_SIGNATURES = {
+    "hdrnet_bilateral_slice_apply_io_px_u16": (_I, [_FP] * 4 + [_I] * 10 + [ctypes.c_float, ctypes.c_float] + [_FP] * 2 +
+                                               [_I, _FP, _U, _I, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_px_u16": (_I, [_FP] * 3 + [_I] * 10 + [ctypes.c_float, ctypes.c_float] + [_FP] * 4 +
+                                                      [_I, _VP, _FP, _I, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv_p016": (_I, [_FP, _FP] + _SURFACE + [_I] * 3 + [_FP] + [_I] * 6 +
+                                                 [_FP, _FP, _I, _FP, _U] + _P016_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv_p016": (_I, [_FP] + _SURFACE + [_I] * 3 + [_FP] + [_I] * 6 + [_FP] * 4 +
+                                                        [_I, _VP, _FP] + _P016_OUTPUT + [_VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -254,6 +269,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(PYRAMID_IO_SIGNATURES)
     table.update(PIXEL_FORMAT_SIGNATURES)
     table.update(YUV_SIGNATURES)
+    table.update(U16_OUT_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

@@ -6,6 +6,7 @@ namespace hdrnet_amd {
 
 bool apply_fwd_io_supported(const ApplyIoArgs& a) {
   if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
+  if (a.output_dtype != 0 && a.output_dtype != 1) return false;  // a 16-bit output: apply_fwd_io_u16.hip
   if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;  // quantised pixels: whole dwords per lane
   if (a.pixel_format != kPxRGB) {
     if (a.pixel_format < 0 || a.pixel_format > kPxBGRA || a.input_dtype == 0) return false;  // integer frames only

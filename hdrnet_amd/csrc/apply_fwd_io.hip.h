@@ -28,6 +28,14 @@
 // This header holds the kernel and its launch; the RGB instantiations are compiled by apply_fwd_io.hip, those of the
 // other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many), those of the YUV
 // surfaces by apply_fwd_io_yuv.hip.
+//
+// 16-BIT OUTPUT (include/hdrnet_amd_u16_out.h): TO = uint16_t stores a uint16 frame, (uint16)(out_white * clip(v, 0, 1)) in
+// the input's pixel format -- the uint8 store's rule with 255 replaced by a run-time constant -- and OUT = kOutP016 a
+// P010 / P016 surface, the NV12 store's row-pair structure with uint16 code words.  Both are further branches of the
+// epilogue behind `if constexpr`: no other instantiation compiles a line of them.  Their instantiations are
+// apply_fwd_io_u16.hip's, DELIBERATELY LIMITED to keep the build small: uint16 and float32 RGB frames and uint16 BGR / RGBA
+// / BGRA frames to a uint16 frame, a uint16 surface to a uint16 surface.  uint8 -> 16 bit, float32 packed orders, a uint16
+// RGB frame out of a YUV surface and the pyramid's up-add are not instantiated and are refused by rule.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,7 +70,8 @@ constexpr int kGuideCurvesCells = 4;  // the curves guide from the PREPARED unif
 // PX beyond the packed formats of white_level.hip.h: the frame is a YUV surface (IoParams::yin); the op still sees R, G, B
 constexpr int kPxYuv = 4;
 // what the kernel stores: a frame of TO in the input's packed format / RGB -- or an NV12 surface (IoParams::yout)
-constexpr int kOutFrame = 0, kOutNV12 = 1;
+// ... or a P010 / P016 surface (uint16 code words of IoParams::code_shift's depth in the high bits)
+constexpr int kOutFrame = 0, kOutNV12 = 1, kOutP016 = 2;
 
 struct GuideNet {
   const float* conv1;  // NN: [n][CIN + 1]            curves: ccm [CIN][CIN + 1] (row = output channel)
@@ -420,6 +429,10 @@ struct IoParams {
   YuvSurface yin, yout;
   const float* to_rgb;    // 12 floats each (yuv_convert.hip.h)
   const float* from_rgb;
+  // 16-bit output (TO = uint16_t / OUT == kOutP016; read by no other instantiation)
+  float out_white;  // a uint16 frame: (uint16)(out_white * clip(v, 0, 1))
+  float code_max;   // a P010 / P016 surface: 2^out_bits - 1 ...
+  int code_shift;   // ... and 16 - out_bits
 };
 
 // Geometry, LDS image and pixel core are apply_fwd_seg.hip's (seg_common.hip.h): a workgroup owns a row
@@ -430,6 +443,9 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   constexpr bool YUV = PX == kPxYuv;          // the input is a YUV surface; the frame the kernel stores is RGB
   constexpr bool NV12OUT = OUT == kOutNV12;   // ... unless the output is an NV12 surface: a workgroup owns a row pair
   static_assert(!NV12OUT || (YUV && sizeof(TO) == 1), "NV12 out: uint8 planes, from a YUV surface");
+  constexpr bool P016OUT = OUT == kOutP016;   // ... or a P010 / P016 surface: the same row pair, uint16 code words
+  static_assert(!P016OUT || (YUV && sizeof(TI) == 2 && sizeof(TO) == 2), "P010 / P016 out: uint16 planes, from a uint16 surface");
+  constexpr bool SURFOUT = NV12OUT || P016OUT;
   constexpr bool PACKED = PX != kPxRGB && !YUV;  // BGR / RGBA / BGRA
   constexpr int SPX = PACKED ? px_stored(PX) : CIN;  // samples per stored pixel of the frame
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
@@ -470,10 +486,10 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   // One image row per workgroup -- or, for an NV12 output, the two rows of a chroma row, one after the other through the
   // same LDS image.  (The loop's condition is a compile-time `false` for one row: no back edge, r == 0, and the
   // single-row kernels compile to the straight code they were.)
-  constexpr int ROWS = NV12OUT ? 2 : 1;
+  constexpr int ROWS = SURFOUT ? 2 : 1;
   int r = 0;
   do {
-    const int y = NV12OUT ? 2 * (int)blockIdx.y + r : (int)blockIdx.y;
+    const int y = SURFOUT ? 2 * (int)blockIdx.y + r : (int)blockIdx.y;
     const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (kLimBH, row_geom.h)
     const size_t px = row * p.W + x;
     const TI* input = static_cast<const TI*>(p.input);
@@ -574,6 +590,90 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
           *reinterpret_cast<uint32_t*>(co) = wc;
         }
       }
+    } else if constexpr (P016OUT) {
+      // A P010 / P016 surface: the NV12 store with uint16 code words -- two dwords of Y per lane and row; the chroma of the
+      // lane's two 2 x 2 blocks after the second row, two dwords (U0 V0 | U1 V1) into the pair's interleaved UV row (block
+      // x / 2 starts at sample x of its row, as the luma does).  Padding beyond the row is not written.
+      if (active) {
+        const YuvMatrix fk = yuv_load_matrix(p.from_rgb);
+        const float cmax = p.code_max;
+        const int sh = p.code_shift;
+        uint32_t wy[2] = {0, 0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          float pu[2], pv[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int k = 2 * h + i;
+            float c[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) c[j] = __builtin_amdgcn_fmed3f(of[k * COUT + j], 0.0f, 1.0f);
+            wy[h] |= yuv_luma_code16(fk, c, cmax, sh) << (16 * i);
+            pu[i] = yuv_chroma_linear(fk, 1, c);
+            pv[i] = yuv_chroma_linear(fk, 2, c);
+          }
+          csum[h][0] += pu[0] + pu[1];  // horizontal pair first; even row (onto 0), then odd row
+          csum[h][1] += pv[0] + pv[1];
+        }
+        char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y +
+                   (size_t)x * 2;
+        reinterpret_cast<uint32_t*>(yo)[0] = wy[0];  // (two dwords: the planes promise 4-byte alignment, not 8)
+        reinterpret_cast<uint32_t*>(yo)[1] = wy[1];
+        if (r == ROWS - 1) {
+          char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
+                     (long long)(y >> 1) * p.yout.pitch_uv + (size_t)x * 2;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            reinterpret_cast<uint32_t*>(co)[h] =
+                yuv_chroma_code16(fk, 1, csum[h][0], cmax, sh) | (yuv_chroma_code16(fk, 2, csum[h][1], cmax, sh) << 16);
+        }
+      }
+    } else if constexpr (sizeof(TO) == 2) {
+      // a uint16 frame: (uint16)(out_white * clip(out, 0, 1)), one multiply and a truncation -- the uint8 store below with a
+      // run-time white level.  24 bytes per lane (32 with alpha), contiguous across the wave: plain per-lane stores.
+      static_assert(COUT == 3, "the 3 -> 3 op");
+      const float wl = p.out_white;
+      if constexpr (PACKED) {
+        // the input's own pixel format; alpha (of a uint16 frame) copied bit for bit
+        static_assert(sizeof(TI) == 2, "packed 16-bit output: from a uint16 frame");
+        if (active) {
+          uint32_t w[2 * SPX];
+#pragma unroll
+          for (int q = 0; q < 2 * SPX; ++q) w[q] = 0;
+#pragma unroll
+          for (int k = 0; k < kPxPerThread; ++k) {
+#pragma unroll
+            for (int i = 0; i < COUT; ++i) {
+              const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);
+              const int pos = px_sample(PX, k, i);
+              w[pos >> 1] |= ((uint32_t)(wl * c)) << (16 * (pos & 1));
+            }
+            if constexpr (SPX == 4) w[2 * k + 1] |= alpha[k] << 16;
+          }
+          uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SPX);
+          if constexpr (SPX == 4) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            reinterpret_cast<u32x4*>(op)[0] = u32x4{w[0], w[1], w[2], w[3]};
+            reinterpret_cast<u32x4*>(op)[1] = u32x4{w[4], w[5], w[6], w[7]};
+          } else {
+#pragma unroll
+            for (int q = 0; q < 2 * SPX; ++q) op[q] = w[q];
+          }
+        }
+      } else if (active) {
+        static_assert(NO % 2 == 0, "whole dwords per thread");
+        uint32_t w[NO / 2];
+#pragma unroll
+        for (int q = 0; q < NO / 2; ++q) w[q] = 0;
+#pragma unroll
+        for (int q = 0; q < NO; ++q) {
+          const float c = __builtin_amdgcn_fmed3f(of[q], 0.0f, 1.0f);
+          w[q >> 1] |= ((uint32_t)(wl * c)) << (16 * (q & 1));
+        }
+        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * COUT);
+#pragma unroll
+        for (int q = 0; q < NO / 2; ++q) op[q] = w[q];
+      }
     } else if constexpr (sizeof(TO) == 1) {
       // tf.cast(255 * clip(out, 0, 1), uint8): truncation.  12 bytes per lane, contiguous across
       // the wave: plain per-lane stores are already dense.
@@ -631,7 +731,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
       float* oseg = static_cast<float*>(p.out) + (row * p.W + xs) * COUT;
       store_slab_seg<COUT>(slab, oseg, (unsigned)(xe - xs), wpx, lane);
     }
-  } while (NV12OUT && ++r < ROWS);
+  } while (SURFOUT && ++r < ROWS);
 }
 
 // The curves instantiations keep their lookup tables in STATIC LDS: no launch passes those bytes, but the workgroup
@@ -669,14 +769,21 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
                      (a.guide_shifts && a.n_feats <= kCurveMaxKnots) ? a.guide_prepared : nullptr};
   p.yin = p.yout = YuvSurface{};
   p.to_rgb = p.from_rgb = nullptr;
+  p.out_white = a.output_white_level;
+  p.code_max = 0.0f;
+  p.code_shift = 0;
   if constexpr (PX == kPxYuv) {
     p.yin = a.yuv->in;
     p.to_rgb = a.yuv->to_rgb;
     p.yout = a.yuv->out;
     p.from_rgb = a.yuv->from_rgb;
+    if constexpr (OUT == kOutP016) {
+      p.code_max = (float)((1 << a.yuv->out_bits) - 1);
+      p.code_shift = 16 - a.yuv->out_bits;
+    }
   }
   // an NV12 output: one workgroup per row PAIR of a segment (H % 2 == 0)
-  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT == kOutNV12 ? a.H / 2 : a.H), (unsigned)a.B);
+  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT != kOutFrame ? a.H / 2 : a.H), (unsigned)a.B);
   apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT><<<grid3, g.pl.threads, g.lds, s>>>(p);
   return hipGetLastError();
 }
@@ -725,5 +832,6 @@ hipError_t dispatch_guides(const ApplyIoArgs& a, hipStream_t s) {
 // apply_fwd_io_px.hip: the same launch for a frame in BGR, RGBA or BGRA order (a.pixel_format != 0)
 hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
 // apply_fwd_io_yuv.hip (launch.hip.h): the same launch for a YUV surface (a.yuv)
+// apply_fwd_io_u16.hip (launch.hip.h): the same launch with a 16-bit output (a.output_dtype == 2)
 
 }  // namespace hdrnet_amd

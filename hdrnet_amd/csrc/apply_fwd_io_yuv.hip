@@ -44,6 +44,7 @@ hipError_t yuv_types(const ApplyIoArgs& a, hipStream_t s) {
 bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a) {
   if (!a.yuv || !(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
   if (a.input_dtype != 1 && a.input_dtype != 2) return false;
+  if (a.yuv->out_kind < 0 || a.yuv->out_kind > HDRNET_YUV_OUT_NV12) return false;  // P010 / P016 out: apply_fwd_io_u16.hip
   if (a.H % 2 != 0 || a.W % 4 != 0) return false;
   return io_geom(a).ok;
 }

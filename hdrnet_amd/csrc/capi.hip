@@ -13,6 +13,7 @@
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_pixel_formats.h"
 #include "../../include/hdrnet_amd_yuv.h"
+#include "../../include/hdrnet_amd_u16_out.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
@@ -167,7 +168,8 @@ int check_upadd_values(int Hc, int Wc, const float* guide, const float* conv1, c
   return HDRNET_OK;
 }
 
-// ---- The wire-format forwards (..._io_ex / _px, ..._io_curves_prepared / _px, ..._upadd_io_ex, ..._io_yuv, ..._io_curves_yuv)
+// ---- The wire-format forwards (..._io_ex / _px, ..._io_curves_prepared / _px, ..._upadd_io_ex, ..._io_yuv, ..._io_curves_yuv,
+// and their 16-bit-output twins ..._px_u16 / ..._yuv_p016 of include/hdrnet_amd_u16_out.h)
 // fill one ApplyIoArgs from a pixel source, a guide source and a launch.  Each side checks values before the zero-size
 // no-op and pointers after it, as two functions: a frame's are check_frame_values / check_pixel_buffers, a YUV surface's
 // check_yuv_io_values / check_yuv_io_pointers; a guide map or network's check_guide_flags / check_guide_given /
@@ -182,8 +184,31 @@ int check_io_format(int input_dtype, float input_white_level, int output_dtype) 
   return HDRNET_OK;
 }
 
-int check_frame_values(int Cin, int Cout, int input_dtype, float input_white_level, int output_dtype) {
+// ... of the entry points with a uint16 frame out (include/hdrnet_amd_u16_out.h: `output_dtype` is not an argument there):
+// uint16 or float32 in, and the white level the output is scaled to
+struct U16Out {
+  const char* what;  // the entry point
+  float white_level;
+};
+
+int check_u16_format(const U16Out& u, int input_dtype, float input_white_level) {
+  if (input_dtype < 0 || input_dtype > 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown dtype code (input %d; 0 f32, 1 u8, 2 u16)", u.what, input_dtype);
+  if (input_dtype == 1)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a uint16 output needs a uint16 or float32 frame (input_dtype 1, uint8: no "
+                "kernel goes from 8 to 16 bits)", u.what);
+  if (!(input_white_level > 0.0f)) return fail(HDRNET_INVALID_ARGUMENT, "%s: input_white_level must be positive", u.what);
+  if (!(u.white_level > 0.0f && u.white_level <= 65535.0f))  // (false for NaN; +inf fails the upper bound)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: output_white_level must be finite with 0 < output_white_level <= 65535 (got %g)",
+                u.what, (double)u.white_level);
+  return HDRNET_OK;
+}
+
+// (`u16`: the call is one of those entry points; output_dtype is then the 2 they pass)
+int check_frame_values(int Cin, int Cout, int input_dtype, float input_white_level, int output_dtype,
+                       const U16Out* u16 = nullptr) {
   if (Cin <= 0 || Cout <= 0) return fail(HDRNET_INVALID_ARGUMENT, "bad channel counts");
+  if (u16) return check_u16_format(*u16, input_dtype, input_white_level);
   return check_io_format(input_dtype, input_white_level, output_dtype);
 }
 
@@ -195,7 +220,7 @@ int check_input_dtype(const char* what, int dtype) {
 }
 
 // the pixel formats of include/hdrnet_amd_pixel_formats.h: integer frames take all four, float32 frames RGB only; a
-// uint8 output has the input's format, a float32 output is RGB
+// uint8 output (and a uint16 one, output_dtype 2: hdrnet_amd_u16_out.h) has the input's format, a float32 output is RGB
 int check_pixel_formats(const char* what, int input_dtype, int output_dtype, int input_format, int output_format) {
   if (input_format < HDRNET_PX_RGB || input_format > HDRNET_PX_BGRA || output_format < HDRNET_PX_RGB ||
       output_format > HDRNET_PX_BGRA)
@@ -204,9 +229,9 @@ int check_pixel_formats(const char* what, int input_dtype, int output_dtype, int
   if (input_dtype == 0 && input_format != HDRNET_PX_RGB)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: float32 frames take HDRNET_PX_RGB only (input_format %d); the other pixel "
                 "formats are those of uint8 / uint16 frames", what, input_format);
-  if (output_dtype == 1 && output_format != input_format)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: a uint8 output has the input's pixel format (input_format %d, output_format %d)",
-                what, input_format, output_format);
+  if (output_dtype != 0 && output_format != input_format)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a %s output has the input's pixel format (input_format %d, output_format %d)",
+                what, output_dtype == 1 ? "uint8" : "uint16", input_format, output_format);
   if (output_dtype == 0 && output_format != HDRNET_PX_RGB)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: a float32 output is [B][H][W][3] in RGB order: output_format must be "
                 "HDRNET_PX_RGB (got %d)", what, output_format);
@@ -214,7 +239,7 @@ int check_pixel_formats(const char* what, int input_dtype, int output_dtype, int
 }
 
 // ... and what a frame in another format than RGB needs of the call: the 3 -> 3 op with offset, W % 4 == 0, 4-byte
-// aligned 3-channel and 16-byte aligned 4-channel integer buffers (`out`: the uint8 output, or null)
+// aligned 3-channel and 16-byte aligned 4-channel integer buffers (`out`: the uint8 / uint16 output, or null)
 int check_pixel_buffers(const char* what, int pixel_format, int Cin, int Cout, int has_offset, int W, const void* input,
                         const void* out) {
   if (pixel_format == HDRNET_PX_RGB) return HDRNET_OK;
@@ -271,22 +296,32 @@ int check_yuv_pointers(const char* what, const char* which, const hdrnet_amd::Yu
 }
 
 // ... and of a fused forward's surfaces and output.  `io`: the call's arguments as given; io.out.y is `out` whatever the
-// output kind.
+// output kind.  `p016`: the call is an entry point of hdrnet_amd_u16_out.h, which has no output kind argument: io.out_kind
+// is then kYuvOutP016 and the output a uint16 surface of io.out_bits bits.
 int check_yuv_io_values(const char* what, const hdrnet_amd::YuvIo& io, int sample_dtype, int B, int H, int W, int Cin, int Cout,
-                        int has_offset) {
+                        int has_offset, bool p016 = false) {
   if (int rc = check_yuv_extents(what, B, H, W)) return rc;
   if (int rc = check_yuv_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
-  if (io.out_kind < HDRNET_YUV_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_OUT_NV12)
+  if (p016) {
+    if (sample_dtype != 2)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: a P010 / P016 output needs a uint16 surface in (sample_dtype 2, got %d: no "
+                  "kernel goes from 8 to 16 bits)", what, sample_dtype);
+    if (io.out_bits != 10 && io.out_bits != 16)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits must be 10 (P010) or 16 (P016), got %d", what, io.out_bits);
+  } else if (io.out_kind < HDRNET_YUV_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_OUT_NV12) {
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 NV12)", what, io.out_kind);
+  }
   if (Cin != 3 || Cout != 3 || !has_offset)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
+  if (p016) return check_yuv_surface(what, "output", 2, io.out, B, H, W);
   if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_surface(what, "output", 1, io.out, B, H, W);
   return HDRNET_OK;
 }
 
 int check_yuv_io_pointers(const char* what, const hdrnet_amd::YuvIo& io) {
   if (int rc = check_yuv_pointers(what, "input", io.in, io.to_rgb)) return rc;
-  if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_pointers(what, "output", io.out, io.from_rgb);
+  if (io.out_kind == HDRNET_YUV_OUT_NV12 || io.out_kind == hdrnet_amd::kYuvOutP016)
+    return check_yuv_pointers(what, "output", io.out, io.from_rgb);
   if (!io.out.y || ((uintptr_t)io.out.y & (io.out_kind == HDRNET_YUV_OUT_RGB_F32 ? 15u : 3u)))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
   return HDRNET_OK;
@@ -321,16 +356,21 @@ int set_curves_prepared(hdrnet_amd::ApplyIoArgs& a, const void* prepared, const 
   return HDRNET_OK;
 }
 
-// The tail: the kernel family is the pixel source's (a.yuv, or `coarse` for the pyramid's up-add), `otherwise` what the
-// entry point supports, `op` its name in a runtime failure.
+// The tail: the kernel family is the 16-bit output's (a.output_dtype == 2), else the pixel source's (a.yuv, or `coarse`
+// for the pyramid's up-add), `otherwise` what the entry point supports, `op` its name in a runtime failure.
 int launch_io(const hdrnet_amd::ApplyIoArgs& a, const float* coarse, int Hc, int Wc, const char* op, const char* otherwise,
               void* stream) {
   using namespace hdrnet_amd;
-  if (!(a.yuv ? apply_fwd_io_yuv_supported(a) : coarse ? apply_fwd_io_upadd_supported(a, coarse) : apply_fwd_io_supported(a)))
+  const bool u16 = a.output_dtype == 2 && !coarse;
+  if (!(u16      ? apply_fwd_io_u16_supported(a)
+        : a.yuv  ? apply_fwd_io_yuv_supported(a)
+        : coarse ? apply_fwd_io_upadd_supported(a, coarse)
+                 : apply_fwd_io_supported(a)))
     return refuse_fused(a.B, a.H, a.W, a.GW, a.GD, a.Cout, rows::kSegLimits, otherwise);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name = "";
-  const hipError_t e = a.yuv    ? launch_apply_fwd_io_yuv(a, s, &name)
+  const hipError_t e = u16      ? launch_apply_fwd_io_u16(a, s, &name)
+                       : a.yuv  ? launch_apply_fwd_io_yuv(a, s, &name)
                        : coarse ? launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name)
                                 : launch_apply_fwd_io(a, s, &name);
   return finish_launch(e, op, name);
@@ -485,7 +525,7 @@ extern "C" {
 //          hdrnet_bilateral_slice_apply_io_curves_px (uint8 / uint16 frames in BGR, RGBA and BGRA order)
 // 0.2.8.7: + include/hdrnet_amd_yuv.h: hdrnet_yuv_to_rgb_f32, hdrnet_lowres_input_yuv, hdrnet_bilateral_slice_apply_io_yuv,
 //          hdrnet_bilateral_slice_apply_io_curves_yuv (NV12 / P010 / P016 surfaces in, RGB or NV12 out)
-int hdrnet_version(void) { return 287; }
+int hdrnet_version(void) { return 288; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -1028,21 +1068,22 @@ int hdrnet_coefficients_bn_grad_wide_f32(const float* lowres, const hdrnet_coeff
 static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
                          int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
                          int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
-                         float* guide_out, unsigned flags, int pixel_format, void* stream) {
+                         float* guide_out, unsigned flags, int pixel_format, void* stream, const U16Out* u16 = nullptr) {
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = check_guide_flags(flags)) return rc;
-  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype)) return rc;
+  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype, u16)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
   if (int rc = check_guide_given("", guide, guide_conv1, guide_conv2, n_feats)) return rc;
-  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset, W, input,
-                                   output_dtype == 1 ? out : nullptr))
+  if (int rc = check_pixel_buffers(u16 ? u16->what : "hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset,
+                                   W, input, output_dtype != 0 ? out : nullptr))
     return rc;
   ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
                 input_dtype, output_dtype, input_white_level, guide_conv1, guide_conv2, n_feats,
                 guide_out};
   a.pixel_format = pixel_format;
+  if (u16) a.output_white_level = u16->white_level;
   if (int rc = set_io_guide_flags(a, flags)) return rc;
   return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIO",
                    "the wire-format forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
@@ -1076,21 +1117,22 @@ static int apply_io_curves_impl(const float* grid, const void* input, void* out,
                                 int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
                                 int output_dtype, const float* guide_ccm, const float* guide_shifts,
                                 const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
-                                float* guide_out, int pixel_format, void* stream) {
+                                float* guide_out, int pixel_format, void* stream, const U16Out* u16 = nullptr) {
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype)) return rc;
+  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype, u16)) return rc;
   if (int rc = check_curves_knots("", npts)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (!grid || !input || !out || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
     return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_pixel_buffers("hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout, has_offset, W,
-                                   input, output_dtype == 1 ? out : nullptr))
+  if (int rc = check_pixel_buffers(u16 ? u16->what : "hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout,
+                                   has_offset, W, input, output_dtype != 0 ? out : nullptr))
     return rc;
   ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
                 input_dtype, output_dtype, input_white_level, guide_ccm, guide_mix, npts,
                 guide_out, guide_shifts, guide_slopes};
   a.pixel_format = pixel_format;
+  if (u16) a.output_white_level = u16->white_level;
   if (int rc = set_curves_prepared(a, prepared, "", "Cin = 3, npts <= 16")) return rc;
   return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIOCurves",
                    "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
@@ -1201,7 +1243,7 @@ int hdrnet_yuv_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int p
 // both fused entry points, once surfaces and guide are checked: `a` reads the surfaces of `io` (an RGB `out` is a.out)
 static int yuv_io_launch(const char* op, hdrnet_amd::ApplyIoArgs& a, hdrnet_amd::YuvIo& io, void* out, void* stream) {
   using namespace hdrnet_amd;
-  if (io.out_kind != HDRNET_YUV_OUT_NV12) {
+  if (io.out_kind < HDRNET_YUV_OUT_NV12) {
     a.out = out;
     io.out = YuvSurface{};
     io.from_rgb = nullptr;
@@ -1262,6 +1304,90 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv(const float* grid, const void* y,
                 guide_out, guide_shifts, guide_slopes};
   if (int rc = set_curves_prepared(a, prepared, prefix, "npts <= 16")) return rc;
   return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, out, stream);
+}
+
+// ---- include/hdrnet_amd_u16_out.h: a uint16 frame / a P010 / P016 surface out ------------------------------------------
+// (the twins of the four entry points above: the same checks in the same order, the output's own rules beside them)
+int hdrnet_bilateral_slice_apply_io_px_u16(const float* grid, const float* guide, const void* input, void* out, int B,
+                                           int H, int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset,
+                                           int input_dtype, float input_white_level, float output_white_level,
+                                           const float* guide_conv1, const float* guide_conv2, int n_feats,
+                                           float* guide_out, unsigned flags, int input_format, int output_format,
+                                           void* stream) {
+  const U16Out u16{"hdrnet_bilateral_slice_apply_io_px_u16", output_white_level};
+  if (int rc = check_u16_format(u16, input_dtype, input_white_level)) return rc;
+  if (int rc = check_pixel_formats(u16.what, input_dtype, 2, input_format, output_format)) return rc;
+  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                       input_white_level, 2, guide_conv1, guide_conv2, n_feats, guide_out, flags, input_format, stream, &u16);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_px_u16(const float* grid, const void* input, void* out, int B, int H, int W,
+                                                  int GH, int GW, int GD, int Cin, int Cout, int has_offset,
+                                                  int input_dtype, float input_white_level, float output_white_level,
+                                                  const float* guide_ccm, const float* guide_shifts,
+                                                  const float* guide_slopes, const float* guide_mix, int npts,
+                                                  const void* prepared, float* guide_out, int input_format,
+                                                  int output_format, void* stream) {
+  const U16Out u16{"hdrnet_bilateral_slice_apply_io_curves_px_u16", output_white_level};
+  if (int rc = check_u16_format(u16, input_dtype, input_white_level)) return rc;
+  if (int rc = check_pixel_formats(u16.what, input_dtype, 2, input_format, output_format)) return rc;
+  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
+                              input_white_level, 2, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared,
+                              guide_out, input_format, stream, &u16);
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv_p016(const float* grid, const float* guide, const void* y, const void* uv,
+                                             int sample_dtype, int pitch_y, int pitch_uv, long long image_stride_y,
+                                             long long image_stride_uv, int B, int H, int W, const float* to_rgb, int GH,
+                                             int GW, int GD, int Cin, int Cout, int has_offset, const float* guide_conv1,
+                                             const float* guide_conv2, int n_feats, float* guide_out, unsigned flags,
+                                             void* out_y, void* out_uv, int out_pitch_y, int out_pitch_uv,
+                                             long long out_image_stride_y, long long out_image_stride_uv,
+                                             const float* from_rgb, int out_bits, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_bilateral_slice_apply_io_yuv_p016";
+  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, kYuvOutP016,
+           {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb, out_bits};
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_guide_flags(flags)) return rc;
+  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, true)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_io_pointers(what, io)) return rc;
+  if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
+  if (int rc = check_guide_given("hdrnet_bilateral_slice_apply_io_yuv_p016: ", guide, guide_conv1, guide_conv2, n_feats)) return rc;
+  ApplyIoArgs a{grid, guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, 2, 1.0f, guide_conv1, guide_conv2, n_feats, guide_out};
+  if (int rc = set_io_guide_flags(a, flags)) return rc;
+  return yuv_io_launch("BilateralSliceApplyIOYuv", a, io, nullptr, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv_p016(const float* grid, const void* y, const void* uv, int sample_dtype,
+                                                    int pitch_y, int pitch_uv, long long image_stride_y,
+                                                    long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                                                    int GH, int GW, int GD, int Cin, int Cout, int has_offset,
+                                                    const float* guide_ccm, const float* guide_shifts,
+                                                    const float* guide_slopes, const float* guide_mix, int npts,
+                                                    const void* prepared, float* guide_out, void* out_y, void* out_uv,
+                                                    int out_pitch_y, int out_pitch_uv, long long out_image_stride_y,
+                                                    long long out_image_stride_uv, const float* from_rgb, int out_bits,
+                                                    void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv_p016";
+  const char* prefix = "hdrnet_bilateral_slice_apply_io_curves_yuv_p016: ";
+  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, kYuvOutP016,
+           {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb, out_bits};
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = check_curves_knots(prefix, npts)) return rc;
+  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, true)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_io_pointers(what, io)) return rc;
+  if (!grid || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
+  ApplyIoArgs a{grid, nullptr, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, 2, 1.0f, guide_ccm, guide_mix, npts,
+                guide_out, guide_shifts, guide_slopes};
+  if (int rc = set_curves_prepared(a, prepared, prefix, "npts <= 16")) return rc;
+  return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, nullptr, stream);
 }
 
 // ---- include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats ---------------------------------------------

@@ -39,7 +39,8 @@ struct ApplyIoArgs {
   const float* grid;
   const float* guide;  // null => guide network (guide_conv1 / guide_conv2)
   const void* input;   // input_dtype: 0 f32, 1 u8, 2 u16; value / white_level
-  void* out;           // output_dtype: 0 f32, 1 u8 = (uint8)(255 * clip(v, 0, 1))
+  void* out;           // output_dtype: 0 f32, 1 u8 = (uint8)(255 * clip(v, 0, 1)),
+                       //   2 u16 = (uint16)(output_white_level * clip(v, 0, 1)) (apply_fwd_io_u16.hip only)
   int B, H, W, GH, GW, GD, Cin, Cout;
   bool has_offset;
   int input_dtype, output_dtype;
@@ -60,14 +61,21 @@ struct ApplyIoArgs {
   // surface's sample dtype (1 u8 = NV12, 2 u16 = P010 / P016), `input` is unused, and `out` is the RGB frame of
   // output_dtype -- or, with yuv->out_kind == HDRNET_YUV_OUT_NV12 (output_dtype = 1), unused too
   const struct YuvIo* yuv = nullptr;
+  // output_dtype == 2 (include/hdrnet_amd_u16_out.h): the white level of the uint16 frame, which has the input's pixel format
+  float output_white_level = 0.0f;
 };
+
+// YuvIo::out_kind beyond the HDRNET_YUV_OUT_* codes, which hdrnet_amd_yuv.h's entry points refuse: a P010 / P016 surface
+// out (include/hdrnet_amd_u16_out.h; output_dtype = 2, YuvIo::out_bits)
+constexpr int kYuvOutP016 = 3;
 
 struct YuvIo {
   YuvSurface in;
   const float* to_rgb;    // device, 12 floats
-  int out_kind;           // HDRNET_YUV_OUT_*
-  YuvSurface out;         // out_kind == HDRNET_YUV_OUT_NV12
+  int out_kind;           // HDRNET_YUV_OUT_*, or kYuvOutP016
+  YuvSurface out;         // out_kind == HDRNET_YUV_OUT_NV12 / kYuvOutP016
   const float* from_rgb;  // device, 12 floats
+  int out_bits = 0;       // kYuvOutP016: 10 or 16 significant bits per sample, in the high bits
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -248,6 +256,10 @@ bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io_yuv(const ApplyIoArgs& a, hipStream_t s, const char** name);
 hipError_t launch_yuv_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,
                              hipStream_t s);
+// apply_fwd_io_u16.hip -- the same forward with a 16-bit output (a.output_dtype == 2): a uint16 frame in the input's pixel
+// format, or (a.yuv, out_kind == kYuvOutP016) a P010 / P016 surface
+bool apply_fwd_io_u16_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_u16(const ApplyIoArgs& a, hipStream_t s, const char** name);
 // apply_fwd_io_upadd.hip -- the same forward + the up-add of the coarser pyramid level (guide map or guide network; every
 // dtype pair but f32 -> f32, which is launch_apply_fwd_upadd's)
 bool apply_fwd_io_upadd_supported(const ApplyIoArgs& a, const float* coarse);

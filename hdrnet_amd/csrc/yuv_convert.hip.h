@@ -1,4 +1,5 @@
-// Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out.
+// Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out -- and
+// P010 / P016 out (include/hdrnet_amd_u16_out.h).
 //
 // Every kernel that reads a surface -- hdrnet_yuv_to_rgb_f32 (apply_fwd_io_yuv.hip), the low-res gather
 // (sample_prep.hip) and the fused forward (apply_fwd_io.hip.h) -- converts a pixel with the ONE function below, and the
@@ -102,6 +103,18 @@ __device__ __forceinline__ float yuv_chroma_linear(const YuvMatrix& k, int i, co
 }
 __device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum4) {
   return (uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, 255.0f);
+}
+
+// P010 / P016 output (include/hdrnet_amd_u16_out.h): the same two chains in code values of out_bits bits -- from_rgb is
+// then in those units (hdrnet_amd/yuv.py: yuv_encode_coefficients) -- clamped to code_max = 2^out_bits - 1, truncated
+// and placed in the HIGH bits of the uint16 sample (shift = 16 - out_bits).  The chroma sum is yuv_chroma_linear's, in
+// the order above.
+__device__ __forceinline__ uint32_t yuv_luma_code16(const YuvMatrix& k, const float* c, float code_max, int shift) {
+  const float t = __builtin_fmaf(k.m[2], c[2], __builtin_fmaf(k.m[1], c[1], __builtin_fmaf(k.m[0], c[0], k.bias[0])));
+  return ((uint32_t)__builtin_amdgcn_fmed3f(t, 0.0f, code_max)) << shift;
+}
+__device__ __forceinline__ uint32_t yuv_chroma_code16(const YuvMatrix& k, int i, float sum4, float code_max, int shift) {
+  return ((uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, code_max)) << shift;
 }
 
 }  // namespace hdrnet_amd

@@ -38,7 +38,8 @@ from . import _lib
 
 __all__ = ["bilateral_slice", "bilateral_slice_apply", "bilateral_slice_apply_rows", "bilateral_slice_apply_nnguide",
            "bilateral_slice_apply_io", "bilateral_slice_apply_curves", "bilateral_slice_apply_upadd", "resize_bilinear", "input_moments",
-           "resize_bilinear_io", "bilateral_slice_apply_upadd_io",
+           "resize_bilinear_io", "bilateral_slice_apply_upadd_io", "bilateral_slice_apply_io_u16",
+           "bilateral_slice_apply_io_yuv_deep",
            "CoefficientWeights", "coefficients", "coefficients_train", "coefficients_train_supported", "guide_fold_batch", "guide_nn_prescale", "curves_guide_prepare",
            "kernel_override", "last_kernel"]
 
@@ -1189,7 +1190,8 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     kernel's load and store, with every guide source.  uint8 / uint16 frames take all four, float32 frames ``"rgb"``
     only.  A uint8 output has the input's format, with alpha carried over (the byte of a uint8 frame, ``alpha >> 8`` of a
     uint16 one: alpha is never divided by the white level or quantised); a float32 output is ``[B, H, W, 3]`` RGB.
-    4-channel frames must be 16-byte aligned.  Out of scope: float32 frames in other orders, uint16 output."""
+    4-channel frames must be 16-byte aligned.  A uint16 frame out is ``bilateral_slice_apply_io_u16``'s.  Out of scope:
+    float32 frames in other orders."""
     input_white_level = _frame_head(input, input_white_level, out_dtype)
     rgb = pixel_format == "rgb"
     if not rgb:  # "rgb": every rule below is the one it always was
@@ -1214,6 +1216,66 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
         rc = getattr(_lib.load(), fn)(*args, *(() if rgb else _px_codes(pixel_format, out_dtype)), _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
+    return (out, gout) if return_guide else out
+
+
+def _output_white_level(value, what: str) -> float:
+    """The white level of a uint16 output (include/hdrnet_amd_u16_out.h): finite, 0 < value <= 65535."""
+    v = float(value)
+    if not (0.0 < v <= 65535.0):  # (false for NaN)
+        raise ValueError(f"{what}: output_white_level must be finite with 0 < output_white_level <= 65535, got {value!r}")
+    return v
+
+
+def bilateral_slice_apply_io_u16(grid: torch.Tensor, input: torch.Tensor,  # noqa: A002
+                                 guide: Optional[torch.Tensor] = None,
+                                 guide_conv1: Optional[torch.Tensor] = None,
+                                 guide_conv2: Optional[torch.Tensor] = None,
+                                 input_white_level: Optional[float] = None,
+                                 output_white_level: float = 65535.0,
+                                 has_offset: bool = True,
+                                 guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
+                                 return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
+                                 curves_prepared: Optional[torch.Tensor] = None, pixel_format: str = "rgb"):
+    """``bilateral_slice_apply_io`` with a UINT16 frame out (include/hdrnet_amd_u16_out.h): per sample
+    ``(uint16)(output_white_level * clip(out, 0, 1))`` -- one float32 multiply, then truncation: the uint8 store's rule
+    with 255 replaced by ``output_white_level`` (finite, 0 < . <= 65535; 32767 for HDR+, 1023 for a 10-bit range).  The
+    arithmetic before the store is that of ``bilateral_slice_apply_io`` on the same arguments, so the result equals its
+    float32 output quantised by that rule, without the float32 frame.  ``input`` is uint16 (any ``pixel_format``) or
+    float32 (``"rgb"``); the output has the input's pixel format, with the alpha of a uint16 frame copied bit for bit.
+    Every other argument is ``bilateral_slice_apply_io``'s; the 3 -> 3 op with offset only.  No autograd.
+    Out of scope: uint8 frames (no kernel goes from 8 to 16 bits), float32 frames in other orders, more than 16 curve
+    knots on a BGR / RGBA / BGRA frame."""
+    what = "bilateral_slice_apply_io_u16"
+    input_white_level = _frame_head(input, input_white_level)
+    if input.dtype == torch.uint8:
+        raise TypeError(f"{what}: a uint16 output needs a uint16 or float32 frame, got uint8 (no kernel goes from 8 to 16 bits)")
+    output_white_level = _output_white_level(output_white_level, what)
+    pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32, what)
+    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset, pixel_format)
+    if (Cin, Cout) != (3, 3) or not has_offset:
+        raise ValueError(f"{what}: the 3 -> 3 op with offset (a [.., 12] grid) only, got Cin = {Cin}, Cout = {Cout}, "
+                         f"has_offset = {bool(has_offset)}")
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), Cin)
+    _require_gpu("grid", grid)
+    _require_gpu("input", input)
+    grid, inp = grid.detach().contiguous(), input.detach().contiguous()
+    dev = inp.device
+    out = torch.empty((B, H, W, _lib.PIXEL_FORMAT_CHANNELS[pixel_format]), dtype=torch.uint16, device=dev)
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    frame = (inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, 1,
+             _DTYPE_CODE[input.dtype], float(input_white_level), output_white_level)
+    code = _lib.PIXEL_FORMATS[pixel_format]
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if curves:
+            rc = lib.hdrnet_bilateral_slice_apply_io_curves_px_u16(
+                grid.data_ptr(), *frame, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), code, code, _stream(dev))
+        else:
+            rc = lib.hdrnet_bilateral_slice_apply_io_px_u16(
+                grid.data_ptr(), _ptr(g[0]), *frame, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None), code, code, _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
     return (out, gout) if return_guide else out
 
@@ -1297,7 +1359,8 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
     ``out="nv12"``: an NV12 uint8 surface, returned as ``(y_out [B, H, W], uv_out [B, H / 2, W])``, encoded by
     ``from_rgb`` (12 floats): Y per pixel, U and V from the mean of each 2 x 2 block, truncated.  ``out_planes``: a
     ``(y_out, uv_out)`` pair to write into (pitched planes are fine; padding is not written).  Planes of the input may be
-    pitched too.  ``return_guide`` appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd."""
+    pitched too.  ``return_guide`` appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd.
+    A P010 / P016 surface out is ``bilateral_slice_apply_io_yuv_deep``'s; a uint16 RGB frame out is out of scope."""
     what = "bilateral_slice_apply_io_yuv"
     if out not in ("rgb", "nv12"):
         raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12')")
@@ -1361,6 +1424,74 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOYuv")
     return (result, gout) if return_guide else result
+
+
+def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
+                                      guide: Optional[torch.Tensor] = None,
+                                      guide_conv1: Optional[torch.Tensor] = None,
+                                      guide_conv2: Optional[torch.Tensor] = None,
+                                      guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
+                                      return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
+                                      curves_prepared: Optional[torch.Tensor] = None,
+                                      from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
+                                      out_planes=None):
+    """``bilateral_slice_apply_io_yuv`` for a uint16 surface in (P010 / P016) with a P010 / P016 surface OUT
+    (include/hdrnet_amd_u16_out.h), returned as ``(y_out [B, H, W], uv_out [B, H / 2, W])`` uint16.  ``out_bits`` is 10
+    (P010) or 16 (P016): the codes have that many bits and sit in the high bits of the sample.  ``from_rgb``: the 12
+    floats of ``yuv.yuv_encode_coefficients(standard, full_range, out_bits)`` on the device -- code units of ``out_bits``
+    bits, the + 0.5 folded in; the kernel clamps to ``[0, 2 ** out_bits - 1]`` and truncates: Y per pixel, U and V from
+    the mean of each 2 x 2 block, in the NV12 store's operation order.  ``out_planes``: a ``(y_out, uv_out)`` pair to write
+    into (pitched planes are fine; padding is not written); tight planes are allocated when none are given.  The guide
+    arguments and the arithmetic before the store are ``bilateral_slice_apply_io_yuv``'s.  ``return_guide`` appends the
+    guide map.  No autograd.  Out of scope: an NV12 surface in, a uint16 RGB frame out of a surface."""
+    what = "bilateral_slice_apply_io_yuv_deep"
+    if from_rgb is None:
+        raise ValueError(f"{what}: needs from_rgb (yuv.yuv_encode_coefficients)")
+    if out_bits not in (10, 16):
+        raise ValueError(f"{what}: out_bits must be 10 (P010) or 16 (P016), got {out_bits!r}")
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    if y.dtype != torch.uint16:
+        raise TypeError(f"{what}: a P010 / P016 output needs a uint16 surface in, got {y.dtype} (no kernel goes from 8 to 16 "
+                        "bits)")
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+    _require_f32("grid", grid)
+    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
+        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
+                         f"{tuple(grid.shape)}")
+    GH, GW, GD = grid.shape[1:4]
+    tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb), ("from_rgb", from_rgb)]
+    oy = ouv = None
+    if out_planes is not None:
+        oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
+        if (oB, oH, oW) != (B, H, W) or oy.dtype != torch.uint16:
+            raise ValueError(f"{what}: out_planes should be a uint16 surface of {[B, H, W]}, got {oy.dtype} {[oB, oH, oW]}")
+        tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
+                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
+    for nm, t in tensors:
+        _require_gpu(nm, t)
+    dev = y.device
+    lib = _lib.load()
+    grid = grid.detach().contiguous()
+    k_in, k_out = to_rgb.detach().contiguous(), from_rgb.detach().contiguous()
+    if oy is None:
+        oy = torch.empty((B, H, W), dtype=torch.uint16, device=dev)
+        ouv = torch.empty((B, H // 2, W), dtype=torch.uint16, device=dev)
+        osurf = (2, 2 * W, 2 * W, 2 * H * W, 2 * (H // 2) * W)
+    output = (oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr(), int(out_bits))
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    with torch.cuda.device(dev):
+        if curves:
+            rc = lib.hdrnet_bilateral_slice_apply_io_curves_yuv_p016(
+                grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), *output, _stream(dev))
+        else:
+            rc = lib.hdrnet_bilateral_slice_apply_io_yuv_p016(
+                grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOYuv")
+    return ((oy, ouv), gout) if return_guide else (oy, ouv)
 
 
 def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002

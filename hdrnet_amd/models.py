@@ -590,7 +590,8 @@ class HDRNetCurves(nn.Module):
         return op(coeffs.reshape(gs[0], gs[1], gs[2], gs[3], gs[4] * gs[5]), *pixels, **kwargs, **self._process_guide_args())
 
     def process(self, frame: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                white_level: Optional[float] = None, pixel_format: Optional[str] = None) -> torch.Tensor:
+                white_level: Optional[float] = None, pixel_format: Optional[str] = None,
+                out_white_level: Optional[float] = None) -> torch.Tensor:
         """Frame in, frame out (inference): ``frame`` ``[B, H, W, 3]`` uint8 / uint16 / float32 on the device ->
         ``data.lowres_input`` -> the coefficient network -> the fused guide + slice-apply, with the wire formats converted
         in registers (``hdrnet_ops.bilateral_slice_apply_io``): ``value / white_level`` in (255 / 65535 / 1 by default),
@@ -603,7 +604,12 @@ class HDRNetCurves(nn.Module):
         3-channel frame; a 4-channel frame must name its format (the order of R and B is not guessed).  The model sees
         R, G, B; the bytes are permuted in the kernels' loads and stores, not in a pass of their own.  A uint8 output has
         the frame's format and its alpha (``alpha >> 8`` of a uint16 frame), a float32 output is ``[B, H, W, 3]`` RGB.
-        Out of scope: float32 frames in other orders, uint16 output, the pyramid model."""
+
+        ``out_dtype=torch.uint16`` (uint16 and float32 frames; ``hdrnet_ops.bilateral_slice_apply_io_u16``): a uint16
+        frame ``= (uint16)(out_white_level * clip(out, 0, 1))`` in the frame's format, the alpha of a uint16 frame copied
+        bit for bit.  ``out_white_level`` defaults to the input white level for a uint16 frame (HDR+ at 32767 stays at
+        32767) and to 65535 for a float32 one.  Out of scope: float32 frames in other orders, uint16 output from a uint8
+        frame, the pyramid model."""
         from . import _lib, data, hdrnet_ops
         if not isinstance(frame, torch.Tensor) or frame.dim() != 4 or frame.shape[3] not in (3, 4):
             raise ValueError("frame should be [B, H, W, 3] (or [B, H, W, 4] with pixel_format='rgba' / 'bgra')")
@@ -613,15 +619,27 @@ class HDRNetCurves(nn.Module):
             raise TypeError(f"{type(self).__name__}.process takes "
                             f"{' / '.join(str(d).replace('torch.', '') for d in self._process_dtypes)} frames, got {frame.dtype}")
         out_dtype = torch.float32 if out_dtype is None else out_dtype
-        if out_dtype not in (torch.float32, torch.uint8):
-            raise TypeError(f"out_dtype must be float32 or uint8, got {out_dtype}")
+        if out_dtype not in (torch.float32, torch.uint8, torch.uint16):
+            raise TypeError(f"out_dtype must be float32, uint8 or uint16, got {out_dtype}")
         if out_dtype != torch.float32 and self._process_dtypes == (torch.float32,):
             raise TypeError(f"{type(self).__name__}.process returns float32 frames only")
+        if out_dtype == torch.uint16:
+            if frame.dtype == torch.uint8:
+                raise TypeError(f"{type(self).__name__}.process: a uint16 output needs a uint16 or float32 frame, got uint8")
+            if out_white_level is None:
+                out_white_level = 65535.0 if frame.dtype == torch.float32 else (65535.0 if white_level is None else white_level)
+            out_white_level = hdrnet_ops._output_white_level(out_white_level, f"{type(self).__name__}.process")
+        elif out_white_level is not None:
+            raise ValueError(f"{type(self).__name__}.process: out_white_level belongs to out_dtype=torch.uint16")
         if self.training:
             raise RuntimeError("process() is inference: call eval() first")
         with torch.no_grad():
             frame = frame.contiguous()
             lowres = data.lowres_input(frame, self.params["net_input_size"], white_level, pixel_format=pixel_format)
+            if out_dtype == torch.uint16:
+                return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_u16, lowres, frame,
+                                              input_white_level=white_level, output_white_level=out_white_level,
+                                              has_offset=True, pixel_format=pixel_format)
             if frame.dtype == torch.float32 and out_dtype == torch.float32:  # float32 is never scaled
                 return self.forward(lowres, frame)
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io, lowres, frame, input_white_level=white_level,
@@ -640,6 +658,15 @@ class HDRNetCurves(nn.Module):
             cache[key] = (torch.from_numpy(to_rgb).to(device), torch.from_numpy(from_rgb).to(device))
         return cache[key]
 
+    def _yuv_encode_constants(self, standard: str, full_range: bool, bits: int, device: torch.device):
+        """``from_rgb`` of ``yuv.yuv_encode_coefficients`` (code units of ``bits`` bits) on ``device``, cached likewise."""
+        from . import yuv
+        cache = self.__dict__.setdefault("_yuv_cache", {})
+        key = ("encode", standard, bool(full_range), int(bits), str(device))
+        if key not in cache:
+            cache[key] = torch.from_numpy(yuv.yuv_encode_coefficients(standard, full_range, bits)).to(device)
+        return cache[key]
+
     def process_yuv(self, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False,
                     bits: Optional[int] = None, out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
                     out_planes=None):
@@ -649,8 +676,10 @@ class HDRNetCurves(nn.Module):
         ``data.lowres_input_yuv`` -> the coefficient network -> ``hdrnet_ops.bilateral_slice_apply_io_yuv`` -- with the
         conversion (``standard`` ``"bt601"`` / ``"bt709"`` / ``"bt2020"``, ``full_range``) in the kernels' loads: no RGB
         frame exists.  ``out="rgb"``: ``[B, H, W, 3]`` float32 (default) or uint8; ``out="nv12"``: an NV12 uint8 surface
-        ``(y_out, uv_out)`` of the same standard and range for an encoder (``out_planes``: the pair to write into).  Planes
-        may be pitched.  Chroma is replicated on the way in and the 2 x 2 mean on the way out.  Capturable."""
+        ``(y_out, uv_out)`` of the same standard and range for an encoder (``out_planes``: the pair to write into);
+        ``out="p010"`` / ``out="p016"``: a uint16 surface of 10- / 16-bit codes in the high bits, of the input's standard
+        and range, from a uint16 surface (``hdrnet_ops.bilateral_slice_apply_io_yuv_deep``).  Planes may be pitched.
+        Chroma is replicated on the way in and the 2 x 2 mean on the way out.  Capturable."""
         from . import data, hdrnet_ops, yuv
         what = f"{type(self).__name__}.process_yuv"
         if self._process_dtypes == (torch.float32,):
@@ -658,9 +687,14 @@ class HDRNetCurves(nn.Module):
                              "surface path (the single-level models' process_yuv takes NV12 / P010 / P016)")
         if standard not in yuv.STANDARDS:
             raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
-        if out not in ("rgb", "nv12"):
-            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12')")
+        if out not in ("rgb", "nv12", "p010", "p016"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12', 'p010', 'p016')")
         y, uv, B, H, W, _ = hdrnet_ops._yuv_surface(y, uv, what)
+        deep = out in ("p010", "p016")
+        if deep and y.dtype != torch.uint16:
+            raise TypeError(f"{what}: out={out!r} needs a uint16 surface in (P010 / P016), got {y.dtype}")
+        if deep and out_dtype not in (None, torch.uint16):
+            raise TypeError(f"{what}: a {out.upper()} output is uint16, got out_dtype = {out_dtype}")
         if bits is None:
             bits = 8 if y.dtype == torch.uint8 else 16
         if bits not in yuv.BITS or (bits == 8) != (y.dtype == torch.uint8):
@@ -671,6 +705,11 @@ class HDRNetCurves(nn.Module):
         with torch.no_grad():
             to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, y.device)
             lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"])
+            if deep:
+                out_bits = 10 if out == "p010" else 16
+                return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_deep, lowres, y, uv, to_rgb,
+                                              from_rgb=self._yuv_encode_constants(standard, full_range, out_bits, y.device),
+                                              out_bits=out_bits, out_planes=out_planes)
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv, lowres, y, uv, to_rgb, out=out,
                                           out_dtype=out_dtype, from_rgb=from_rgb if out == "nv12" else None,
                                           out_planes=out_planes)

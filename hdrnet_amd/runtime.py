@@ -79,13 +79,17 @@ class GraphedInference:
 class _Process(torch.nn.Module):
     """``model.process`` as the module a ``GraphedInference`` captures (parameters and buffers are the model's)."""
 
-    def __init__(self, model: torch.nn.Module, out_dtype, white_level, pixel_format=None):
+    def __init__(self, model: torch.nn.Module, out_dtype, white_level, pixel_format=None, out_white_level=None):
         super().__init__()
         self.model, self.out_dtype, self.white_level, self.pixel_format = model, out_dtype, white_level, pixel_format
+        self.out_white_level = out_white_level
 
     def forward(self, frame: torch.Tensor) -> torch.Tensor:
         # a model whose process() is float32-only offers its wire formats as process_wire() (HDRNetGaussianPyrNN)
-        if hasattr(self.model, "process_wire") and (frame.dtype != torch.float32 or self.out_dtype == torch.uint8):
+        if self.out_dtype == torch.uint16 and not hasattr(self.model, "process_wire"):  # (the pyramid model refuses it)
+            kw = {} if self.pixel_format is None else {"pixel_format": self.pixel_format}
+            return self.model.process(frame, self.out_dtype, self.white_level, out_white_level=self.out_white_level, **kw)
+        if hasattr(self.model, "process_wire") and (frame.dtype != torch.float32 or self.out_dtype in (torch.uint8, torch.uint16)):
             if self.pixel_format is not None:
                 return self.model.process_wire(frame, self.out_dtype, self.white_level, pixel_format=self.pixel_format)
             return self.model.process_wire(frame, self.out_dtype, self.white_level)
@@ -97,13 +101,14 @@ class _Process(torch.nn.Module):
 class FrameInference(GraphedInference):
     """Frame in, frame out from a hipGraph: a ``GraphedInference`` whose captured callable is ``model.process`` (low-res
     input, coefficient network, fused guide + slice-apply with the wire formats in registers).  One input, the frame
-    (uint8 / uint16 / float32 ``[B, H, W, 3]``); ``out_dtype`` float32 (default) or uint8.  ``pixel_format``: as
-    ``model.process`` -- with ``"bgra"`` the captured graph replays ``[B, H, W, 4]`` frames as a decoder delivers them."""
+    (uint8 / uint16 / float32 ``[B, H, W, 3]``); ``out_dtype`` float32 (default), uint8 or -- the single-level models, from
+    uint16 / float32 frames -- uint16 at ``out_white_level``.  ``pixel_format``: as ``model.process`` -- with ``"bgra"`` the
+    captured graph replays ``[B, H, W, 4]`` frames as a decoder delivers them."""
 
     def __init__(self, model: torch.nn.Module, example_frame: torch.Tensor, out_dtype=None, white_level=None,
-                 warmup: int = 3, check_parameters: bool = True, pixel_format=None):
-        super().__init__(_Process(model.eval(), out_dtype, white_level, pixel_format), [example_frame], warmup=warmup,
-                         check_parameters=check_parameters)
+                 warmup: int = 3, check_parameters: bool = True, pixel_format=None, out_white_level=None):
+        super().__init__(_Process(model.eval(), out_dtype, white_level, pixel_format, out_white_level), [example_frame],
+                         warmup=warmup, check_parameters=check_parameters)
 
 
 class _ProcessYuv(torch.nn.Module):
@@ -125,7 +130,8 @@ class YuvFrameInference(GraphedInference):
     in the kernels' loads and stores).  Two inputs, the planes ``y`` ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (uint8 NV12
     or uint16 P010 / P016), copied into static planes unless they ARE the static planes (``static_inputs``: a decoder can
     write into them in place).  ``out="nv12"``: the static output is the ``(y_out, uv_out)`` pair of an NV12 uint8
-    surface; ``out="rgb"``: a ``[B, H, W, 3]`` frame of ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
+    surface (``"p010"`` / ``"p016"``: of a uint16 surface, from uint16 planes); ``out="rgb"``: a ``[B, H, W, 3]`` frame of
+    ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
     ``process_yuv``.  Beside ``FrameInference``, which keeps its signature."""
 
     def __init__(self, model: torch.nn.Module, y_like: torch.Tensor, uv_like: torch.Tensor, standard: str = "bt709",

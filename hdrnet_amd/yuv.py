@@ -12,7 +12,7 @@ from typing import Tuple
 
 import numpy as np
 
-__all__ = ["STANDARDS", "BITS", "yuv_coefficients", "code_ranges"]
+__all__ = ["STANDARDS", "BITS", "yuv_coefficients", "yuv_encode_coefficients", "code_ranges"]
 
 # (Kr, Kb) of the luma equation  Y' = Kr R' + Kg G' + Kb B'
 STANDARDS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}
@@ -56,11 +56,26 @@ def yuv_coefficients(standard: str = "bt709", full_range: bool = False, bits: in
         to_rgb[3 * i + 1] = cu[i] / (c_scale * stored)
         to_rgb[3 * i + 2] = cv[i] / (c_scale * stored)
         to_rgb[9 + i] = -y_off / y_scale - (cu[i] + cv[i]) * c_off / c_scale
-    y8_off, y8_scale, c8_off, c8_scale = code_ranges(bool(full_range), 8)
+    return to_rgb.astype(np.float32), yuv_encode_coefficients(standard, full_range, 8)
+
+
+def yuv_encode_coefficients(standard: str = "bt709", full_range: bool = False, bits: int = 8) -> np.ndarray:
+    """``from_rgb``: 12 float32 numbers, a row-major 3 x 3 matrix then 3 biases, that applied to R, G, B in [0, 1] give
+    Y, U, V in CODE values of ``bits`` bits (8: NV12, 10: P010, 16: P016) of ``standard`` and range, with the + 0.5 of the
+    rounding folded into the biases: the kernel clamps to ``[0, 2 ** bits - 1]`` and truncates, and for P010 places the
+    code in the high bits itself (``out_bits``).  ``bits = 8`` is ``yuv_coefficients(...)[1]``, bit for bit."""
+    if standard not in STANDARDS:
+        raise ValueError(f"yuv_encode_coefficients: unknown standard {standard!r} (takes "
+                         f"{', '.join(repr(k) for k in STANDARDS)})")
+    if bits not in BITS:
+        raise ValueError(f"yuv_encode_coefficients: bits must be one of {BITS}, got {bits!r}")
+    kr, kb = STANDARDS[standard]
+    kg = 1.0 - kr - kb
+    y_off, y_scale, c_off, c_scale = code_ranges(bool(full_range), bits)
     luma = np.array([kr, kg, kb])
     from_rgb = np.zeros(12, np.float64)
-    from_rgb[0:3] = y8_scale * luma
-    from_rgb[3:6] = c8_scale * (np.array([0.0, 0.0, 1.0]) - luma) / (2.0 * (1.0 - kb))  # Cb' = (B - Y') / (2 (1 - Kb))
-    from_rgb[6:9] = c8_scale * (np.array([1.0, 0.0, 0.0]) - luma) / (2.0 * (1.0 - kr))  # Cr' = (R - Y') / (2 (1 - Kr))
-    from_rgb[9:12] = [y8_off + 0.5, c8_off + 0.5, c8_off + 0.5]
-    return to_rgb.astype(np.float32), from_rgb.astype(np.float32)
+    from_rgb[0:3] = y_scale * luma
+    from_rgb[3:6] = c_scale * (np.array([0.0, 0.0, 1.0]) - luma) / (2.0 * (1.0 - kb))  # Cb' = (B - Y') / (2 (1 - Kb))
+    from_rgb[6:9] = c_scale * (np.array([1.0, 0.0, 0.0]) - luma) / (2.0 * (1.0 - kr))  # Cr' = (R - Y') / (2 (1 - Kr))
+    from_rgb[9:12] = [y_off + 0.5, c_off + 0.5, c_off + 0.5]
+    return from_rgb.astype(np.float32)

@@ -18,7 +18,8 @@
  *   - Anything else is refused with HDRNET_INVALID_ARGUMENT and a text that names the rule, before any HIP call.
  * With both formats HDRNET_PX_RGB every entry point IS the one it extends: the same kernel, the same label.
  * Out of scope: the pyramid model's entry points (hdrnet_amd_pyramid_io.h), hdrnet_prepare_batch, float32 frames in
- * other orders, uint16 output. */
+ * other orders.  A uint16 output is include/hdrnet_amd_u16_out.h's: the entry points below keep refusing
+ * output_dtype 2. */
 #ifndef HDRNET_AMD_PIXEL_FORMATS_H_
 #define HDRNET_AMD_PIXEL_FORMATS_H_
 

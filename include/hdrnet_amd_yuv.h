@@ -31,7 +31,10 @@
  *     extends, and see R, G, B.
  *   - Anything else is refused with HDRNET_INVALID_ARGUMENT and a text that names the rule, before any HIP call.  B = 0 is
  *     a no-op (kernel name "noop").
- * Out of scope: sited / bilinear chroma, planar (I420) and 4:2:2 / 4:4:4 surfaces, P010 output, the pyramid model. */
+ * A P010 / P016 surface OUT (from a uint16 surface) is include/hdrnet_amd_u16_out.h's; the entry points below keep
+ * refusing any other output_kind than the three defined here.
+ * Out of scope: sited / bilinear chroma, planar (I420) and 4:2:2 / 4:4:4 surfaces, a uint16 RGB frame out of a surface,
+ * NV12 in -> P010 / P016 out, the pyramid model. */
 #ifndef HDRNET_AMD_YUV_H_
 #define HDRNET_AMD_YUV_H_
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -19,7 +19,10 @@ of the chain a caller wrote before it (index-select to RGB -> process -> flip + 
 fused kernel alone, BGRA u8 -> u8 against RGB u8 -> u8; `yuv` = HDRNetPointwiseNNGuide on NV12 surfaces at 4K and 1080p: a
 hipGraph of process_yuv(..., out="nv12") against a hipGraph of the stock chain (planes -> repeat_interleave -> affine + clamp
 -> process -> affine -> 2 x 2 mean -> quantise), alternating, and beside it the fused kernel alone, NV12 -> NV12 and NV12 ->
-u8 RGB against RGB u8 -> u8.  --tools loads the tools build and adds the un-fused
+u8 RGB against RGB u8 -> u8; `u16_out` = 16-bit output (include/hdrnet_amd_u16_out.h): a hipGraph of process(u16 -> u16 at
+32767) against a hipGraph of the chain a caller had before it (process -> float32, clamp * wl, .to(uint16)) at 4000x3000,
+4K and 1080p, process_yuv(P010 -> P010) against the stock encode chain at 4K, and the kernel alone, u16 -> u16 against
+u16 -> f32 at 4000x3000, all alternating.  --tools loads the tools build and adds the un-fused
 gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -96,6 +99,8 @@ def main():
         return pixel_formats(lib, dev, args)
     if args.workload == "yuv":
         return yuv_surfaces(lib, dev, args)
+    if args.workload == "u16_out":
+        return u16_out(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -738,6 +743,150 @@ def yuv_surfaces(lib, dev, args):
         del sets
     if args.json:
         json.dump(dict(workload="yuv", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _QuantiseChain(torch.nn.Module):
+    """What a caller with a 16-bit pipeline wrote before process() stored uint16: take the float32 frame and quantise it
+    with stock ops -- clamp, scale, convert: three more full-frame launches around the fused kernels."""
+
+    def __init__(self, model, white_level):
+        super().__init__()
+        self.model, self.white_level = model, white_level
+
+    def forward(self, frame):
+        out = self.model.process(frame, out_dtype=torch.float32, white_level=self.white_level)
+        return (out.clamp(0.0, 1.0) * self.white_level).to(torch.uint16)
+
+
+class _P010StockChain(torch.nn.Module):
+    """process_yuv(out="rgb") of a P010 surface, then _YuvStockChain's encode chain with 10-bit constants: an affine to
+    Y, U, V, the 2 x 2 mean of the chroma, quantise to 10-bit codes, shift into the high bits, interleave."""
+
+    def __init__(self, model, from_rgb):
+        super().__init__()
+        self.model = model
+        self.register_buffer("m_out", from_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)
+        self.register_buffer("b_out", from_rgb[9:].contiguous(), persistent=False)
+
+    def forward(self, y, uv):
+        B, H, W = y.shape
+        out = self.model.process_yuv(y, uv, bits=10, out="rgb").clamp_(0.0, 1.0)
+        enc = out @ self.m_out
+        yq = (enc[..., 0] + self.b_out[0]).clamp_(0.0, 1023.0).to(torch.int32) << 6
+        cm = enc[..., 1:].reshape(B, H // 2, 2, W // 2, 2, 2).mean(dim=(2, 4)) + self.b_out[1:]
+        cq = cm.clamp_(0.0, 1023.0).to(torch.int32) << 6
+        return yq.to(torch.uint16), cq.to(torch.uint16).reshape(B, H // 2, W)
+
+
+def u16_out(lib, dev, args):
+    """16-bit output (include/hdrnet_amd_u16_out.h) through HDRNetPointwiseNNGuide, one hipGraph each, ALTERNATING three
+    times each in one process, reported as mean and range (device events around `steps` replays):
+      model    4000x3000 (BASELINE config #5's frame, 32x32 grid), 4K, 1080p: process(u16 -> u16 at 32767) against
+               _QuantiseChain (process -> float32, clamp * wl, .to(uint16));
+      surface  4K: process_yuv(P010 -> P010) against _P010StockChain;
+      kernel   4000x3000, guide map, grid 32x32x8: u16 -> u16 against its float32-store sibling u16 -> f32, over buffer sets
+               that together exceed the Infinity Cache.
+    The new path counts as faster where its mean is below the chain's by more than the chain's own spread."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import FrameInference, GraphedInference, YuvFrameInference
+    torch.manual_seed(7)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    WL = 32767.0
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def u16(hi, *shape):
+        return torch.randint(0, hi, shape, device=dev, dtype=torch.int32, generator=gen).to(torch.uint16)
+
+    def report(name, b, n, chain_label, new_label):
+        mb, mn = statistics.mean(b), statistics.mean(n)
+        spread = max(b) - min(b)
+        rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                         us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                         faster_beyond_chain_spread=bool(mb - mn > spread)))
+        print(f"{name:40s} {chain_label} {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   {new_label} {mn:8.2f} us "
+              f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+              f"faster by more than the chain's spread: {mb - mn > spread}")
+
+    for H, W, spatial_bin in ((3000, 4000, 32), (2160, 3840, 16), (1080, 1920, 16)):
+        torch.manual_seed(7)
+        m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False, spatial_bin=spatial_bin)).to(dev).eval()
+        frames = [u16(int(WL) + 1, 1, H, W, 3) for _ in range(3)]
+        new = FrameInference(m, frames[0], out_dtype=torch.uint16, white_level=WL)
+        base = GraphedInference(_QuantiseChain(m, WL), [frames[0]])
+        d = (new(frames[1]).int() - base(frames[1]).int()).abs()
+        # (the chain multiplies the same float32 values by the same white level: it returns the same frame)
+        assert int(d.max()) == 0, "the two paths return the same frame"
+        b, n = alternate(lambda k: base(frames[k % 3]), lambda k: new(frames[k % 3]))
+        report(f"{H}x{W} model, u16 -> u16 / 32767", b, n, "quantise chain", "out_dtype=uint16")
+        del new, base, frames
+
+    # the surface: P010 in, P010 out at 4K
+    H, W = 2160, 3840
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    from_rgb = torch.from_numpy(yuv.yuv_encode_coefficients("bt709", False, 10)).to(dev)
+    def p010(*shape):  # 10-bit codes in the high bits
+        return (torch.randint(0, 1024, shape, device=dev, dtype=torch.int32, generator=gen) << 6).to(torch.uint16)
+
+    surfaces = [(p010(1, H, W), p010(1, H // 2, W)) for _ in range(3)]
+    new = YuvFrameInference(m, *surfaces[0], bits=10, out="p010")
+    base = GraphedInference(_P010StockChain(m, from_rgb), list(surfaces[0]))
+    (ny, nuv), (by, buv) = new(*surfaces[1]), base(*surfaces[1])
+    dy, duv = ((ny.int() - by.int()).abs() >> 6), ((nuv.int() - buv.int()).abs() >> 6)
+    # (the chain rounds its affine ops in another order: it is a timing opponent, not the reference of the tests)
+    print(f"{H}x{W}: fused vs chain, codes that differ: Y {int((dy > 0).sum())} (max {int(dy.max())}), "
+          f"UV {int((duv > 0).sum())} (max {int(duv.max())}) of {dy.numel()} + {duv.numel()}")
+    assert int(dy.max()) <= 1 and int(duv.max()) <= 1, "the two paths encode the same surface to within a code"
+    b, n = alternate(lambda k: base(*surfaces[k % 3]), lambda k: new(*surfaces[k % 3]))
+    report(f"{H}x{W} model, p010 -> p010", b, n, "stock chain", "process_yuv")
+    del new, base, surfaces
+
+    # the kernel alone: config #5's frame and grid with a guide map, 6 against 12 bytes per pixel stored
+    H, W, GH, GW, GD = 3000, 4000, 32, 32, 8
+    nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 22)))
+    grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+    sets = [dict(inp=u16(int(WL) + 1, 1, H, W, 3), guide=torch.rand((1, H, W), device=dev, generator=gen),
+                 out16=torch.empty((1, H, W, 3), device=dev, dtype=torch.uint16),
+                 out32=torch.empty((1, H, W, 3), device=dev, dtype=torch.float32)) for _ in range(nsets)]
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(lib.hdrnet_last_error().decode())
+
+    def to_f32(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_io_ex(grid.data_ptr(), t["guide"].data_ptr(), t["inp"].data_ptr(),
+                                                     t["out32"].data_ptr(), 1, H, W, GH, GW, GD, 3, 3, 1, 2, WL, 0, None, None,
+                                                     0, None, 0, stream))
+
+    def to_u16(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_io_px_u16(grid.data_ptr(), t["guide"].data_ptr(), t["inp"].data_ptr(),
+                                                         t["out16"].data_ptr(), 1, H, W, GH, GW, GD, 3, 3, 1, 2, WL, WL, None,
+                                                         None, 0, None, 0, 0, 0, stream))
+
+    f, q = alternate(to_f32, to_u16)
+    name = f"{H}x{W} kernel, u16 / 32767 in, guide map"
+    rows.append(dict(op=name, us_u16_f32=round(statistics.mean(f), 2), us_u16_f32_min=round(min(f), 2),
+                     us_u16_f32_max=round(max(f), 2), us_u16_u16=round(statistics.mean(q), 2), us_u16_u16_min=round(min(q), 2),
+                     us_u16_u16_max=round(max(q), 2)))
+    print(f"{name:40s} u16 -> f32 (12 B/px stored) {statistics.mean(f):8.2f} us ({min(f):8.2f} .. {max(f):8.2f})   "
+          f"u16 -> u16 (6 B/px stored) {statistics.mean(q):8.2f} us ({min(q):8.2f} .. {max(q):8.2f})   "
+          f"u16 / f32 {statistics.mean(q) / statistics.mean(f):6.3f}")
+    if args.json:
+        json.dump(dict(workload="u16_out", rows=rows), open(args.json, "w"), indent=1)
 
 
 def metrics_monitor(dev, args):
