@@ -5,12 +5,25 @@
  * and bench.py's cpu_baseline leg may load this; the product path
  * (hdrnet_amd/) never does.
  *
- * Parity status: PINNED.  tests/test_oracle_pinning.py checks every function
- * here bit-for-bit against oracle/_ref/libhdrnet_ref.so (the reference's own
- * .cc files compiled unchanged, see oracle/Makefile) when that library is
- * present, and against tests/golden/ fixtures generated from it
- * (tests/golden/make_golden.py) everywhere else, plus the reference's
- * known-answer test (hdrnet/test/ops_test.py:61-86).
+ * Parity status: PINNED, in two parts.
+ *   ARITHMETIC: tests/test_oracle_pinning.py checks every function here
+ *   bit-for-bit against oracle/_ref/libhdrnet_ref.so when that library is
+ *   present, and against tests/golden/ fixtures generated from it
+ *   (tests/golden/make_golden.py) everywhere else, plus the reference's
+ *   known-answer test (hdrnet/test/ops_test.py:61-86).  _ref is the
+ *   reference's .cc files over a STAND-IN header (oracle/shim/third_party/
+ *   array/array.h: the reference vendors no array.h) behind this repository's
+ *   harness (oracle/ref_harness.cc), which hands it the arrays in the layout
+ *   below.  So _ref holds the reference's statements and operand order; the
+ *   memory layout it is driven with is this repository's reading of the op
+ *   wrappers, the same reading this file has.
+ *   LAYOUT AND SAMPLING CONVENTIONS (the five grid dimensions, c = i*Cj + j,
+ *   the +0.5 pixel centres, clamped taps, the 0.9999 peak of the smoothed tent,
+ *   the x GD of the guide derivative): tests/test_closed_form.py holds this
+ *   file, _ref, the numpy JAX twin and the float64 restatements to closed-form
+ *   answers (tests/closed_form.py) that pass through none of them -- address
+ *   codes read back cell by cell, one-axis grids, one-plane guides.  Those, not
+ *   _ref, are the layout pin.
  *
  * Layouts are the TF/NHWC ones of the op wrappers
  * (hdrnet/ops/bilateral_slice_apply_op.cc:201-227):

@@ -16,7 +16,11 @@ hdrnet/hdrnet_ops_jax_tf2_test.py:23-24.
 
 Parity status: pinned indirectly -- tests/test_oracle_pinning.py checks it
 against oracle/_ref (the reference C++ op) at the reference's own JAX==op bar
-(``assertAllClose`` defaults rtol=atol=1e-6, hdrnet_ops_jax_tf2_test.py:48).
+(``assertAllClose`` defaults rtol=atol=1e-6, hdrnet_ops_jax_tf2_test.py:48).  Layout and sampling conventions:
+tests/test_closed_form.py holds it to closed-form answers that pass through no oracle.  One property of the JAX code
+shows there and is restated faithfully: ``_compute_range_weights`` splats to floor(gk - 0.5) AND ceil(gk - 0.5), which
+are the same plane for a guide exactly on a plane centre, so that plane receives the weight twice in
+``bilateral_slice_grid_vjp`` (the C++ op: once).
 """
 from __future__ import annotations
 

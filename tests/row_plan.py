@@ -20,19 +20,20 @@ def row_plan(W):
     return min(_rup(-(-seg // 4), 64), 256), nseg, seg
 
 
-def seg_fits(W, GW, GD, guide_map):
-    """seg_fwd_geom(dma = true, guide_map).ok: (GD + 2) planes of the window's columns + the slabs in 64 KiB."""
+def seg_fits(W, GW, GD, guide_map, C=12, chan=3):
+    """seg_fwd_geom(dma = true, guide_map).ok: (GD + 2) planes of the window's columns + the slabs in 64 KiB.  `C`: grid
+    channels, `chan`: max(Cin, Cout), of a fast shape other than 3 -> 3 with offset."""
     threads, _, seg = row_plan(W)
     cols = (seg - 1) * GW // W + 4
-    slabw = 256 * 3 + (256 if guide_map else 0)
-    return (_rup(cols * (GD + 2) * 12, 4) + threads // 64 * slabw) * 4 <= 65536
+    slabw = 256 * chan + (256 if guide_map else 0)
+    return (_rup(cols * (GD + 2) * C, 4) + threads // 64 * slabw) * 4 <= 65536
 
 
-def rows_fits(W, GW, GD):
+def rows_fits(W, GW, GD, C=12, chan=3):
     """rows_fwd_geom(...).ok: GD planes of at most GW columns + the per-wave slabs in 64 KiB."""
     threads, _, seg = row_plan(W)
     cols = min((seg - 1) * GW // W + 4, GW)
-    return (cols * GD * 12 + 4 + threads // 64 * 256 * 3) * 4 <= 65536
+    return (cols * GD * C + 4 + threads // 64 * 256 * chan) * 4 <= 65536
 
 
 def io_fits(W, GW, GD):
@@ -80,26 +81,37 @@ def launch_fits(B, H, W):
     return B * H * nseg * threads <= MAX_LAUNCH_THREADS
 
 
-def seg_reaches(B, H, W, GW, GD, guide_map=True, io=False):
+# HDRNET_APPLY_FAST_SHAPES of launch.hip.h: (Cin, Cout, has_offset)
+APPLY_FAST_SHAPES = ((3, 3, True), (3, 3, False), (3, 4, True), (1, 1, True), (1, 1, False), (1, 3, True), (4, 4, True),
+                     (4, 4, False))
+SLICE_FAST_CHANNELS = (1, 2, 4, 8, 12, 16)   # HDRNET_SLICE_FAST_CHANNELS
+
+
+def seg_reaches(B, H, W, GW, GD, guide_map=True, io=False, shape=(3, 3, True)):
     """The segment family's predicate for a frame: shape and LDS as above, and the extents."""
+    Cin, Cout, off = shape
+    C, chan = Cout * (Cin + off), max(Cin, Cout)
     _, _, seg = row_plan(W)
-    staged = ((seg - 1) * GW // W + 4) * GD * 12
-    fits = io_fits(W, GW, GD) if io else seg_fits(W, GW, GD, guide_map)
-    return vec4(W) and fits and staged < (1 << 20) and extent_limit(B, H, W, "seg") is None
+    staged = ((seg - 1) * GW // W + 4) * GD * C
+    fits = io_fits(W, GW, GD) if io else seg_fits(W, GW, GD, guide_map, C, chan)
+    return vec4(W) and fits and staged < (1 << 20) and extent_limit(B, H, W, "seg", Cout) is None
 
 
-def rows_reaches(B, H, W, GW, GD, aligned=True):
+def rows_reaches(B, H, W, GW, GD, aligned=True, shape=(3, 3, True)):
     """rows_fwd_geom(...).ok for a frame, and whether the four-pixel kernel serves it."""
-    ok = rows_fits(W, GW, GD) and launch_fits(B, H, W)
+    Cin, Cout, off = shape
+    ok = rows_fits(W, GW, GD, Cout * (Cin + off), max(Cin, Cout)) and launch_fits(B, H, W)
     return ok, ok and vec4(W, aligned)
 
 
-def forward_kernel(B, H, W, GW, GD, aligned=True):
-    """hdrnet_bilateral_slice_apply_f32 under HDRNET_KERNEL_AUTO."""
-    ok, four = rows_reaches(B, H, W, GW, GD, aligned)
+def forward_kernel(B, H, W, GW, GD, aligned=True, shape=(3, 3, True)):
+    """hdrnet_bilateral_slice_apply_f32 under HDRNET_KERNEL_AUTO for the fast shape `shape` = (Cin, Cout, has_offset)
+    (16-B aligned buffers: a grid of C % 4 != 0 channels is staged by single floats)."""
+    assert tuple(shape) in APPLY_FAST_SHAPES, shape
+    ok, four = rows_reaches(B, H, W, GW, GD, aligned, shape)
     if not ok:
         return "apply_fwd_generic"
-    if aligned and seg_reaches(B, H, W, GW, GD):
+    if aligned and seg_reaches(B, H, W, GW, GD, shape=shape):
         return "apply_fwd_seg/vec4"
     return "apply_fwd_rows/vec4" if four else "apply_fwd_rows/scalar"
 
