@@ -1,19 +1,42 @@
 // BilateralSliceApply forward with the product's wire formats fused in: the RGB instantiations of the kernel in
-// apply_fwd_io.hip.h, the launch's front end (predicate, geometry, kernel label) and the curves guide's prepare kernel.
+// apply_fwd_io.hip.h, their launch (predicate, geometry), the choice of the kernel family among this unit and its
+// siblings, and the curves guide's prepare kernel.  What the units' front ends share -- kernel label, guide-form dispatch,
+// the predicates' common rules -- is in the header.
 #include "apply_fwd_io.hip.h"
 
 namespace hdrnet_amd {
 
 bool apply_fwd_io_supported(const ApplyIoArgs& a) {
-  if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
   if (a.output_dtype != 0 && a.output_dtype != 1) return false;  // a 16-bit output: apply_fwd_io_u16.hip
-  if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;  // quantised pixels: whole dwords per lane
-  if (a.pixel_format != kPxRGB) {
-    if (a.pixel_format < 0 || a.pixel_format > kPxBGRA || a.input_dtype == 0) return false;  // integer frames only
-    // pixels with alpha: one 16-byte access per lane, each way
-    if (px_stored(a.pixel_format) == 4 && (((uintptr_t)a.input | (a.output_dtype == 1 ? (uintptr_t)a.out : 0)) & 15u)) return false;
+  return io_frame_ok(a);
+}
+
+// The kernel family of a call, chosen HERE and nowhere else: the 16-bit output's (a.output_dtype == 2), else the pixel
+// source's (a.yuv, or `coarse` for the pyramid's up-add).
+namespace {
+enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd };
+IoFamily io_family(const ApplyIoArgs& a, const float* coarse) {
+  return a.output_dtype == 2 && !coarse ? kFamilyU16 : a.yuv ? kFamilyYuv : coarse ? kFamilyUpAdd : kFamilyFrame;
+}
+}  // namespace
+
+bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse) {
+  switch (io_family(a, coarse)) {
+    case kFamilyU16: return apply_fwd_io_u16_supported(a);
+    case kFamilyYuv: return apply_fwd_io_yuv_supported(a);
+    case kFamilyUpAdd: return apply_fwd_io_upadd_supported(a, coarse);
+    default: return apply_fwd_io_supported(a);
   }
-  return io_geom(a).ok;
+}
+
+hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
+                                      const char** name) {
+  switch (io_family(a, coarse)) {
+    case kFamilyU16: return launch_apply_fwd_io_u16(a, s, name);
+    case kFamilyYuv: return launch_apply_fwd_io_yuv(a, s, name);
+    case kFamilyUpAdd: return launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, name);
+    default: return launch_apply_fwd_io(a, s, name);
+  }
 }
 
 rows::RowGeom apply_fwd_io_geom(const ApplyIoArgs& a) { return io_geom(a); }
@@ -31,13 +54,7 @@ hipError_t launch_curves_guide_prepare(const float* shifts, const float* slopes,
 
 hipError_t launch_apply_fwd_io(const ApplyIoArgs& a, hipStream_t s, const char** name) {
   if (!apply_fwd_io_supported(a)) return hipErrorInvalidValue;
-  static const char* const io[3][2] = {{"f32->f32", "f32->u8"}, {"u8->f32", "u8->u8"}, {"u16->f32", "u16->u8"}};
-  static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
-  static const char* const px[4] = {"", "/bgr", "/rgba", "/bgra"};
-  static thread_local char label[64];
-  snprintf(label, sizeof label, "apply_fwd_io/%s%s%s", io[a.input_dtype][a.output_dtype], suffix[io_guide_form(a)],
-           px[a.pixel_format]);
-  *name = label;
+  *name = io_label(a);
   return a.pixel_format == kPxRGB ? dispatch_guides<kPxRGB>(a, s) : launch_apply_fwd_io_px(a, s);
 }
 

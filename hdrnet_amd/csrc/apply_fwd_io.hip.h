@@ -25,14 +25,15 @@
 // PAIR, runs the stage-image / pixel phase twice over the same LDS region and keeps the 2 x 2 blocks' chroma sums in
 // registers in between.  Neither changes a line of what the other instantiations compile.
 //
-// This header holds the kernel and its launch; the RGB instantiations are compiled by apply_fwd_io.hip, those of the
+// This header holds the kernel, its launch and what the front ends share (label, guide-form dispatch, common predicate
+// rules); the RGB instantiations are compiled by apply_fwd_io.hip, those of the
 // other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many), those of the YUV
 // surfaces by apply_fwd_io_yuv.hip.
 //
 // 16-BIT OUTPUT (include/hdrnet_amd_u16_out.h): TO = uint16_t stores a uint16 frame, (uint16)(out_white * clip(v, 0, 1)) in
 // the input's pixel format -- the uint8 store's rule with 255 replaced by a run-time constant -- and OUT = kOutP016 a
-// P010 / P016 surface, the NV12 store's row-pair structure with uint16 code words.  Both are further branches of the
-// epilogue behind `if constexpr`: no other instantiation compiles a line of them.  Their instantiations are
+// P010 / P016 surface, the NV12 store's row-pair structure with uint16 code words.  Each shares its store with the 8-bit
+// sibling, written once on sizeof(TO); the 8-bit constants (255, shift 0) stay compile-time literals.  Their instantiations are
 // apply_fwd_io_u16.hip's, DELIBERATELY LIMITED to keep the build small: uint16 and float32 RGB frames and uint16 BGR / RGBA
 // / BGRA frames to a uint16 frame, a uint16 surface to a uint16 surface.  uint8 -> 16 bit, float32 packed orders, a uint16
 // RGB frame out of a YUV surface and the pyramid's up-add are not instantiated and are refused by rule.
@@ -44,6 +45,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "launch.hip.h"
 #include "numerics.hip.h"
@@ -556,12 +558,19 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
       }
     }
 
-    if constexpr (NV12OUT) {
-      // An NV12 surface: one dword of Y per lane and row; the chroma of the lane's two 2 x 2 blocks after the second row,
-      // one dword (U0 V0 U1 V1) into the pair's interleaved UV row.  Padding beyond the row is not written.
+    if constexpr (SURFOUT) {
+      // A semi-planar surface, NV12 (uint8 code words) or P010 / P016 (uint16, IoParams::code_max / code_shift): sizeof(TO)
+      // dwords of Y per lane and row; the chroma of the lane's two 2 x 2 blocks after the second row, as many dwords (U0 V0
+      // U1 V1) into the pair's interleaved UV row (block x / 2 starts at sample x of its row, as the luma does).  Padding
+      // beyond the row is not written.
+      constexpr int S = (int)sizeof(TO), PER = 4 / S;  // bytes per code word; code words per dword
       if (active) {
         const YuvMatrix fk = yuv_load_matrix(p.from_rgb);
-        uint32_t wy = 0;
+        const float cmax = S == 1 ? 255.0f : p.code_max;  // (NV12: compile-time constants)
+        const int sh = S == 1 ? 0 : p.code_shift;
+        uint32_t wy[S];
+#pragma unroll
+        for (int q = 0; q < S; ++q) wy[q] = 0;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           float pu[2], pv[2];
@@ -571,44 +580,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
             float c[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) c[j] = __builtin_amdgcn_fmed3f(of[k * COUT + j], 0.0f, 1.0f);
-            wy |= yuv_luma_code(fk, c) << (8 * k);
-            pu[i] = yuv_chroma_linear(fk, 1, c);
-            pv[i] = yuv_chroma_linear(fk, 2, c);
-          }
-          csum[h][0] += pu[0] + pu[1];  // horizontal pair first; even row (onto 0), then odd row
-          csum[h][1] += pv[0] + pv[1];
-        }
-        char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y + x;
-        *reinterpret_cast<uint32_t*>(yo) = wy;
-        if (r == ROWS - 1) {
-          uint32_t wc = 0;
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            wc |= (yuv_chroma_code(fk, 1, csum[h][0]) | (yuv_chroma_code(fk, 2, csum[h][1]) << 8)) << (16 * h);
-          char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
-                     (long long)(y >> 1) * p.yout.pitch_uv + x;
-          *reinterpret_cast<uint32_t*>(co) = wc;
-        }
-      }
-    } else if constexpr (P016OUT) {
-      // A P010 / P016 surface: the NV12 store with uint16 code words -- two dwords of Y per lane and row; the chroma of the
-      // lane's two 2 x 2 blocks after the second row, two dwords (U0 V0 | U1 V1) into the pair's interleaved UV row (block
-      // x / 2 starts at sample x of its row, as the luma does).  Padding beyond the row is not written.
-      if (active) {
-        const YuvMatrix fk = yuv_load_matrix(p.from_rgb);
-        const float cmax = p.code_max;
-        const int sh = p.code_shift;
-        uint32_t wy[2] = {0, 0};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          float pu[2], pv[2];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int k = 2 * h + i;
-            float c[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) c[j] = __builtin_amdgcn_fmed3f(of[k * COUT + j], 0.0f, 1.0f);
-            wy[h] |= yuv_luma_code16(fk, c, cmax, sh) << (16 * i);
+            wy[k / PER] |= yuv_luma_code(fk, c, cmax, sh) << (8 * S * (k % PER));
             pu[i] = yuv_chroma_linear(fk, 1, c);
             pv[i] = yuv_chroma_linear(fk, 2, c);
           }
@@ -616,106 +588,60 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
           csum[h][1] += pv[0] + pv[1];
         }
         char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y +
-                   (size_t)x * 2;
-        reinterpret_cast<uint32_t*>(yo)[0] = wy[0];  // (two dwords: the planes promise 4-byte alignment, not 8)
-        reinterpret_cast<uint32_t*>(yo)[1] = wy[1];
+                   (size_t)x * sizeof(TO);
+#pragma unroll
+        for (int q = 0; q < S; ++q) reinterpret_cast<uint32_t*>(yo)[q] = wy[q];  // (dwords: the planes promise 4-byte alignment, not 8)
         if (r == ROWS - 1) {
           char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
-                     (long long)(y >> 1) * p.yout.pitch_uv + (size_t)x * 2;
+                     (long long)(y >> 1) * p.yout.pitch_uv + (size_t)x * sizeof(TO);
+          [[maybe_unused]] uint32_t wc = 0;
 #pragma unroll
-          for (int h = 0; h < 2; ++h)
-            reinterpret_cast<uint32_t*>(co)[h] =
-                yuv_chroma_code16(fk, 1, csum[h][0], cmax, sh) | (yuv_chroma_code16(fk, 2, csum[h][1], cmax, sh) << 16);
+          for (int h = 0; h < 2; ++h) {
+            const uint32_t uv = yuv_chroma_code(fk, 1, csum[h][0], cmax, sh) | (yuv_chroma_code(fk, 2, csum[h][1], cmax, sh) << (8 * S));
+            if constexpr (S == 2) reinterpret_cast<uint32_t*>(co)[h] = uv;
+            else wc |= uv << (16 * h);
+          }
+          if constexpr (S == 1) *reinterpret_cast<uint32_t*>(co) = wc;
         }
       }
-    } else if constexpr (sizeof(TO) == 2) {
-      // a uint16 frame: (uint16)(out_white * clip(out, 0, 1)), one multiply and a truncation -- the uint8 store below with a
-      // run-time white level.  24 bytes per lane (32 with alpha), contiguous across the wave: plain per-lane stores.
-      static_assert(COUT == 3, "the 3 -> 3 op");
-      const float wl = p.out_white;
-      if constexpr (PACKED) {
-        // the input's own pixel format; alpha (of a uint16 frame) copied bit for bit
-        static_assert(sizeof(TI) == 2, "packed 16-bit output: from a uint16 frame");
-        if (active) {
-          uint32_t w[2 * SPX];
+    } else if constexpr (sizeof(TO) < 4) {
+      // A quantised frame: tf.cast(255 * clip(out, 0, 1), uint8), truncation (hdrnet/bin/run.py:95) -- or, for a uint16
+      // frame, (uint16)(out_white * clip(out, 0, 1)): the same multiply and truncation with a run-time white level.  The
+      // samples of a lane's 4 pixels are whole dwords, contiguous across the wave: plain per-lane stores are already dense.
+      // A packed frame has the input's own pixel format: colour channel c of pixel k goes where load_pixels found it, alpha
+      // beside it (copied bit for bit; into a uint8 frame, the upper byte of a uint16 alpha).
+      constexpr int S = (int)sizeof(TO), PER = 4 / S;  // bytes per sample; samples per dword
+      constexpr int SO = PACKED ? SPX : COUT;          // samples per stored pixel of the output
+      constexpr int NW = kPxPerThread * SO / PER;      // dwords per lane
+      static_assert(S == 1 || COUT == 3, "16-bit output: the 3 -> 3 op");
+      static_assert(S == 1 || !PACKED || sizeof(TI) == 2, "packed 16-bit output: from a uint16 frame");
+      static_assert(kPxPerThread * SO % PER == 0, "whole dwords per thread");
+      const float wl = S == 1 ? 255.0f : p.out_white;  // (uint8: a compile-time constant)
+      if (active) {
+        uint32_t w[NW];
 #pragma unroll
-          for (int q = 0; q < 2 * SPX; ++q) w[q] = 0;
+        for (int q = 0; q < NW; ++q) w[q] = 0;
 #pragma unroll
-          for (int k = 0; k < kPxPerThread; ++k) {
+        for (int k = 0; k < kPxPerThread; ++k) {
 #pragma unroll
-            for (int i = 0; i < COUT; ++i) {
-              const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);
-              const int pos = px_sample(PX, k, i);
-              w[pos >> 1] |= ((uint32_t)(wl * c)) << (16 * (pos & 1));
-            }
-            if constexpr (SPX == 4) w[2 * k + 1] |= alpha[k] << 16;
+          for (int i = 0; i < COUT; ++i) {
+            const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);  // clip: folds into the affine's last fma (clamp)
+            const int pos = PACKED ? px_sample(PX, k, i) : k * COUT + i;
+            w[pos / PER] |= ((uint32_t)(wl * c)) << (8 * S * (pos % PER));
           }
-          uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SPX);
-          if constexpr (SPX == 4) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            reinterpret_cast<u32x4*>(op)[0] = u32x4{w[0], w[1], w[2], w[3]};
-            reinterpret_cast<u32x4*>(op)[1] = u32x4{w[4], w[5], w[6], w[7]};
-          } else {
-#pragma unroll
-            for (int q = 0; q < 2 * SPX; ++q) op[q] = w[q];
-          }
+          if constexpr (PACKED && SPX == 4)
+            w[(4 * k + 3) / PER] |= ((int)sizeof(TI) > S ? alpha[k] >> 8 : alpha[k]) << (8 * S * ((4 * k + 3) % PER));
         }
-      } else if (active) {
-        static_assert(NO % 2 == 0, "whole dwords per thread");
-        uint32_t w[NO / 2];
+        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SO);
+        if constexpr (PACKED && SPX == 4) {  // pixels with alpha: 16-byte stores (written out: a loop moved registers about)
+          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+          reinterpret_cast<u32x4*>(op)[0] = u32x4{w[0], w[1], w[2], w[3]};
+          static_assert(NW == 4 * S, "one 16-byte store per lane for uint8 samples, two for uint16");
+          if constexpr (S == 2) reinterpret_cast<u32x4*>(op)[1] = u32x4{w[4], w[5], w[6], w[7]};
+        } else {
 #pragma unroll
-        for (int q = 0; q < NO / 2; ++q) w[q] = 0;
-#pragma unroll
-        for (int q = 0; q < NO; ++q) {
-          const float c = __builtin_amdgcn_fmed3f(of[q], 0.0f, 1.0f);
-          w[q >> 1] |= ((uint32_t)(wl * c)) << (16 * (q & 1));
+          for (int q = 0; q < NW; ++q) op[q] = w[q];
         }
-        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * COUT);
-#pragma unroll
-        for (int q = 0; q < NO / 2; ++q) op[q] = w[q];
-      }
-    } else if constexpr (sizeof(TO) == 1) {
-      // tf.cast(255 * clip(out, 0, 1), uint8): truncation.  12 bytes per lane, contiguous across
-      // the wave: plain per-lane stores are already dense.
-      static_assert(NO % 4 == 0, "whole dwords per thread");
-      if constexpr (PACKED) {
-        // the input's own pixel format: colour channel c of pixel k goes where load_pixels found it, alpha beside it
-        // (copied; the upper byte of a uint16 alpha) -- 12 or 16 bytes per lane, contiguous across the wave
-        if (active) {
-          uint32_t w[SPX];
-#pragma unroll
-          for (int q = 0; q < SPX; ++q) w[q] = 0;
-#pragma unroll
-          for (int k = 0; k < kPxPerThread; ++k) {
-#pragma unroll
-            for (int i = 0; i < COUT; ++i) {
-              const float c = __builtin_amdgcn_fmed3f(of[k * COUT + i], 0.0f, 1.0f);
-              const int pos = px_sample(PX, k, i);
-              w[pos >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (pos & 3));
-            }
-            if constexpr (SPX == 4) w[k] |= (sizeof(TI) == 2 ? alpha[k] >> 8 : alpha[k]) << 24;
-          }
-          uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * SPX);
-          if constexpr (SPX == 4) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u32x4*>(op) = u32x4{w[0], w[1], w[2], w[3]};
-          } else {
-#pragma unroll
-            for (int q = 0; q < SPX; ++q) op[q] = w[q];
-          }
-        }
-      } else if (active) {
-        uint32_t w[NO / 4];
-#pragma unroll
-        for (int q = 0; q < NO / 4; ++q) w[q] = 0;
-#pragma unroll
-        for (int q = 0; q < NO; ++q) {
-          const float c = __builtin_amdgcn_fmed3f(of[q], 0.0f, 1.0f);  // clip: folds into the affine's last fma (clamp)
-          w[q >> 2] |= ((uint32_t)(255.0f * c)) << (8 * (q & 3));
-        }
-        uint32_t* op = reinterpret_cast<uint32_t*>(static_cast<TO*>(p.out) + px * COUT);
-#pragma unroll
-        for (int q = 0; q < NO / 4; ++q) op[q] = w[q];
       }
     } else {
       // float output: lane-contiguous nontemporal buffer stores through the per-wave LDS slab
@@ -816,15 +742,55 @@ inline int io_guide_form(const ApplyIoArgs& a) {
   return a.guide_prepared ? kGuideCurvesCells : kGuideCurves;
 }
 
+// ... as a compile-time constant: f(std::integral_constant<int, GUIDE>) with the call's guide form.  Every translation
+// unit's launch goes through this one switch.
+template <class F>
+hipError_t with_guide_form(const ApplyIoArgs& a, F&& f) {
+  switch (io_guide_form(a)) {
+    case kGuideMap: return f(std::integral_constant<int, kGuideMap>{});
+    case kGuideNN: return f(std::integral_constant<int, kGuideNN>{});
+    case kGuideCurves: return f(std::integral_constant<int, kGuideCurves>{});
+    case kGuideCurvesCells: return f(std::integral_constant<int, kGuideCurvesCells>{});
+    default: return f(std::integral_constant<int, kGuideCurvesScan>{});
+  }
+}
+
 template <int PX>
 hipError_t dispatch_guides(const ApplyIoArgs& a, hipStream_t s) {
-  switch (io_guide_form(a)) {
-    case kGuideMap: return dispatch_types<kGuideMap, PX>(a, s);
-    case kGuideNN: return dispatch_types<kGuideNN, PX>(a, s);
-    case kGuideCurves: return dispatch_types<kGuideCurves, PX>(a, s);
-    case kGuideCurvesCells: return dispatch_types<kGuideCurvesCells, PX>(a, s);
-    default: return dispatch_types<kGuideCurvesScan, PX>(a, s);
+  return with_guide_form(a, [&](auto guide) { return dispatch_types<decltype(guide)::value, PX>(a, s); });
+}
+
+// The name hdrnet_last_kernel reports: apply_fwd_io/<in>-><out><guide form><pixel format>, of the call's thread.
+inline const char* io_label(const ApplyIoArgs& a) {
+  static const char* const frame[3] = {"f32", "u8", "u16"};           // input_dtype / output_dtype
+  static const char* const surface[4] = {"f32", "u8", "nv12", "p016"};  // YuvIo::out_kind
+  static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
+  static const char* const px[4] = {"", "/bgr", "/rgba", "/bgra"};
+  static thread_local char label[64];
+  if (a.yuv)
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", a.input_dtype == 1 ? "nv12" : "p016", surface[a.yuv->out_kind],
+             suffix[io_guide_form(a)]);
+  else
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s%s", frame[a.input_dtype], frame[a.output_dtype],
+             suffix[io_guide_form(a)], px[a.pixel_format]);
+  return label;
+}
+
+// What every predicate asks of a FRAME: the 3 -> 3 op with offset, whole dwords per lane of quantised pixels, the packed
+// formats on integer frames only -- with alpha, one 16-byte access per lane each way -- and a launch geometry that fits.
+inline bool io_frame_ok(const ApplyIoArgs& a) {
+  if (!(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
+  if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;
+  if (a.pixel_format != kPxRGB) {
+    if (a.pixel_format < 0 || a.pixel_format > kPxBGRA || a.input_dtype == 0) return false;
+    if (px_stored(a.pixel_format) == 4 && (((uintptr_t)a.input | (a.output_dtype != 0 ? (uintptr_t)a.out : 0)) & 15u)) return false;
   }
+  return io_geom(a).ok;
+}
+
+// ... and of a YUV SURFACE: the same op, whole row pairs and lanes, the same geometry.
+inline bool io_surface_ok(const ApplyIoArgs& a) {
+  return a.Cin == 3 && a.Cout == 3 && a.has_offset && a.H % 2 == 0 && a.W % 4 == 0 && io_geom(a).ok;
 }
 
 }  // namespace

@@ -40,41 +40,19 @@ hipError_t u16_formats(const ApplyIoArgs& a, hipStream_t s) {
 }  // namespace
 
 bool apply_fwd_io_u16_supported(const ApplyIoArgs& a) {
-  if (a.output_dtype != 2 || !(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
-  if (a.yuv) {  // a uint16 surface in, a uint16 surface out
-    if (a.input_dtype != 2 || a.yuv->out_kind != kYuvOutP016 || (a.yuv->out_bits != 10 && a.yuv->out_bits != 16)) return false;
-    if (a.H % 2 != 0 || a.W % 4 != 0) return false;
-    return io_geom(a).ok;
-  }
-  if (a.input_dtype != 0 && a.input_dtype != 2) return false;
-  if (((uintptr_t)a.input | (uintptr_t)a.out) & 3u) return false;  // whole dwords per lane
-  if (a.pixel_format != kPxRGB) {
-    if (a.pixel_format < 0 || a.pixel_format > kPxBGRA || a.input_dtype != 2) return false;  // uint16 frames only
-    if (io_guide_form(a) == kGuideCurvesScan) return false;
-    // pixels with alpha: 16-byte accesses, each way
-    if (px_stored(a.pixel_format) == 4 && (((uintptr_t)a.input | (uintptr_t)a.out) & 15u)) return false;
-  }
-  return io_geom(a).ok;
+  if (a.output_dtype != 2) return false;
+  if (a.yuv)  // a uint16 surface in, a uint16 surface out
+    return a.input_dtype == 2 && a.yuv->out_kind == kYuvOutP016 && (a.yuv->out_bits == 10 || a.yuv->out_bits == 16) &&
+           io_surface_ok(a);
+  if (a.input_dtype != 0 && a.input_dtype != 2) return false;  // (so a packed order's integer frame is a uint16 one)
+  if (a.pixel_format != kPxRGB && io_guide_form(a) == kGuideCurvesScan) return false;
+  return io_frame_ok(a);
 }
 
 hipError_t launch_apply_fwd_io_u16(const ApplyIoArgs& a, hipStream_t s, const char** name) {
   if (!apply_fwd_io_u16_supported(a)) return hipErrorInvalidValue;
-  static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
-  static const char* const px[4] = {"", "/bgr", "/rgba", "/bgra"};
-  static thread_local char label[64];
-  if (a.yuv)
-    snprintf(label, sizeof label, "apply_fwd_io/p016->p016%s", suffix[io_guide_form(a)]);
-  else
-    snprintf(label, sizeof label, "apply_fwd_io/%s->u16%s%s", a.input_dtype == 2 ? "u16" : "f32", suffix[io_guide_form(a)],
-             px[a.pixel_format]);
-  *name = label;
-  switch (io_guide_form(a)) {
-    case kGuideMap: return u16_formats<kGuideMap>(a, s);
-    case kGuideNN: return u16_formats<kGuideNN>(a, s);
-    case kGuideCurves: return u16_formats<kGuideCurves>(a, s);
-    case kGuideCurvesCells: return u16_formats<kGuideCurvesCells>(a, s);
-    default: return u16_formats<kGuideCurvesScan>(a, s);
-  }
+  *name = io_label(a);
+  return with_guide_form(a, [&](auto guide) { return u16_formats<decltype(guide)::value>(a, s); });
 }
 
 }  // namespace hdrnet_amd

@@ -42,29 +42,15 @@ hipError_t yuv_types(const ApplyIoArgs& a, hipStream_t s) {
 }  // namespace
 
 bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a) {
-  if (!a.yuv || !(a.Cin == 3 && a.Cout == 3 && a.has_offset)) return false;
-  if (a.input_dtype != 1 && a.input_dtype != 2) return false;
+  if (!a.yuv || (a.input_dtype != 1 && a.input_dtype != 2)) return false;
   if (a.yuv->out_kind < 0 || a.yuv->out_kind > HDRNET_YUV_OUT_NV12) return false;  // P010 / P016 out: apply_fwd_io_u16.hip
-  if (a.H % 2 != 0 || a.W % 4 != 0) return false;
-  return io_geom(a).ok;
+  return io_surface_ok(a);
 }
 
 hipError_t launch_apply_fwd_io_yuv(const ApplyIoArgs& a, hipStream_t s, const char** name) {
   if (!apply_fwd_io_yuv_supported(a)) return hipErrorInvalidValue;
-  static const char* const out[3] = {"f32", "u8", "nv12"};
-  static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
-  if (a.yuv->out_kind < 0 || a.yuv->out_kind > 2) return hipErrorInvalidValue;
-  static thread_local char label[64];
-  snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", a.input_dtype == 1 ? "nv12" : "p016", out[a.yuv->out_kind],
-           suffix[io_guide_form(a)]);
-  *name = label;
-  switch (io_guide_form(a)) {
-    case kGuideMap: return yuv_types<kGuideMap>(a, s);
-    case kGuideNN: return yuv_types<kGuideNN>(a, s);
-    case kGuideCurves: return yuv_types<kGuideCurves>(a, s);
-    case kGuideCurvesCells: return yuv_types<kGuideCurvesCells>(a, s);
-    default: return yuv_types<kGuideCurvesScan>(a, s);
-  }
+  *name = io_label(a);
+  return with_guide_form(a, [&](auto guide) { return yuv_types<decltype(guide)::value>(a, s); });
 }
 
 hipError_t launch_yuv_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,

@@ -356,23 +356,15 @@ int set_curves_prepared(hdrnet_amd::ApplyIoArgs& a, const void* prepared, const 
   return HDRNET_OK;
 }
 
-// The tail: the kernel family is the 16-bit output's (a.output_dtype == 2), else the pixel source's (a.yuv, or `coarse`
-// for the pyramid's up-add), `otherwise` what the entry point supports, `op` its name in a runtime failure.
+// The tail: the call's kernel family (apply_fwd_io.hip chooses it; `coarse`: the pyramid's up-add), `otherwise` what the
+// entry point supports, `op` its name in a runtime failure.
 int launch_io(const hdrnet_amd::ApplyIoArgs& a, const float* coarse, int Hc, int Wc, const char* op, const char* otherwise,
               void* stream) {
   using namespace hdrnet_amd;
-  const bool u16 = a.output_dtype == 2 && !coarse;
-  if (!(u16      ? apply_fwd_io_u16_supported(a)
-        : a.yuv  ? apply_fwd_io_yuv_supported(a)
-        : coarse ? apply_fwd_io_upadd_supported(a, coarse)
-                 : apply_fwd_io_supported(a)))
+  if (!apply_fwd_io_family_supported(a, coarse))
     return refuse_fused(a.B, a.H, a.W, a.GW, a.GD, a.Cout, rows::kSegLimits, otherwise);
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name = "";
-  const hipError_t e = u16      ? launch_apply_fwd_io_u16(a, s, &name)
-                       : a.yuv  ? launch_apply_fwd_io_yuv(a, s, &name)
-                       : coarse ? launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, &name)
-                                : launch_apply_fwd_io(a, s, &name);
+  const hipError_t e = launch_apply_fwd_io_family(a, coarse, Hc, Wc, static_cast<hipStream_t>(stream), &name);
   return finish_launch(e, op, name);
 }
 
@@ -1064,27 +1056,68 @@ int hdrnet_coefficients_bn_grad_wide_f32(const float* lowres, const hdrnet_coeff
 }
 
 // ---- include/hdrnet_amd.h: the wire formats (uint8 / uint16 / float32 frames in, float32 / uint8 out) --------------------
-// with a guide map or the guide network, for a frame in `pixel_format` (io_ex: HDRNET_PX_RGB)
-static int apply_io_impl(const float* grid, const float* guide, const void* input, void* out, int B, int H, int W, int GH,
+// The guide side of an entry point, in the fields of ApplyIoArgs.  Two kinds: a guide map or the guide network with its
+// flags (`guide`, conv1, conv2, n = n_feats), or the curves guide (conv1 = ccm, conv2 = mix, shifts, slopes, n = npts,
+// the prepared cell tables or null).
+struct IoGuide {
+  bool curves;
+  const float* guide;
+  const float* conv1;
+  const float* conv2;
+  int n;
+  float* guide_out;
+  unsigned flags;
+  const float* shifts;
+  const float* slopes;
+  const void* prepared;
+};
+
+static IoGuide io_guide_network(const float* guide, const float* conv1, const float* conv2, int n_feats, float* guide_out,
+                                unsigned flags) {
+  return IoGuide{false, guide, conv1, conv2, n_feats, guide_out, flags, nullptr, nullptr, nullptr};
+}
+
+static IoGuide io_guide_curves(const float* ccm, const float* shifts, const float* slopes, const float* mix, int npts,
+                               const void* prepared, float* guide_out) {
+  return IoGuide{true, nullptr, ccm, mix, npts, guide_out, 0u, shifts, slopes, prepared};
+}
+
+// the guide's last word before the launch: the network's flags against the pointers, or the curves' prepared tables
+static int set_io_guide(hdrnet_amd::ApplyIoArgs& a, const IoGuide& g, const char* prefix, const char* prepared_needs) {
+  return g.curves ? set_curves_prepared(a, g.prepared, prefix, prepared_needs) : set_io_guide_flags(a, g.flags);
+}
+
+// A frame in `pixel_format` (HDRNET_PX_RGB for the entry points of this header) with either guide.  The network's flags
+// answer before the frame's values, the curves' knots after them.
+static int apply_io_impl(const float* grid, const IoGuide& g, const void* input, void* out, int B, int H, int W, int GH,
                          int GW, int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                         int output_dtype, const float* guide_conv1, const float* guide_conv2, int n_feats,
-                         float* guide_out, unsigned flags, int pixel_format, void* stream, const U16Out* u16 = nullptr) {
+                         int output_dtype, int pixel_format, void* stream, const U16Out* u16 = nullptr) {
   using namespace hdrnet_amd;
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_guide_flags(flags)) return rc;
+  if (!g.curves)
+    if (int rc = check_guide_flags(g.flags)) return rc;
   if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype, u16)) return rc;
+  if (g.curves)
+    if (int rc = check_curves_knots("", g.n)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
-  if (!grid || !input || !out) return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_guide_given("", guide, guide_conv1, guide_conv2, n_feats)) return rc;
-  if (int rc = check_pixel_buffers(u16 ? u16->what : "hdrnet_bilateral_slice_apply_io_px", pixel_format, Cin, Cout, has_offset,
-                                   W, input, output_dtype != 0 ? out : nullptr))
+  if (!grid || !input || !out || (g.curves && (!g.conv1 || !g.shifts || !g.slopes || !g.conv2)))
+    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
+  if (!g.curves)
+    if (int rc = check_guide_given("", g.guide, g.conv1, g.conv2, g.n)) return rc;
+  const char* px_what = g.curves ? "hdrnet_bilateral_slice_apply_io_curves_px" : "hdrnet_bilateral_slice_apply_io_px";
+  if (int rc = check_pixel_buffers(u16 ? u16->what : px_what, pixel_format, Cin, Cout, has_offset, W, input,
+                                   output_dtype != 0 ? out : nullptr))
     return rc;
-  ApplyIoArgs a{grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
-                input_dtype, output_dtype, input_white_level, guide_conv1, guide_conv2, n_feats,
-                guide_out};
+  ApplyIoArgs a{grid, g.guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
+                input_dtype, output_dtype, input_white_level, g.conv1, g.conv2, g.n,
+                g.guide_out, g.shifts, g.slopes};
   a.pixel_format = pixel_format;
   if (u16) a.output_white_level = u16->white_level;
-  if (int rc = set_io_guide_flags(a, flags)) return rc;
+  if (int rc = set_io_guide(a, g, "", "Cin = 3, npts <= 16")) return rc;
+  if (g.curves)
+    return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIOCurves",
+                     "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
+                     "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32", stream);
   return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIO",
                    "the wire-format forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
                    "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_f32", stream);
@@ -1096,9 +1129,9 @@ int hdrnet_bilateral_slice_apply_io_ex(const float* grid, const float* guide, co
                                        float input_white_level, int output_dtype,
                                        const float* guide_conv1, const float* guide_conv2, int n_feats,
                                        float* guide_out, unsigned flags, void* stream) {
-  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                       input_white_level, output_dtype, guide_conv1, guide_conv2, n_feats, guide_out, flags,
-                       HDRNET_PX_RGB, stream);
+  return apply_io_impl(grid, io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), input, out, B, H,
+                       W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, output_dtype, HDRNET_PX_RGB,
+                       stream);
 }
 
 int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const void* input,
@@ -1110,33 +1143,6 @@ int hdrnet_bilateral_slice_apply_io(const float* grid, const float* guide, const
   return hdrnet_bilateral_slice_apply_io_ex(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset,
                                             input_dtype, input_white_level, output_dtype, guide_conv1, guide_conv2,
                                             n_feats, guide_out, 0u, stream);
-}
-
-// ... and with the curves guide (..._io_curves_prepared: HDRNET_PX_RGB)
-static int apply_io_curves_impl(const float* grid, const void* input, void* out, int B, int H, int W, int GH, int GW,
-                                int GD, int Cin, int Cout, int has_offset, int input_dtype, float input_white_level,
-                                int output_dtype, const float* guide_ccm, const float* guide_shifts,
-                                const float* guide_slopes, const float* guide_mix, int npts, const void* prepared,
-                                float* guide_out, int pixel_format, void* stream, const U16Out* u16 = nullptr) {
-  using namespace hdrnet_amd;
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_frame_values(Cin, Cout, input_dtype, input_white_level, output_dtype, u16)) return rc;
-  if (int rc = check_curves_knots("", npts)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (!grid || !input || !out || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
-    return fail(HDRNET_INVALID_ARGUMENT, "null buffer");
-  if (int rc = check_pixel_buffers(u16 ? u16->what : "hdrnet_bilateral_slice_apply_io_curves_px", pixel_format, Cin, Cout,
-                                   has_offset, W, input, output_dtype != 0 ? out : nullptr))
-    return rc;
-  ApplyIoArgs a{grid, nullptr, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset != 0,
-                input_dtype, output_dtype, input_white_level, guide_ccm, guide_mix, npts,
-                guide_out, guide_shifts, guide_slopes};
-  a.pixel_format = pixel_format;
-  if (u16) a.output_white_level = u16->white_level;
-  if (int rc = set_curves_prepared(a, prepared, "", "Cin = 3, npts <= 16")) return rc;
-  return launch_io(a, nullptr, 0, 0, "BilateralSliceApplyIOCurves",
-                   "the fused curves-guide forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
-                   "buffers; evaluate the guide on the caller's side and use hdrnet_bilateral_slice_apply_f32", stream);
 }
 
 size_t hdrnet_curves_guide_prepared_bytes(int Cin) { return hdrnet_amd::curves_guide_prepared_bytes(Cin); }
@@ -1176,9 +1182,9 @@ int hdrnet_bilateral_slice_apply_io_curves_prepared(const float* grid, const voi
                                                     const float* guide_shifts, const float* guide_slopes,
                                                     const float* guide_mix, int npts, const void* prepared,
                                                     float* guide_out, void* stream) {
-  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
-                              prepared, guide_out, HDRNET_PX_RGB, stream);
+  return apply_io_impl(grid, io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
+                       input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, output_dtype,
+                       HDRNET_PX_RGB, stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_curves(const float* grid, const void* input, void* out, int B, int H,
@@ -1204,8 +1210,8 @@ int hdrnet_bilateral_slice_apply_io_px(const float* grid, const float* guide, co
   if (int rc = check_io_format(input_dtype, input_white_level, output_dtype)) return rc;
   if (int rc = check_pixel_formats("hdrnet_bilateral_slice_apply_io_px", input_dtype, output_dtype, input_format, output_format))
     return rc;
-  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                       input_white_level, output_dtype, guide_conv1, guide_conv2, n_feats, guide_out, flags, input_format,
+  return apply_io_impl(grid, io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), input, out, B, H,
+                       W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, output_dtype, input_format,
                        stream);
 }
 
@@ -1219,9 +1225,9 @@ int hdrnet_bilateral_slice_apply_io_curves_px(const float* grid, const void* inp
   if (int rc = check_pixel_formats("hdrnet_bilateral_slice_apply_io_curves_px", input_dtype, output_dtype, input_format,
                                    output_format))
     return rc;
-  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                              input_white_level, output_dtype, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts,
-                              prepared, guide_out, input_format, stream);
+  return apply_io_impl(grid, io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
+                       input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, output_dtype,
+                       input_format, stream);
 }
 
 // ---- include/hdrnet_amd_yuv.h: semi-planar YUV 4:2:0 surfaces (hdrnet_lowres_input_yuv: sample preparation, below) --------
@@ -1240,16 +1246,38 @@ int hdrnet_yuv_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int p
                        "yuv_to_rgb");
 }
 
-// both fused entry points, once surfaces and guide are checked: `a` reads the surfaces of `io` (an RGB `out` is a.out)
-static int yuv_io_launch(const char* op, hdrnet_amd::ApplyIoArgs& a, hdrnet_amd::YuvIo& io, void* out, void* stream) {
+// The four fused entry points (`what`): a surface in with either guide; `io`: the call's surfaces as given, io.out.y the
+// RGB frame where the output is one; `p016`: an entry point of hdrnet_amd_u16_out.h (io.out_kind is then kYuvOutP016,
+// which the others refuse as a caller's output kind).  Either guide's values answer before the surfaces'.
+static int apply_io_yuv_impl(const char* what, bool p016, const float* grid, const IoGuide& g, hdrnet_amd::YuvIo io,
+                             int sample_dtype, int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset,
+                             void* stream) {
   using namespace hdrnet_amd;
-  if (io.out_kind < HDRNET_YUV_OUT_NV12) {
-    a.out = out;
+  char prefix[96];
+  snprintf(prefix, sizeof prefix, "%s: ", what);
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = g.curves ? check_curves_knots(prefix, g.n) : check_guide_flags(g.flags)) return rc;
+  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, p016)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_io_pointers(what, io)) return rc;
+  if (g.curves) {
+    if (!grid || !g.conv1 || !g.shifts || !g.slopes || !g.conv2)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
+  } else {
+    if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
+    if (int rc = check_guide_given(prefix, g.guide, g.conv1, g.conv2, g.n)) return rc;
+  }
+  ApplyIoArgs a{grid, g.guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, p016 ? 2 : io.out_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, g.conv1, g.conv2, g.n,
+                g.guide_out, g.shifts, g.slopes};
+  if (int rc = set_io_guide(a, g, prefix, "npts <= 16")) return rc;
+  if (io.out_kind < HDRNET_YUV_OUT_NV12) {  // an RGB frame out: a.out
+    a.out = const_cast<void*>(io.out.y);
     io.out = YuvSurface{};
     io.from_rgb = nullptr;
   }
   a.yuv = &io;
-  return launch_io(a, nullptr, 0, 0, op,
+  return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuv" : "BilateralSliceApplyIOYuv",
                    "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers", stream);
 }
 
@@ -1261,21 +1289,11 @@ int hdrnet_bilateral_slice_apply_io_yuv(const float* grid, const float* guide, c
                                         int output_kind, void* out, void* out_uv, int out_pitch_y, int out_pitch_uv,
                                         long long out_image_stride_y, long long out_image_stride_uv,
                                         const float* from_rgb, void* stream) {
-  using namespace hdrnet_amd;
-  const char* what = "hdrnet_bilateral_slice_apply_io_yuv";
-  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
-           {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_guide_flags(flags)) return rc;
-  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (int rc = check_yuv_io_pointers(what, io)) return rc;
-  if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
-  if (int rc = check_guide_given("hdrnet_bilateral_slice_apply_io_yuv: ", guide, guide_conv1, guide_conv2, n_feats)) return rc;
-  ApplyIoArgs a{grid, guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
-                sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_conv1, guide_conv2, n_feats, guide_out};
-  if (int rc = set_io_guide_flags(a, flags)) return rc;
-  return yuv_io_launch("BilateralSliceApplyIOYuv", a, io, out, stream);
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+                             {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_io_yuv", false, grid,
+                           io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io, sample_dtype, B,
+                           H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_curves_yuv(const float* grid, const void* y, const void* uv, int sample_dtype,
@@ -1287,27 +1305,15 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv(const float* grid, const void* y,
                                                int output_kind, void* out, void* out_uv, int out_pitch_y,
                                                int out_pitch_uv, long long out_image_stride_y,
                                                long long out_image_stride_uv, const float* from_rgb, void* stream) {
-  using namespace hdrnet_amd;
-  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv";
-  const char* prefix = "hdrnet_bilateral_slice_apply_io_curves_yuv: ";
-  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
-           {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_curves_knots(prefix, npts)) return rc;
-  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (int rc = check_yuv_io_pointers(what, io)) return rc;
-  if (!grid || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
-  ApplyIoArgs a{grid, nullptr, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
-                sample_dtype, output_kind == HDRNET_YUV_OUT_RGB_F32 ? 0 : 1, 1.0f, guide_ccm, guide_mix, npts,
-                guide_out, guide_shifts, guide_slopes};
-  if (int rc = set_curves_prepared(a, prepared, prefix, "npts <= 16")) return rc;
-  return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, out, stream);
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+                             {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_io_curves_yuv", false, grid,
+                           io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out), io,
+                           sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 // ---- include/hdrnet_amd_u16_out.h: a uint16 frame / a P010 / P016 surface out ------------------------------------------
-// (the twins of the four entry points above: the same checks in the same order, the output's own rules beside them)
+// (the four entry points above with the output's own rules beside them: the same bodies, so the same checks in the same order)
 int hdrnet_bilateral_slice_apply_io_px_u16(const float* grid, const float* guide, const void* input, void* out, int B,
                                            int H, int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset,
                                            int input_dtype, float input_white_level, float output_white_level,
@@ -1317,8 +1323,8 @@ int hdrnet_bilateral_slice_apply_io_px_u16(const float* grid, const float* guide
   const U16Out u16{"hdrnet_bilateral_slice_apply_io_px_u16", output_white_level};
   if (int rc = check_u16_format(u16, input_dtype, input_white_level)) return rc;
   if (int rc = check_pixel_formats(u16.what, input_dtype, 2, input_format, output_format)) return rc;
-  return apply_io_impl(grid, guide, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                       input_white_level, 2, guide_conv1, guide_conv2, n_feats, guide_out, flags, input_format, stream, &u16);
+  return apply_io_impl(grid, io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), input, out, B, H,
+                       W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, 2, input_format, stream, &u16);
 }
 
 int hdrnet_bilateral_slice_apply_io_curves_px_u16(const float* grid, const void* input, void* out, int B, int H, int W,
@@ -1331,9 +1337,9 @@ int hdrnet_bilateral_slice_apply_io_curves_px_u16(const float* grid, const void*
   const U16Out u16{"hdrnet_bilateral_slice_apply_io_curves_px_u16", output_white_level};
   if (int rc = check_u16_format(u16, input_dtype, input_white_level)) return rc;
   if (int rc = check_pixel_formats(u16.what, input_dtype, 2, input_format, output_format)) return rc;
-  return apply_io_curves_impl(grid, input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype,
-                              input_white_level, 2, guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared,
-                              guide_out, input_format, stream, &u16);
+  return apply_io_impl(grid, io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
+                       input, out, B, H, W, GH, GW, GD, Cin, Cout, has_offset, input_dtype, input_white_level, 2,
+                       input_format, stream, &u16);
 }
 
 int hdrnet_bilateral_slice_apply_io_yuv_p016(const float* grid, const float* guide, const void* y, const void* uv,
@@ -1344,21 +1350,12 @@ int hdrnet_bilateral_slice_apply_io_yuv_p016(const float* grid, const float* gui
                                              void* out_y, void* out_uv, int out_pitch_y, int out_pitch_uv,
                                              long long out_image_stride_y, long long out_image_stride_uv,
                                              const float* from_rgb, int out_bits, void* stream) {
-  using namespace hdrnet_amd;
-  const char* what = "hdrnet_bilateral_slice_apply_io_yuv_p016";
-  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, kYuvOutP016,
-           {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb, out_bits};
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_guide_flags(flags)) return rc;
-  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, true)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (int rc = check_yuv_io_pointers(what, io)) return rc;
-  if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
-  if (int rc = check_guide_given("hdrnet_bilateral_slice_apply_io_yuv_p016: ", guide, guide_conv1, guide_conv2, n_feats)) return rc;
-  ApplyIoArgs a{grid, guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
-                sample_dtype, 2, 1.0f, guide_conv1, guide_conv2, n_feats, guide_out};
-  if (int rc = set_io_guide_flags(a, flags)) return rc;
-  return yuv_io_launch("BilateralSliceApplyIOYuv", a, io, nullptr, stream);
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, hdrnet_amd::kYuvOutP016,
+                             {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb,
+                             out_bits};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_io_yuv_p016", true, grid,
+                           io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io, sample_dtype, B,
+                           H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_curves_yuv_p016(const float* grid, const void* y, const void* uv, int sample_dtype,
@@ -1371,23 +1368,12 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv_p016(const float* grid, const voi
                                                     int out_pitch_y, int out_pitch_uv, long long out_image_stride_y,
                                                     long long out_image_stride_uv, const float* from_rgb, int out_bits,
                                                     void* stream) {
-  using namespace hdrnet_amd;
-  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv_p016";
-  const char* prefix = "hdrnet_bilateral_slice_apply_io_curves_yuv_p016: ";
-  YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, kYuvOutP016,
-           {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb, out_bits};
-  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
-  if (int rc = check_curves_knots(prefix, npts)) return rc;
-  if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, true)) return rc;
-  if ((long long)B * H * W == 0) return finish_noop();
-  if (int rc = check_yuv_io_pointers(what, io)) return rc;
-  if (!grid || !guide_ccm || !guide_shifts || !guide_slopes || !guide_mix)
-    return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
-  ApplyIoArgs a{grid, nullptr, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
-                sample_dtype, 2, 1.0f, guide_ccm, guide_mix, npts,
-                guide_out, guide_shifts, guide_slopes};
-  if (int rc = set_curves_prepared(a, prepared, prefix, "npts <= 16")) return rc;
-  return yuv_io_launch("BilateralSliceApplyIOCurvesYuv", a, io, nullptr, stream);
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, hdrnet_amd::kYuvOutP016,
+                             {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb,
+                             out_bits};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_io_curves_yuv_p016", true, grid,
+                           io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out), io,
+                           sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 // ---- include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats ---------------------------------------------

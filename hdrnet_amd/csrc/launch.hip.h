@@ -265,6 +265,11 @@ hipError_t launch_apply_fwd_io_u16(const ApplyIoArgs& a, hipStream_t s, const ch
 bool apply_fwd_io_upadd_supported(const ApplyIoArgs& a, const float* coarse);
 hipError_t launch_apply_fwd_io_upadd(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
                                      const char** name);
+// apply_fwd_io.hip -- what the C ABI calls: the pair of whichever of the four families above the call belongs to (the
+// 16-bit output's, else the pixel source's; `coarse`: the up-add's coarser level, or null)
+bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse);
+hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
+                                      const char** name);
 // the curves guide's uniform cell tables (apply_fwd_io.hip: CurveCells), prepared once per parameter set
 size_t curves_guide_prepared_bytes(int Cin);  // 0: no cell tables for this channel count
 size_t curves_guide_prepared_ok_offset(int Cin);  // float index of the buffer's `ok` word

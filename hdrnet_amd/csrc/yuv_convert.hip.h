@@ -91,29 +91,21 @@ __device__ __forceinline__ void yuv_load_px(const YuvSurface& s, const YuvMatrix
   yuv_to_rgb_px(k, (float)yp[x], (float)cp[xc], (float)cp[xc + 1], rgb);
 }
 
-// NV12 output (uint8 code values; the + 0.5 of the rounding is in the bias of from_rgb).  c: R, G, B already clipped to
-// [0, 1].  Luma per pixel; the LINEAR part of chroma row i per pixel, summed over the 2 x 2 block by the caller --
-// horizontal pair first, even row then odd row -- and finished by yuv_chroma_code (x 0.25, + bias, clamp).
-__device__ __forceinline__ uint32_t yuv_luma_code(const YuvMatrix& k, const float* c) {
+// Surface output: code values clamped to code_max and truncated (the + 0.5 of the rounding is in the bias of from_rgb),
+// placed `shift` bits up in the sample.  NV12 (uint8): code_max = 255, shift = 0, as compile-time constants.  P010 / P016
+// (include/hdrnet_amd_u16_out.h): from_rgb is in code values of out_bits bits (hdrnet_amd/yuv.py:
+// yuv_encode_coefficients), code_max = 2^out_bits - 1, and the code sits in the HIGH bits of the uint16 sample (shift = 16
+// - out_bits).  c: R, G, B already clipped to [0, 1].  Luma per pixel; the LINEAR part of chroma row i per pixel, summed
+// over the 2 x 2 block by the caller -- horizontal pair first, even row then odd row -- and finished by yuv_chroma_code
+// (x 0.25, + bias, clamp).
+__device__ __forceinline__ uint32_t yuv_luma_code(const YuvMatrix& k, const float* c, float code_max, int shift) {
   const float t = __builtin_fmaf(k.m[2], c[2], __builtin_fmaf(k.m[1], c[1], __builtin_fmaf(k.m[0], c[0], k.bias[0])));
-  return (uint32_t)__builtin_amdgcn_fmed3f(t, 0.0f, 255.0f);
+  return ((uint32_t)__builtin_amdgcn_fmed3f(t, 0.0f, code_max)) << shift;
 }
 __device__ __forceinline__ float yuv_chroma_linear(const YuvMatrix& k, int i, const float* c) {
   return __builtin_fmaf(k.m[3 * i + 2], c[2], __builtin_fmaf(k.m[3 * i + 1], c[1], k.m[3 * i] * c[0]));
 }
-__device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum4) {
-  return (uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, 255.0f);
-}
-
-// P010 / P016 output (include/hdrnet_amd_u16_out.h): the same two chains in code values of out_bits bits -- from_rgb is
-// then in those units (hdrnet_amd/yuv.py: yuv_encode_coefficients) -- clamped to code_max = 2^out_bits - 1, truncated
-// and placed in the HIGH bits of the uint16 sample (shift = 16 - out_bits).  The chroma sum is yuv_chroma_linear's, in
-// the order above.
-__device__ __forceinline__ uint32_t yuv_luma_code16(const YuvMatrix& k, const float* c, float code_max, int shift) {
-  const float t = __builtin_fmaf(k.m[2], c[2], __builtin_fmaf(k.m[1], c[1], __builtin_fmaf(k.m[0], c[0], k.bias[0])));
-  return ((uint32_t)__builtin_amdgcn_fmed3f(t, 0.0f, code_max)) << shift;
-}
-__device__ __forceinline__ uint32_t yuv_chroma_code16(const YuvMatrix& k, int i, float sum4, float code_max, int shift) {
+__device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum4, float code_max, int shift) {
   return ((uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, code_max)) << shift;
 }
 

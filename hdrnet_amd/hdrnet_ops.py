@@ -1150,14 +1150,64 @@ def curves_guide_prepare(shifts: torch.Tensor, slopes: torch.Tensor) -> Optional
 
 
 def _out_channels(pixel_format: str, out_dtype, Cout: int) -> int:
-    """Channels of the output tensor: a uint8 output has the input's pixel format, a float32 output is RGB."""
-    return _lib.PIXEL_FORMAT_CHANNELS[pixel_format] if (pixel_format != "rgb" and out_dtype == torch.uint8) else Cout
+    """Channels of the output tensor: a uint8 / uint16 output has the input's pixel format, a float32 output is RGB."""
+    return _lib.PIXEL_FORMAT_CHANNELS[pixel_format] if (pixel_format != "rgb" and out_dtype != torch.float32) else Cout
 
 
 def _px_codes(pixel_format: str, out_dtype):
-    """``(input_format, output_format)`` of the ..._px entry points (HDRNET_PX_*)."""
+    """``(input_format, output_format)`` of the ..._px / ..._px_u16 entry points (HDRNET_PX_*)."""
     code = _lib.PIXEL_FORMATS[pixel_format]
-    return code, (code if out_dtype == torch.uint8 else _lib.PIXEL_FORMATS["rgb"])
+    return code, (code if out_dtype != torch.float32 else _lib.PIXEL_FORMATS["rgb"])
+
+
+def _output_white_level(value, what: str) -> float:
+    """The white level of a uint16 output (include/hdrnet_amd_u16_out.h): finite, 0 < value <= 65535."""
+    v = float(value)
+    if not (0.0 < v <= 65535.0):  # (false for NaN)
+        raise ValueError(f"{what}: output_white_level must be finite with 0 < output_white_level <= 65535, got {value!r}")
+    return v
+
+
+def _apply_io_frame(u16, grid, input, guide, guide_conv1, guide_conv2, input_white_level, out_dtype, has_offset,  # noqa: A002
+                    guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, pixel_format,
+                    output_white_level=None):
+    """The body of ``bilateral_slice_apply_io`` and (``u16``: ``out_dtype`` uint16, scaled to ``output_white_level``) of
+    ``bilateral_slice_apply_io_u16``: the uint16 output's own rules stand beside the shared ones, in the order the C ABI
+    checks them."""
+    what = "bilateral_slice_apply_io_u16" if u16 else "bilateral_slice_apply_io"
+    input_white_level = _frame_head(input, input_white_level, torch.float32 if u16 else out_dtype)
+    if u16:
+        if input.dtype == torch.uint8:
+            raise TypeError(f"{what}: a uint16 output needs a uint16 or float32 frame, got uint8 (no kernel goes from 8 to 16 bits)")
+        output_white_level = _output_white_level(output_white_level, what)
+    plain = pixel_format == "rgb" and not u16  # the entry points without format codes: every rule is the one it always was
+    if not plain:
+        pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32, what)
+    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset, pixel_format)
+    if u16 and ((Cin, Cout) != (3, 3) or not has_offset):
+        raise ValueError(f"{what}: the 3 -> 3 op with offset (a [.., 12] grid) only, got Cin = {Cin}, Cout = {Cout}, "
+                         f"has_offset = {bool(has_offset)}")
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), Cin)
+    _require_gpu("grid", grid)
+    _require_gpu("input", input)
+    grid, inp = grid.detach().contiguous(), input.detach().contiguous()
+    dev = inp.device
+    out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    frame = (inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, int(bool(has_offset)),
+             _DTYPE_CODE[input.dtype], float(input_white_level), output_white_level if u16 else _DTYPE_CODE[out_dtype])
+    suffix = "_px_u16" if u16 else "_px" if not plain else "_prepared" if curves else "_ex"
+    if curves:
+        fn = "hdrnet_bilateral_slice_apply_io_curves" + suffix
+        args = (grid.data_ptr(), *frame, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
+    else:
+        fn = "hdrnet_bilateral_slice_apply_io" + suffix
+        args = (grid.data_ptr(), _ptr(g[0]), *frame, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None))
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), fn)(*args, *(() if plain else _px_codes(pixel_format, out_dtype)), _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
+    return (out, gout) if return_guide else out
 
 
 def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A002
@@ -1192,40 +1242,8 @@ def bilateral_slice_apply_io(grid: torch.Tensor, input: torch.Tensor,  # noqa: A
     uint16 one: alpha is never divided by the white level or quantised); a float32 output is ``[B, H, W, 3]`` RGB.
     4-channel frames must be 16-byte aligned.  A uint16 frame out is ``bilateral_slice_apply_io_u16``'s.  Out of scope:
     float32 frames in other orders."""
-    input_white_level = _frame_head(input, input_white_level, out_dtype)
-    rgb = pixel_format == "rgb"
-    if not rgb:  # "rgb": every rule below is the one it always was
-        pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32,
-                                         "bilateral_slice_apply_io")
-    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset, pixel_format)
-    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), Cin)
-    _require_gpu("grid", grid)
-    _require_gpu("input", input)
-    grid, inp = grid.detach().contiguous(), input.detach().contiguous()
-    dev = inp.device
-    out = torch.empty((B, H, W, _out_channels(pixel_format, out_dtype, Cout)), dtype=out_dtype, device=dev)
-    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    frame = (inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, int(bool(has_offset)),
-             _DTYPE_CODE[input.dtype], float(input_white_level), _DTYPE_CODE[out_dtype])
-    if curves:
-        fn = "hdrnet_bilateral_slice_apply_io_curves" + ("_prepared" if rgb else "_px")
-        args = (grid.data_ptr(), *frame, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
-    else:
-        fn = "hdrnet_bilateral_slice_apply_io" + ("_ex" if rgb else "_px")
-        args = (grid.data_ptr(), _ptr(g[0]), *frame, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
-                _guide_flags(fast_sigmoid, prescaled and g[0] is None))
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), fn)(*args, *(() if rgb else _px_codes(pixel_format, out_dtype)), _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
-    return (out, gout) if return_guide else out
-
-
-def _output_white_level(value, what: str) -> float:
-    """The white level of a uint16 output (include/hdrnet_amd_u16_out.h): finite, 0 < value <= 65535."""
-    v = float(value)
-    if not (0.0 < v <= 65535.0):  # (false for NaN)
-        raise ValueError(f"{what}: output_white_level must be finite with 0 < output_white_level <= 65535, got {value!r}")
-    return v
+    return _apply_io_frame(False, grid, input, guide, guide_conv1, guide_conv2, input_white_level, out_dtype, has_offset,
+                           guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, pixel_format)
 
 
 def bilateral_slice_apply_io_u16(grid: torch.Tensor, input: torch.Tensor,  # noqa: A002
@@ -1247,37 +1265,9 @@ def bilateral_slice_apply_io_u16(grid: torch.Tensor, input: torch.Tensor,  # noq
     Every other argument is ``bilateral_slice_apply_io``'s; the 3 -> 3 op with offset only.  No autograd.
     Out of scope: uint8 frames (no kernel goes from 8 to 16 bits), float32 frames in other orders, more than 16 curve
     knots on a BGR / RGBA / BGRA frame."""
-    what = "bilateral_slice_apply_io_u16"
-    input_white_level = _frame_head(input, input_white_level)
-    if input.dtype == torch.uint8:
-        raise TypeError(f"{what}: a uint16 output needs a uint16 or float32 frame, got uint8 (no kernel goes from 8 to 16 bits)")
-    output_white_level = _output_white_level(output_white_level, what)
-    pixel_format = _lib.pixel_format(pixel_format, input.shape[3], input.dtype == torch.float32, what)
-    B, H, W, GH, GW, GD, Cin, Cout = _check_io(grid, input, has_offset, pixel_format)
-    if (Cin, Cout) != (3, 3) or not has_offset:
-        raise ValueError(f"{what}: the 3 -> 3 op with offset (a [.., 12] grid) only, got Cin = {Cin}, Cout = {Cout}, "
-                         f"has_offset = {bool(has_offset)}")
-    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), Cin)
-    _require_gpu("grid", grid)
-    _require_gpu("input", input)
-    grid, inp = grid.detach().contiguous(), input.detach().contiguous()
-    dev = inp.device
-    out = torch.empty((B, H, W, _lib.PIXEL_FORMAT_CHANNELS[pixel_format]), dtype=torch.uint16, device=dev)
-    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    frame = (inp.data_ptr(), out.data_ptr(), B, H, W, GH, GW, GD, Cin, Cout, 1,
-             _DTYPE_CODE[input.dtype], float(input_white_level), output_white_level)
-    code = _lib.PIXEL_FORMATS[pixel_format]
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        if curves:
-            rc = lib.hdrnet_bilateral_slice_apply_io_curves_px_u16(
-                grid.data_ptr(), *frame, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), code, code, _stream(dev))
-        else:
-            rc = lib.hdrnet_bilateral_slice_apply_io_px_u16(
-                grid.data_ptr(), _ptr(g[0]), *frame, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
-                _guide_flags(fast_sigmoid, prescaled and g[0] is None), code, code, _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOCurves" if curves else "BilateralSliceApplyIO")
-    return (out, gout) if return_guide else out
+    return _apply_io_frame(True, grid, input, guide, guide_conv1, guide_conv2, input_white_level, torch.uint16, has_offset,
+                           guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, pixel_format,
+                           output_white_level)
 
 
 # ---- semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h) ------------------------------------------------------------
@@ -1341,6 +1331,71 @@ def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor) -> torch
     return out
 
 
+def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
+                      return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits=None):
+    """The body of ``bilateral_slice_apply_io_yuv`` and ``bilateral_slice_apply_io_yuv_deep`` (``what``), once each has
+    checked the arguments that say what comes out.  ``surface_dtype``: None for an RGB frame of ``out_dtype``, uint8 for an
+    NV12 surface, uint16 for a P010 / P016 surface of ``out_bits`` from a uint16 surface."""
+    deep = surface_dtype == torch.uint16
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    if deep and y.dtype != torch.uint16:
+        raise TypeError(f"{what}: a P010 / P016 output needs a uint16 surface in, got {y.dtype} (no kernel goes from 8 to 16 "
+                        "bits)")
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    if deep:  # (names its encode constants before the grid; the NV12 output after it)
+        from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+    _require_f32("grid", grid)
+    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
+        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
+                         f"{tuple(grid.shape)}")
+    GH, GW, GD = grid.shape[1:4]
+    tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb)]
+    oy = ouv = None
+    if surface_dtype is not None:
+        if not deep:
+            from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+        tensors.append(("from_rgb", from_rgb))
+        if out_planes is not None:
+            oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
+            if (oB, oH, oW) != (B, H, W) or oy.dtype != surface_dtype:
+                raise ValueError(f"{what}: out_planes should be a {'uint16' if deep else 'uint8'} surface of {[B, H, W]}, got "
+                                 f"{oy.dtype} {[oB, oH, oW]}")
+            tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
+                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
+    for nm, t in tensors:
+        _require_gpu(nm, t)
+    dev = y.device
+    grid = grid.detach().contiguous()
+    k_in = to_rgb.detach().contiguous()
+    if surface_dtype is not None:
+        if oy is None:  # tight planes
+            size = _YUV_SAMPLE[surface_dtype]
+            oy = torch.empty((B, H, W), dtype=surface_dtype, device=dev)
+            ouv = torch.empty((B, H // 2, W), dtype=surface_dtype, device=dev)
+            osurf = (size, size * W, size * W, size * H * W, size * (H // 2) * W)
+        k_out = from_rgb.detach().contiguous()
+        planes = (oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr())
+        output = (*planes, int(out_bits)) if deep else (_lib.YUV_OUT["nv12"], *planes)
+        result = (oy, ouv)
+    else:
+        result = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
+        output = (_lib.YUV_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), None, 0, 0, 0, 0, None)
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    if curves:
+        fn = "hdrnet_bilateral_slice_apply_io_curves_yuv"
+        args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
+    else:
+        fn = "hdrnet_bilateral_slice_apply_io_yuv"
+        args = (grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None))
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), fn + ("_p016" if deep else ""))(*args, *output, _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOYuv")
+    return (result, gout) if return_guide else result
+
+
 def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
                                  guide: Optional[torch.Tensor] = None,
                                  guide_conv1: Optional[torch.Tensor] = None,
@@ -1375,55 +1430,9 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
             raise TypeError(f"{what}: an NV12 output is uint8, got out_dtype = {out_dtype}")
         if from_rgb is None:
             raise ValueError(f"{what}: out='nv12' needs from_rgb (yuv.yuv_coefficients)")
-    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
-    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
-    _require_f32("grid", grid)
-    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
-        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
-                         f"{tuple(grid.shape)}")
-    GH, GW, GD = grid.shape[1:4]
-    tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb)]
-    oy = ouv = None
-    if out == "nv12":
-        from_rgb = _yuv_constants("from_rgb", from_rgb, what)
-        tensors.append(("from_rgb", from_rgb))
-        if out_planes is not None:
-            oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
-            if (oB, oH, oW) != (B, H, W) or oy.dtype != torch.uint8:
-                raise ValueError(f"{what}: out_planes should be a uint8 surface of {[B, H, W]}, got {oy.dtype} {[oB, oH, oW]}")
-            tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
-    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
-                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
-    for nm, t in tensors:
-        _require_gpu(nm, t)
-    dev = y.device
-    lib = _lib.load()
-    grid = grid.detach().contiguous()
-    k_in = to_rgb.detach().contiguous()
-    if out == "nv12":
-        if oy is None:
-            oy = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-            ouv = torch.empty((B, H // 2, W), dtype=torch.uint8, device=dev)
-            osurf = (1, W, W, H * W, (H // 2) * W)
-        k_out = from_rgb.detach().contiguous()
-        output = (_lib.YUV_OUT["nv12"], oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr())
-        result = (oy, ouv)
-    else:
-        frame = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
-        output = (_lib.YUV_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], frame.data_ptr(), None, 0, 0, 0, 0, None)
-        result = frame
-    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
-    with torch.cuda.device(dev):
-        if curves:
-            rc = lib.hdrnet_bilateral_slice_apply_io_curves_yuv(
-                grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), *output, _stream(dev))
-        else:
-            rc = lib.hdrnet_bilateral_slice_apply_io_yuv(
-                grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
-                _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOYuv")
-    return (result, gout) if return_guide else result
+    return _apply_io_surface(what, None if out == "rgb" else torch.uint8, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1,
+                             guide_conv2, guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb,
+                             out_planes)
 
 
 def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
@@ -1449,49 +1458,8 @@ def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: t
         raise ValueError(f"{what}: needs from_rgb (yuv.yuv_encode_coefficients)")
     if out_bits not in (10, 16):
         raise ValueError(f"{what}: out_bits must be 10 (P010) or 16 (P016), got {out_bits!r}")
-    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
-    if y.dtype != torch.uint16:
-        raise TypeError(f"{what}: a P010 / P016 output needs a uint16 surface in, got {y.dtype} (no kernel goes from 8 to 16 "
-                        "bits)")
-    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
-    from_rgb = _yuv_constants("from_rgb", from_rgb, what)
-    _require_f32("grid", grid)
-    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
-        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
-                         f"{tuple(grid.shape)}")
-    GH, GW, GD = grid.shape[1:4]
-    tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb), ("from_rgb", from_rgb)]
-    oy = ouv = None
-    if out_planes is not None:
-        oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
-        if (oB, oH, oW) != (B, H, W) or oy.dtype != torch.uint16:
-            raise ValueError(f"{what}: out_planes should be a uint16 surface of {[B, H, W]}, got {oy.dtype} {[oB, oH, oW]}")
-        tensors += [("out_planes[0]", oy), ("out_planes[1]", ouv)]
-    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
-                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
-    for nm, t in tensors:
-        _require_gpu(nm, t)
-    dev = y.device
-    lib = _lib.load()
-    grid = grid.detach().contiguous()
-    k_in, k_out = to_rgb.detach().contiguous(), from_rgb.detach().contiguous()
-    if oy is None:
-        oy = torch.empty((B, H, W), dtype=torch.uint16, device=dev)
-        ouv = torch.empty((B, H // 2, W), dtype=torch.uint16, device=dev)
-        osurf = (2, 2 * W, 2 * W, 2 * H * W, 2 * (H // 2) * W)
-    output = (oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr(), int(out_bits))
-    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
-    with torch.cuda.device(dev):
-        if curves:
-            rc = lib.hdrnet_bilateral_slice_apply_io_curves_yuv_p016(
-                grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), *output, _stream(dev))
-        else:
-            rc = lib.hdrnet_bilateral_slice_apply_io_yuv_p016(
-                grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
-                _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOYuv")
-    return ((oy, ouv), gout) if return_guide else (oy, ouv)
+    return _apply_io_surface(what, torch.uint16, None, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
+                             return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits)
 
 
 def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002
