@@ -215,6 +215,21 @@ U16_OUT_SIGNATURES = {
                                                         [_I, _VP, _FP] + _P016_OUTPUT + [_VP]),
 }
 
+# include/hdrnet_amd_yuv_planar.h: planar YUV 4:2:0 surfaces (I420, yuv420p10le / yuv420p16le) through the same paths, a
+# planar surface out.  A surface travels as (y, u, v, sample_dtype, three pitches, three image strides); the output as
+# (output_kind, out, out_u, out_v, three pitches, three image strides, from_rgb, out_bits).
+_PLANAR_SURFACE = [_FP, _FP, _FP, _I, _I, _I, _I, _LL, _LL, _LL]
+YUV_PLANAR_OUT = {"rgb_f32": 0, "rgb_u8": 1, "planar": 2}  # HDRNET_YUV_PLANAR_OUT_*
+_PLANAR_OUTPUT = [_I, _FP, _FP, _FP, _I, _I, _I, _LL, _LL, _LL, _FP, _I]
+YUV_PLANAR_SIGNATURES = {
+    "hdrnet_yuv_planar_to_rgb_f32": (_I, _PLANAR_SURFACE + [_I] * 3 + [_FP, _FP, _VP]),
+    "hdrnet_lowres_input_yuv_planar": (_I, _PLANAR_SURFACE + [_I] * 3 + [_FP, _FP, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv_planar": (_I, [_FP, _FP] + _PLANAR_SURFACE + [_I] * 3 + [_FP] + [_I] * 6 +
+                                                   [_FP, _FP, _I, _FP, _U] + _PLANAR_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv_planar": (_I, [_FP] + _PLANAR_SURFACE + [_I] * 3 + [_FP] + [_I] * 6 +
+                                                          [_FP] * 4 + [_I, _VP, _FP] + _PLANAR_OUTPUT + [_VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -270,6 +285,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(PIXEL_FORMAT_SIGNATURES)
     table.update(YUV_SIGNATURES)
     table.update(U16_OUT_SIGNATURES)
+    table.update(YUV_PLANAR_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

@@ -12,10 +12,11 @@ bool apply_fwd_io_supported(const ApplyIoArgs& a) {
 }
 
 // The kernel family of a call, chosen HERE and nowhere else: the 16-bit output's (a.output_dtype == 2), else the pixel
-// source's (a.yuv, or `coarse` for the pyramid's up-add).
+// source's (a.yuv, a.yuvp, or `coarse` for the pyramid's up-add).
 namespace {
-enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd };
+enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd, kFamilyYuvPlanar };
 IoFamily io_family(const ApplyIoArgs& a, const float* coarse) {
+  if (a.yuvp) return kFamilyYuvPlanar;  // (a planar surface carries its own output kinds, the 16-bit one among them)
   return a.output_dtype == 2 && !coarse ? kFamilyU16 : a.yuv ? kFamilyYuv : coarse ? kFamilyUpAdd : kFamilyFrame;
 }
 }  // namespace
@@ -24,6 +25,7 @@ bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse) {
   switch (io_family(a, coarse)) {
     case kFamilyU16: return apply_fwd_io_u16_supported(a);
     case kFamilyYuv: return apply_fwd_io_yuv_supported(a);
+    case kFamilyYuvPlanar: return !coarse && apply_fwd_io_yuv_planar_supported(a);
     case kFamilyUpAdd: return apply_fwd_io_upadd_supported(a, coarse);
     default: return apply_fwd_io_supported(a);
   }
@@ -34,6 +36,7 @@ hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse,
   switch (io_family(a, coarse)) {
     case kFamilyU16: return launch_apply_fwd_io_u16(a, s, name);
     case kFamilyYuv: return launch_apply_fwd_io_yuv(a, s, name);
+    case kFamilyYuvPlanar: return launch_apply_fwd_io_yuv_planar(a, s, name);
     case kFamilyUpAdd: return launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, name);
     default: return launch_apply_fwd_io(a, s, name);
   }

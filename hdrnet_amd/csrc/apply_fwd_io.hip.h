@@ -28,7 +28,12 @@
 // This header holds the kernel, its launch and what the front ends share (label, guide-form dispatch, common predicate
 // rules); the RGB instantiations are compiled by apply_fwd_io.hip, those of the
 // other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many), those of the YUV
-// surfaces by apply_fwd_io_yuv.hip.
+// surfaces by apply_fwd_io_yuv.hip, those of the planar surfaces by apply_fwd_io_yuv_planar.hip.
+//
+// PLANAR SURFACES (include/hdrnet_amd_yuv_planar.h): I420 / yuv420p10le / yuv420p16le, three planes each way.  PX =
+// kPxYuvPlanar is the surface load with one narrower access into each of the U and V planes in place of the interleaved
+// one (yuv_convert.hip.h), and OUT = kOutI420 / kOutI016 the row-pair store above with the chroma code words split the
+// same way; everything between load and store is the semi-planar instantiation's, so the two give the same bits.
 //
 // 16-BIT OUTPUT (include/hdrnet_amd_u16_out.h): TO = uint16_t stores a uint16 frame, (uint16)(out_white * clip(v, 0, 1)) in
 // the input's pixel format -- the uint8 store's rule with 255 replaced by a run-time constant -- and OUT = kOutP016 a
@@ -71,9 +76,12 @@ constexpr int kGuideCurvesCells = 4;  // the curves guide from the PREPARED unif
 
 // PX beyond the packed formats of white_level.hip.h: the frame is a YUV surface (IoParams::yin); the op still sees R, G, B
 constexpr int kPxYuv = 4;
+constexpr int kPxYuvPlanar = 5;  // ... or a PLANAR one (IoParams::pin): the same samples, chroma in two planes
 // what the kernel stores: a frame of TO in the input's packed format / RGB -- or an NV12 surface (IoParams::yout)
 // ... or a P010 / P016 surface (uint16 code words of IoParams::code_shift's depth in the high bits)
 constexpr int kOutFrame = 0, kOutNV12 = 1, kOutP016 = 2;
+// ... or a planar surface (IoParams::pout): I420 (uint8 code words) / uint16 code words in the LOW bits (code_shift = 0)
+constexpr int kOutI420 = 3, kOutI016 = 4;
 
 struct GuideNet {
   const float* conv1;  // NN: [n][CIN + 1]            curves: ccm [CIN][CIN + 1] (row = output channel)
@@ -435,6 +443,9 @@ struct IoParams {
   float out_white;  // a uint16 frame: (uint16)(out_white * clip(v, 0, 1))
   float code_max;   // a P010 / P016 surface: 2^out_bits - 1 ...
   int code_shift;   // ... and 16 - out_bits
+  // planar surfaces (PX == kPxYuvPlanar / OUT == kOutI420, kOutI016; read by no other instantiation): to_rgb / from_rgb and,
+  // for uint16 code words, code_max are the fields above; code_shift is 0
+  YuvPlanarSurface pin, pout;
 };
 
 // Geometry, LDS image and pixel core are apply_fwd_seg.hip's (seg_common.hip.h): a workgroup owns a row
@@ -442,12 +453,17 @@ struct IoParams {
 template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
 __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   static_assert(PX == kPxRGB || (CIN == 3 && COUT == 3 && sizeof(TI) < 4), "pixel formats: integer frames, 3 -> 3");
-  constexpr bool YUV = PX == kPxYuv;          // the input is a YUV surface; the frame the kernel stores is RGB
+  constexpr bool PLANAR = PX == kPxYuvPlanar;  // the input is a planar YUV surface: three planes
+  constexpr bool YUV = PX == kPxYuv || PLANAR;  // the input is a YUV surface; the frame the kernel stores is RGB
   constexpr bool NV12OUT = OUT == kOutNV12;   // ... unless the output is an NV12 surface: a workgroup owns a row pair
   static_assert(!NV12OUT || (YUV && sizeof(TO) == 1), "NV12 out: uint8 planes, from a YUV surface");
   constexpr bool P016OUT = OUT == kOutP016;   // ... or a P010 / P016 surface: the same row pair, uint16 code words
   static_assert(!P016OUT || (YUV && sizeof(TI) == 2 && sizeof(TO) == 2), "P010 / P016 out: uint16 planes, from a uint16 surface");
-  constexpr bool SURFOUT = NV12OUT || P016OUT;
+  constexpr bool I420OUT = OUT == kOutI420, I016OUT = OUT == kOutI016;  // ... or a planar one, of the input's sample width
+  static_assert(!I420OUT || (PLANAR && sizeof(TI) == 1 && sizeof(TO) == 1), "I420 out: uint8 planes, from a uint8 planar surface");
+  static_assert(!I016OUT || (PLANAR && sizeof(TI) == 2 && sizeof(TO) == 2), "uint16 planar out: from a uint16 planar surface");
+  constexpr bool PLANAROUT = I420OUT || I016OUT;
+  constexpr bool SURFOUT = NV12OUT || P016OUT || PLANAROUT;
   constexpr bool PACKED = PX != kPxRGB && !YUV;  // BGR / RGBA / BGRA
   constexpr int SPX = PACKED ? px_stored(PX) : CIN;  // samples per stored pixel of the frame
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
@@ -506,7 +522,8 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
         const float4 g4 = *reinterpret_cast<const float4*>(p.guide + px);
         gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
       }
-      if constexpr (YUV) yuv_load_quad<TI>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      if constexpr (PLANAR) yuv_load_quad<TI>(p.pin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      else if constexpr (YUV) yuv_load_quad<TI>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
       else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
     }
 
@@ -589,9 +606,28 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
         }
         char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y +
                    (size_t)x * sizeof(TO);
+        if constexpr (PLANAROUT)  // (the Y plane of the planar surface; the store itself is the same)
+          yo = static_cast<char*>(const_cast<void*>(p.pout.y)) + (long long)b * p.pout.image_y + (long long)y * p.pout.pitch_y +
+               (size_t)x * sizeof(TO);
 #pragma unroll
         for (int q = 0; q < S; ++q) reinterpret_cast<uint32_t*>(yo)[q] = wy[q];  // (dwords: the planes promise 4-byte alignment, not 8)
-        if (r == ROWS - 1) {
+        if constexpr (PLANAROUT) {
+          // A planar surface: the lane's two U code words into the pair's U row and its two V code words into the V row, at
+          // sample x / 2 of each -- one 16-bit store each for uint8 code words, one dword each for uint16 (the chroma planes
+          // promise 2- / 4-byte alignment).
+          if (r == ROWS - 1) {
+            typedef std::conditional_t<S == 1, uint16_t, uint32_t> TW;  // two code words
+            const size_t xc = (size_t)(x >> 1) * sizeof(TO);
+            char* uo = static_cast<char*>(const_cast<void*>(p.pout.u)) + (long long)b * p.pout.image_u +
+                       (long long)(y >> 1) * p.pout.pitch_u + xc;
+            char* vo = static_cast<char*>(const_cast<void*>(p.pout.v)) + (long long)b * p.pout.image_v +
+                       (long long)(y >> 1) * p.pout.pitch_v + xc;
+            const uint32_t wu = yuv_chroma_code(fk, 1, csum[0][0], cmax, sh) | (yuv_chroma_code(fk, 1, csum[1][0], cmax, sh) << (8 * S));
+            const uint32_t wv = yuv_chroma_code(fk, 2, csum[0][1], cmax, sh) | (yuv_chroma_code(fk, 2, csum[1][1], cmax, sh) << (8 * S));
+            *reinterpret_cast<TW*>(uo) = (TW)wu;
+            *reinterpret_cast<TW*>(vo) = (TW)wv;
+          }
+        } else if (r == ROWS - 1) {
           char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
                      (long long)(y >> 1) * p.yout.pitch_uv + (size_t)x * sizeof(TO);
           [[maybe_unused]] uint32_t wc = 0;
@@ -698,6 +734,14 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   p.out_white = a.output_white_level;
   p.code_max = 0.0f;
   p.code_shift = 0;
+  p.pin = p.pout = YuvPlanarSurface{};
+  if constexpr (PX == kPxYuvPlanar) {
+    p.pin = a.yuvp->in;
+    p.to_rgb = a.yuvp->to_rgb;
+    p.pout = a.yuvp->out;
+    p.from_rgb = a.yuvp->from_rgb;
+    if constexpr (OUT == kOutI016) p.code_max = (float)((1 << a.yuvp->out_bits) - 1);  // code_shift stays 0: low bits
+  }
   if constexpr (PX == kPxYuv) {
     p.yin = a.yuv->in;
     p.to_rgb = a.yuv->to_rgb;
@@ -767,7 +811,11 @@ inline const char* io_label(const ApplyIoArgs& a) {
   static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
   static const char* const px[4] = {"", "/bgr", "/rgba", "/bgra"};
   static thread_local char label[64];
-  if (a.yuv)
+  if (a.yuvp) {  // a planar surface: the label states the sample WIDTH (i420 uint8, i016 uint16), as p016 does
+    const char* const in = a.input_dtype == 1 ? "i420" : "i016";
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", in,
+             a.yuvp->out_kind == kYuvPlanarOutPlanar ? in : surface[a.yuvp->out_kind], suffix[io_guide_form(a)]);
+  } else if (a.yuv)
     snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", a.input_dtype == 1 ? "nv12" : "p016", surface[a.yuv->out_kind],
              suffix[io_guide_form(a)]);
   else
@@ -799,5 +847,6 @@ inline bool io_surface_ok(const ApplyIoArgs& a) {
 hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
 // apply_fwd_io_yuv.hip (launch.hip.h): the same launch for a YUV surface (a.yuv)
 // apply_fwd_io_u16.hip (launch.hip.h): the same launch with a 16-bit output (a.output_dtype == 2)
+// apply_fwd_io_yuv_planar.hip (launch.hip.h): the same launch for a planar YUV surface (a.yuvp)
 
 }  // namespace hdrnet_amd

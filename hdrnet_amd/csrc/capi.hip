@@ -13,6 +13,7 @@
 #include "../../include/hdrnet_amd.h"
 #include "../../include/hdrnet_amd_pixel_formats.h"
 #include "../../include/hdrnet_amd_yuv.h"
+#include "../../include/hdrnet_amd_yuv_planar.h"
 #include "../../include/hdrnet_amd_u16_out.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
@@ -327,6 +328,70 @@ int check_yuv_io_pointers(const char* what, const hdrnet_amd::YuvIo& io) {
   return HDRNET_OK;
 }
 
+// Pixel side, a PLANAR YUV 4:2:0 surface (include/hdrnet_amd_yuv_planar.h): the extents are check_yuv_extents'; each rule of
+// a surface is stated once below and shared by the four entry points (`which`: "input" / "output").
+int check_yuv_planar_surface(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvPlanarSurface& s, int B,
+                             int H, int W) {
+  if (sample_dtype != 1 && sample_dtype != 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
+                sample_dtype);
+  const long long row = (long long)W * sample_dtype, crow = row / 2;
+  if (s.pitch_y < row || s.pitch_u < crow || s.pitch_v < crow)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a pitch of the %s surface is below the row's bytes (%lld luma, %lld chroma; "
+                "pitch_y=%d, pitch_u=%d, pitch_v=%d)", what, which, row, crow, s.pitch_y, s.pitch_u, s.pitch_v);
+  // a lane touches 4 luma samples (dwords) and 2 samples of each chroma plane: 2 bytes of uint8, 4 of uint16
+  const int cmask = sample_dtype == 1 ? 1 : 3;
+  if ((s.pitch_y & 3) || ((s.pitch_u | s.pitch_v) & cmask))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitches of the %s surface must be multiples of 4 (luma) and of %d (%s chroma) "
+                "(pitch_y=%d, pitch_u=%d, pitch_v=%d)", what, which, cmask + 1, sample_dtype == 1 ? "uint8" : "uint16", s.pitch_y,
+                s.pitch_u, s.pitch_v);
+  if (s.image_y < 0 || s.image_u < 0 || s.image_v < 0 || (s.image_y & 3) || ((s.image_u | s.image_v) & cmask))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4 (luma) and "
+                "of %d (%s chroma)", what, which, cmask + 1, sample_dtype == 1 ? "uint8" : "uint16");
+  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_u < (long long)s.pitch_u * (H / 2) ||
+                s.image_v < (long long)s.pitch_v * (H / 2)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
+  return HDRNET_OK;
+}
+
+int check_yuv_planar_pointers(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvPlanarSurface& s,
+                              const float* coef) {
+  if (!s.y || !s.u || !s.v) return fail(HDRNET_INVALID_ARGUMENT, "%s: null plane of the %s surface", what, which);
+  if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
+  if (((uintptr_t)s.y | (uintptr_t)coef) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the Y plane and constants of the %s surface must be 4-B aligned", what, which);
+  if (((uintptr_t)s.u | (uintptr_t)s.v) & (sample_dtype == 1 ? 1u : 3u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the chroma planes of the %s surface must be %d-B aligned (%s samples: a lane "
+                "touches 2 of them)", what, which, sample_dtype == 1 ? 2 : 4, sample_dtype == 1 ? "uint8" : "uint16");
+  return HDRNET_OK;
+}
+
+// ... and of a fused forward's surfaces and output.  io.out.y is `out` whatever the output kind.
+int check_yuv_planar_io_values(const char* what, const hdrnet_amd::YuvPlanarIo& io, int sample_dtype, int B, int H, int W,
+                               int Cin, int Cout, int has_offset) {
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
+  if (io.out_kind < HDRNET_YUV_PLANAR_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_PLANAR_OUT_PLANAR)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 a planar surface of the "
+                "input's sample dtype)", what, io.out_kind);
+  if (Cin != 3 || Cout != 3 || !has_offset)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
+  if (io.out_kind != HDRNET_YUV_PLANAR_OUT_PLANAR) return HDRNET_OK;
+  if (sample_dtype == 1 ? io.out_bits != 8 : (io.out_bits != 10 && io.out_bits != 16))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits does not fit the sample dtype: a planar output has the input's (uint8 "
+                "samples: 8; uint16 samples: 10 or 16; got out_bits = %d for sample_dtype %d)", what, io.out_bits, sample_dtype);
+  return check_yuv_planar_surface(what, "output", sample_dtype, io.out, B, H, W);
+}
+
+int check_yuv_planar_io_pointers(const char* what, const hdrnet_amd::YuvPlanarIo& io, int sample_dtype) {
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, io.in, io.to_rgb)) return rc;
+  if (io.out_kind == HDRNET_YUV_PLANAR_OUT_PLANAR)
+    return check_yuv_planar_pointers(what, "output", sample_dtype, io.out, io.from_rgb);
+  if (!io.out.y || ((uintptr_t)io.out.y & (io.out_kind == HDRNET_YUV_PLANAR_OUT_RGB_F32 ? 15u : 3u)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
+  return HDRNET_OK;
+}
+
 // Guide side, a map or the network.  Here the map wins over a network given beside it (the up-add entry points refuse
 // that: check_upadd_values), so with a map there is nothing to prescale: the refusal's Cin is then 0.
 int check_guide_given(const char* prefix, const float* guide, const float* conv1, const float* conv2, int n_feats) {
@@ -517,7 +582,10 @@ extern "C" {
 //          hdrnet_bilateral_slice_apply_io_curves_px (uint8 / uint16 frames in BGR, RGBA and BGRA order)
 // 0.2.8.7: + include/hdrnet_amd_yuv.h: hdrnet_yuv_to_rgb_f32, hdrnet_lowres_input_yuv, hdrnet_bilateral_slice_apply_io_yuv,
 //          hdrnet_bilateral_slice_apply_io_curves_yuv (NV12 / P010 / P016 surfaces in, RGB or NV12 out)
-int hdrnet_version(void) { return 288; }
+// 0.2.8.9: + include/hdrnet_amd_yuv_planar.h: hdrnet_yuv_planar_to_rgb_f32, hdrnet_lowres_input_yuv_planar,
+//          hdrnet_bilateral_slice_apply_io_yuv_planar, hdrnet_bilateral_slice_apply_io_curves_yuv_planar (I420 / yuv420p10le /
+//          yuv420p16le surfaces in, RGB or a planar surface out)
+int hdrnet_version(void) { return 289; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -1376,6 +1444,100 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv_p016(const float* grid, const voi
                            sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
+// ---- include/hdrnet_amd_yuv_planar.h: planar YUV 4:2:0 surfaces (hdrnet_lowres_input_yuv_planar: sample preparation, below)
+int hdrnet_yuv_planar_to_rgb_f32(const void* y, const void* u, const void* v, int sample_dtype, int pitch_y, int pitch_u,
+                                 int pitch_v, long long image_stride_y, long long image_stride_u,
+                                 long long image_stride_v, int B, int H, int W, const float* to_rgb, float* rgb,
+                                 void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_yuv_planar_to_rgb_f32";
+  const YuvPlanarSurface in{y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, in, to_rgb)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
+  return finish_launch(launch_yuv_planar_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, static_cast<hipStream_t>(stream)), what,
+                       "yuv_planar_to_rgb");
+}
+
+// The two fused entry points (`what`): a planar surface in with either guide; `io`: the call's surfaces as given, io.out.y
+// the RGB frame where the output is one.  apply_io_yuv_impl's checks in its order.
+static int apply_io_yuv_planar_impl(const char* what, const float* grid, const IoGuide& g, hdrnet_amd::YuvPlanarIo io,
+                                    int sample_dtype, int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout,
+                                    int has_offset, void* stream) {
+  using namespace hdrnet_amd;
+  char prefix[96];
+  snprintf(prefix, sizeof prefix, "%s: ", what);
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = g.curves ? check_curves_knots(prefix, g.n) : check_guide_flags(g.flags)) return rc;
+  if (int rc = check_yuv_planar_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_planar_io_pointers(what, io, sample_dtype)) return rc;
+  if (g.curves) {
+    if (!grid || !g.conv1 || !g.shifts || !g.slopes || !g.conv2)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
+  } else {
+    if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
+    if (int rc = check_guide_given(prefix, g.guide, g.conv1, g.conv2, g.n)) return rc;
+  }
+  const bool planar_out = io.out_kind == HDRNET_YUV_PLANAR_OUT_PLANAR;
+  ApplyIoArgs a{grid, g.guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, planar_out ? sample_dtype : io.out_kind == HDRNET_YUV_PLANAR_OUT_RGB_F32 ? 0 : 1, 1.0f, g.conv1,
+                g.conv2, g.n, g.guide_out, g.shifts, g.slopes};
+  if (int rc = set_io_guide(a, g, prefix, "npts <= 16")) return rc;
+  if (!planar_out) {  // an RGB frame out: a.out
+    a.out = const_cast<void*>(io.out.y);
+    io.out = YuvPlanarSurface{};
+    io.from_rgb = nullptr;
+    io.out_bits = 0;
+  }
+  a.yuvp = &io;
+  return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuvPlanar" : "BilateralSliceApplyIOYuvPlanar",
+                   "the planar YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers", stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv_planar(const float* grid, const float* guide, const void* y, const void* u,
+                                               const void* v, int sample_dtype, int pitch_y, int pitch_u, int pitch_v,
+                                               long long image_stride_y, long long image_stride_u,
+                                               long long image_stride_v, int B, int H, int W, const float* to_rgb, int GH,
+                                               int GW, int GD, int Cin, int Cout, int has_offset,
+                                               const float* guide_conv1, const float* guide_conv2, int n_feats,
+                                               float* guide_out, unsigned flags, int output_kind, void* out, void* out_u,
+                                               void* out_v, int out_pitch_y, int out_pitch_u, int out_pitch_v,
+                                               long long out_image_stride_y, long long out_image_stride_u,
+                                               long long out_image_stride_v, const float* from_rgb, int out_bits,
+                                               void* stream) {
+  const hdrnet_amd::YuvPlanarIo io{
+      {y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v}, to_rgb, output_kind,
+      {out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v, out_image_stride_y, out_image_stride_u, out_image_stride_v},
+      from_rgb, out_bits};
+  return apply_io_yuv_planar_impl("hdrnet_bilateral_slice_apply_io_yuv_planar", grid,
+                                  io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io, sample_dtype,
+                                  B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv_planar(const float* grid, const void* y, const void* u, const void* v,
+                                                      int sample_dtype, int pitch_y, int pitch_u, int pitch_v,
+                                                      long long image_stride_y, long long image_stride_u,
+                                                      long long image_stride_v, int B, int H, int W, const float* to_rgb,
+                                                      int GH, int GW, int GD, int Cin, int Cout, int has_offset,
+                                                      const float* guide_ccm, const float* guide_shifts,
+                                                      const float* guide_slopes, const float* guide_mix, int npts,
+                                                      const void* prepared, float* guide_out, int output_kind, void* out,
+                                                      void* out_u, void* out_v, int out_pitch_y, int out_pitch_u,
+                                                      int out_pitch_v, long long out_image_stride_y,
+                                                      long long out_image_stride_u, long long out_image_stride_v,
+                                                      const float* from_rgb, int out_bits, void* stream) {
+  const hdrnet_amd::YuvPlanarIo io{
+      {y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v}, to_rgb, output_kind,
+      {out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v, out_image_stride_y, out_image_stride_u, out_image_stride_v},
+      from_rgb, out_bits};
+  return apply_io_yuv_planar_impl("hdrnet_bilateral_slice_apply_io_curves_yuv_planar", grid,
+                                  io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
+                                  io, sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
 // ---- include/hdrnet_amd_pyramid_io.h: the pyramid model's wire formats ---------------------------------------------
 int hdrnet_resize_bilinear_io(const void* input, int input_dtype, float white_level, float* out, int B, int Hin, int Win,
                               int Hout, int Wout, int C, void* stream) {
@@ -1546,6 +1708,27 @@ int hdrnet_lowres_input_yuv(const void* y, const void* uv, int sample_dtype, int
   SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
                    false};
   a.yuv = &in;
+  a.yuv_to_rgb = to_rgb;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+int hdrnet_lowres_input_yuv_planar(const void* y, const void* u, const void* v, int sample_dtype, int pitch_y, int pitch_u,
+                                   int pitch_v, long long image_stride_y, long long image_stride_u,
+                                   long long image_stride_v, int B, int H, int W, const float* to_rgb, float* lowres,
+                                   int net_input_size, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_lowres_input_yuv_planar";
+  const YuvPlanarSurface in{y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, in, to_rgb)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
+                   false};
+  a.yuv_planar = &in;
   a.yuv_to_rgb = to_rgb;
   return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
 }

@@ -61,6 +61,10 @@ struct ApplyIoArgs {
   // surface's sample dtype (1 u8 = NV12, 2 u16 = P010 / P016), `input` is unused, and `out` is the RGB frame of
   // output_dtype -- or, with yuv->out_kind == HDRNET_YUV_OUT_NV12 (output_dtype = 1), unused too
   const struct YuvIo* yuv = nullptr;
+  // ... or a PLANAR one (include/hdrnet_amd_yuv_planar.h; apply_fwd_io_yuv_planar.hip): input_dtype is the sample dtype
+  // (1 u8 = I420, 2 u16), `out` the RGB frame of output_dtype -- or, with yuvp->out_kind == kYuvPlanarOutPlanar
+  // (output_dtype = input_dtype), unused
+  const struct YuvPlanarIo* yuvp = nullptr;
   // output_dtype == 2 (include/hdrnet_amd_u16_out.h): the white level of the uint16 frame, which has the input's pixel format
   float output_white_level = 0.0f;
 };
@@ -76,6 +80,19 @@ struct YuvIo {
   YuvSurface out;         // out_kind == HDRNET_YUV_OUT_NV12 / kYuvOutP016
   const float* from_rgb;  // device, 12 floats
   int out_bits = 0;       // kYuvOutP016: 10 or 16 significant bits per sample, in the high bits
+};
+
+// The planar counterpart (include/hdrnet_amd_yuv_planar.h): out_kind is HDRNET_YUV_PLANAR_OUT_* -- a float32 / uint8 RGB
+// frame, or a planar surface of the input's sample dtype
+constexpr int kYuvPlanarOutPlanar = 2;
+
+struct YuvPlanarIo {
+  YuvPlanarSurface in;
+  const float* to_rgb;    // device, 12 floats
+  int out_kind;           // HDRNET_YUV_PLANAR_OUT_*
+  YuvPlanarSurface out;   // out_kind == kYuvPlanarOutPlanar
+  const float* from_rgb;  // device, 12 floats
+  int out_bits = 0;       // kYuvPlanarOutPlanar: 8 (uint8 samples), 10 or 16 (uint16): the code's bits, in the LOW bits
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -245,6 +262,8 @@ struct SamplePrepArgs {
   // the low-res gather of a YUV surface (hdrnet_lowres_input_yuv): src_input is unused, input_dtype the sample dtype
   const YuvSurface* yuv = nullptr;
   const float* yuv_to_rgb = nullptr;
+  // ... or of a planar one (hdrnet_lowres_input_yuv_planar): yuv_to_rgb as above
+  const YuvPlanarSurface* yuv_planar = nullptr;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 
@@ -256,6 +275,12 @@ bool apply_fwd_io_yuv_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io_yuv(const ApplyIoArgs& a, hipStream_t s, const char** name);
 hipError_t launch_yuv_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,
                              hipStream_t s);
+// apply_fwd_io_yuv_planar.hip -- the same forward reading a PLANAR YUV surface (a.yuvp), and its surface -> float32 RGB
+// conversion
+bool apply_fwd_io_yuv_planar_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_yuv_planar(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_yuv_planar_to_rgb(const YuvPlanarSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H,
+                                    int W, hipStream_t s);
 // apply_fwd_io_u16.hip -- the same forward with a 16-bit output (a.output_dtype == 2): a uint16 frame in the input's pixel
 // format, or (a.yuv, out_kind == kYuvOutP016) a P010 / P016 surface
 bool apply_fwd_io_u16_supported(const ApplyIoArgs& a);

@@ -60,7 +60,8 @@ struct PrepJob {
   float* dst;
   WhiteLevel white;
   int dtype;   // 0 f32 (copied unscaled), 1 u8, 2 u16
-  int lowres;  // 0: [B][H][W][3];  1: [B][n][n][3];  2: [B][n][n][3] gathered from a YUV surface (PrepParams::yuv)
+  int lowres;  // 0: [B][H][W][3];  1: [B][n][n][3];  2: [B][n][n][3] gathered from a YUV surface (PrepParams::yuv);
+               // 3: ... from a planar YUV surface (PrepParams::yuv_planar)
 };
 
 struct PrepParams {
@@ -79,6 +80,8 @@ struct PrepParams {
   // of yuv_convert.hip.h; the job's dtype is the sample dtype
   YuvSurface yuv;
   const float* yuv_to_rgb;
+  // ... of a planar one (hdrnet_lowres_input_yuv_planar, job kind 3): three planes, the same constants
+  YuvPlanarSurface yuv_planar;
 };
 
 typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
@@ -344,8 +347,9 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
 // The same gather from a YUV surface: output sample (yl, xl) takes the source pixel lowres_job takes (identity geometry:
 // hdrnet_lowres_input's), its luma from (y, x) and its chroma from (y >> 1, x >> 1), converted by yuv_to_rgb_px -- the
 // bits of lowres_job on the float32 frame hdrnet_yuv_to_rgb_f32 writes.
-template <typename T>
-__device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const PrepJob& job, int b) {
+// (`surf`: p.yuv, or p.yuv_planar for a planar surface -- the chroma then comes from two planes)
+template <typename T, typename SURF>
+__device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const SURF& surf, const PrepJob& job, int b) {
   const int npx = p.n * p.n;
   float* out = job.dst + (long long)b * npx * 3;
   const bool vec = (npx & 3) == 0;
@@ -359,7 +363,7 @@ __device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const PrepJo
       int y = (int)__builtin_floorf((float)yl * p.scale_y), x = (int)__builtin_floorf((float)xl * p.scale_x);
       y = y < p.H - 1 ? y : p.H - 1;
       x = x < p.W - 1 ? x : p.W - 1;
-      yuv_load_px<T>(p.yuv, k, b, y, x, v[j]);
+      yuv_load_px<T>(surf, k, b, y, x, v[j]);
     }
     store_lowres_4px(out, px0, npx, vec, v);
   }
@@ -370,10 +374,15 @@ __global__ __launch_bounds__(kThreads) void sample_prep_kernel(const PrepParams 
   __shared__ __attribute__((aligned(16))) float tile[kTileH * kPitch];
   const PrepJob& job = p.job[blockIdx.z];
   const int b = blockIdx.y;
-  if (job.lowres == 2) {  // a YUV surface: no geometry record, no packed source
+  if (job.lowres >= 2) {  // a YUV surface, semi-planar (2) or planar (3): no geometry record, no packed source
     if constexpr (!RAGGED) {
-      if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, job, b);
-      else lowres_job_yuv<uint16_t>(p, job, b);
+      if (job.lowres == 2) {
+        if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, p.yuv, job, b);
+        else lowres_job_yuv<uint16_t>(p, p.yuv, job, b);
+      } else {
+        if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, p.yuv_planar, job, b);
+        else lowres_job_yuv<uint16_t>(p, p.yuv_planar, job, b);
+      }
     }
     return;
   }
@@ -399,7 +408,7 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   if (a.image_input) { p.job[nj++] = PrepJob{a.src_input, a.image_input, io_white_level(a.input_white_level), a.input_dtype, 0}; full = true; }
   if (a.image_target) { p.job[nj++] = PrepJob{a.src_target, a.image_target, io_white_level(a.target_white_level), a.target_dtype, 0}; full = true; }
   if (a.lowres_input)
-    p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype, a.yuv ? 2 : 1};
+    p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype, a.yuv_planar ? 3 : a.yuv ? 2 : 1};
   if (nj == 0 || a.B == 0) return hipSuccess;
   p.ops = a.ops;
   p.N = a.N; p.Hs = a.Hs; p.Ws = a.Ws; p.B = a.B; p.H = a.H; p.W = a.W; p.n = a.n;
@@ -414,6 +423,10 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.px_b_first = px_b_first(a.pixel_format) ? 1 : 0;
   if (a.yuv) {
     p.yuv = *a.yuv;
+    p.yuv_to_rgb = a.yuv_to_rgb;
+  }
+  if (a.yuv_planar) {
+    p.yuv_planar = *a.yuv_planar;
     p.yuv_to_rgb = a.yuv_to_rgb;
   }
   const long long low_blocks = ((long long)a.n * a.n + 4 * kThreads - 1) / (4 * kThreads);

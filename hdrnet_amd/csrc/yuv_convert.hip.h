@@ -1,5 +1,6 @@
 // Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out -- and
-// P010 / P016 out (include/hdrnet_amd_u16_out.h).
+// P010 / P016 out (include/hdrnet_amd_u16_out.h) -- and planar surfaces, I420 / yuv420p10le / yuv420p16le, in and out
+// (include/hdrnet_amd_yuv_planar.h): the same functions with the chroma in two planes.
 //
 // Every kernel that reads a surface -- hdrnet_yuv_to_rgb_f32 (apply_fwd_io_yuv.hip), the low-res gather
 // (sample_prep.hip) and the fused forward (apply_fwd_io.hip.h) -- converts a pixel with the ONE function below, and the
@@ -89,6 +90,63 @@ __device__ __forceinline__ void yuv_load_px(const YuvSurface& s, const YuvMatrix
                                              (long long)(row >> 1) * s.pitch_uv);
   const int xc = (x >> 1) * 2;
   yuv_to_rgb_px(k, (float)yp[x], (float)cp[xc], (float)cp[xc + 1], rgb);
+}
+
+// ---- planar 4:2:0 surfaces (include/hdrnet_amd_yuv_planar.h): I420 (uint8) and yuv420p10le / yuv420p16le (uint16) -----------
+// Three planes of a batch, each with its own bytes per row and bytes between images: y [B][H][W], u and v [B][H/2][W/2].
+// (YV12: the caller passes the planes in the other order.)  Padding is never read and never written.
+struct YuvPlanarSurface {
+  const void* y;
+  const void* u;
+  const void* v;
+  int pitch_y, pitch_u, pitch_v;
+  long long image_y, image_u, image_v;
+};
+
+// The planar counterpart of yuv_load_quad: the lane's two chroma samples (x >> 1) and (x >> 1) + 1 of chroma row
+// (row >> 1) are one 16-bit load from each of U and V for uint8 samples (the chroma planes promise 2-byte alignment, and
+// x / 2 is even), one dword from each for uint16 (4-byte alignment); the luma is yuv_load_quad's.  The same
+// yuv_to_rgb_px on the same samples: the bits of yuv_load_quad on the interleaved surface.
+template <typename TI>
+__device__ __forceinline__ void yuv_load_quad(const YuvPlanarSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                              float* __restrict__ rgb) {
+  static_assert(sizeof(TI) == 1 || sizeof(TI) == 2, "uint8 or uint16 samples");
+  const char* yp = static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y + (size_t)x * sizeof(TI);
+  const size_t xc = (size_t)(x >> 1) * sizeof(TI);
+  const char* up = static_cast<const char*>(s.u) + (long long)b * s.image_u + (long long)(row >> 1) * s.pitch_u + xc;
+  const char* vp = static_cast<const char*>(s.v) + (long long)b * s.image_v + (long long)(row >> 1) * s.pitch_v + xc;
+  float Y[4], U[2], V[2];
+  if constexpr (sizeof(TI) == 1) {
+    const uint32_t wy = *reinterpret_cast<const uint32_t*>(yp);
+    const uint32_t wu = *reinterpret_cast<const uint16_t*>(up);
+    const uint32_t wv = *reinterpret_cast<const uint16_t*>(vp);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Y[q] = (float)((wy >> (8 * q)) & 0xffu);
+    U[0] = (float)(wu & 0xffu); U[1] = (float)(wu >> 8);
+    V[0] = (float)(wv & 0xffu); V[1] = (float)(wv >> 8);
+  } else {
+    const uint2 wy = make_uint2(reinterpret_cast<const uint32_t*>(yp)[0], reinterpret_cast<const uint32_t*>(yp)[1]);
+    const uint32_t wu = *reinterpret_cast<const uint32_t*>(up);
+    const uint32_t wv = *reinterpret_cast<const uint32_t*>(vp);
+    Y[0] = (float)(wy.x & 0xffffu); Y[1] = (float)(wy.x >> 16);
+    Y[2] = (float)(wy.y & 0xffffu); Y[3] = (float)(wy.y >> 16);
+    U[0] = (float)(wu & 0xffffu); U[1] = (float)(wu >> 16);
+    V[0] = (float)(wv & 0xffffu); V[1] = (float)(wv >> 16);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) yuv_to_rgb_px(k, Y[q], U[q >> 1], V[q >> 1], rgb + 3 * q);
+}
+
+// One pixel (row, x) of a planar surface, any x: scalar sample loads (the low-res gather).
+template <typename TI>
+__device__ __forceinline__ void yuv_load_px(const YuvPlanarSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                            float* __restrict__ rgb) {
+  const TI* yp = reinterpret_cast<const TI*>(static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y);
+  const TI* up = reinterpret_cast<const TI*>(static_cast<const char*>(s.u) + (long long)b * s.image_u +
+                                             (long long)(row >> 1) * s.pitch_u);
+  const TI* vp = reinterpret_cast<const TI*>(static_cast<const char*>(s.v) + (long long)b * s.image_v +
+                                             (long long)(row >> 1) * s.pitch_v);
+  yuv_to_rgb_px(k, (float)yp[x], (float)up[x >> 1], (float)vp[x >> 1], rgb);
 }
 
 // Surface output: code values clamped to code_max and truncated (the + 0.5 of the rounding is in the bias of from_rgb),

@@ -34,7 +34,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["lowres_input", "lowres_input_yuv", "draw_ops", "check_ops", "prepare_batch", "DeviceDataset", "pack_images",
+__all__ = ["lowres_input", "lowres_input_yuv", "lowres_input_yuv_planar", "draw_ops", "check_ops", "prepare_batch", "DeviceDataset", "pack_images",
            "prepare_batch_ragged", "RaggedDeviceDataset"]
 
 _DTYPE_CODE = {torch.float32: 0, torch.uint8: 1, torch.uint16: 2}
@@ -145,6 +145,35 @@ def lowres_input_yuv(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, ne
     with torch.cuda.device(y.device):
         rc = _lib.load().hdrnet_lowres_input_yuv(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(), n,
                                                  _stream(y.device))
+    _lib.check(rc, "LowresInput")
+    return out
+
+
+def lowres_input_yuv_planar(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor,
+                            net_input_size: int = 256, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``lowres_input_yuv`` of a PLANAR YUV 4:2:0 surface (``hdrnet_lowres_input_yuv_planar``,
+    include/hdrnet_amd_yuv_planar.h): ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with
+    the code in the low bits, possibly pitched; ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients(...,
+    msb_aligned=False)`` on the device.  The bits of ``lowres_input_yuv`` on the interleaved surface.  One launch on the
+    current stream; capturable."""
+    from . import hdrnet_ops
+    what = "lowres_input_yuv_planar"
+    B, H, W, surf = hdrnet_ops._yuv_planar_surface(y, u, v, what)
+    to_rgb = hdrnet_ops._yuv_constants("to_rgb", to_rgb, what)
+    n = int(net_input_size)
+    if n <= 0:
+        raise ValueError(f"{what}: net_input_size must be positive, got {net_input_size}")
+    for nm, t in (("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{nm} is on {t.device}: sample preparation runs on an MI355X (HIP) device only")
+    k = to_rgb.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, n, n, 3), dtype=torch.float32, device=y.device)
+    else:
+        _check_out("lowres_input", out, (B, n, n, 3), y.device)
+    with torch.cuda.device(y.device):
+        rc = _lib.load().hdrnet_lowres_input_yuv_planar(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k.data_ptr(),
+                                                        out.data_ptr(), n, _stream(y.device))
     _lib.check(rc, "LowresInput")
     return out
 

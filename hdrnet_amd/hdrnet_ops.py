@@ -39,7 +39,7 @@ from . import _lib
 __all__ = ["bilateral_slice", "bilateral_slice_apply", "bilateral_slice_apply_rows", "bilateral_slice_apply_nnguide",
            "bilateral_slice_apply_io", "bilateral_slice_apply_curves", "bilateral_slice_apply_upadd", "resize_bilinear", "input_moments",
            "resize_bilinear_io", "bilateral_slice_apply_upadd_io", "bilateral_slice_apply_io_u16",
-           "bilateral_slice_apply_io_yuv_deep",
+           "bilateral_slice_apply_io_yuv_deep", "yuv_planar_to_rgb", "bilateral_slice_apply_io_yuv_planar",
            "CoefficientWeights", "coefficients", "coefficients_train", "coefficients_train_supported", "guide_fold_batch", "guide_nn_prescale", "curves_guide_prepare",
            "kernel_override", "last_kernel"]
 
@@ -1460,6 +1460,161 @@ def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: t
         raise ValueError(f"{what}: out_bits must be 10 (P010) or 16 (P016), got {out_bits!r}")
     return _apply_io_surface(what, torch.uint16, None, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
                              return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits)
+
+
+# ---- planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv_planar.h) -----------------------------------------------------------
+def _yuv_planar_surface(y, u, v, what: str, names=("y", "u", "v")):
+    """The rules of a planar surface, on the host: ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` of one dtype,
+    uint8 or uint16, last-dimension stride 1; the luma's row and image strides multiples of 4 bytes, the chroma's of 2
+    bytes (uint8) / 4 bytes (uint16).  Returns ``(B, H, W, (sample_dtype, pitch_y, pitch_u, pitch_v, image_stride_y,
+    image_stride_u, image_stride_v))``, in bytes."""
+    planes = tuple(zip(names, (y, u, v)))
+    for nm, t in planes:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {nm} must be a torch.Tensor, got {type(t).__name__}")
+    if y.dim() != 3:
+        raise ValueError(f"{what}: {names[0]} should be [B, H, W], got {tuple(y.shape)}")
+    B, H, W = y.shape
+    if y.dtype not in _YUV_SAMPLE or u.dtype != y.dtype or v.dtype != y.dtype:
+        raise TypeError(f"{what}: {', '.join(names)} must all be uint8 (I420) or all uint16 (yuv420p10le / yuv420p16le), got "
+                        f"{y.dtype}, {u.dtype}, {v.dtype}")
+    if H % 2 != 0:
+        raise ValueError(f"{what}: H must be even (a chroma row serves two image rows), got H = {H}")
+    if W % 4 != 0:
+        raise ValueError(f"{what}: W % 4 != 0 (W = {W})")
+    for nm, t in planes[1:]:
+        if t.dim() != 3 or tuple(t.shape) != (B, H // 2, W // 2):
+            raise ValueError(f"{what}: {nm} should be [B, H / 2, W / 2] = {[B, H // 2, W // 2]}, got {list(t.shape)}")
+    size = y.element_size()
+    for i, (nm, t) in enumerate(planes):
+        row, unit = (W, 4) if i == 0 else (W // 2, 2 * size)
+        if B * H * W and (t.stride(2) != 1 or t.stride(1) < row or (t.stride(1) * size) % unit or (t.stride(0) * size) % unit):
+            raise ValueError(f"{what}: {nm} must have last-dimension stride 1, a row stride >= {row} samples and pitches that "
+                             f"are multiples of {unit} bytes, got strides {tuple(t.stride())}")
+    return B, H, W, (_YUV_SAMPLE[y.dtype], *(t.stride(1) * size for t in (y, u, v)), *(t.stride(0) * size for t in (y, u, v)))
+
+
+def yuv_planar_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor) -> torch.Tensor:
+    """``yuv_to_rgb`` for a PLANAR YUV 4:2:0 surface (``hdrnet_yuv_planar_to_rgb_f32``, include/hdrnet_amd_yuv_planar.h):
+    ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420; YV12 with the planes swapped) or uint16 with the
+    code in the low bits (yuv420p10le / yuv420p16le); ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients(...,
+    msb_aligned=False)`` on the device.  The bits of ``yuv_to_rgb`` on the interleaved surface.  Planes may be pitched;
+    padding is not read.  No autograd."""
+    what = "yuv_planar_to_rgb"
+    B, H, W, surf = _yuv_planar_surface(y, u, v, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    for nm, t in (("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)):
+        _require_gpu(nm, t)
+    dev = y.device
+    k = to_rgb.detach().contiguous()
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().hdrnet_yuv_planar_to_rgb_f32(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k.data_ptr(),
+                                                      out.data_ptr(), _stream(dev))
+    _lib.check(rc, "YuvPlanarToRgb")
+    return out
+
+
+def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                                        to_rgb: torch.Tensor,
+                                        guide: Optional[torch.Tensor] = None,
+                                        guide_conv1: Optional[torch.Tensor] = None,
+                                        guide_conv2: Optional[torch.Tensor] = None,
+                                        guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
+                                        return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
+                                        curves_prepared: Optional[torch.Tensor] = None,
+                                        out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                                        from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
+                                        out_planes=None):
+    """``bilateral_slice_apply_io_yuv`` for a PLANAR YUV 4:2:0 surface in (include/hdrnet_amd_yuv_planar.h): ``y``
+    ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with the code in the low bits
+    (yuv420p10le / yuv420p16le), converted in the kernel's load by ``to_rgb`` (``yuv.yuv_coefficients(...,
+    msb_aligned=False)``): the bits of ``bilateral_slice_apply_io_yuv`` on the interleaved surface.  The guide arguments
+    are those of ``bilateral_slice_apply_io``.
+
+    ``out="rgb"``: ``[B, H, W, 3]`` RGB, ``out_dtype`` float32 (default) or uint8.  ``out="planar"``: a planar surface of the
+    input's dtype, returned as ``(y_out, u_out, v_out)``, encoded by ``from_rgb`` (``yuv.yuv_encode_coefficients(standard,
+    full_range, out_bits)``) with ``out_bits`` 8 for uint8 planes and 10 or 16 for uint16 planes: codes clamped to
+    ``2 ** out_bits - 1``, truncated, in the low bits.  ``out_planes``: a ``(y_out, u_out, v_out)`` triple to write into
+    (pitched planes are fine; padding is not written); tight planes are allocated when none are given.  ``return_guide``
+    appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd.  Out of scope: uint16 planes in ->
+    uint8 planes out, a semi-planar surface out."""
+    what = "bilateral_slice_apply_io_yuv_planar"
+    if out not in ("rgb", "planar"):
+        raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
+    planar = out == "planar"
+    if not planar:
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"{what}: out_dtype must be float32 or uint8, got {out_dtype}")
+        if from_rgb is not None or out_planes is not None or out_bits is not None:
+            raise ValueError(f"{what}: from_rgb / out_bits / out_planes belong to out='planar'")
+    elif from_rgb is None:
+        raise ValueError(f"{what}: out='planar' needs from_rgb (yuv.yuv_encode_coefficients)")
+    B, H, W, surf = _yuv_planar_surface(y, u, v, what)
+    if planar:
+        if out_dtype not in (None, y.dtype):
+            raise TypeError(f"{what}: a planar output has the input's dtype ({y.dtype}), got out_dtype = {out_dtype}")
+        if out_bits is None:
+            out_bits = 8 if y.dtype == torch.uint8 else 16
+        if out_bits not in ((8,) if y.dtype == torch.uint8 else (10, 16)):
+            raise ValueError(f"{what}: out_bits = {out_bits!r} does not fit {y.dtype} planes (uint8: 8; uint16: 10 or 16)")
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    _require_f32("grid", grid)
+    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
+        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
+                         f"{tuple(grid.shape)}")
+    GH, GW, GD = grid.shape[1:4]
+    tensors = [("grid", grid), ("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)]
+    planes = osurf = None
+    if planar:
+        from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+        tensors.append(("from_rgb", from_rgb))
+        if out_planes is not None:
+            planes = tuple(out_planes)
+            if len(planes) != 3:
+                raise ValueError(f"{what}: out_planes should be a (y_out, u_out, v_out) triple, got {len(planes)} planes")
+            names = tuple(f"out_planes[{i}]" for i in range(3))
+            oB, oH, oW, osurf = _yuv_planar_surface(*planes, what, names)
+            if (oB, oH, oW) != (B, H, W) or planes[0].dtype != y.dtype:
+                raise ValueError(f"{what}: out_planes should be a {str(y.dtype).replace('torch.', '')} planar surface of "
+                                 f"{[B, H, W]}, got {planes[0].dtype} {[oB, oH, oW]}")
+            tensors += list(zip(names, planes))
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
+                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
+    for nm, t in tensors:
+        _require_gpu(nm, t)
+    dev = y.device
+    grid = grid.detach().contiguous()
+    k_in = to_rgb.detach().contiguous()
+    if planar:
+        if planes is None:  # tight planes
+            size = _YUV_SAMPLE[y.dtype]
+            planes = (torch.empty((B, H, W), dtype=y.dtype, device=dev),
+                      torch.empty((B, H // 2, W // 2), dtype=y.dtype, device=dev),
+                      torch.empty((B, H // 2, W // 2), dtype=y.dtype, device=dev))
+            cw, cp = size * (W // 2), size * (H // 2) * (W // 2)
+            osurf = (size, size * W, cw, cw, size * H * W, cp, cp)
+        k_out = from_rgb.detach().contiguous()
+        output = (_lib.YUV_PLANAR_OUT["planar"], *(t.data_ptr() for t in planes), *osurf[1:], k_out.data_ptr(), int(out_bits))
+        result = planes
+    else:
+        result = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
+        output = (_lib.YUV_PLANAR_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), None, None,
+                  0, 0, 0, 0, 0, 0, None, 0)
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    head = (y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    if curves:
+        fn = "hdrnet_bilateral_slice_apply_io_curves_yuv_planar"
+        args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
+    else:
+        fn = "hdrnet_bilateral_slice_apply_io_yuv_planar"
+        args = (grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None))
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), fn)(*args, *output, _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOYuvPlanar")
+    return (result, gout) if return_guide else result
 
 
 def resize_bilinear_io(input: torch.Tensor, height: int, width: int,  # noqa: A002

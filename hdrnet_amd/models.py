@@ -647,14 +647,14 @@ class HDRNetCurves(nn.Module):
 
 
     # ---- YUV surface in, frame or NV12 surface out ------------------------------------------------------------------------
-    def _yuv_constants(self, standard: str, full_range: bool, bits: int, device: torch.device):
+    def _yuv_constants(self, standard: str, full_range: bool, bits: int, device: torch.device, msb_aligned: bool = True):
         """``(to_rgb, from_rgb)`` of ``yuv.yuv_coefficients`` on ``device``, cached per (standard, range, bits): a
-        captured graph holds pointers to them."""
+        captured graph holds pointers to them.  ``msb_aligned=False``: for codes in the low bits (planar surfaces)."""
         from . import yuv
         cache = self.__dict__.setdefault("_yuv_cache", {})
-        key = (standard, bool(full_range), int(bits), str(device))
+        key = (standard, bool(full_range), int(bits), str(device)) + (() if msb_aligned else ("low bits",))
         if key not in cache:
-            to_rgb, from_rgb = yuv.yuv_coefficients(standard, full_range, bits)
+            to_rgb, from_rgb = yuv.yuv_coefficients(standard, full_range, bits, msb_aligned=msb_aligned)
             cache[key] = (torch.from_numpy(to_rgb).to(device), torch.from_numpy(from_rgb).to(device))
         return cache[key]
 
@@ -713,6 +713,49 @@ class HDRNetCurves(nn.Module):
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv, lowres, y, uv, to_rgb, out=out,
                                           out_dtype=out_dtype, from_rgb=from_rgb if out == "nv12" else None,
                                           out_planes=out_planes)
+
+
+    def process_yuv_planar(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709",
+                           full_range: bool = False, bits: Optional[int] = None, out: str = "rgb",
+                           out_dtype: Optional[torch.dtype] = None, out_planes=None):
+        """``process_yuv`` for a PLANAR YUV 4:2:0 surface as a software decoder delivers it
+        (include/hdrnet_amd_yuv_planar.h): ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` on the device, uint8
+        (I420 / FFmpeg's yuv420p; YV12 with the planes swapped) or uint16 with the code in the low bits (yuv420p10le with
+        ``bits=10``, yuv420p16le with ``bits=16``; ``bits=None`` is 8 for uint8 and 16 for uint16).  ``process_yuv`` step
+        for step -- ``data.lowres_input_yuv_planar`` -> the coefficient network ->
+        ``hdrnet_ops.bilateral_slice_apply_io_yuv_planar`` -- with no interleaving or shifting pass.  ``out="rgb"``:
+        ``[B, H, W, 3]`` float32 (default) or uint8; ``out="planar"``: a planar surface ``(y_out, u_out, v_out)`` of the
+        input's dtype, depth, standard and range (``out_planes``: the triple to write into).  Planes may be pitched.
+        Capturable."""
+        from . import data, hdrnet_ops, yuv
+        what = f"{type(self).__name__}.process_yuv_planar"
+        if self._process_dtypes == (torch.float32,):
+            raise ValueError(f"{what}: the pyramid model's resize and up-add kernels read RGB frames only: there is no YUV "
+                             "surface path (the single-level models' process_yuv_planar takes I420 / yuv420p10le / "
+                             "yuv420p16le)")
+        if standard not in yuv.STANDARDS:
+            raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
+        if out not in ("rgb", "planar"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
+        hdrnet_ops._yuv_planar_surface(y, u, v, what)
+        if out == "planar" and out_dtype not in (None, y.dtype):
+            raise TypeError(f"{what}: a planar output has the input's dtype ({y.dtype}), got out_dtype = {out_dtype}")
+        if bits is None:
+            bits = 8 if y.dtype == torch.uint8 else 16
+        if bits not in yuv.BITS or (bits == 8) != (y.dtype == torch.uint8):
+            raise ValueError(f"{what}: bits = {bits!r} does not fit {y.dtype} planes (uint8: 8; uint16: 10 or 16)")
+        if self.training:
+            raise RuntimeError("process_yuv_planar() is inference: call eval() first")
+        hdrnet_ops._require_gpu("y", y)
+        with torch.no_grad():
+            to_rgb, _ = self._yuv_constants(standard, full_range, bits, y.device, msb_aligned=False)
+            lowres = data.lowres_input_yuv_planar(y, u, v, to_rgb, self.params["net_input_size"])
+            if out == "planar":
+                return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_planar, lowres, y, u, v, to_rgb,
+                                              out="planar", out_bits=bits, out_planes=out_planes,
+                                              from_rgb=self._yuv_encode_constants(standard, full_range, bits, y.device))
+            return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_planar, lowres, y, u, v, to_rgb, out="rgb",
+                                          out_dtype=out_dtype)
 
 
 class HDRNetPointwiseNNGuide(HDRNetCurves):

@@ -141,6 +141,34 @@ class YuvFrameInference(GraphedInference):
                          warmup=warmup, check_parameters=check_parameters)
 
 
+class _ProcessYuvPlanar(torch.nn.Module):
+    """``model.process_yuv_planar`` as the module a ``GraphedInference`` captures."""
+
+    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype):
+        super().__init__()
+        self.model, self.standard, self.full_range, self.bits = model, standard, full_range, bits
+        self.out, self.out_dtype = out, out_dtype
+
+    def forward(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor):
+        return self.model.process_yuv_planar(y, u, v, standard=self.standard, full_range=self.full_range, bits=self.bits,
+                                             out=self.out, out_dtype=self.out_dtype)
+
+
+class PlanarYuvFrameInference(GraphedInference):
+    """``YuvFrameInference`` for PLANAR surfaces (include/hdrnet_amd_yuv_planar.h): the captured callable is
+    ``model.process_yuv_planar``.  Three inputs, the planes ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` (uint8
+    I420, or uint16 with the code in the low bits), copied into static planes unless they ARE the static planes.
+    ``out="planar"``: the static output is the ``(y_out, u_out, v_out)`` triple of a surface of the input's dtype and
+    depth; ``out="rgb"``: a ``[B, H, W, 3]`` frame of ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
+    ``process_yuv_planar``.  Beside ``YuvFrameInference``, which keeps its signature."""
+
+    def __init__(self, model: torch.nn.Module, y_like: torch.Tensor, u_like: torch.Tensor, v_like: torch.Tensor,
+                 standard: str = "bt709", full_range: bool = False, bits=None, out: str = "planar", out_dtype=None,
+                 warmup: int = 3, check_parameters: bool = True):
+        super().__init__(_ProcessYuvPlanar(model.eval(), standard, full_range, bits, out, out_dtype),
+                         [y_like, u_like, v_like], warmup=warmup, check_parameters=check_parameters)
+
+
 class FramePipeline:
     """Independent frames round-robin over ``depth`` HIP streams.
 

@@ -1,4 +1,4 @@
-"""Colour constants of the YUV surface path (include/hdrnet_amd_yuv.h).
+"""Colour constants of the YUV surface paths (include/hdrnet_amd_yuv.h, include/hdrnet_amd_yuv_planar.h).
 
 The kernels know nothing of colour standards, ranges or bit depths: they apply 12 floats to the samples as stored.
 ``yuv_coefficients`` computes those floats from the published BT.601 / BT.709 / BT.2020 luma weights (ITU-R BT.601-7,
@@ -29,12 +29,18 @@ def code_ranges(full_range: bool, bits: int) -> Tuple[float, float, float, float
     return 16.0 * unit, 219.0 * unit, 128.0 * unit, 224.0 * unit
 
 
-def yuv_coefficients(standard: str = "bt709", full_range: bool = False, bits: int = 8) -> Tuple[np.ndarray, np.ndarray]:
+def yuv_coefficients(standard: str = "bt709", full_range: bool = False, bits: int = 8,
+                     msb_aligned: bool = True) -> Tuple[np.ndarray, np.ndarray]:
     """``(to_rgb, from_rgb)``: two float32 arrays of 12 numbers, a row-major 3 x 3 matrix then 3 biases.
 
     ``to_rgb`` applied to the RAW STORED samples (Y, U, V) as floats gives R, G, B, nominally in [0, 1]: range scaling and
     the chroma offset are in the numbers, and for ``bits = 10`` so is P010's placement of the code in the high bits (the
     sample as stored is ``code << 6``).  ``bits = 8`` is NV12, ``bits = 16`` P016.
+
+    ``msb_aligned=False``: the code sits in the LOW bits of the sample, as in the planar ``yuv420p10le`` surfaces of
+    include/hdrnet_amd_yuv_planar.h (the sample as stored is the code).  Only ``bits = 10`` differs: the matrix is exactly
+    64 x the default one and the biases are equal (scaling by a power of two commutes with the float64 division and with
+    the rounding to float32).
 
     ``from_rgb`` applied to R, G, B in [0, 1] gives Y, U, V in UINT8 code values of the same standard and range (the
     output surface is NV12 whatever the input's depth), with the + 0.5 of the rounding folded into the biases: the
@@ -46,7 +52,7 @@ def yuv_coefficients(standard: str = "bt709", full_range: bool = False, bits: in
     kr, kb = STANDARDS[standard]
     kg = 1.0 - kr - kb
     y_off, y_scale, c_off, c_scale = code_ranges(bool(full_range), bits)
-    stored = 64.0 if bits == 10 else 1.0  # P010: code << 6
+    stored = 64.0 if bits == 10 and msb_aligned else 1.0  # P010: code << 6
     # R = Y' + 2 (1 - Kr) Cr',  B = Y' + 2 (1 - Kb) Cb',  G from the luma equation
     cu = np.array([0.0, -2.0 * kb * (1.0 - kb) / kg, 2.0 * (1.0 - kb)])  # weight of Cb' in R, G, B
     cv = np.array([2.0 * (1.0 - kr), -2.0 * kr * (1.0 - kr) / kg, 0.0])  # weight of Cr'

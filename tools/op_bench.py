@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -22,7 +22,11 @@ hipGraph of process_yuv(..., out="nv12") against a hipGraph of the stock chain (
 u8 RGB against RGB u8 -> u8; `u16_out` = 16-bit output (include/hdrnet_amd_u16_out.h): a hipGraph of process(u16 -> u16 at
 32767) against a hipGraph of the chain a caller had before it (process -> float32, clamp * wl, .to(uint16)) at 4000x3000,
 4K and 1080p, process_yuv(P010 -> P010) against the stock encode chain at 4K, and the kernel alone, u16 -> u16 against
-u16 -> f32 at 4000x3000, all alternating.  --tools loads the tools build and adds the un-fused
+u16 -> f32 at 4000x3000, all alternating; `yuv_planar` = planar surfaces (include/hdrnet_amd_yuv_planar.h):
+HDRNetPointwiseNNGuide on I420 uint8 planes at 4K and 1080p, a hipGraph of process_yuv_planar(..., out="planar") against a
+hipGraph of the chain a caller had before it (interleave U, V -> process_yuv(out="nv12") -> split the chroma), the same
+pair for yuv420p10le (the chain shifts by 6 each way around P010), and the fused kernel alone at 4K, I420 -> I420 against
+NV12 -> NV12, all alternating.  --tools loads the tools build and adds the un-fused
 gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -101,6 +105,8 @@ def main():
         return yuv_surfaces(lib, dev, args)
     if args.workload == "u16_out":
         return u16_out(lib, dev, args)
+    if args.workload == "yuv_planar":
+        return yuv_planar(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -743,6 +749,119 @@ def yuv_surfaces(lib, dev, args):
         del sets
     if args.json:
         json.dump(dict(workload="yuv", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _PlanarChain(torch.nn.Module):
+    """What a caller with a planar surface wrote before process_yuv_planar: interleave U and V into a new plane (10-bit:
+    shift every sample up by 6 as well), process_yuv to a semi-planar surface, split the chroma again (and shift back)."""
+
+    def __init__(self, model, bits):
+        super().__init__()
+        self.model, self.bits = model, bits
+
+    def forward(self, y, u, v):
+        if self.bits == 8:
+            oy, ouv = self.model.process_yuv(y, torch.stack((u, v), dim=-1).flatten(2), out="nv12")
+            return oy, ouv[:, :, 0::2].contiguous(), ouv[:, :, 1::2].contiguous()
+        # (stock torch has neither shifts nor stack for uint16: through int32, the shift fused into the conversion's pass)
+        up = lambda t: (t << 6).to(torch.uint16)  # noqa: E731
+        down = lambda t: (t.int() >> 6).to(torch.uint16)  # noqa: E731
+        oy, ouv = self.model.process_yuv(up(y.int()), up(torch.stack((u.int(), v.int()), dim=-1).flatten(2)), bits=10, out="p010")
+        return down(oy), down(ouv[:, :, 0::2]), down(ouv[:, :, 1::2])
+
+
+def yuv_planar(lib, dev, args):
+    """Planar 4:2:0 surfaces through HDRNetPointwiseNNGuide at 4K and 1080p: one hipGraph of process_yuv_planar(y, u, v,
+    out="planar") against one hipGraph of _PlanarChain, I420 uint8 and yuv420p10le; both warmed, then run ALTERNATING three
+    times each in one process; reported: the mean of the three and their range.  Beside it, at 4K: the fused guide-network
+    kernel alone, I420 -> I420 against NV12 -> NV12 (the same bytes, two narrower chroma accesses per lane each way), over
+    buffer sets that together exceed the Infinity Cache, alternating the same way."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import GraphedInference, PlanarYuvFrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def samples(bits, *shape):
+        t = torch.randint(0, 2 ** bits, shape, device=dev, dtype=torch.int32, generator=gen)
+        return t.to(torch.uint8 if bits == 8 else torch.uint16)
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        for bits, fmt in ((8, "i420"), (10, "yuv420p10le")):
+            surfaces = [(samples(bits, 1, H, W), samples(bits, 1, H // 2, W // 2), samples(bits, 1, H // 2, W // 2))
+                        for _ in range(3)]
+            new = PlanarYuvFrameInference(m, *surfaces[0], bits=bits, out="planar")
+            base = GraphedInference(_PlanarChain(m, bits), list(surfaces[0]))
+            for a, b in zip(new(*surfaces[1]), base(*surfaces[1])):
+                assert torch.equal(a, b), "the fused path and the chain around process_yuv give the same planes"
+            b, n = alternate(lambda k: base(*surfaces[k % 3]), lambda k: new(*surfaces[k % 3]))
+            mb, mn = statistics.mean(b), statistics.mean(n)
+            spread = max(b) - min(b)
+            name = f"{H}x{W} model, {fmt} -> {fmt}"
+            rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                             us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                             faster_beyond_chain_spread=bool(mb - mn > spread)))
+            print(f"{name:46s} chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_yuv_planar {mn:8.2f} us "
+                  f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+                  f"faster by more than the chain's spread: {mb - mn > spread}")
+            del new, base, surfaces
+
+    # the kernel alone at 4K: the same grid and guide network, the same samples in two surface layouts
+    H, W = 2160, 3840
+    GH, GW, GD = 16, 16, 8
+    to_rgb, from_rgb = (torch.from_numpy(a).to(dev) for a in yuv.yuv_coefficients("bt709", False, 8))
+    nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 3)))
+    grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+    conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+    conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+    Hc, Wc = H // 2, W // 2
+    e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.uint8)  # noqa: E731
+    sets = [dict(y=samples(8, 1, H, W), uv=samples(8, 1, Hc, W), u=samples(8, 1, Hc, Wc), v=samples(8, 1, Hc, Wc),
+                 oy=e(1, H, W), ouv=e(1, Hc, W), ou=e(1, Hc, Wc), ov=e(1, Hc, Wc)) for _ in range(nsets)]
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(lib.hdrnet_last_error().decode())
+
+    def nv12_kernel(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_io_yuv(grid.data_ptr(), None, t["y"].data_ptr(), t["uv"].data_ptr(), 1, W, W, H * W,
+                                                      Hc * W, 1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1, conv1.data_ptr(),
+                                                      conv2.data_ptr(), 16, None, _lib.GUIDE_SIGMOID_FAST, 2, t["oy"].data_ptr(),
+                                                      t["ouv"].data_ptr(), W, W, H * W, Hc * W, from_rgb.data_ptr(), stream))
+
+    def i420_kernel(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_io_yuv_planar(
+            grid.data_ptr(), None, t["y"].data_ptr(), t["u"].data_ptr(), t["v"].data_ptr(), 1, W, Wc, Wc, H * W, Hc * Wc, Hc * Wc,
+            1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1, conv1.data_ptr(), conv2.data_ptr(), 16, None,
+            _lib.GUIDE_SIGMOID_FAST, 2, t["oy"].data_ptr(), t["ou"].data_ptr(), t["ov"].data_ptr(), W, Wc, Wc, H * W, Hc * Wc,
+            Hc * Wc, from_rgb.data_ptr(), 8, stream))
+
+    q, p = alternate(nv12_kernel, i420_kernel)
+    name = f"{H}x{W} kernel, +nnguide"
+    row = dict(op=name)
+    text = []
+    for key, label, t in (("nv12_nv12", "nv12 -> nv12 (3 B/px)", q), ("i420_i420", "i420 -> i420 (3 B/px)", p)):
+        row.update({f"us_{key}": round(statistics.mean(t), 2), f"us_{key}_min": round(min(t), 2), f"us_{key}_max": round(max(t), 2)})
+        text.append(f"{label} {statistics.mean(t):8.2f} us ({min(t):8.2f} .. {max(t):8.2f})")
+    rows.append(row)
+    print(f"{name:28s} " + "   ".join(text))
+    if args.json:
+        json.dump(dict(workload="yuv_planar", rows=rows), open(args.json, "w"), indent=1)
 
 
 class _QuantiseChain(torch.nn.Module):
