@@ -145,7 +145,8 @@ __global__ __launch_bounds__(256) void apply_vjp_seg(const VjpSegParams p) {
             const float dw0 = (qza > 1.0f) ? 0.0f : gd_f * (dza * rza);
             const float Da = sza * (sza + fabsf(dza)), Db = szb * (szb + fabsf(dzb));
             dwsum = (gd_f * kSmoothEps) * ((Db - Da) * __builtin_amdgcn_rcpf(Da * Db));
-            dwsum = (qza > 1.0f || qzb > 1.0f) ? dw0 + dw1 : dwsum;
+            // (dza > 0: gzf - 0.5f rounded up onto a tap switch; the closed form takes dza <= 0 -- grid_grad_mfma.hip)
+            dwsum = (qza > 1.0f || qzb > 1.0f || dza > 0.0f) ? dw0 + dw1 : dwsum;
           } else {
             sza = __builtin_amdgcn_sqrtf(qza);
             szb = __builtin_amdgcn_sqrtf(qzb);

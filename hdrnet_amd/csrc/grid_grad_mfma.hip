@@ -502,10 +502,15 @@ __attribute__((amdgpu_waves_per_eu(((WG || WI) && COUT * (APPLY ? CIN + (OFFSET 
             // e_a - e_b = eps (D_b - D_a) / (D_a D_b), D = s (s + |dz|): one reciprocal for both taps
             const float Da = sza * (sza + fabsf(dza)), Db = szb * (szb + fabsf(dzb));
             dwsum = (gd_f * kSmoothEps) * ((Db - Da) * __builtin_amdgcn_rcpf(Da * Db));
-            if (__builtin_expect(__ballot(qza > 1.0f || qzb > 1.0f) != 0ull, 0)) {  // wave-uniform; wild guides only:
+            // The closed form takes dza <= 0 < dzb.  dza > 0 happens: for a guide within an ulp below a tap switch
+            // gzf - 0.5f rounds UP onto the integer, floorf() lands one plane high and the lower tap's offset is a
+            // positive ulp of gzf (the reference's own arithmetic: it evaluates dza / sza with that sign; the closed
+            // form would negate it, 2 GD dza / sza = up to 1e-2 GD of <G0, U>).  Such a lane takes the direct sum with
+            // the wild guides: dw0 is tiny there and nothing cancels.
+            if (__builtin_expect(__ballot(qza > 1.0f || qzb > 1.0f || dza > 0.0f) != 0ull, 0)) {  // wave-uniform; rare:
               // a tap past its cell has derivative 0 (numerics.h:116-126), the sum is the direct one
               const float dw0 = (qza > 1.0f) ? 0.0f : gd_f * (dza * __builtin_amdgcn_rcpf(sza));
-              if (qza > 1.0f || qzb > 1.0f) dwsum = dw0 + dw1;
+              if (qza > 1.0f || qzb > 1.0f || dza > 0.0f) dwsum = dw0 + dw1;
             }
           }
           // Direct form (no 2 x C blended-coefficient accumulators: 4 scalars instead of 24 registers
