@@ -230,6 +230,25 @@ YUV_PLANAR_SIGNATURES = {
                                                           [_FP] * 4 + [_I, _VP, _FP] + _PLANAR_OUTPUT + [_VP]),
 }
 
+# include/hdrnet_amd_yuv_chroma.h: the entry points of the three tables above with a chroma layout -- `chroma` follows the
+# surface, and every surface output carries `out_bits`.
+CHROMA = {"420": 0, "422": 1, "444": 2}  # HDRNET_CHROMA_*
+CHROMA_OUT = {"rgb_f32": 0, "rgb_u8": 1, "surface_u8": 2, "surface_u16": 3}  # HDRNET_CHROMA_OUT_*
+YUV_CHROMA_SIGNATURES = {
+    "hdrnet_yuv_chroma_to_rgb_f32": (_I, _SURFACE + [_I] * 4 + [_FP, _FP, _VP]),
+    "hdrnet_lowres_input_yuv_chroma": (_I, _SURFACE + [_I] * 4 + [_FP, _FP, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv_chroma": (_I, [_FP, _FP] + _SURFACE + [_I] * 4 + [_FP] + [_I] * 6 +
+                                                   [_FP, _FP, _I, _FP, _U] + _YUV_OUTPUT + [_I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv_chroma": (_I, [_FP] + _SURFACE + [_I] * 4 + [_FP] + [_I] * 6 + [_FP] * 4 +
+                                                          [_I, _VP, _FP] + _YUV_OUTPUT + [_I, _VP]),
+    "hdrnet_yuv_planar_chroma_to_rgb_f32": (_I, _PLANAR_SURFACE + [_I] * 4 + [_FP, _FP, _VP]),
+    "hdrnet_lowres_input_yuv_planar_chroma": (_I, _PLANAR_SURFACE + [_I] * 4 + [_FP, _FP, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv_planar_chroma": (_I, [_FP, _FP] + _PLANAR_SURFACE + [_I] * 4 + [_FP] + [_I] * 6 +
+                                                          [_FP, _FP, _I, _FP, _U] + _PLANAR_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv_planar_chroma": (_I, [_FP] + _PLANAR_SURFACE + [_I] * 4 + [_FP] + [_I] * 6 +
+                                                                 [_FP] * 4 + [_I, _VP, _FP] + _PLANAR_OUTPUT + [_VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -286,6 +305,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(YUV_SIGNATURES)
     table.update(U16_OUT_SIGNATURES)
     table.update(YUV_PLANAR_SIGNATURES)
+    table.update(YUV_CHROMA_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

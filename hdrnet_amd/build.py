@@ -44,6 +44,10 @@ SOURCES = [
     ("apply_fwd_io_yuv.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     # ... and for planar YUV surfaces in (I420, 10 / 16-bit), RGB or a planar surface out (include/hdrnet_amd_yuv_planar.h)
     ("apply_fwd_io_yuv_planar.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    # ... and for 4:2:2 / 4:4:4 surfaces (include/hdrnet_amd_yuv_chroma.h): NV16 / P210 / P216, and one unit per planar layout
+    ("apply_fwd_io_yuv_422.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    ("apply_fwd_io_yuv_planar_422.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    ("apply_fwd_io_yuv_planar_444.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     # ... and with a 16-bit output: a uint16 frame, a P010 / P016 surface (include/hdrnet_amd_u16_out.h)
     ("apply_fwd_io_u16.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_upadd.hip", ["-fno-slp-vectorize"]),
@@ -112,7 +116,7 @@ def _deps() -> List[str]:
            os.path.join(INCLUDE, "hdrnet_amd_coeff_bn.h"), os.path.join(INCLUDE, "hdrnet_amd_coeff_wide.h"),
            os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"), os.path.join(INCLUDE, "hdrnet_amd_pixel_formats.h"),
            os.path.join(INCLUDE, "hdrnet_amd_yuv.h"), os.path.join(INCLUDE, "hdrnet_amd_u16_out.h"),
-           os.path.join(INCLUDE, "hdrnet_amd_yuv_planar.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_yuv_planar.h"), os.path.join(INCLUDE, "hdrnet_amd_yuv_chroma.h"),
            os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):

@@ -35,6 +35,11 @@
 // one (yuv_convert.hip.h), and OUT = kOutI420 / kOutI016 the row-pair store above with the chroma code words split the
 // same way; everything between load and store is the semi-planar instantiation's, so the two give the same bits.
 //
+// CHROMA LAYOUTS (include/hdrnet_amd_yuv_chroma.h): CH = kChroma422 / kChroma444 is one more compile-time axis of the surface
+// load and store: which chroma sample a pixel reads, and the footprint a stored chroma sample is the mean of.  Both have a
+// chroma row per image row, so a surface output needs no row pair: one row per workgroup, launch grid y = H.  The default
+// CH = kChroma420 compiles every instantiation above to the code it was.
+//
 // 16-BIT OUTPUT (include/hdrnet_amd_u16_out.h): TO = uint16_t stores a uint16 frame, (uint16)(out_white * clip(v, 0, 1)) in
 // the input's pixel format -- the uint8 store's rule with 255 replaced by a run-time constant -- and OUT = kOutP016 a
 // P010 / P016 surface, the NV12 store's row-pair structure with uint16 code words.  Each shares its store with the 8-bit
@@ -450,7 +455,8 @@ struct IoParams {
 
 // Geometry, LDS image and pixel core are apply_fwd_seg.hip's (seg_common.hip.h): a workgroup owns a row
 // segment, 3-D launch grid (segment, row, image), padded y-pre-lerped coefficient image.
-template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
+template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame,
+          int CH = kChroma420>
 __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   static_assert(PX == kPxRGB || (CIN == 3 && COUT == 3 && sizeof(TI) < 4), "pixel formats: integer frames, 3 -> 3");
   constexpr bool PLANAR = PX == kPxYuvPlanar;  // the input is a planar YUV surface: three planes
@@ -464,6 +470,11 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   static_assert(!I016OUT || (PLANAR && sizeof(TI) == 2 && sizeof(TO) == 2), "uint16 planar out: from a uint16 planar surface");
   constexpr bool PLANAROUT = I420OUT || I016OUT;
   constexpr bool SURFOUT = NV12OUT || P016OUT || PLANAROUT;
+  // CH: the surfaces' chroma layout (yuv_convert.hip.h).  4:2:2 and 4:4:4 have a chroma row per image row: a surface
+  // output is then ONE row per workgroup, as a frame is, and its chroma is stored after that row.
+  static_assert(CH == kChroma420 || YUV, "a chroma layout belongs to a YUV surface");
+  static_assert(CH != kChroma444 || PLANAR, "4:4:4: planar surfaces only");
+  constexpr bool ROWPAIR = SURFOUT && CH == kChroma420;
   constexpr bool PACKED = PX != kPxRGB && !YUV;  // BGR / RGBA / BGRA
   constexpr int SPX = PACKED ? px_stored(PX) : CIN;  // samples per stored pixel of the frame
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
@@ -504,10 +515,10 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   // One image row per workgroup -- or, for an NV12 output, the two rows of a chroma row, one after the other through the
   // same LDS image.  (The loop's condition is a compile-time `false` for one row: no back edge, r == 0, and the
   // single-row kernels compile to the straight code they were.)
-  constexpr int ROWS = SURFOUT ? 2 : 1;
+  constexpr int ROWS = ROWPAIR ? 2 : 1;
   int r = 0;
   do {
-    const int y = SURFOUT ? 2 * (int)blockIdx.y + r : (int)blockIdx.y;
+    const int y = ROWPAIR ? 2 * (int)blockIdx.y + r : (int)blockIdx.y;
     const size_t row = (unsigned)b * (unsigned)p.H + (unsigned)y;  // B, H <= 65535 (kLimBH, row_geom.h)
     const size_t px = row * p.W + x;
     const TI* input = static_cast<const TI*>(p.input);
@@ -522,8 +533,8 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
         const float4 g4 = *reinterpret_cast<const float4*>(p.guide + px);
         gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
       }
-      if constexpr (PLANAR) yuv_load_quad<TI>(p.pin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
-      else if constexpr (YUV) yuv_load_quad<TI>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      if constexpr (PLANAR) yuv_load_quad<TI, CH>(p.pin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      else if constexpr (YUV) yuv_load_quad<TI, CH>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
       else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
     }
 
@@ -588,6 +599,12 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
         uint32_t wy[S];
 #pragma unroll
         for (int q = 0; q < S; ++q) wy[q] = 0;
+        // 4:4:4: a chroma code per pixel (footprint 1), packed as the luma is: S dwords of U and S of V
+        [[maybe_unused]] uint32_t wu4[S], wv4[S];
+        if constexpr (CH == kChroma444) {
+#pragma unroll
+          for (int q = 0; q < S; ++q) wu4[q] = wv4[q] = 0;
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           float pu[2], pv[2];
@@ -600,10 +617,21 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
             wy[k / PER] |= yuv_luma_code(fk, c, cmax, sh) << (8 * S * (k % PER));
             pu[i] = yuv_chroma_linear(fk, 1, c);
             pv[i] = yuv_chroma_linear(fk, 2, c);
+            if constexpr (CH == kChroma444) {
+              wu4[k / PER] |= yuv_chroma_code(fk, 1, pu[i], cmax, sh, 1.0f) << (8 * S * (k % PER));
+              wv4[k / PER] |= yuv_chroma_code(fk, 2, pv[i], cmax, sh, 1.0f) << (8 * S * (k % PER));
+            }
           }
-          csum[h][0] += pu[0] + pu[1];  // horizontal pair first; even row (onto 0), then odd row
-          csum[h][1] += pv[0] + pv[1];
+          if constexpr (CH == kChroma420) {
+            csum[h][0] += pu[0] + pu[1];  // horizontal pair first; even row (onto 0), then odd row
+            csum[h][1] += pv[0] + pv[1];
+          } else if constexpr (CH == kChroma422) {
+            csum[h][0] = pu[0] + pu[1];  // the horizontal pair is the whole footprint
+            csum[h][1] = pv[0] + pv[1];
+          }
         }
+        constexpr float CW = CH == kChroma420 ? 0.25f : 0.5f;  // footprint weight of the summed layouts
+        const int yc = yuv_chroma_row(CH, y);
         char* yo = static_cast<char*>(const_cast<void*>(p.yout.y)) + (long long)b * p.yout.image_y + (long long)y * p.yout.pitch_y +
                    (size_t)x * sizeof(TO);
         if constexpr (PLANAROUT)  // (the Y plane of the planar surface; the store itself is the same)
@@ -615,25 +643,37 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
           // A planar surface: the lane's two U code words into the pair's U row and its two V code words into the V row, at
           // sample x / 2 of each -- one 16-bit store each for uint8 code words, one dword each for uint16 (the chroma planes
           // promise 2- / 4-byte alignment).
-          if (r == ROWS - 1) {
+          // (4:2:2: the same stores into chroma row y.  4:4:4: four code words per plane at sample x of chroma row y, whole
+          // dwords as the luma's -- a 4:4:4 chroma plane promises the luma's alignment.)
+          if constexpr (CH == kChroma444) {
+            char* uo = static_cast<char*>(const_cast<void*>(p.pout.u)) + (long long)b * p.pout.image_u +
+                       (long long)yc * p.pout.pitch_u + (size_t)x * sizeof(TO);
+            char* vo = static_cast<char*>(const_cast<void*>(p.pout.v)) + (long long)b * p.pout.image_v +
+                       (long long)yc * p.pout.pitch_v + (size_t)x * sizeof(TO);
+#pragma unroll
+            for (int q = 0; q < S; ++q) {
+              reinterpret_cast<uint32_t*>(uo)[q] = wu4[q];
+              reinterpret_cast<uint32_t*>(vo)[q] = wv4[q];
+            }
+          } else if (r == ROWS - 1) {
             typedef std::conditional_t<S == 1, uint16_t, uint32_t> TW;  // two code words
             const size_t xc = (size_t)(x >> 1) * sizeof(TO);
             char* uo = static_cast<char*>(const_cast<void*>(p.pout.u)) + (long long)b * p.pout.image_u +
-                       (long long)(y >> 1) * p.pout.pitch_u + xc;
+                       (long long)yc * p.pout.pitch_u + xc;
             char* vo = static_cast<char*>(const_cast<void*>(p.pout.v)) + (long long)b * p.pout.image_v +
-                       (long long)(y >> 1) * p.pout.pitch_v + xc;
-            const uint32_t wu = yuv_chroma_code(fk, 1, csum[0][0], cmax, sh) | (yuv_chroma_code(fk, 1, csum[1][0], cmax, sh) << (8 * S));
-            const uint32_t wv = yuv_chroma_code(fk, 2, csum[0][1], cmax, sh) | (yuv_chroma_code(fk, 2, csum[1][1], cmax, sh) << (8 * S));
+                       (long long)yc * p.pout.pitch_v + xc;
+            const uint32_t wu = yuv_chroma_code(fk, 1, csum[0][0], cmax, sh, CW) | (yuv_chroma_code(fk, 1, csum[1][0], cmax, sh, CW) << (8 * S));
+            const uint32_t wv = yuv_chroma_code(fk, 2, csum[0][1], cmax, sh, CW) | (yuv_chroma_code(fk, 2, csum[1][1], cmax, sh, CW) << (8 * S));
             *reinterpret_cast<TW*>(uo) = (TW)wu;
             *reinterpret_cast<TW*>(vo) = (TW)wv;
           }
         } else if (r == ROWS - 1) {
           char* co = static_cast<char*>(const_cast<void*>(p.yout.uv)) + (long long)b * p.yout.image_uv +
-                     (long long)(y >> 1) * p.yout.pitch_uv + (size_t)x * sizeof(TO);
+                     (long long)yc * p.yout.pitch_uv + (size_t)x * sizeof(TO);
           [[maybe_unused]] uint32_t wc = 0;
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const uint32_t uv = yuv_chroma_code(fk, 1, csum[h][0], cmax, sh) | (yuv_chroma_code(fk, 2, csum[h][1], cmax, sh) << (8 * S));
+            const uint32_t uv = yuv_chroma_code(fk, 1, csum[h][0], cmax, sh, CW) | (yuv_chroma_code(fk, 2, csum[h][1], cmax, sh, CW) << (8 * S));
             if constexpr (S == 2) reinterpret_cast<uint32_t*>(co)[h] = uv;
             else wc |= uv << (16 * h);
           }
@@ -693,7 +733,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
       float* oseg = static_cast<float*>(p.out) + (row * p.W + xs) * COUT;
       store_slab_seg<COUT>(slab, oseg, (unsigned)(xe - xs), wpx, lane);
     }
-  } while (SURFOUT && ++r < ROWS);
+  } while (ROWPAIR && ++r < ROWS);
 }
 
 // The curves instantiations keep their lookup tables in STATIC LDS: no launch passes those bytes, but the workgroup
@@ -709,7 +749,8 @@ RowGeom io_geom(const ApplyIoArgs& a) {
                               a.input_dtype == 0 ? a.input : nullptr));
 }
 
-template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame>
+template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame,
+          int CH = kChroma420>
 hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   const RowGeom g = io_geom(a);
@@ -752,9 +793,9 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
       p.code_shift = 16 - a.yuv->out_bits;
     }
   }
-  // an NV12 output: one workgroup per row PAIR of a segment (H % 2 == 0)
-  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT != kOutFrame ? a.H / 2 : a.H), (unsigned)a.B);
-  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT><<<grid3, g.pl.threads, g.lds, s>>>(p);
+  // a 4:2:0 surface output: one workgroup per row PAIR of a segment (H % 2 == 0); 4:2:2 / 4:4:4: per row, as a frame
+  const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT != kOutFrame && CH == kChroma420 ? a.H / 2 : a.H), (unsigned)a.B);
+  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT, CH><<<grid3, g.pl.threads, g.lds, s>>>(p);
   return hipGetLastError();
 }
 
@@ -811,7 +852,18 @@ inline const char* io_label(const ApplyIoArgs& a) {
   static const char* const suffix[5] = {"", "+nnguide", "+curvesguide", "+curvesguide/scan", "+curvesguide/cells"};
   static const char* const px[4] = {"", "/bgr", "/rgba", "/bgra"};
   static thread_local char label[64];
-  if (a.yuvp) {  // a planar surface: the label states the sample WIDTH (i420 uint8, i016 uint16), as p016 does
+  // a 4:2:2 / 4:4:4 surface (include/hdrnet_amd_yuv_chroma.h): container, layout and sample width -- nv16 / p216 semi-planar,
+  // i422 / i216 / i444 / i416 planar
+  if (a.yuvp && a.yuvp->chroma != kChroma420) {
+    static const char* const planar[2][2] = {{"i422", "i216"}, {"i444", "i416"}};
+    const char* const in = planar[a.yuvp->chroma == kChroma444][a.input_dtype == 2];
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", in,
+             a.yuvp->out_kind == kYuvPlanarOutPlanar ? in : surface[a.yuvp->out_kind], suffix[io_guide_form(a)]);
+  } else if (a.yuv && a.yuv->chroma != kChroma420) {
+    static const char* const surface422[4] = {"f32", "u8", "nv16", "p216"};
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", a.input_dtype == 1 ? "nv16" : "p216", surface422[a.yuv->out_kind],
+             suffix[io_guide_form(a)]);
+  } else if (a.yuvp) {  // a planar surface: the label states the sample WIDTH (i420 uint8, i016 uint16), as p016 does
     const char* const in = a.input_dtype == 1 ? "i420" : "i016";
     snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", in,
              a.yuvp->out_kind == kYuvPlanarOutPlanar ? in : surface[a.yuvp->out_kind], suffix[io_guide_form(a)]);
@@ -836,9 +888,9 @@ inline bool io_frame_ok(const ApplyIoArgs& a) {
   return io_geom(a).ok;
 }
 
-// ... and of a YUV SURFACE: the same op, whole row pairs and lanes, the same geometry.
-inline bool io_surface_ok(const ApplyIoArgs& a) {
-  return a.Cin == 3 && a.Cout == 3 && a.has_offset && a.H % 2 == 0 && a.W % 4 == 0 && io_geom(a).ok;
+// ... and of a YUV SURFACE: the same op, whole row pairs (4:2:0) and lanes, the same geometry.
+inline bool io_surface_ok(const ApplyIoArgs& a, int chroma = kChroma420) {
+  return a.Cin == 3 && a.Cout == 3 && a.has_offset && (chroma != kChroma420 || a.H % 2 == 0) && a.W % 4 == 0 && io_geom(a).ok;
 }
 
 }  // namespace
@@ -848,5 +900,6 @@ hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
 // apply_fwd_io_yuv.hip (launch.hip.h): the same launch for a YUV surface (a.yuv)
 // apply_fwd_io_u16.hip (launch.hip.h): the same launch with a 16-bit output (a.output_dtype == 2)
 // apply_fwd_io_yuv_planar.hip (launch.hip.h): the same launch for a planar YUV surface (a.yuvp)
+// apply_fwd_io_yuv_422.hip, apply_fwd_io_yuv_planar_422.hip / _444.hip (launch.hip.h): ... of another chroma layout
 
 }  // namespace hdrnet_amd

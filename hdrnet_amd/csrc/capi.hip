@@ -14,6 +14,7 @@
 #include "../../include/hdrnet_amd_pixel_formats.h"
 #include "../../include/hdrnet_amd_yuv.h"
 #include "../../include/hdrnet_amd_yuv_planar.h"
+#include "../../include/hdrnet_amd_yuv_chroma.h"
 #include "../../include/hdrnet_amd_u16_out.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_train.h"
@@ -259,9 +260,11 @@ int check_pixel_buffers(const char* what, int pixel_format, int Cin, int Cout, i
 
 // Pixel side, a semi-planar YUV 4:2:0 surface (include/hdrnet_amd_yuv.h).  The rules of one surface (`which`: "input" /
 // "output"), checked before any HIP call:
-int check_yuv_extents(const char* what, int B, int H, int W) {
+// (`chroma`, here and below: the surface's chroma layout, include/hdrnet_amd_yuv_chroma.h -- 4:2:2 and 4:4:4 have a chroma row
+// per image row: any H, and H rows in a chroma plane)
+int check_yuv_extents(const char* what, int B, int H, int W, int chroma = HDRNET_CHROMA_420) {
   if (B < 0 || H < 0 || W < 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: negative image extent (B=%d, H=%d, W=%d)", what, B, H, W);
-  if (H % 2 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: H %% 2 != 0 (H=%d): a chroma row serves two image rows", what, H);
+  if (chroma == HDRNET_CHROMA_420 && H % 2 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: H %% 2 != 0 (H=%d): a chroma row serves two image rows", what, H);
   if (W % 4 != 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: W %% 4 != 0 (W=%d): a lane owns 4 pixels", what, W);
   if (B > 65535 || H > 65535 || (long long)W * 12 >= (1LL << 31))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: image or batch too large (B, H <= 65535)", what);
@@ -269,7 +272,7 @@ int check_yuv_extents(const char* what, int B, int H, int W) {
 }
 
 int check_yuv_surface(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvSurface& s, int B, int H,
-                      int W) {
+                      int W, int chroma = HDRNET_CHROMA_420) {
   if (sample_dtype != 1 && sample_dtype != 2)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
                 sample_dtype);
@@ -283,7 +286,7 @@ int check_yuv_surface(const char* what, const char* which, int sample_dtype, con
   if (s.image_y < 0 || s.image_uv < 0 || ((s.image_y | s.image_uv) & 3))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4", what,
                 which);
-  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_uv < (long long)s.pitch_uv * (H / 2)))
+  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_uv < (long long)s.pitch_uv * hdrnet_amd::yuv_chroma_row(chroma, H)))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
   return HDRNET_OK;
 }
@@ -301,21 +304,23 @@ int check_yuv_pointers(const char* what, const char* which, const hdrnet_amd::Yu
 // is then kYuvOutP016 and the output a uint16 surface of io.out_bits bits.
 int check_yuv_io_values(const char* what, const hdrnet_amd::YuvIo& io, int sample_dtype, int B, int H, int W, int Cin, int Cout,
                         int has_offset, bool p016 = false) {
-  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
-  if (int rc = check_yuv_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
+  const bool c422 = io.chroma == HDRNET_CHROMA_422;
+  if (int rc = check_yuv_extents(what, B, H, W, io.chroma)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, io.in, B, H, W, io.chroma)) return rc;
   if (p016) {
     if (sample_dtype != 2)
-      return fail(HDRNET_INVALID_ARGUMENT, "%s: a P010 / P016 output needs a uint16 surface in (sample_dtype 2, got %d: no "
-                  "kernel goes from 8 to 16 bits)", what, sample_dtype);
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: a %s output needs a uint16 surface in (sample_dtype 2, got %d: no "
+                  "kernel goes from 8 to 16 bits)", what, c422 ? "P210 / P216" : "P010 / P016", sample_dtype);
     if (io.out_bits != 10 && io.out_bits != 16)
-      return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits must be 10 (P010) or 16 (P016), got %d", what, io.out_bits);
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits must be 10 (%s) or 16 (%s), got %d", what, c422 ? "P210" : "P010",
+                  c422 ? "P216" : "P016", io.out_bits);
   } else if (io.out_kind < HDRNET_YUV_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_OUT_NV12) {
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 NV12)", what, io.out_kind);
   }
   if (Cin != 3 || Cout != 3 || !has_offset)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
-  if (p016) return check_yuv_surface(what, "output", 2, io.out, B, H, W);
-  if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_surface(what, "output", 1, io.out, B, H, W);
+  if (p016) return check_yuv_surface(what, "output", 2, io.out, B, H, W, io.chroma);
+  if (io.out_kind == HDRNET_YUV_OUT_NV12) return check_yuv_surface(what, "output", 1, io.out, B, H, W, io.chroma);
   return HDRNET_OK;
 }
 
@@ -331,35 +336,41 @@ int check_yuv_io_pointers(const char* what, const hdrnet_amd::YuvIo& io) {
 // Pixel side, a PLANAR YUV 4:2:0 surface (include/hdrnet_amd_yuv_planar.h): the extents are check_yuv_extents'; each rule of
 // a surface is stated once below and shared by the four entry points (`which`: "input" / "output").
 int check_yuv_planar_surface(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvPlanarSurface& s, int B,
-                             int H, int W) {
+                             int H, int W, int chroma = HDRNET_CHROMA_420) {
   if (sample_dtype != 1 && sample_dtype != 2)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16)", what, which,
                 sample_dtype);
-  const long long row = (long long)W * sample_dtype, crow = row / 2;
+  const bool c444 = chroma == HDRNET_CHROMA_444;  // a chroma plane as wide as the luma: the luma's rules
+  const long long row = (long long)W * sample_dtype, crow = c444 ? row : row / 2;
   if (s.pitch_y < row || s.pitch_u < crow || s.pitch_v < crow)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: a pitch of the %s surface is below the row's bytes (%lld luma, %lld chroma; "
                 "pitch_y=%d, pitch_u=%d, pitch_v=%d)", what, which, row, crow, s.pitch_y, s.pitch_u, s.pitch_v);
   // a lane touches 4 luma samples (dwords) and 2 samples of each chroma plane: 2 bytes of uint8, 4 of uint16
-  const int cmask = sample_dtype == 1 ? 1 : 3;
+  // (4:4:4: 4 samples of each chroma plane, whole dwords)
+  const int cmask = sample_dtype == 1 && !c444 ? 1 : 3;
+  const char* const ckind = c444 ? "4:4:4" : sample_dtype == 1 ? "uint8" : "uint16";
   if ((s.pitch_y & 3) || ((s.pitch_u | s.pitch_v) & cmask))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitches of the %s surface must be multiples of 4 (luma) and of %d (%s chroma) "
-                "(pitch_y=%d, pitch_u=%d, pitch_v=%d)", what, which, cmask + 1, sample_dtype == 1 ? "uint8" : "uint16", s.pitch_y,
-                s.pitch_u, s.pitch_v);
+                "(pitch_y=%d, pitch_u=%d, pitch_v=%d)", what, which, cmask + 1, ckind, s.pitch_y, s.pitch_u, s.pitch_v);
   if (s.image_y < 0 || s.image_u < 0 || s.image_v < 0 || (s.image_y & 3) || ((s.image_u | s.image_v) & cmask))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the image strides of the %s surface must be non-negative multiples of 4 (luma) and "
-                "of %d (%s chroma)", what, which, cmask + 1, sample_dtype == 1 ? "uint8" : "uint16");
-  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_u < (long long)s.pitch_u * (H / 2) ||
-                s.image_v < (long long)s.pitch_v * (H / 2)))
+                "of %d (%s chroma)", what, which, cmask + 1, ckind);
+  const int crows = hdrnet_amd::yuv_chroma_row(chroma, H);
+  if (B > 1 && (s.image_y < (long long)s.pitch_y * H || s.image_u < (long long)s.pitch_u * crows ||
+                s.image_v < (long long)s.pitch_v * crows))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: an image stride of the %s surface is below its plane (pitch * rows)", what, which);
   return HDRNET_OK;
 }
 
 int check_yuv_planar_pointers(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvPlanarSurface& s,
-                              const float* coef) {
+                              const float* coef, int chroma = HDRNET_CHROMA_420) {
   if (!s.y || !s.u || !s.v) return fail(HDRNET_INVALID_ARGUMENT, "%s: null plane of the %s surface", what, which);
   if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
   if (((uintptr_t)s.y | (uintptr_t)coef) & 3u)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the Y plane and constants of the %s surface must be 4-B aligned", what, which);
+  if (chroma == HDRNET_CHROMA_444 && (((uintptr_t)s.u | (uintptr_t)s.v) & 3u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the chroma planes of the %s surface must be 4-B aligned (4:4:4: a lane touches 4 "
+                "samples of each, as of the luma)", what, which);
   if (((uintptr_t)s.u | (uintptr_t)s.v) & (sample_dtype == 1 ? 1u : 3u))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: the chroma planes of the %s surface must be %d-B aligned (%s samples: a lane "
                 "touches 2 of them)", what, which, sample_dtype == 1 ? 2 : 4, sample_dtype == 1 ? "uint8" : "uint16");
@@ -369,8 +380,8 @@ int check_yuv_planar_pointers(const char* what, const char* which, int sample_dt
 // ... and of a fused forward's surfaces and output.  io.out.y is `out` whatever the output kind.
 int check_yuv_planar_io_values(const char* what, const hdrnet_amd::YuvPlanarIo& io, int sample_dtype, int B, int H, int W,
                                int Cin, int Cout, int has_offset) {
-  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
-  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
+  if (int rc = check_yuv_extents(what, B, H, W, io.chroma)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, io.in, B, H, W, io.chroma)) return rc;
   if (io.out_kind < HDRNET_YUV_PLANAR_OUT_RGB_F32 || io.out_kind > HDRNET_YUV_PLANAR_OUT_PLANAR)
     return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 a planar surface of the "
                 "input's sample dtype)", what, io.out_kind);
@@ -380,13 +391,13 @@ int check_yuv_planar_io_values(const char* what, const hdrnet_amd::YuvPlanarIo& 
   if (sample_dtype == 1 ? io.out_bits != 8 : (io.out_bits != 10 && io.out_bits != 16))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits does not fit the sample dtype: a planar output has the input's (uint8 "
                 "samples: 8; uint16 samples: 10 or 16; got out_bits = %d for sample_dtype %d)", what, io.out_bits, sample_dtype);
-  return check_yuv_planar_surface(what, "output", sample_dtype, io.out, B, H, W);
+  return check_yuv_planar_surface(what, "output", sample_dtype, io.out, B, H, W, io.chroma);
 }
 
 int check_yuv_planar_io_pointers(const char* what, const hdrnet_amd::YuvPlanarIo& io, int sample_dtype) {
-  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, io.in, io.to_rgb)) return rc;
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, io.in, io.to_rgb, io.chroma)) return rc;
   if (io.out_kind == HDRNET_YUV_PLANAR_OUT_PLANAR)
-    return check_yuv_planar_pointers(what, "output", sample_dtype, io.out, io.from_rgb);
+    return check_yuv_planar_pointers(what, "output", sample_dtype, io.out, io.from_rgb, io.chroma);
   if (!io.out.y || ((uintptr_t)io.out.y & (io.out_kind == HDRNET_YUV_PLANAR_OUT_RGB_F32 ? 15u : 3u)))
     return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
   return HDRNET_OK;
@@ -585,7 +596,9 @@ extern "C" {
 // 0.2.8.9: + include/hdrnet_amd_yuv_planar.h: hdrnet_yuv_planar_to_rgb_f32, hdrnet_lowres_input_yuv_planar,
 //          hdrnet_bilateral_slice_apply_io_yuv_planar, hdrnet_bilateral_slice_apply_io_curves_yuv_planar (I420 / yuv420p10le /
 //          yuv420p16le surfaces in, RGB or a planar surface out)
-int hdrnet_version(void) { return 289; }
+// 0.2.9.0: + include/hdrnet_amd_yuv_chroma.h: the eight entry points of the three headers above with a `chroma` argument (4:2:2
+//          NV16 / P210 / P216 / yuv422p..., 4:4:4 yuv444p... surfaces in, RGB or a surface of the input's container and layout out)
+int hdrnet_version(void) { return 290; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -1346,7 +1359,10 @@ static int apply_io_yuv_impl(const char* what, bool p016, const float* grid, con
   }
   a.yuv = &io;
   return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuv" : "BilateralSliceApplyIOYuv",
-                   "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers", stream);
+                   io.chroma != HDRNET_CHROMA_420
+                       ? "the 4:2:2 YUV forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned buffers"
+                       : "the YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers",
+                   stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_yuv(const float* grid, const float* guide, const void* y, const void* uv,
@@ -1494,7 +1510,10 @@ static int apply_io_yuv_planar_impl(const char* what, const float* grid, const I
   }
   a.yuvp = &io;
   return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuvPlanar" : "BilateralSliceApplyIOYuvPlanar",
-                   "the planar YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers", stream);
+                   io.chroma != HDRNET_CHROMA_420
+                       ? "the 4:2:2 / 4:4:4 planar YUV forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned buffers"
+                       : "the planar YUV forward supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers",
+                   stream);
 }
 
 int hdrnet_bilateral_slice_apply_io_yuv_planar(const float* grid, const float* guide, const void* y, const void* u,
@@ -1731,6 +1750,261 @@ int hdrnet_lowres_input_yuv_planar(const void* y, const void* u, const void* v, 
   a.yuv_planar = &in;
   a.yuv_to_rgb = to_rgb;
   return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+// ---- include/hdrnet_amd_yuv_chroma.h: 4:2:2 / 4:4:4 surfaces -- the entry points above with a chroma layout -------------------
+// With HDRNET_CHROMA_420 each one forwards to the entry point it mirrors; otherwise it runs that entry point's body -- the same
+// checks in the same order -- with the layout in the surface rules.
+namespace {
+
+// the layout code, for a semi-planar (`planar` false: no 4:4:4) or a planar surface
+int check_chroma_code(const char* what, int chroma, bool planar) {
+  if (chroma < HDRNET_CHROMA_420 || chroma > HDRNET_CHROMA_444)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown chroma layout code %d (0 4:2:0, 1 4:2:2, 2 4:4:4)", what, chroma);
+  if (!planar && chroma == HDRNET_CHROMA_444)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: semi-planar 4:4:4 (NV24 / P410) is out of scope: 4:4:4 surfaces are planar "
+                "(yuv444p, yuv444p10le / yuv444p16le)", what);
+  return HDRNET_OK;
+}
+
+// the output kind; a planar surface output has the input's sample width
+int check_chroma_out_kind(const char* what, int kind, int sample_dtype, bool planar) {
+  if (kind < HDRNET_CHROMA_OUT_RGB_F32 || kind > HDRNET_CHROMA_OUT_SURFACE_U16)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown output kind %d (0 float32 RGB, 1 uint8 RGB, 2 a uint8 surface, 3 a uint16 "
+                "surface of the input's container and chroma layout)", what, kind);
+  if (planar && kind >= HDRNET_CHROMA_OUT_SURFACE_U8 && (sample_dtype == 1 || sample_dtype == 2) &&
+      (kind == HDRNET_CHROMA_OUT_SURFACE_U8) != (sample_dtype == 1))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a planar surface output has the input's sample width (output kind %d, a %s surface, "
+                "for sample_dtype %d)", what, kind, kind == HDRNET_CHROMA_OUT_SURFACE_U8 ? "uint8" : "uint16", sample_dtype);
+  return HDRNET_OK;
+}
+
+}  // namespace
+
+int hdrnet_yuv_chroma_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                                 long long image_stride_y, long long image_stride_uv, int chroma, int B, int H, int W,
+                                 const float* to_rgb, float* rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_yuv_chroma_to_rgb_f32";
+  if (int rc = check_chroma_code(what, chroma, false)) return rc;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_yuv_to_rgb_f32(y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb, rgb,
+                                 stream);
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  if (int rc = check_yuv_extents(what, B, H, W, chroma)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, in, B, H, W, chroma)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", in, to_rgb)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
+  return finish_launch(launch_yuv_422_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, static_cast<hipStream_t>(stream)), what,
+                       "yuv_422_to_rgb");
+}
+
+int hdrnet_yuv_planar_chroma_to_rgb_f32(const void* y, const void* u, const void* v, int sample_dtype, int pitch_y,
+                                        int pitch_u, int pitch_v, long long image_stride_y, long long image_stride_u,
+                                        long long image_stride_v, int chroma, int B, int H, int W, const float* to_rgb,
+                                        float* rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_yuv_planar_chroma_to_rgb_f32";
+  if (int rc = check_chroma_code(what, chroma, true)) return rc;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_yuv_planar_to_rgb_f32(y, u, v, sample_dtype, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u,
+                                        image_stride_v, B, H, W, to_rgb, rgb, stream);
+  const YuvPlanarSurface in{y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v};
+  if (int rc = check_yuv_extents(what, B, H, W, chroma)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, in, B, H, W, chroma)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, in, to_rgb, chroma)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  if (chroma == HDRNET_CHROMA_422)
+    return finish_launch(launch_yuv_planar_422_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, s), what, "yuv_planar_422_to_rgb");
+  return finish_launch(launch_yuv_planar_444_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, s), what, "yuv_planar_444_to_rgb");
+}
+
+int hdrnet_lowres_input_yuv_chroma(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                                   long long image_stride_y, long long image_stride_uv, int chroma, int B, int H, int W,
+                                   const float* to_rgb, float* lowres, int net_input_size, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_lowres_input_yuv_chroma";
+  if (int rc = check_chroma_code(what, chroma, false)) return rc;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_lowres_input_yuv(y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv, B, H, W, to_rgb,
+                                   lowres, net_input_size, stream);
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  if (int rc = check_yuv_extents(what, B, H, W, chroma)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, in, B, H, W, chroma)) return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", in, to_rgb)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
+                   false};
+  a.yuv = &in;
+  a.yuv_to_rgb = to_rgb;
+  a.yuv_chroma = chroma;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+int hdrnet_lowres_input_yuv_planar_chroma(const void* y, const void* u, const void* v, int sample_dtype, int pitch_y,
+                                          int pitch_u, int pitch_v, long long image_stride_y, long long image_stride_u,
+                                          long long image_stride_v, int chroma, int B, int H, int W, const float* to_rgb,
+                                          float* lowres, int net_input_size, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_lowres_input_yuv_planar_chroma";
+  if (int rc = check_chroma_code(what, chroma, true)) return rc;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_lowres_input_yuv_planar(y, u, v, sample_dtype, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u,
+                                          image_stride_v, B, H, W, to_rgb, lowres, net_input_size, stream);
+  const YuvPlanarSurface in{y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v};
+  if (int rc = check_yuv_extents(what, B, H, W, chroma)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, in, B, H, W, chroma)) return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, in, to_rgb, chroma)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  SamplePrepArgs a{y, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres, net_input_size,
+                   false};
+  a.yuv_planar = &in;
+  a.yuv_to_rgb = to_rgb;
+  a.yuv_chroma = chroma;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv_chroma(const float* grid, const float* guide, const void* y, const void* uv,
+                                               int sample_dtype, int pitch_y, int pitch_uv, long long image_stride_y,
+                                               long long image_stride_uv, int chroma, int B, int H, int W,
+                                               const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                               int has_offset, const float* guide_conv1, const float* guide_conv2,
+                                               int n_feats, float* guide_out, unsigned flags, int output_kind, void* out,
+                                               void* out_uv, int out_pitch_y, int out_pitch_uv,
+                                               long long out_image_stride_y, long long out_image_stride_uv,
+                                               const float* from_rgb, int out_bits, void* stream) {
+  const char* what = "hdrnet_bilateral_slice_apply_io_yuv_chroma";
+  if (int rc = check_chroma_code(what, chroma, false)) return rc;
+  if (int rc = check_chroma_out_kind(what, output_kind, sample_dtype, false)) return rc;
+  const bool deep = output_kind == HDRNET_CHROMA_OUT_SURFACE_U16;
+  if (chroma == HDRNET_CHROMA_420) {
+    if (deep)
+      return hdrnet_bilateral_slice_apply_io_yuv_p016(grid, guide, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y,
+                                                      image_stride_uv, B, H, W, to_rgb, GH, GW, GD, Cin, Cout, has_offset,
+                                                      guide_conv1, guide_conv2, n_feats, guide_out, flags, out, out_uv,
+                                                      out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv,
+                                                      from_rgb, out_bits, stream);
+    return hdrnet_bilateral_slice_apply_io_yuv(grid, guide, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y,
+                                               image_stride_uv, B, H, W, to_rgb, GH, GW, GD, Cin, Cout, has_offset,
+                                               guide_conv1, guide_conv2, n_feats, guide_out, flags, output_kind, out, out_uv,
+                                               out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv, from_rgb,
+                                               stream);
+  }
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+                             {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb,
+                             deep ? out_bits : 0, chroma};
+  return apply_io_yuv_impl(what, deep, grid, io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io,
+                           sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv_chroma(const float* grid, const void* y, const void* uv, int sample_dtype,
+                                                      int pitch_y, int pitch_uv, long long image_stride_y,
+                                                      long long image_stride_uv, int chroma, int B, int H, int W,
+                                                      const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                                      int has_offset, const float* guide_ccm, const float* guide_shifts,
+                                                      const float* guide_slopes, const float* guide_mix, int npts,
+                                                      const void* prepared, float* guide_out, int output_kind, void* out,
+                                                      void* out_uv, int out_pitch_y, int out_pitch_uv,
+                                                      long long out_image_stride_y, long long out_image_stride_uv,
+                                                      const float* from_rgb, int out_bits, void* stream) {
+  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv_chroma";
+  if (int rc = check_chroma_code(what, chroma, false)) return rc;
+  if (int rc = check_chroma_out_kind(what, output_kind, sample_dtype, false)) return rc;
+  const bool deep = output_kind == HDRNET_CHROMA_OUT_SURFACE_U16;
+  if (chroma == HDRNET_CHROMA_420) {
+    if (deep)
+      return hdrnet_bilateral_slice_apply_io_curves_yuv_p016(grid, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y,
+                                                             image_stride_uv, B, H, W, to_rgb, GH, GW, GD, Cin, Cout,
+                                                             has_offset, guide_ccm, guide_shifts, guide_slopes, guide_mix,
+                                                             npts, prepared, guide_out, out, out_uv, out_pitch_y,
+                                                             out_pitch_uv, out_image_stride_y, out_image_stride_uv, from_rgb,
+                                                             out_bits, stream);
+    return hdrnet_bilateral_slice_apply_io_curves_yuv(grid, y, uv, sample_dtype, pitch_y, pitch_uv, image_stride_y,
+                                                      image_stride_uv, B, H, W, to_rgb, GH, GW, GD, Cin, Cout, has_offset,
+                                                      guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared,
+                                                      guide_out, output_kind, out, out_uv, out_pitch_y, out_pitch_uv,
+                                                      out_image_stride_y, out_image_stride_uv, from_rgb, stream);
+  }
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+                             {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb,
+                             deep ? out_bits : 0, chroma};
+  return apply_io_yuv_impl(what, deep, grid,
+                           io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out), io,
+                           sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv_planar_chroma(const float* grid, const float* guide, const void* y, const void* u,
+                                                      const void* v, int sample_dtype, int pitch_y, int pitch_u,
+                                                      int pitch_v, long long image_stride_y, long long image_stride_u,
+                                                      long long image_stride_v, int chroma, int B, int H, int W,
+                                                      const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                                      int has_offset, const float* guide_conv1, const float* guide_conv2,
+                                                      int n_feats, float* guide_out, unsigned flags, int output_kind,
+                                                      void* out, void* out_u, void* out_v, int out_pitch_y, int out_pitch_u,
+                                                      int out_pitch_v, long long out_image_stride_y,
+                                                      long long out_image_stride_u, long long out_image_stride_v,
+                                                      const float* from_rgb, int out_bits, void* stream) {
+  const char* what = "hdrnet_bilateral_slice_apply_io_yuv_planar_chroma";
+  if (int rc = check_chroma_code(what, chroma, true)) return rc;
+  if (int rc = check_chroma_out_kind(what, output_kind, sample_dtype, true)) return rc;
+  // (both surface kinds are the planar header's one: a planar surface of the input's sample dtype)
+  const int kind = output_kind >= HDRNET_CHROMA_OUT_SURFACE_U8 ? HDRNET_YUV_PLANAR_OUT_PLANAR : output_kind;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_bilateral_slice_apply_io_yuv_planar(grid, guide, y, u, v, sample_dtype, pitch_y, pitch_u, pitch_v,
+                                                      image_stride_y, image_stride_u, image_stride_v, B, H, W, to_rgb, GH, GW,
+                                                      GD, Cin, Cout, has_offset, guide_conv1, guide_conv2, n_feats, guide_out,
+                                                      flags, kind, out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v,
+                                                      out_image_stride_y, out_image_stride_u, out_image_stride_v, from_rgb,
+                                                      out_bits, stream);
+  const hdrnet_amd::YuvPlanarIo io{
+      {y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v}, to_rgb, kind,
+      {out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v, out_image_stride_y, out_image_stride_u, out_image_stride_v},
+      from_rgb, out_bits, chroma};
+  return apply_io_yuv_planar_impl(what, grid, io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io,
+                                  sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv_planar_chroma(const float* grid, const void* y, const void* u, const void* v,
+                                                             int sample_dtype, int pitch_y, int pitch_u, int pitch_v,
+                                                             long long image_stride_y, long long image_stride_u,
+                                                             long long image_stride_v, int chroma, int B, int H, int W,
+                                                             const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                                             int has_offset, const float* guide_ccm,
+                                                             const float* guide_shifts, const float* guide_slopes,
+                                                             const float* guide_mix, int npts, const void* prepared,
+                                                             float* guide_out, int output_kind, void* out, void* out_u,
+                                                             void* out_v, int out_pitch_y, int out_pitch_u, int out_pitch_v,
+                                                             long long out_image_stride_y, long long out_image_stride_u,
+                                                             long long out_image_stride_v, const float* from_rgb,
+                                                             int out_bits, void* stream) {
+  const char* what = "hdrnet_bilateral_slice_apply_io_curves_yuv_planar_chroma";
+  if (int rc = check_chroma_code(what, chroma, true)) return rc;
+  if (int rc = check_chroma_out_kind(what, output_kind, sample_dtype, true)) return rc;
+  const int kind = output_kind >= HDRNET_CHROMA_OUT_SURFACE_U8 ? HDRNET_YUV_PLANAR_OUT_PLANAR : output_kind;
+  if (chroma == HDRNET_CHROMA_420)
+    return hdrnet_bilateral_slice_apply_io_curves_yuv_planar(grid, y, u, v, sample_dtype, pitch_y, pitch_u, pitch_v,
+                                                             image_stride_y, image_stride_u, image_stride_v, B, H, W, to_rgb,
+                                                             GH, GW, GD, Cin, Cout, has_offset, guide_ccm, guide_shifts,
+                                                             guide_slopes, guide_mix, npts, prepared, guide_out, kind, out,
+                                                             out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v,
+                                                             out_image_stride_y, out_image_stride_u, out_image_stride_v,
+                                                             from_rgb, out_bits, stream);
+  const hdrnet_amd::YuvPlanarIo io{
+      {y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v}, to_rgb, kind,
+      {out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v, out_image_stride_y, out_image_stride_u, out_image_stride_v},
+      from_rgb, out_bits, chroma};
+  return apply_io_yuv_planar_impl(what, grid,
+                                  io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
+                                  io, sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 size_t hdrnet_bilateral_slice_apply_grad_workspace_bytes(int B, int H, int W, int GH, int GW,

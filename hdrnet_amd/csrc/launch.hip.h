@@ -80,6 +80,7 @@ struct YuvIo {
   YuvSurface out;         // out_kind == HDRNET_YUV_OUT_NV12 / kYuvOutP016
   const float* from_rgb;  // device, 12 floats
   int out_bits = 0;       // kYuvOutP016: 10 or 16 significant bits per sample, in the high bits
+  int chroma = kChroma420;  // both surfaces' chroma layout (include/hdrnet_amd_yuv_chroma.h): kChroma420 / kChroma422
 };
 
 // The planar counterpart (include/hdrnet_amd_yuv_planar.h): out_kind is HDRNET_YUV_PLANAR_OUT_* -- a float32 / uint8 RGB
@@ -93,6 +94,7 @@ struct YuvPlanarIo {
   YuvPlanarSurface out;   // out_kind == kYuvPlanarOutPlanar
   const float* from_rgb;  // device, 12 floats
   int out_bits = 0;       // kYuvPlanarOutPlanar: 8 (uint8 samples), 10 or 16 (uint16): the code's bits, in the LOW bits
+  int chroma = kChroma420;  // both surfaces' chroma layout (include/hdrnet_amd_yuv_chroma.h): kChroma420 / 422 / 444
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -264,6 +266,8 @@ struct SamplePrepArgs {
   const float* yuv_to_rgb = nullptr;
   // ... or of a planar one (hdrnet_lowres_input_yuv_planar): yuv_to_rgb as above
   const YuvPlanarSurface* yuv_planar = nullptr;
+  // the surface's chroma layout (include/hdrnet_amd_yuv_chroma.h): kChroma420 / kChroma422 / kChroma444 (planar only)
+  int yuv_chroma = kChroma420;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 
@@ -281,6 +285,20 @@ bool apply_fwd_io_yuv_planar_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io_yuv_planar(const ApplyIoArgs& a, hipStream_t s, const char** name);
 hipError_t launch_yuv_planar_to_rgb(const YuvPlanarSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H,
                                     int W, hipStream_t s);
+// apply_fwd_io_yuv_422.hip, apply_fwd_io_yuv_planar_422.hip / _444.hip -- the same forwards and conversions for surfaces of
+// another chroma layout (include/hdrnet_amd_yuv_chroma.h: a.yuv->chroma / a.yuvp->chroma != kChroma420), every output kind
+// of theirs, the P210 / P216 one (kYuvOutP016) included
+bool apply_fwd_io_yuv_422_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_yuv_422(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_yuv_422_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,
+                                 hipStream_t s);
+bool apply_fwd_io_yuv_planar_chroma_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_yuv_planar_422(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_apply_fwd_io_yuv_planar_444(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_yuv_planar_422_to_rgb(const YuvPlanarSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B,
+                                        int H, int W, hipStream_t s);
+hipError_t launch_yuv_planar_444_to_rgb(const YuvPlanarSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B,
+                                        int H, int W, hipStream_t s);
 // apply_fwd_io_u16.hip -- the same forward with a 16-bit output (a.output_dtype == 2): a uint16 frame in the input's pixel
 // format, or (a.yuv, out_kind == kYuvOutP016) a P010 / P016 surface
 bool apply_fwd_io_u16_supported(const ApplyIoArgs& a);

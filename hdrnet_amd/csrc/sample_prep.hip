@@ -82,6 +82,7 @@ struct PrepParams {
   const float* yuv_to_rgb;
   // ... of a planar one (hdrnet_lowres_input_yuv_planar, job kind 3): three planes, the same constants
   YuvPlanarSurface yuv_planar;
+  int yuv_chroma;  // the surface's chroma layout (yuv_convert.hip.h: kChroma420 / 422 / 444; include/hdrnet_amd_yuv_chroma.h)
 };
 
 typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
@@ -348,7 +349,8 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
 // hdrnet_lowres_input's), its luma from (y, x) and its chroma from (y >> 1, x >> 1), converted by yuv_to_rgb_px -- the
 // bits of lowres_job on the float32 frame hdrnet_yuv_to_rgb_f32 writes.
 // (`surf`: p.yuv, or p.yuv_planar for a planar surface -- the chroma then comes from two planes)
-template <typename T, typename SURF>
+// (CH: the surface's chroma layout -- 4:2:2 takes the chroma from (y, x >> 1), 4:4:4 from (y, x))
+template <typename T, int CH, typename SURF>
 __device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const SURF& surf, const PrepJob& job, int b) {
   const int npx = p.n * p.n;
   float* out = job.dst + (long long)b * npx * 3;
@@ -363,7 +365,7 @@ __device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const SURF& 
       int y = (int)__builtin_floorf((float)yl * p.scale_y), x = (int)__builtin_floorf((float)xl * p.scale_x);
       y = y < p.H - 1 ? y : p.H - 1;
       x = x < p.W - 1 ? x : p.W - 1;
-      yuv_load_px<T>(surf, k, b, y, x, v[j]);
+      yuv_load_px<T, CH>(surf, k, b, y, x, v[j]);
     }
     store_lowres_4px(out, px0, npx, vec, v);
   }
@@ -377,11 +379,20 @@ __global__ __launch_bounds__(kThreads) void sample_prep_kernel(const PrepParams 
   if (job.lowres >= 2) {  // a YUV surface, semi-planar (2) or planar (3): no geometry record, no packed source
     if constexpr (!RAGGED) {
       if (job.lowres == 2) {
-        if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, p.yuv, job, b);
-        else lowres_job_yuv<uint16_t>(p, p.yuv, job, b);
+        if (p.yuv_chroma == kChroma422) {
+          if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma422>(p, p.yuv, job, b);
+          else lowres_job_yuv<uint16_t, kChroma422>(p, p.yuv, job, b);
+        } else if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma420>(p, p.yuv, job, b);
+        else lowres_job_yuv<uint16_t, kChroma420>(p, p.yuv, job, b);
       } else {
-        if (job.dtype == 1) lowres_job_yuv<uint8_t>(p, p.yuv_planar, job, b);
-        else lowres_job_yuv<uint16_t>(p, p.yuv_planar, job, b);
+        if (p.yuv_chroma == kChroma422) {
+          if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma422>(p, p.yuv_planar, job, b);
+          else lowres_job_yuv<uint16_t, kChroma422>(p, p.yuv_planar, job, b);
+        } else if (p.yuv_chroma == kChroma444) {
+          if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma444>(p, p.yuv_planar, job, b);
+          else lowres_job_yuv<uint16_t, kChroma444>(p, p.yuv_planar, job, b);
+        } else if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma420>(p, p.yuv_planar, job, b);
+        else lowres_job_yuv<uint16_t, kChroma420>(p, p.yuv_planar, job, b);
       }
     }
     return;
@@ -421,6 +432,7 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.n_samples = a.n_samples;
   p.px_stride = px_stored(a.pixel_format);
   p.px_b_first = px_b_first(a.pixel_format) ? 1 : 0;
+  p.yuv_chroma = a.yuv_chroma;
   if (a.yuv) {
     p.yuv = *a.yuv;
     p.yuv_to_rgb = a.yuv_to_rgb;

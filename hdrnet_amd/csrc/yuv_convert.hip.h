@@ -1,6 +1,7 @@
 // Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out -- and
 // P010 / P016 out (include/hdrnet_amd_u16_out.h) -- and planar surfaces, I420 / yuv420p10le / yuv420p16le, in and out
-// (include/hdrnet_amd_yuv_planar.h): the same functions with the chroma in two planes.
+// (include/hdrnet_amd_yuv_planar.h): the same functions with the chroma in two planes -- and 4:2:2 / 4:4:4 surfaces
+// (include/hdrnet_amd_yuv_chroma.h): the same functions with a compile-time chroma layout, 4:2:0 by default.
 //
 // Every kernel that reads a surface -- hdrnet_yuv_to_rgb_f32 (apply_fwd_io_yuv.hip), the low-res gather
 // (sample_prep.hip) and the fused forward (apply_fwd_io.hip.h) -- converts a pixel with the ONE function below, and the
@@ -24,6 +25,12 @@ struct YuvSurface {
   int pitch_y, pitch_uv;
   long long image_y, image_uv;
 };
+
+// Chroma layout of a surface (include/hdrnet_amd_yuv_chroma.h), a compile-time axis of every load and store below: which
+// chroma sample serves pixel (y, x).  4:2:0 (y >> 1, x >> 1), the default and the only one the headers above know; 4:2:2
+// (y, x >> 1); 4:4:4 (y, x), planar surfaces only.  Chroma is replicated in all three.
+constexpr int kChroma420 = 0, kChroma422 = 1, kChroma444 = 2;
+__host__ __device__ constexpr int yuv_chroma_row(int chroma, int row) { return chroma == kChroma420 ? row >> 1 : row; }
 
 typedef __attribute__((address_space(4))) const float yuv_cfloat;  // the 12 constants: wave-uniform, s_load
 
@@ -54,12 +61,14 @@ __device__ __forceinline__ void yuv_to_rgb_px(const YuvMatrix& k, float Y, float
 // A lane's 4 pixels x .. x + 3 of image row `row` (x % 4 == 0): one dword of Y and one of UV for uint8 samples, two of
 // each for uint16 -- the chroma pairs (x >> 1) and (x >> 1) + 1 of chroma row (row >> 1) start at the same sample offset x
 // of their row as the luma does in its own.  rgb[3 q + c]: pixel q, channel c (R, G, B).  Chroma is replicated.
-template <typename TI>
+// (CH == kChroma422, NV16 / P210 / P216: the same access into chroma row `row`.)
+template <typename TI, int CH = kChroma420>
 __device__ __forceinline__ void yuv_load_quad(const YuvSurface& s, const YuvMatrix& k, int b, int row, int x,
                                               float* __restrict__ rgb) {
   static_assert(sizeof(TI) == 1 || sizeof(TI) == 2, "uint8 or uint16 samples");
+  static_assert(CH == kChroma420 || CH == kChroma422, "semi-planar 4:4:4 (NV24, P410) is out of scope");
   const char* yp = static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y + (size_t)x * sizeof(TI);
-  const char* cp = static_cast<const char*>(s.uv) + (long long)b * s.image_uv + (long long)(row >> 1) * s.pitch_uv + (size_t)x * sizeof(TI);
+  const char* cp = static_cast<const char*>(s.uv) + (long long)b * s.image_uv + (long long)yuv_chroma_row(CH, row) * s.pitch_uv + (size_t)x * sizeof(TI);
   float Y[4], U[2], V[2];
   if constexpr (sizeof(TI) == 1) {
     const uint32_t wy = *reinterpret_cast<const uint32_t*>(yp);
@@ -82,12 +91,13 @@ __device__ __forceinline__ void yuv_load_quad(const YuvSurface& s, const YuvMatr
 }
 
 // One pixel (row, x) of a surface, any x: scalar sample loads (the low-res gather).
-template <typename TI>
+template <typename TI, int CH = kChroma420>
 __device__ __forceinline__ void yuv_load_px(const YuvSurface& s, const YuvMatrix& k, int b, int row, int x,
                                             float* __restrict__ rgb) {
+  static_assert(CH == kChroma420 || CH == kChroma422, "semi-planar 4:4:4 (NV24, P410) is out of scope");
   const TI* yp = reinterpret_cast<const TI*>(static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y);
   const TI* cp = reinterpret_cast<const TI*>(static_cast<const char*>(s.uv) + (long long)b * s.image_uv +
-                                             (long long)(row >> 1) * s.pitch_uv);
+                                             (long long)yuv_chroma_row(CH, row) * s.pitch_uv);
   const int xc = (x >> 1) * 2;
   yuv_to_rgb_px(k, (float)yp[x], (float)cp[xc], (float)cp[xc + 1], rgb);
 }
@@ -107,46 +117,65 @@ struct YuvPlanarSurface {
 // (row >> 1) are one 16-bit load from each of U and V for uint8 samples (the chroma planes promise 2-byte alignment, and
 // x / 2 is even), one dword from each for uint16 (4-byte alignment); the luma is yuv_load_quad's.  The same
 // yuv_to_rgb_px on the same samples: the bits of yuv_load_quad on the interleaved surface.
-template <typename TI>
+// (CH == kChroma422, yuv422p...: the same accesses into chroma row `row`.  CH == kChroma444, yuv444p...: the lane's four U and
+// four V samples x .. x + 3 of chroma row `row` -- one dword from each plane for uint8 samples, two from each for uint16:
+// a 4:4:4 chroma plane promises the luma's alignment.)
+template <typename TI, int CH = kChroma420>
 __device__ __forceinline__ void yuv_load_quad(const YuvPlanarSurface& s, const YuvMatrix& k, int b, int row, int x,
                                               float* __restrict__ rgb) {
   static_assert(sizeof(TI) == 1 || sizeof(TI) == 2, "uint8 or uint16 samples");
+  constexpr bool FULL = CH == kChroma444;  // one chroma sample per pixel
+  constexpr int NC = FULL ? 4 : 2;         // chroma samples of each plane per lane
   const char* yp = static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y + (size_t)x * sizeof(TI);
-  const size_t xc = (size_t)(x >> 1) * sizeof(TI);
-  const char* up = static_cast<const char*>(s.u) + (long long)b * s.image_u + (long long)(row >> 1) * s.pitch_u + xc;
-  const char* vp = static_cast<const char*>(s.v) + (long long)b * s.image_v + (long long)(row >> 1) * s.pitch_v + xc;
-  float Y[4], U[2], V[2];
+  const size_t xc = (size_t)(FULL ? x : x >> 1) * sizeof(TI);
+  const char* up = static_cast<const char*>(s.u) + (long long)b * s.image_u + (long long)yuv_chroma_row(CH, row) * s.pitch_u + xc;
+  const char* vp = static_cast<const char*>(s.v) + (long long)b * s.image_v + (long long)yuv_chroma_row(CH, row) * s.pitch_v + xc;
+  float Y[4], U[NC], V[NC];
   if constexpr (sizeof(TI) == 1) {
     const uint32_t wy = *reinterpret_cast<const uint32_t*>(yp);
-    const uint32_t wu = *reinterpret_cast<const uint16_t*>(up);
-    const uint32_t wv = *reinterpret_cast<const uint16_t*>(vp);
 #pragma unroll
     for (int q = 0; q < 4; ++q) Y[q] = (float)((wy >> (8 * q)) & 0xffu);
-    U[0] = (float)(wu & 0xffu); U[1] = (float)(wu >> 8);
-    V[0] = (float)(wv & 0xffu); V[1] = (float)(wv >> 8);
+    if constexpr (FULL) {
+      const uint32_t wu = *reinterpret_cast<const uint32_t*>(up);
+      const uint32_t wv = *reinterpret_cast<const uint32_t*>(vp);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        U[q] = (float)((wu >> (8 * q)) & 0xffu);
+        V[q] = (float)((wv >> (8 * q)) & 0xffu);
+      }
+    } else {
+      const uint32_t wu = *reinterpret_cast<const uint16_t*>(up);
+      const uint32_t wv = *reinterpret_cast<const uint16_t*>(vp);
+      U[0] = (float)(wu & 0xffu); U[1] = (float)(wu >> 8);
+      V[0] = (float)(wv & 0xffu); V[1] = (float)(wv >> 8);
+    }
   } else {
     const uint2 wy = make_uint2(reinterpret_cast<const uint32_t*>(yp)[0], reinterpret_cast<const uint32_t*>(yp)[1]);
-    const uint32_t wu = *reinterpret_cast<const uint32_t*>(up);
-    const uint32_t wv = *reinterpret_cast<const uint32_t*>(vp);
     Y[0] = (float)(wy.x & 0xffffu); Y[1] = (float)(wy.x >> 16);
     Y[2] = (float)(wy.y & 0xffffu); Y[3] = (float)(wy.y >> 16);
-    U[0] = (float)(wu & 0xffffu); U[1] = (float)(wu >> 16);
-    V[0] = (float)(wv & 0xffffu); V[1] = (float)(wv >> 16);
+#pragma unroll
+    for (int d = 0; d < NC / 2; ++d) {  // (dwords: the planes promise 4-byte alignment, not 8)
+      const uint32_t wu = reinterpret_cast<const uint32_t*>(up)[d];
+      const uint32_t wv = reinterpret_cast<const uint32_t*>(vp)[d];
+      U[2 * d] = (float)(wu & 0xffffu); U[2 * d + 1] = (float)(wu >> 16);
+      V[2 * d] = (float)(wv & 0xffffu); V[2 * d + 1] = (float)(wv >> 16);
+    }
   }
 #pragma unroll
-  for (int q = 0; q < 4; ++q) yuv_to_rgb_px(k, Y[q], U[q >> 1], V[q >> 1], rgb + 3 * q);
+  for (int q = 0; q < 4; ++q) yuv_to_rgb_px(k, Y[q], U[FULL ? q : q >> 1], V[FULL ? q : q >> 1], rgb + 3 * q);
 }
 
 // One pixel (row, x) of a planar surface, any x: scalar sample loads (the low-res gather).
-template <typename TI>
+template <typename TI, int CH = kChroma420>
 __device__ __forceinline__ void yuv_load_px(const YuvPlanarSurface& s, const YuvMatrix& k, int b, int row, int x,
                                             float* __restrict__ rgb) {
   const TI* yp = reinterpret_cast<const TI*>(static_cast<const char*>(s.y) + (long long)b * s.image_y + (long long)row * s.pitch_y);
   const TI* up = reinterpret_cast<const TI*>(static_cast<const char*>(s.u) + (long long)b * s.image_u +
-                                             (long long)(row >> 1) * s.pitch_u);
+                                             (long long)yuv_chroma_row(CH, row) * s.pitch_u);
   const TI* vp = reinterpret_cast<const TI*>(static_cast<const char*>(s.v) + (long long)b * s.image_v +
-                                             (long long)(row >> 1) * s.pitch_v);
-  yuv_to_rgb_px(k, (float)yp[x], (float)up[x >> 1], (float)vp[x >> 1], rgb);
+                                             (long long)yuv_chroma_row(CH, row) * s.pitch_v);
+  const int xc = CH == kChroma444 ? x : x >> 1;
+  yuv_to_rgb_px(k, (float)yp[x], (float)up[xc], (float)vp[xc], rgb);
 }
 
 // Surface output: code values clamped to code_max and truncated (the + 0.5 of the rounding is in the bias of from_rgb),
@@ -163,8 +192,11 @@ __device__ __forceinline__ uint32_t yuv_luma_code(const YuvMatrix& k, const floa
 __device__ __forceinline__ float yuv_chroma_linear(const YuvMatrix& k, int i, const float* c) {
   return __builtin_fmaf(k.m[3 * i + 2], c[2], __builtin_fmaf(k.m[3 * i + 1], c[1], k.m[3 * i] * c[0]));
 }
-__device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum4, float code_max, int shift) {
-  return ((uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum4, 0.25f, k.bias[i]), 0.0f, code_max)) << shift;
+// (`weight`: the reciprocal of the chroma sample's footprint -- 0.25 for the 2 x 2 block of 4:2:0, 0.5 for the horizontal pair
+// of 4:2:2, 1 for the single pixel of 4:4:4 -- applied in the fmaf that adds the bias.)
+__device__ __forceinline__ uint32_t yuv_chroma_code(const YuvMatrix& k, int i, float sum, float code_max, int shift,
+                                                    float weight = 0.25f) {
+  return ((uint32_t)__builtin_amdgcn_fmed3f(__builtin_fmaf(sum, weight, k.bias[i]), 0.0f, code_max)) << shift;
 }
 
 }  // namespace hdrnet_amd

@@ -121,15 +121,17 @@ def _lowres_input_px(frames, n: int, white_level, out, pixel_format: str) -> tor
 
 
 def lowres_input_yuv(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, net_input_size: int = 256,
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, chroma: str = "420") -> torch.Tensor:
     """``lowres_input`` of a semi-planar YUV 4:2:0 surface (``hdrnet_lowres_input_yuv``, include/hdrnet_amd_yuv.h): ``y``
     ``[B, H, W]``, ``uv`` ``[B, H / 2, W]`` (interleaved U, V), uint8 (NV12) or uint16 (P010 / P016), possibly pitched;
     ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients`` on the device.  The same source pixel per output sample as
     ``lowres_input``, its chroma from ``(y >> 1, x >> 1)``: the bits of ``lowres_input(hdrnet_ops.yuv_to_rgb(y, uv,
-    to_rgb))`` without the float32 frame.  One launch on the current stream; capturable."""
+    to_rgb))`` without the float32 frame.  One launch on the current stream; capturable.  ``chroma="422"``
+    (include/hdrnet_amd_yuv_chroma.h): an NV16 / P210 / P216 surface, ``uv`` ``[B, H, W]``, chroma from ``(y, x >> 1)``."""
     from . import hdrnet_ops
     what = "lowres_input_yuv"
-    y, uv, B, H, W, surf = hdrnet_ops._yuv_surface(y, uv, what)
+    chroma = hdrnet_ops._check_chroma(what, chroma, False)
+    y, uv, B, H, W, surf = hdrnet_ops._yuv_surface(y, uv, what, chroma=chroma)
     to_rgb = hdrnet_ops._yuv_constants("to_rgb", to_rgb, what)
     n = int(net_input_size)
     if n <= 0:
@@ -143,22 +145,29 @@ def lowres_input_yuv(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, ne
     else:
         _check_out("lowres_input", out, (B, n, n, 3), y.device)
     with torch.cuda.device(y.device):
-        rc = _lib.load().hdrnet_lowres_input_yuv(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(), n,
-                                                 _stream(y.device))
+        if chroma != "420":
+            rc = _lib.load().hdrnet_lowres_input_yuv_chroma(y.data_ptr(), uv.data_ptr(), *surf, _lib.CHROMA[chroma], B, H, W,
+                                                            k.data_ptr(), out.data_ptr(), n, _stream(y.device))
+        else:
+            rc = _lib.load().hdrnet_lowres_input_yuv(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
+                                                     n, _stream(y.device))
     _lib.check(rc, "LowresInput")
     return out
 
 
 def lowres_input_yuv_planar(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor,
-                            net_input_size: int = 256, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            net_input_size: int = 256, out: Optional[torch.Tensor] = None,
+                            chroma: str = "420") -> torch.Tensor:
     """``lowres_input_yuv`` of a PLANAR YUV 4:2:0 surface (``hdrnet_lowres_input_yuv_planar``,
     include/hdrnet_amd_yuv_planar.h): ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with
     the code in the low bits, possibly pitched; ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients(...,
     msb_aligned=False)`` on the device.  The bits of ``lowres_input_yuv`` on the interleaved surface.  One launch on the
-    current stream; capturable."""
+    current stream; capturable.  ``chroma`` (include/hdrnet_amd_yuv_chroma.h): ``"422"`` -- ``u`` and ``v`` ``[B, H, W / 2]``,
+    chroma from ``(y, x >> 1)`` -- or ``"444"`` -- ``[B, H, W]``, chroma from ``(y, x)``."""
     from . import hdrnet_ops
     what = "lowres_input_yuv_planar"
-    B, H, W, surf = hdrnet_ops._yuv_planar_surface(y, u, v, what)
+    chroma = hdrnet_ops._check_chroma(what, chroma, True)
+    B, H, W, surf = hdrnet_ops._yuv_planar_surface(y, u, v, what, chroma=chroma)
     to_rgb = hdrnet_ops._yuv_constants("to_rgb", to_rgb, what)
     n = int(net_input_size)
     if n <= 0:
@@ -172,8 +181,13 @@ def lowres_input_yuv_planar(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, t
     else:
         _check_out("lowres_input", out, (B, n, n, 3), y.device)
     with torch.cuda.device(y.device):
-        rc = _lib.load().hdrnet_lowres_input_yuv_planar(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k.data_ptr(),
-                                                        out.data_ptr(), n, _stream(y.device))
+        if chroma != "420":
+            rc = _lib.load().hdrnet_lowres_input_yuv_planar_chroma(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf,
+                                                                   _lib.CHROMA[chroma], B, H, W, k.data_ptr(), out.data_ptr(), n,
+                                                                   _stream(y.device))
+        else:
+            rc = _lib.load().hdrnet_lowres_input_yuv_planar(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W,
+                                                            k.data_ptr(), out.data_ptr(), n, _stream(y.device))
     _lib.check(rc, "LowresInput")
     return out
 

@@ -1274,11 +1274,25 @@ def bilateral_slice_apply_io_u16(grid: torch.Tensor, input: torch.Tensor,  # noq
 _YUV_SAMPLE = {torch.uint8: 1, torch.uint16: 2}
 
 
-def _yuv_surface(y, uv, what: str, names=("y", "uv")):
+def _check_chroma(what: str, chroma, planar: bool) -> str:
+    """The ``chroma`` keyword of the surface paths (include/hdrnet_amd_yuv_chroma.h): ``"420"`` (the default), ``"422"``, or
+    -- planar surfaces only -- ``"444"``.  The layout is NAMED by the caller; it is never guessed from the plane shapes."""
+    if chroma not in _lib.CHROMA:
+        raise ValueError(f"{what}: unknown chroma {chroma!r} (takes '420', '422', '444')")
+    if not planar and chroma == "444":
+        raise ValueError(f"{what}: semi-planar 4:4:4 (NV24 / P410) is out of scope: 4:4:4 surfaces are planar "
+                         "(yuv_planar_to_rgb, bilateral_slice_apply_io_yuv_planar, process_yuv_planar)")
+    return chroma
+
+
+def _yuv_surface(y, uv, what: str, names=("y", "uv"), chroma: str = "420"):
     """The rules of a surface, on the host: ``y`` ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (interleaved U, V; or
     ``[B, H / 2, W / 2, 2]``) of one dtype, uint8 or uint16, last-dimension stride 1, row stride >= W samples.  Returns
-    ``(y, uv, B, H, W, (sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv))``, pitches in bytes."""
+    ``(y, uv, B, H, W, (sample_dtype, pitch_y, pitch_uv, image_stride_y, image_stride_uv))``, pitches in bytes.
+    ``chroma="422"`` (NV16 / P210 / P216): ``uv`` is ``[B, H, W]`` and H is any positive number."""
     ny, nuv = names
+    if chroma != "420":
+        return _yuv_surface_422(y, uv, what, names)
     for nm, t in ((ny, y), (nuv, uv)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{what}: {nm} must be a torch.Tensor, got {type(t).__name__}")
@@ -1304,6 +1318,33 @@ def _yuv_surface(y, uv, what: str, names=("y", "uv")):
                             uv.stride(0) * size)
 
 
+def _yuv_surface_422(y, uv, what: str, names):
+    """``_yuv_surface`` for a semi-planar 4:2:2 surface: the same rules with a chroma row per image row."""
+    ny, nuv = names
+    for nm, t in ((ny, y), (nuv, uv)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {nm} must be a torch.Tensor, got {type(t).__name__}")
+    if y.dim() != 3:
+        raise ValueError(f"{what}: {ny} should be [B, H, W], got {tuple(y.shape)}")
+    B, H, W = y.shape
+    if uv.dim() == 4 and uv.shape[3] == 2 and uv.stride(3) == 1 and uv.stride(2) == 2:
+        uv = uv.as_strided((uv.shape[0], uv.shape[1], 2 * uv.shape[2]), (uv.stride(0), uv.stride(1), 1))
+    if y.dtype not in _YUV_SAMPLE or uv.dtype != y.dtype:
+        raise TypeError(f"{what}: {ny} and {nuv} must both be uint8 (NV16) or uint16 (P210 / P216), got {y.dtype}, {uv.dtype}")
+    if W % 4 != 0:
+        raise ValueError(f"{what}: W % 4 != 0 (W = {W})")
+    if uv.dim() != 3 or tuple(uv.shape) != (B, H, W):
+        raise ValueError(f"{what}: chroma='422': {nuv} should be [B, H, W] = {[B, H, W]} (interleaved U, V, full height), got "
+                         f"{list(uv.shape)}")
+    size = y.element_size()
+    for nm, t in ((ny, y), (nuv, uv)):
+        if B * H * W and (t.stride(2) != 1 or t.stride(1) < W or (t.stride(1) * size) % 4 or (t.stride(0) * size) % 4):
+            raise ValueError(f"{what}: {nm} must have last-dimension stride 1, a row stride >= W samples and pitches that are "
+                             f"multiples of 4 bytes, got strides {tuple(t.stride())}")
+    return y, uv, B, H, W, (_YUV_SAMPLE[y.dtype], y.stride(1) * size, uv.stride(1) * size, y.stride(0) * size,
+                            uv.stride(0) * size)
+
+
 def _yuv_constants(name: str, t, what: str) -> torch.Tensor:
     _require_f32(name, t)
     if t.numel() != 12:
@@ -1311,13 +1352,16 @@ def _yuv_constants(name: str, t, what: str) -> torch.Tensor:
     return t
 
 
-def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor) -> torch.Tensor:
+def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, chroma: str = "420") -> torch.Tensor:
     """A semi-planar YUV 4:2:0 surface -> float32 ``[B, H, W, 3]`` RGB in [0, 1] (``hdrnet_yuv_to_rgb_f32``): ``y``
     ``[B, H, W]``, ``uv`` ``[B, H / 2, W]`` (interleaved), uint8 (NV12) or uint16 (P010 / P016); ``to_rgb`` the 12 floats of
     ``yuv.yuv_coefficients`` on the device.  Chroma is replicated over its 2 x 2 block; the result is clamped.  Planes may
-    be pitched (row stride > W); padding is not read.  The yardstick of ``bilateral_slice_apply_io_yuv``.  No autograd."""
+    be pitched (row stride > W); padding is not read.  The yardstick of ``bilateral_slice_apply_io_yuv``.  No autograd.
+    ``chroma="422"`` (include/hdrnet_amd_yuv_chroma.h): an NV16 / P210 / P216 surface, ``uv`` ``[B, H, W]``, any H; chroma
+    sample ``(y, x >> 1)`` serves its horizontal pair."""
     what = "yuv_to_rgb"
-    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    chroma = _check_chroma(what, chroma, False)
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what, chroma=chroma)
     to_rgb = _yuv_constants("to_rgb", to_rgb, what)
     for nm, t in (("y", y), ("uv", uv), ("to_rgb", to_rgb)):
         _require_gpu(nm, t)
@@ -1325,22 +1369,27 @@ def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor) -> torch
     k = to_rgb.detach().contiguous()
     out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.load().hdrnet_yuv_to_rgb_f32(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
-                                               _stream(dev))
+        if chroma != "420":
+            rc = _lib.load().hdrnet_yuv_chroma_to_rgb_f32(y.data_ptr(), uv.data_ptr(), *surf, _lib.CHROMA[chroma], B, H, W,
+                                                          k.data_ptr(), out.data_ptr(), _stream(dev))
+        else:
+            rc = _lib.load().hdrnet_yuv_to_rgb_f32(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
+                                                   _stream(dev))
     _lib.check(rc, "YuvToRgb")
     return out
 
 
 def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
-                      return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits=None):
+                      return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits=None,
+                      chroma: str = "420"):
     """The body of ``bilateral_slice_apply_io_yuv`` and ``bilateral_slice_apply_io_yuv_deep`` (``what``), once each has
     checked the arguments that say what comes out.  ``surface_dtype``: None for an RGB frame of ``out_dtype``, uint8 for an
     NV12 surface, uint16 for a P010 / P016 surface of ``out_bits`` from a uint16 surface."""
     deep = surface_dtype == torch.uint16
-    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what, chroma=chroma)
     if deep and y.dtype != torch.uint16:
-        raise TypeError(f"{what}: a P010 / P016 output needs a uint16 surface in, got {y.dtype} (no kernel goes from 8 to 16 "
-                        "bits)")
+        raise TypeError(f"{what}: a {'P010 / P016' if chroma == '420' else 'P210 / P216'} output needs a uint16 surface in, got "
+                        f"{y.dtype} (no kernel goes from 8 to 16 bits)")
     to_rgb = _yuv_constants("to_rgb", to_rgb, what)
     if deep:  # (names its encode constants before the grid; the NV12 output after it)
         from_rgb = _yuv_constants("from_rgb", from_rgb, what)
@@ -1356,7 +1405,8 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
             from_rgb = _yuv_constants("from_rgb", from_rgb, what)
         tensors.append(("from_rgb", from_rgb))
         if out_planes is not None:
-            oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"))
+            oy, ouv, oB, oH, oW, osurf = _yuv_surface(out_planes[0], out_planes[1], what, ("out_planes[0]", "out_planes[1]"),
+                                                      chroma=chroma)
             if (oB, oH, oW) != (B, H, W) or oy.dtype != surface_dtype:
                 raise ValueError(f"{what}: out_planes should be a {'uint16' if deep else 'uint8'} surface of {[B, H, W]}, got "
                                  f"{oy.dtype} {[oB, oH, oW]}")
@@ -1372,17 +1422,24 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
         if oy is None:  # tight planes
             size = _YUV_SAMPLE[surface_dtype]
             oy = torch.empty((B, H, W), dtype=surface_dtype, device=dev)
-            ouv = torch.empty((B, H // 2, W), dtype=surface_dtype, device=dev)
-            osurf = (size, size * W, size * W, size * H * W, size * (H // 2) * W)
+            crows = H // 2 if chroma == "420" else H
+            ouv = torch.empty((B, crows, W), dtype=surface_dtype, device=dev)
+            osurf = (size, size * W, size * W, size * H * W, size * crows * W)
         k_out = from_rgb.detach().contiguous()
         planes = (oy.data_ptr(), ouv.data_ptr(), *osurf[1:], k_out.data_ptr())
-        output = (*planes, int(out_bits)) if deep else (_lib.YUV_OUT["nv12"], *planes)
+        if chroma != "420":  # (one entry point for both surface widths: the kind says which)
+            output = (_lib.CHROMA_OUT["surface_u16" if deep else "surface_u8"], *planes, int(out_bits) if deep else 0)
+        else:
+            output = (*planes, int(out_bits)) if deep else (_lib.YUV_OUT["nv12"], *planes)
         result = (oy, ouv)
     else:
         result = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
         output = (_lib.YUV_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), None, 0, 0, 0, 0, None)
+        if chroma != "420":
+            output += (0,)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    head = (y.data_ptr(), uv.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W, k_in.data_ptr(),
+            GH, GW, GD, 3, 3, 1)
     if curves:
         fn = "hdrnet_bilateral_slice_apply_io_curves_yuv"
         args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
@@ -1391,7 +1448,7 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
         args = (grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), fn + ("_p016" if deep else ""))(*args, *output, _stream(dev))
+        rc = getattr(_lib.load(), fn + ("_chroma" if chroma != "420" else "_p016" if deep else ""))(*args, *output, _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOYuv")
     return (result, gout) if return_guide else result
 
@@ -1404,7 +1461,7 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
                                  return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
                                  curves_prepared: Optional[torch.Tensor] = None,
                                  out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
-                                 from_rgb: Optional[torch.Tensor] = None, out_planes=None):
+                                 from_rgb: Optional[torch.Tensor] = None, out_planes=None, chroma: str = "420"):
     """``bilateral_slice_apply_io`` for a semi-planar YUV 4:2:0 surface in (include/hdrnet_amd_yuv.h): ``y`` ``[B, H, W]``,
     ``uv`` ``[B, H / 2, W]``, uint8 (NV12) or uint16 (P010 / P016), converted in the kernel's load by ``to_rgb`` (12
     floats, ``yuv.yuv_coefficients``) -- exactly ``bilateral_slice_apply_io(grid, yuv_to_rgb(y, uv, to_rgb), ...)`` on
@@ -1415,9 +1472,22 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
     ``from_rgb`` (12 floats): Y per pixel, U and V from the mean of each 2 x 2 block, truncated.  ``out_planes``: a
     ``(y_out, uv_out)`` pair to write into (pitched planes are fine; padding is not written).  Planes of the input may be
     pitched too.  ``return_guide`` appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd.
-    A P010 / P016 surface out is ``bilateral_slice_apply_io_yuv_deep``'s; a uint16 RGB frame out is out of scope."""
+    A P010 / P016 surface out is ``bilateral_slice_apply_io_yuv_deep``'s; a uint16 RGB frame out is out of scope.
+
+    ``chroma="422"`` (include/hdrnet_amd_yuv_chroma.h): an NV16 / P210 / P216 surface in, ``uv`` ``[B, H, W]``, any H;
+    ``out="nv16"`` is then the uint8 surface out, ``(y_out [B, H, W], uv_out [B, H, W])``, U and V from the mean of each
+    horizontal pair.  Exactly ``bilateral_slice_apply_io(grid, yuv_to_rgb(y, uv, to_rgb, chroma="422"), ...)``."""
     what = "bilateral_slice_apply_io_yuv"
-    if out not in ("rgb", "nv12"):
+    chroma = _check_chroma(what, chroma, False)
+    if chroma != "420":
+        if out not in ("rgb", "nv16"):
+            raise ValueError(f"{what}: unknown out {out!r} (chroma='422' takes 'rgb', 'nv16')")
+        if out == "nv16":
+            if out_dtype not in (None, torch.uint8):
+                raise TypeError(f"{what}: an NV16 output is uint8, got out_dtype = {out_dtype}")
+            if from_rgb is None:
+                raise ValueError(f"{what}: out='nv16' needs from_rgb (yuv.yuv_coefficients)")
+    elif out not in ("rgb", "nv12"):
         raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12')")
     if out == "rgb":
         out_dtype = torch.float32 if out_dtype is None else out_dtype
@@ -1425,14 +1495,14 @@ def bilateral_slice_apply_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.
             raise TypeError(f"{what}: out_dtype must be float32 or uint8, got {out_dtype}")
         if from_rgb is not None or out_planes is not None:
             raise ValueError(f"{what}: from_rgb / out_planes belong to out='nv12'")
-    else:
+    elif chroma == "420":
         if out_dtype not in (None, torch.uint8):
             raise TypeError(f"{what}: an NV12 output is uint8, got out_dtype = {out_dtype}")
         if from_rgb is None:
             raise ValueError(f"{what}: out='nv12' needs from_rgb (yuv.yuv_coefficients)")
     return _apply_io_surface(what, None if out == "rgb" else torch.uint8, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1,
                              guide_conv2, guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb,
-                             out_planes)
+                             out_planes, chroma=chroma)
 
 
 def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
@@ -1443,7 +1513,7 @@ def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: t
                                       return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
                                       curves_prepared: Optional[torch.Tensor] = None,
                                       from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
-                                      out_planes=None):
+                                      out_planes=None, chroma: str = "420"):
     """``bilateral_slice_apply_io_yuv`` for a uint16 surface in (P010 / P016) with a P010 / P016 surface OUT
     (include/hdrnet_amd_u16_out.h), returned as ``(y_out [B, H, W], uv_out [B, H / 2, W])`` uint16.  ``out_bits`` is 10
     (P010) or 16 (P016): the codes have that many bits and sit in the high bits of the sample.  ``from_rgb``: the 12
@@ -1452,22 +1522,29 @@ def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: t
     the mean of each 2 x 2 block, in the NV12 store's operation order.  ``out_planes``: a ``(y_out, uv_out)`` pair to write
     into (pitched planes are fine; padding is not written); tight planes are allocated when none are given.  The guide
     arguments and the arithmetic before the store are ``bilateral_slice_apply_io_yuv``'s.  ``return_guide`` appends the
-    guide map.  No autograd.  Out of scope: an NV12 surface in, a uint16 RGB frame out of a surface."""
+    guide map.  No autograd.  Out of scope: an NV12 surface in, a uint16 RGB frame out of a surface.
+    ``chroma="422"`` (include/hdrnet_amd_yuv_chroma.h): P210 / P216 in and out, ``uv`` planes ``[B, H, W]``, any H; U and V
+    from the mean of each horizontal pair."""
     what = "bilateral_slice_apply_io_yuv_deep"
+    chroma = _check_chroma(what, chroma, False)
     if from_rgb is None:
         raise ValueError(f"{what}: needs from_rgb (yuv.yuv_encode_coefficients)")
     if out_bits not in (10, 16):
         raise ValueError(f"{what}: out_bits must be 10 (P010) or 16 (P016), got {out_bits!r}")
     return _apply_io_surface(what, torch.uint16, None, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
-                             return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits)
+                             return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits,
+                             chroma=chroma)
 
 
 # ---- planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv_planar.h) -----------------------------------------------------------
-def _yuv_planar_surface(y, u, v, what: str, names=("y", "u", "v")):
+def _yuv_planar_surface(y, u, v, what: str, names=("y", "u", "v"), chroma: str = "420"):
     """The rules of a planar surface, on the host: ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` of one dtype,
     uint8 or uint16, last-dimension stride 1; the luma's row and image strides multiples of 4 bytes, the chroma's of 2
     bytes (uint8) / 4 bytes (uint16).  Returns ``(B, H, W, (sample_dtype, pitch_y, pitch_u, pitch_v, image_stride_y,
-    image_stride_u, image_stride_v))``, in bytes."""
+    image_stride_u, image_stride_v))``, in bytes.  ``chroma="422"``: ``u`` and ``v`` are ``[B, H, W / 2]``; ``"444"``:
+    ``[B, H, W]`` with the luma's alignment; both take any H."""
+    if chroma != "420":
+        return _yuv_planar_surface_chroma(y, u, v, what, names, chroma)
     planes = tuple(zip(names, (y, u, v)))
     for nm, t in planes:
         if not isinstance(t, torch.Tensor):
@@ -1494,14 +1571,47 @@ def _yuv_planar_surface(y, u, v, what: str, names=("y", "u", "v")):
     return B, H, W, (_YUV_SAMPLE[y.dtype], *(t.stride(1) * size for t in (y, u, v)), *(t.stride(0) * size for t in (y, u, v)))
 
 
-def yuv_planar_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor) -> torch.Tensor:
+def _yuv_planar_surface_chroma(y, u, v, what: str, names, chroma: str):
+    """``_yuv_planar_surface`` for a 4:2:2 or 4:4:4 planar surface: a chroma row per image row, and for 4:4:4 a chroma
+    sample per pixel (whole dwords per lane: the luma's alignment)."""
+    planes = tuple(zip(names, (y, u, v)))
+    for nm, t in planes:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {nm} must be a torch.Tensor, got {type(t).__name__}")
+    if y.dim() != 3:
+        raise ValueError(f"{what}: {names[0]} should be [B, H, W], got {tuple(y.shape)}")
+    B, H, W = y.shape
+    fmt = "yuv%sp" % chroma
+    if y.dtype not in _YUV_SAMPLE or u.dtype != y.dtype or v.dtype != y.dtype:
+        raise TypeError(f"{what}: {', '.join(names)} must all be uint8 ({fmt}) or all uint16 ({fmt}10le / {fmt}16le), got "
+                        f"{y.dtype}, {u.dtype}, {v.dtype}")
+    if W % 4 != 0:
+        raise ValueError(f"{what}: W % 4 != 0 (W = {W})")
+    cw = W if chroma == "444" else W // 2
+    for nm, t in planes[1:]:
+        if t.dim() != 3 or tuple(t.shape) != (B, H, cw):
+            raise ValueError(f"{what}: chroma={chroma!r}: {nm} should be [B, H, {'W' if chroma == '444' else 'W / 2'}] = "
+                             f"{[B, H, cw]}, got {list(t.shape)}")
+    size = y.element_size()
+    for i, (nm, t) in enumerate(planes):
+        row, unit = (W, 4) if i == 0 or chroma == "444" else (cw, 2 * size)
+        if B * H * W and (t.stride(2) != 1 or t.stride(1) < row or (t.stride(1) * size) % unit or (t.stride(0) * size) % unit):
+            raise ValueError(f"{what}: {nm} must have last-dimension stride 1, a row stride >= {row} samples and pitches that "
+                             f"are multiples of {unit} bytes, got strides {tuple(t.stride())}")
+    return B, H, W, (_YUV_SAMPLE[y.dtype], *(t.stride(1) * size for t in (y, u, v)), *(t.stride(0) * size for t in (y, u, v)))
+
+
+def yuv_planar_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor,
+                      chroma: str = "420") -> torch.Tensor:
     """``yuv_to_rgb`` for a PLANAR YUV 4:2:0 surface (``hdrnet_yuv_planar_to_rgb_f32``, include/hdrnet_amd_yuv_planar.h):
     ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420; YV12 with the planes swapped) or uint16 with the
     code in the low bits (yuv420p10le / yuv420p16le); ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients(...,
     msb_aligned=False)`` on the device.  The bits of ``yuv_to_rgb`` on the interleaved surface.  Planes may be pitched;
-    padding is not read.  No autograd."""
+    padding is not read.  No autograd.  ``chroma`` (include/hdrnet_amd_yuv_chroma.h): ``"422"`` -- yuv422p..., ``u`` and ``v``
+    ``[B, H, W / 2]`` -- or ``"444"`` -- yuv444p..., ``[B, H, W]`` -- with any H."""
     what = "yuv_planar_to_rgb"
-    B, H, W, surf = _yuv_planar_surface(y, u, v, what)
+    chroma = _check_chroma(what, chroma, True)
+    B, H, W, surf = _yuv_planar_surface(y, u, v, what, chroma=chroma)
     to_rgb = _yuv_constants("to_rgb", to_rgb, what)
     for nm, t in (("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)):
         _require_gpu(nm, t)
@@ -1509,8 +1619,13 @@ def yuv_planar_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb:
     k = to_rgb.detach().contiguous()
     out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.load().hdrnet_yuv_planar_to_rgb_f32(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k.data_ptr(),
-                                                      out.data_ptr(), _stream(dev))
+        if chroma != "420":
+            rc = _lib.load().hdrnet_yuv_planar_chroma_to_rgb_f32(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf,
+                                                                 _lib.CHROMA[chroma], B, H, W, k.data_ptr(), out.data_ptr(),
+                                                                 _stream(dev))
+        else:
+            rc = _lib.load().hdrnet_yuv_planar_to_rgb_f32(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W,
+                                                          k.data_ptr(), out.data_ptr(), _stream(dev))
     _lib.check(rc, "YuvPlanarToRgb")
     return out
 
@@ -1525,7 +1640,7 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
                                         curves_prepared: Optional[torch.Tensor] = None,
                                         out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
                                         from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
-                                        out_planes=None):
+                                        out_planes=None, chroma: str = "420"):
     """``bilateral_slice_apply_io_yuv`` for a PLANAR YUV 4:2:0 surface in (include/hdrnet_amd_yuv_planar.h): ``y``
     ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with the code in the low bits
     (yuv420p10le / yuv420p16le), converted in the kernel's load by ``to_rgb`` (``yuv.yuv_coefficients(...,
@@ -1538,8 +1653,13 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
     ``2 ** out_bits - 1``, truncated, in the low bits.  ``out_planes``: a ``(y_out, u_out, v_out)`` triple to write into
     (pitched planes are fine; padding is not written); tight planes are allocated when none are given.  ``return_guide``
     appends the guide map.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd.  Out of scope: uint16 planes in ->
-    uint8 planes out, a semi-planar surface out."""
+    uint8 planes out, a semi-planar surface out.
+
+    ``chroma`` (include/hdrnet_amd_yuv_chroma.h): ``"422"`` -- yuv422p / yuv422p10le / yuv422p16le, ``u`` and ``v``
+    ``[B, H, W / 2]`` -- or ``"444"`` -- yuv444p..., ``[B, H, W]`` -- with any H; ``out="planar"`` is then a surface of the
+    same layout, U and V from the mean of each horizontal pair (4:2:2) or per pixel (4:4:4)."""
     what = "bilateral_slice_apply_io_yuv_planar"
+    chroma = _check_chroma(what, chroma, True)
     if out not in ("rgb", "planar"):
         raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
     planar = out == "planar"
@@ -1551,7 +1671,7 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
             raise ValueError(f"{what}: from_rgb / out_bits / out_planes belong to out='planar'")
     elif from_rgb is None:
         raise ValueError(f"{what}: out='planar' needs from_rgb (yuv.yuv_encode_coefficients)")
-    B, H, W, surf = _yuv_planar_surface(y, u, v, what)
+    B, H, W, surf = _yuv_planar_surface(y, u, v, what, chroma=chroma)
     if planar:
         if out_dtype not in (None, y.dtype):
             raise TypeError(f"{what}: a planar output has the input's dtype ({y.dtype}), got out_dtype = {out_dtype}")
@@ -1575,7 +1695,7 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
             if len(planes) != 3:
                 raise ValueError(f"{what}: out_planes should be a (y_out, u_out, v_out) triple, got {len(planes)} planes")
             names = tuple(f"out_planes[{i}]" for i in range(3))
-            oB, oH, oW, osurf = _yuv_planar_surface(*planes, what, names)
+            oB, oH, oW, osurf = _yuv_planar_surface(*planes, what, names, chroma=chroma)
             if (oB, oH, oW) != (B, H, W) or planes[0].dtype != y.dtype:
                 raise ValueError(f"{what}: out_planes should be a {str(y.dtype).replace('torch.', '')} planar surface of "
                                  f"{[B, H, W]}, got {planes[0].dtype} {[oB, oH, oW]}")
@@ -1590,20 +1710,24 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
     if planar:
         if planes is None:  # tight planes
             size = _YUV_SAMPLE[y.dtype]
+            ch, cw = (H // 2 if chroma == "420" else H), (W if chroma == "444" else W // 2)
             planes = (torch.empty((B, H, W), dtype=y.dtype, device=dev),
-                      torch.empty((B, H // 2, W // 2), dtype=y.dtype, device=dev),
-                      torch.empty((B, H // 2, W // 2), dtype=y.dtype, device=dev))
-            cw, cp = size * (W // 2), size * (H // 2) * (W // 2)
+                      torch.empty((B, ch, cw), dtype=y.dtype, device=dev),
+                      torch.empty((B, ch, cw), dtype=y.dtype, device=dev))
+            cw, cp = size * cw, size * ch * cw
             osurf = (size, size * W, cw, cw, size * H * W, cp, cp)
         k_out = from_rgb.detach().contiguous()
-        output = (_lib.YUV_PLANAR_OUT["planar"], *(t.data_ptr() for t in planes), *osurf[1:], k_out.data_ptr(), int(out_bits))
+        kind = (_lib.YUV_PLANAR_OUT["planar"] if chroma == "420"
+                else _lib.CHROMA_OUT["surface_u8" if y.dtype == torch.uint8 else "surface_u16"])
+        output = (kind, *(t.data_ptr() for t in planes), *osurf[1:], k_out.data_ptr(), int(out_bits))
         result = planes
     else:
         result = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
         output = (_lib.YUV_PLANAR_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), None, None,
                   0, 0, 0, 0, 0, 0, None, 0)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    head = (y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W,
+            k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
     if curves:
         fn = "hdrnet_bilateral_slice_apply_io_curves_yuv_planar"
         args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
@@ -1612,7 +1736,7 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
         args = (grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), fn)(*args, *output, _stream(dev))
+        rc = getattr(_lib.load(), fn + ("_chroma" if chroma != "420" else ""))(*args, *output, _stream(dev))
     _lib.check(rc, "BilateralSliceApplyIOYuvPlanar")
     return (result, gout) if return_guide else result
 

@@ -669,7 +669,7 @@ class HDRNetCurves(nn.Module):
 
     def process_yuv(self, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False,
                     bits: Optional[int] = None, out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
-                    out_planes=None):
+                    out_planes=None, chroma: str = "420"):
         """``process`` for a semi-planar YUV 4:2:0 surface as a video decoder delivers it (include/hdrnet_amd_yuv.h): ``y``
         ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` (interleaved U, V) on the device, uint8 (NV12) or uint16 (P010 with
         ``bits=10``, P016 with ``bits=16``; ``bits=None`` is 8 for uint8 and 16 for uint16).  ``process`` step for step --
@@ -679,7 +679,11 @@ class HDRNetCurves(nn.Module):
         ``(y_out, uv_out)`` of the same standard and range for an encoder (``out_planes``: the pair to write into);
         ``out="p010"`` / ``out="p016"``: a uint16 surface of 10- / 16-bit codes in the high bits, of the input's standard
         and range, from a uint16 surface (``hdrnet_ops.bilateral_slice_apply_io_yuv_deep``).  Planes may be pitched.
-        Chroma is replicated on the way in and the 2 x 2 mean on the way out.  Capturable."""
+        Chroma is replicated on the way in and the 2 x 2 mean on the way out.  Capturable.
+
+        ``chroma="422"`` (include/hdrnet_amd_yuv_chroma.h): an NV16 / P210 / P216 surface, ``uv`` ``[B, H, W]``, any H;
+        ``out`` is then ``"rgb"``, ``"nv16"`` (uint8) or ``"p210"`` / ``"p216"`` (from a uint16 surface), chroma the mean of
+        each horizontal pair on the way out."""
         from . import data, hdrnet_ops, yuv
         what = f"{type(self).__name__}.process_yuv"
         if self._process_dtypes == (torch.float32,):
@@ -687,12 +691,17 @@ class HDRNetCurves(nn.Module):
                              "surface path (the single-level models' process_yuv takes NV12 / P010 / P016)")
         if standard not in yuv.STANDARDS:
             raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
-        if out not in ("rgb", "nv12", "p010", "p016"):
+        chroma = hdrnet_ops._check_chroma(what, chroma, False)
+        if chroma != "420":
+            if out not in ("rgb", "nv16", "p210", "p216"):
+                raise ValueError(f"{what}: unknown out {out!r} (chroma='422' takes 'rgb', 'nv16', 'p210', 'p216')")
+        elif out not in ("rgb", "nv12", "p010", "p016"):
             raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12', 'p010', 'p016')")
-        y, uv, B, H, W, _ = hdrnet_ops._yuv_surface(y, uv, what)
-        deep = out in ("p010", "p016")
+        y, uv, B, H, W, _ = hdrnet_ops._yuv_surface(y, uv, what, chroma=chroma)
+        deep = out in ("p010", "p016", "p210", "p216")
         if deep and y.dtype != torch.uint16:
-            raise TypeError(f"{what}: out={out!r} needs a uint16 surface in (P010 / P016), got {y.dtype}")
+            raise TypeError(f"{what}: out={out!r} needs a uint16 surface in "
+                            f"({'P010 / P016' if chroma == '420' else 'P210 / P216'}), got {y.dtype}")
         if deep and out_dtype not in (None, torch.uint16):
             raise TypeError(f"{what}: a {out.upper()} output is uint16, got out_dtype = {out_dtype}")
         if bits is None:
@@ -704,20 +713,21 @@ class HDRNetCurves(nn.Module):
         hdrnet_ops._require_gpu("y", y)
         with torch.no_grad():
             to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, y.device)
-            lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"])
+            layout = {} if chroma == "420" else {"chroma": chroma}  # (the default: the call as it always was)
+            lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"], **layout)
             if deep:
-                out_bits = 10 if out == "p010" else 16
+                out_bits = 10 if out in ("p010", "p210") else 16
                 return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_deep, lowres, y, uv, to_rgb,
                                               from_rgb=self._yuv_encode_constants(standard, full_range, out_bits, y.device),
-                                              out_bits=out_bits, out_planes=out_planes)
+                                              out_bits=out_bits, out_planes=out_planes, **layout)
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv, lowres, y, uv, to_rgb, out=out,
-                                          out_dtype=out_dtype, from_rgb=from_rgb if out == "nv12" else None,
-                                          out_planes=out_planes)
+                                          out_dtype=out_dtype, from_rgb=from_rgb if out in ("nv12", "nv16") else None,
+                                          out_planes=out_planes, **layout)
 
 
     def process_yuv_planar(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709",
                            full_range: bool = False, bits: Optional[int] = None, out: str = "rgb",
-                           out_dtype: Optional[torch.dtype] = None, out_planes=None):
+                           out_dtype: Optional[torch.dtype] = None, out_planes=None, chroma: str = "420"):
         """``process_yuv`` for a PLANAR YUV 4:2:0 surface as a software decoder delivers it
         (include/hdrnet_amd_yuv_planar.h): ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` on the device, uint8
         (I420 / FFmpeg's yuv420p; YV12 with the planes swapped) or uint16 with the code in the low bits (yuv420p10le with
@@ -726,7 +736,8 @@ class HDRNetCurves(nn.Module):
         ``hdrnet_ops.bilateral_slice_apply_io_yuv_planar`` -- with no interleaving or shifting pass.  ``out="rgb"``:
         ``[B, H, W, 3]`` float32 (default) or uint8; ``out="planar"``: a planar surface ``(y_out, u_out, v_out)`` of the
         input's dtype, depth, standard and range (``out_planes``: the triple to write into).  Planes may be pitched.
-        Capturable."""
+        Capturable.  ``chroma`` (include/hdrnet_amd_yuv_chroma.h): ``"422"`` -- yuv422p..., ``u`` and ``v``
+        ``[B, H, W / 2]`` -- or ``"444"`` -- yuv444p..., ``[B, H, W]`` -- with any H; ``out="planar"`` has the input's layout."""
         from . import data, hdrnet_ops, yuv
         what = f"{type(self).__name__}.process_yuv_planar"
         if self._process_dtypes == (torch.float32,):
@@ -737,7 +748,9 @@ class HDRNetCurves(nn.Module):
             raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
         if out not in ("rgb", "planar"):
             raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
-        hdrnet_ops._yuv_planar_surface(y, u, v, what)
+        chroma = hdrnet_ops._check_chroma(what, chroma, True)
+        layout = {} if chroma == "420" else {"chroma": chroma}  # (the default: the calls as they always were)
+        hdrnet_ops._yuv_planar_surface(y, u, v, what, chroma=chroma)
         if out == "planar" and out_dtype not in (None, y.dtype):
             raise TypeError(f"{what}: a planar output has the input's dtype ({y.dtype}), got out_dtype = {out_dtype}")
         if bits is None:
@@ -749,13 +762,14 @@ class HDRNetCurves(nn.Module):
         hdrnet_ops._require_gpu("y", y)
         with torch.no_grad():
             to_rgb, _ = self._yuv_constants(standard, full_range, bits, y.device, msb_aligned=False)
-            lowres = data.lowres_input_yuv_planar(y, u, v, to_rgb, self.params["net_input_size"])
+            lowres = data.lowres_input_yuv_planar(y, u, v, to_rgb, self.params["net_input_size"], **layout)
             if out == "planar":
                 return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_planar, lowres, y, u, v, to_rgb,
                                               out="planar", out_bits=bits, out_planes=out_planes,
-                                              from_rgb=self._yuv_encode_constants(standard, full_range, bits, y.device))
+                                              from_rgb=self._yuv_encode_constants(standard, full_range, bits, y.device),
+                                              **layout)
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_planar, lowres, y, u, v, to_rgb, out="rgb",
-                                          out_dtype=out_dtype)
+                                          out_dtype=out_dtype, **layout)
 
 
 class HDRNetPointwiseNNGuide(HDRNetCurves):

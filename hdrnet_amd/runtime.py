@@ -114,14 +114,15 @@ class FrameInference(GraphedInference):
 class _ProcessYuv(torch.nn.Module):
     """``model.process_yuv`` as the module a ``GraphedInference`` captures."""
 
-    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype):
+    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype, chroma="420"):
         super().__init__()
         self.model, self.standard, self.full_range, self.bits = model, standard, full_range, bits
         self.out, self.out_dtype = out, out_dtype
+        self.layout = {} if chroma == "420" else {"chroma": chroma}
 
     def forward(self, y: torch.Tensor, uv: torch.Tensor):
         return self.model.process_yuv(y, uv, standard=self.standard, full_range=self.full_range, bits=self.bits,
-                                      out=self.out, out_dtype=self.out_dtype)
+                                      out=self.out, out_dtype=self.out_dtype, **self.layout)
 
 
 class YuvFrameInference(GraphedInference):
@@ -132,26 +133,28 @@ class YuvFrameInference(GraphedInference):
     write into them in place).  ``out="nv12"``: the static output is the ``(y_out, uv_out)`` pair of an NV12 uint8
     surface (``"p010"`` / ``"p016"``: of a uint16 surface, from uint16 planes); ``out="rgb"``: a ``[B, H, W, 3]`` frame of
     ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
-    ``process_yuv``.  Beside ``FrameInference``, which keeps its signature."""
+    ``process_yuv``.  ``chroma="422"``: NV16 / P210 / P216 planes (``uv`` ``[B, H, W]``), ``out`` ``"nv16"``, ``"p210"``,
+    ``"p216"`` or ``"rgb"``.  Beside ``FrameInference``, which keeps its signature."""
 
     def __init__(self, model: torch.nn.Module, y_like: torch.Tensor, uv_like: torch.Tensor, standard: str = "bt709",
                  full_range: bool = False, bits=None, out: str = "nv12", out_dtype=None, warmup: int = 3,
-                 check_parameters: bool = True):
-        super().__init__(_ProcessYuv(model.eval(), standard, full_range, bits, out, out_dtype), [y_like, uv_like],
+                 check_parameters: bool = True, chroma: str = "420"):
+        super().__init__(_ProcessYuv(model.eval(), standard, full_range, bits, out, out_dtype, chroma), [y_like, uv_like],
                          warmup=warmup, check_parameters=check_parameters)
 
 
 class _ProcessYuvPlanar(torch.nn.Module):
     """``model.process_yuv_planar`` as the module a ``GraphedInference`` captures."""
 
-    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype):
+    def __init__(self, model: torch.nn.Module, standard, full_range, bits, out, out_dtype, chroma="420"):
         super().__init__()
         self.model, self.standard, self.full_range, self.bits = model, standard, full_range, bits
         self.out, self.out_dtype = out, out_dtype
+        self.layout = {} if chroma == "420" else {"chroma": chroma}
 
     def forward(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor):
         return self.model.process_yuv_planar(y, u, v, standard=self.standard, full_range=self.full_range, bits=self.bits,
-                                             out=self.out, out_dtype=self.out_dtype)
+                                             out=self.out, out_dtype=self.out_dtype, **self.layout)
 
 
 class PlanarYuvFrameInference(GraphedInference):
@@ -160,12 +163,13 @@ class PlanarYuvFrameInference(GraphedInference):
     I420, or uint16 with the code in the low bits), copied into static planes unless they ARE the static planes.
     ``out="planar"``: the static output is the ``(y_out, u_out, v_out)`` triple of a surface of the input's dtype and
     depth; ``out="rgb"``: a ``[B, H, W, 3]`` frame of ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
-    ``process_yuv_planar``.  Beside ``YuvFrameInference``, which keeps its signature."""
+    ``process_yuv_planar``.  ``chroma``: ``"422"`` / ``"444"`` planes (``u``, ``v`` ``[B, H, W / 2]`` / ``[B, H, W]``).  Beside
+    ``YuvFrameInference``, which keeps its signature."""
 
     def __init__(self, model: torch.nn.Module, y_like: torch.Tensor, u_like: torch.Tensor, v_like: torch.Tensor,
                  standard: str = "bt709", full_range: bool = False, bits=None, out: str = "planar", out_dtype=None,
-                 warmup: int = 3, check_parameters: bool = True):
-        super().__init__(_ProcessYuvPlanar(model.eval(), standard, full_range, bits, out, out_dtype),
+                 warmup: int = 3, check_parameters: bool = True, chroma: str = "420"):
+        super().__init__(_ProcessYuvPlanar(model.eval(), standard, full_range, bits, out, out_dtype, chroma),
                          [y_like, u_like, v_like], warmup=warmup, check_parameters=check_parameters)
 
 

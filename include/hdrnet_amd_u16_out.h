@@ -32,6 +32,8 @@
  *     with at most 16 knots per channel.
  *   - Anything else is refused with HDRNET_INVALID_ARGUMENT and a text that names the rule, before any HIP call.
  *     B * H * W = 0 is a no-op (kernel name "noop").
+ * P210 / P216 surfaces out (4:2:2) are include/hdrnet_amd_yuv_chroma.h's: the surface entry points below with a `chroma`
+ * argument.
  * Out of scope (the kernels are instantiated for the cases above only): uint8 frames or NV12 surfaces to a 16-bit output,
  * float32 frames in other orders than RGB, a uint16 RGB frame out of a YUV surface, the pyramid model. */
 #ifndef HDRNET_AMD_U16_OUT_H_

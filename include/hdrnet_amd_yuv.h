@@ -34,8 +34,10 @@
  * A P010 / P016 surface OUT (from a uint16 surface) is include/hdrnet_amd_u16_out.h's; the entry points below keep
  * refusing any other output_kind than the three defined here.
  * Planar surfaces (I420, yuv420p10le / yuv420p16le: three planes) are include/hdrnet_amd_yuv_planar.h's.
- * Out of scope: sited / bilinear chroma, 4:2:2 / 4:4:4 surfaces, a uint16 RGB frame out of a surface, NV12 in -> P010 /
- * P016 out, the pyramid model. */
+ * 4:2:2 surfaces (NV16, P210 / P216) and planar 4:4:4 ones are include/hdrnet_amd_yuv_chroma.h's: these entry points with a
+ * `chroma` argument.  The entry points below keep refusing them (H % 2, the UV plane's rows).
+ * Out of scope: sited / bilinear chroma, a uint16 RGB frame out of a surface, NV12 in -> P010 / P016 out, the pyramid
+ * model. */
 #ifndef HDRNET_AMD_YUV_H_
 #define HDRNET_AMD_YUV_H_
 

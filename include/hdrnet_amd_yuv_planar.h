@@ -35,8 +35,10 @@
  *     extends, and see R, G, B.
  *   - Anything else is refused with HDRNET_INVALID_ARGUMENT and a text that names the rule, before any HIP call.  B = 0 is
  *     a no-op (kernel name "noop").
- * Out of scope: 12-bit depth, 4:2:2 / 4:4:4, sited or bilinear chroma, uint16 planar in -> uint8 planar out, planar in ->
- * semi-planar out and semi-planar in -> planar out, the pyramid model. */
+ * 4:2:2 and 4:4:4 planar surfaces (yuv422p..., yuv444p...) are include/hdrnet_amd_yuv_chroma.h's: these entry points with a
+ * `chroma` argument.  The entry points below keep refusing them.
+ * Out of scope: 12-bit depth, sited or bilinear chroma, uint16 planar in -> uint8 planar out, planar in -> semi-planar out
+ * and semi-planar in -> planar out, the pyramid model. */
 #ifndef HDRNET_AMD_YUV_PLANAR_H_
 #define HDRNET_AMD_YUV_PLANAR_H_
 

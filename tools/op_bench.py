@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|yuv_chroma|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -26,7 +26,10 @@ u16 -> f32 at 4000x3000, all alternating; `yuv_planar` = planar surfaces (includ
 HDRNetPointwiseNNGuide on I420 uint8 planes at 4K and 1080p, a hipGraph of process_yuv_planar(..., out="planar") against a
 hipGraph of the chain a caller had before it (interleave U, V -> process_yuv(out="nv12") -> split the chroma), the same
 pair for yuv420p10le (the chain shifts by 6 each way around P010), and the fused kernel alone at 4K, I420 -> I420 against
-NV12 -> NV12, all alternating.  --tools loads the tools build and adds the un-fused
+NV12 -> NV12, all alternating; `yuv_chroma` = 4:2:2 / 4:4:4 surfaces (include/hdrnet_amd_yuv_chroma.h): a hipGraph of
+process_yuv_planar(..., chroma=..., out="planar") against a hipGraph of the stock chain (replicate chroma -> affine + clamp
+-> process -> affine -> footprint mean -> quantise) for yuv422p10le and yuv444p at 4K and 1080p, and the fused kernel alone at
+4K, yuv422p -> yuv422p and yuv444p -> yuv444p against NV12 -> NV12, all alternating.  --tools loads the tools build and adds the un-fused
 gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -107,6 +110,8 @@ def main():
         return u16_out(lib, dev, args)
     if args.workload == "yuv_planar":
         return yuv_planar(lib, dev, args)
+    if args.workload == "yuv_chroma":
+        return yuv_chroma(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -862,6 +867,138 @@ def yuv_planar(lib, dev, args):
     print(f"{name:28s} " + "   ".join(text))
     if args.json:
         json.dump(dict(workload="yuv_planar", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _ChromaStockChain(torch.nn.Module):
+    """What a caller with a planar 4:2:2 / 4:4:4 surface writes around process() today: replicate the chroma over its
+    footprint, an affine and a clamp into a float32 RGB frame, process, and for the encoder the mirror image -- an affine to Y,
+    U, V, the mean of the chroma over the footprint, quantise."""
+
+    def __init__(self, model, to_rgb, from_rgb, chroma, bits):
+        super().__init__()
+        self.model, self.fx, self.top = model, (1 if chroma == "444" else 2), float(2 ** bits - 1)
+        self.dtype = torch.uint8 if bits == 8 else torch.uint16
+        self.register_buffer("m_in", to_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)   # [Y U V] @ m_in -> RGB
+        self.register_buffer("b_in", to_rgb[9:].contiguous(), persistent=False)
+        self.register_buffer("m_out", from_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)
+        self.register_buffer("b_out", from_rgb[9:].contiguous(), persistent=False)
+
+    def forward(self, y, u, v):
+        B, H, W = y.shape
+        wide = (lambda t: t.float().repeat_interleave(2, dim=2)) if self.fx == 2 else (lambda t: t.float())
+        yuv = torch.stack([y.float(), wide(u), wide(v)], -1)
+        rgb = (yuv @ self.m_in + self.b_in).clamp_(0.0, 1.0)
+        out = self.model.process(rgb).clamp_(0.0, 1.0)
+        enc = out @ self.m_out
+        yq = (enc[..., 0] + self.b_out[0]).clamp_(0.0, self.top).to(self.dtype)
+        cm = enc[..., 1:].reshape(B, H, W // self.fx, self.fx, 2).mean(dim=3) + self.b_out[1:]
+        cq = cm.clamp_(0.0, self.top).to(self.dtype)
+        return yq, cq[..., 0].contiguous(), cq[..., 1].contiguous()
+
+
+def yuv_chroma(lib, dev, args):
+    """4:2:2 / 4:4:4 planar surfaces (include/hdrnet_amd_yuv_chroma.h) through HDRNetPointwiseNNGuide at 4K and 1080p,
+    yuv422p10le -> yuv422p10le and yuv444p -> yuv444p: one hipGraph of process_yuv_planar(y, u, v, chroma=..., out="planar")
+    against one hipGraph of _ChromaStockChain; both warmed, then run ALTERNATING three times each in one process; reported:
+    the mean of the three and their range.  Beside it, at 4K: the fused guide-network kernel alone, yuv422p -> yuv422p (2 + 2
+    B/px) and yuv444p -> yuv444p (3 + 3 B/px) against NV12 -> NV12 (1.5 + 1.5 B/px), over buffer sets that together exceed the
+    Infinity Cache, alternating the same way."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import GraphedInference, PlanarYuvFrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def samples(bits, *shape):
+        t = torch.randint(0, 2 ** bits, shape, device=dev, dtype=torch.int32, generator=gen)
+        return t.to(torch.uint8 if bits == 8 else torch.uint16)
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        for chroma, bits, fmt in (("422", 10, "yuv422p10le"), ("444", 8, "yuv444p")):
+            Wc = W if chroma == "444" else W // 2
+            surfaces = [(samples(bits, 1, H, W), samples(bits, 1, H, Wc), samples(bits, 1, H, Wc)) for _ in range(3)]
+            to_rgb = torch.from_numpy(yuv.yuv_coefficients("bt709", False, bits, msb_aligned=False)[0]).to(dev)
+            from_rgb = torch.from_numpy(yuv.yuv_encode_coefficients("bt709", False, bits)).to(dev)
+            new = PlanarYuvFrameInference(m, *surfaces[0], bits=bits, out="planar", chroma=chroma)
+            base = GraphedInference(_ChromaStockChain(m, to_rgb, from_rgb, chroma, bits), list(surfaces[0]))
+            worst = 0
+            for a, b in zip(new(*surfaces[1]), base(*surfaces[1])):
+                worst = max(worst, int((a.int() - b.int()).abs().max()))
+            # (the chain rounds its affine ops in another order: it is a timing opponent, not the reference of the tests)
+            print(f"{H}x{W} {fmt}: fused vs chain, largest code difference {worst}")
+            assert worst <= 1, "the two paths encode the same surface to within a code"
+            b, n = alternate(lambda k: base(*surfaces[k % 3]), lambda k: new(*surfaces[k % 3]))
+            mb, mn = statistics.mean(b), statistics.mean(n)
+            spread = max(b) - min(b)
+            name = f"{H}x{W} model, {fmt} -> {fmt}"
+            rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                             us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                             faster_beyond_chain_spread=bool(mb - mn > spread)))
+            print(f"{name:46s} stock chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_yuv_planar {mn:8.2f} us "
+                  f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+                  f"faster by more than the chain's spread: {mb - mn > spread}")
+            del new, base, surfaces
+
+    # the kernel alone at 4K: the same grid and guide network over three surface layouts
+    H, W = 2160, 3840
+    GH, GW, GD = 16, 16, 8
+    to_rgb, from_rgb = (torch.from_numpy(a).to(dev) for a in yuv.yuv_coefficients("bt709", False, 8))
+    nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 3)))
+    grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+    conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+    conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+    e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.uint8)  # noqa: E731
+    sets = [dict(y=samples(8, 1, H, W), uv=samples(8, 1, H // 2, W), u2=samples(8, 1, H, W // 2), v2=samples(8, 1, H, W // 2),
+                 u4=samples(8, 1, H, W), v4=samples(8, 1, H, W), oy=e(1, H, W), ouv=e(1, H // 2, W), ou2=e(1, H, W // 2),
+                 ov2=e(1, H, W // 2), ou4=e(1, H, W), ov4=e(1, H, W)) for _ in range(nsets)]
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(lib.hdrnet_last_error().decode())
+
+    def nv12_kernel(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_io_yuv(grid.data_ptr(), None, t["y"].data_ptr(), t["uv"].data_ptr(), 1, W, W, H * W,
+                                                      H // 2 * W, 1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1, conv1.data_ptr(),
+                                                      conv2.data_ptr(), 16, None, _lib.GUIDE_SIGMOID_FAST, 2, t["oy"].data_ptr(),
+                                                      t["ouv"].data_ptr(), W, W, H * W, H // 2 * W, from_rgb.data_ptr(), stream))
+
+    def planar_kernel(k, chroma):
+        t = sets[k % nsets]
+        s, Wc = ("4", W) if chroma == 2 else ("2", W // 2)
+        check(lib.hdrnet_bilateral_slice_apply_io_yuv_planar_chroma(
+            grid.data_ptr(), None, t["y"].data_ptr(), t["u" + s].data_ptr(), t["v" + s].data_ptr(), 1, W, Wc, Wc, H * W, H * Wc,
+            H * Wc, chroma, 1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1, conv1.data_ptr(), conv2.data_ptr(), 16, None,
+            _lib.GUIDE_SIGMOID_FAST, 2, t["oy"].data_ptr(), t["ou" + s].data_ptr(), t["ov" + s].data_ptr(), W, Wc, Wc, H * W,
+            H * Wc, H * Wc, from_rgb.data_ptr(), 8, stream))
+
+    q, p2, p4 = alternate(nv12_kernel, lambda k: planar_kernel(k, 1), lambda k: planar_kernel(k, 2))
+    name = f"{H}x{W} kernel, +nnguide"
+    row = dict(op=name)
+    text = []
+    for key, label, t in (("nv12_nv12", "nv12 -> nv12 (3 B/px)", q), ("i422_i422", "yuv422p -> yuv422p (4 B/px)", p2),
+                          ("i444_i444", "yuv444p -> yuv444p (6 B/px)", p4)):
+        row.update({f"us_{key}": round(statistics.mean(t), 2), f"us_{key}_min": round(min(t), 2), f"us_{key}_max": round(max(t), 2)})
+        text.append(f"{label} {statistics.mean(t):8.2f} us ({min(t):8.2f} .. {max(t):8.2f})")
+    row["i422_over_nv12"] = round(statistics.mean(p2) / statistics.mean(q), 3)
+    row["i444_over_nv12"] = round(statistics.mean(p4) / statistics.mean(q), 3)
+    rows.append(row)
+    print(f"{name:28s} " + "   ".join(text))
+    if args.json:
+        json.dump(dict(workload="yuv_chroma", rows=rows), open(args.json, "w"), indent=1)
 
 
 class _QuantiseChain(torch.nn.Module):
