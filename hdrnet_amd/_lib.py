@@ -249,6 +249,21 @@ YUV_CHROMA_SIGNATURES = {
                                                                  [_FP] * 4 + [_I, _VP, _FP] + _PLANAR_OUTPUT + [_VP]),
 }
 
+# include/hdrnet_amd_pyramid_yuv.h: the pyramid model on YUV 4:2:0 surfaces -- the resize that reads a surface (the
+# surface, B, H, W, to_rgb, out, Hout, Wout) and the finest level's slice-apply + up-add: the single-level surface entry
+# points with (coarse, Hc, Wc) after to_rgb and without guide_out.
+_COARSE = [_FP, _I, _I]
+PYRAMID_YUV_SIGNATURES = {
+    "hdrnet_resize_bilinear_yuv": (_I, _SURFACE + [_I] * 3 + [_FP, _FP, _I, _I, _VP]),
+    "hdrnet_resize_bilinear_yuv_planar": (_I, _PLANAR_SURFACE + [_I] * 3 + [_FP, _FP, _I, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_upadd_io_yuv": (_I, [_FP, _FP] + _SURFACE + [_I] * 3 + [_FP] + _COARSE + [_I] * 6 +
+                                                  [_FP, _FP, _I, _U] + _YUV_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_upadd_io_yuv_p016": (_I, [_FP, _FP] + _SURFACE + [_I] * 3 + [_FP] + _COARSE + [_I] * 6 +
+                                                       [_FP, _FP, _I, _U] + _P016_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_upadd_io_yuv_planar": (_I, [_FP, _FP] + _PLANAR_SURFACE + [_I] * 3 + [_FP] + _COARSE +
+                                                         [_I] * 6 + [_FP, _FP, _I, _U] + _PLANAR_OUTPUT + [_VP]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 _tools_lib: Optional[ctypes.CDLL] = None
@@ -306,6 +321,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(U16_OUT_SIGNATURES)
     table.update(YUV_PLANAR_SIGNATURES)
     table.update(YUV_CHROMA_SIGNATURES)
+    table.update(PYRAMID_YUV_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)
     for name, (res, args) in table.items():

@@ -51,12 +51,16 @@ SOURCES = [
     # ... and with a 16-bit output: a uint16 frame, a P010 / P016 surface (include/hdrnet_amd_u16_out.h)
     ("apply_fwd_io_u16.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_upadd.hip", ["-fno-slp-vectorize"]),
+    # ... and the pyramid's finest level reading a 4:2:0 surface (include/hdrnet_amd_pyramid_yuv.h): the YUV units' kernel
+    # with the up-add, so their flags
+    ("apply_fwd_io_upadd_yuv.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_bwd_rows.hip", ["-fno-slp-vectorize"]),
     ("apply_vjp_seg.hip", ["-fno-slp-vectorize"]),
     ("slice_fwd_rows.hip", ["-fno-slp-vectorize"]),
     ("grid_grad_mfma.hip", ["-fno-slp-vectorize"]),
     ("guide_grad.hip", ["-fno-slp-vectorize"]),
     ("resize_bilinear.hip", []),
+    ("resize_bilinear_yuv.hip", []),
     ("coeff_net.hip", []),
     ("coeff_net_train.hip", []),
     ("coeff_net_bn.hip", []),
@@ -117,6 +121,7 @@ def _deps() -> List[str]:
            os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"), os.path.join(INCLUDE, "hdrnet_amd_pixel_formats.h"),
            os.path.join(INCLUDE, "hdrnet_amd_yuv.h"), os.path.join(INCLUDE, "hdrnet_amd_u16_out.h"),
            os.path.join(INCLUDE, "hdrnet_amd_yuv_planar.h"), os.path.join(INCLUDE, "hdrnet_amd_yuv_chroma.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_pyramid_yuv.h"),
            os.path.abspath(__file__)]
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h")):

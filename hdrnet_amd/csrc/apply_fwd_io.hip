@@ -14,11 +14,13 @@ bool apply_fwd_io_supported(const ApplyIoArgs& a) {
 // The kernel family of a call, chosen HERE and nowhere else: the 16-bit output's (a.output_dtype == 2), else the pixel
 // source's (a.yuv, a.yuvp, or `coarse` for the pyramid's up-add).
 namespace {
-enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd, kFamilyYuvPlanar, kFamilyYuv422, kFamilyYuvPlanarChroma };
+enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd, kFamilyYuvPlanar, kFamilyYuv422, kFamilyYuvPlanarChroma,
+                kFamilyUpAddYuv };
 IoFamily io_family(const ApplyIoArgs& a, const float* coarse) {
   // (a 4:2:2 / 4:4:4 surface carries every output kind of its own, as a planar one does)
   if (a.yuvp && a.yuvp->chroma != kChroma420) return kFamilyYuvPlanarChroma;
   if (a.yuv && a.yuv->chroma != kChroma420) return kFamilyYuv422;
+  if (coarse && (a.yuv || a.yuvp)) return kFamilyUpAddYuv;  // (the pyramid's finest level on a 4:2:0 surface, any output kind)
   if (a.yuvp) return kFamilyYuvPlanar;  // (a planar surface carries its own output kinds, the 16-bit one among them)
   return a.output_dtype == 2 && !coarse ? kFamilyU16 : a.yuv ? kFamilyYuv : coarse ? kFamilyUpAdd : kFamilyFrame;
 }
@@ -32,6 +34,7 @@ bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse) {
     case kFamilyYuv422: return !coarse && apply_fwd_io_yuv_422_supported(a);
     case kFamilyYuvPlanarChroma: return !coarse && apply_fwd_io_yuv_planar_chroma_supported(a);
     case kFamilyUpAdd: return apply_fwd_io_upadd_supported(a, coarse);
+    case kFamilyUpAddYuv: return apply_fwd_io_upadd_yuv_supported(a, coarse);
     default: return apply_fwd_io_supported(a);
   }
 }
@@ -47,6 +50,7 @@ hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse,
       return a.yuvp->chroma == kChroma422 ? launch_apply_fwd_io_yuv_planar_422(a, s, name)
                                           : launch_apply_fwd_io_yuv_planar_444(a, s, name);
     case kFamilyUpAdd: return launch_apply_fwd_io_upadd(a, coarse, Hc, Wc, s, name);
+    case kFamilyUpAddYuv: return launch_apply_fwd_io_upadd_yuv(a, coarse, Hc, Wc, s, name);
     default: return launch_apply_fwd_io(a, s, name);
   }
 }

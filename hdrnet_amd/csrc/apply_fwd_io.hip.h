@@ -47,6 +47,11 @@
 // apply_fwd_io_u16.hip's, DELIBERATELY LIMITED to keep the build small: uint16 and float32 RGB frames and uint16 BGR / RGBA
 // / BGRA frames to a uint16 frame, a uint16 surface to a uint16 surface.  uint8 -> 16 bit, float32 packed orders, a uint16
 // RGB frame out of a YUV surface and the pyramid's up-add are not instantiated and are refused by rule.
+//
+// THE PYRAMID ON A SURFACE (include/hdrnet_amd_pyramid_yuv.h): UPADD = true adds the bilinearly up-sampled coarser level
+// (upadd_quad, rows_common.hip.h; IoUpParams::up) to a lane's pixels between the pixel phase and the store -- the finest level of
+// HDRNetGaussianPyrNN reading a 4:2:0 surface.  Its instantiations are apply_fwd_io_upadd_yuv.hip's; UPADD = false, the
+// default, compiles every instantiation above to the code it was.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -453,11 +458,20 @@ struct IoParams {
   YuvPlanarSurface pin, pout;
 };
 
+// The pyramid's finest level on a surface (UPADD): the coarser level to up-sample and add, appended at the END.  A type of
+// its own, which only the UPADD instantiations take: a longer IoParams moved the kernel-argument loads of instantiations
+// that never read the field (the float32 curves forward: 64 -> 63 VGPRs), and every kernel shipped keeps its machine code.
+struct IoUpParams : IoParams {
+  UpAdd up;
+};
+template <bool UPADD>
+using IoParamsOf = std::conditional_t<UPADD, IoUpParams, IoParams>;
+
 // Geometry, LDS image and pixel core are apply_fwd_seg.hip's (seg_common.hip.h): a workgroup owns a row
 // segment, 3-D launch grid (segment, row, image), padded y-pre-lerped coefficient image.
 template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame,
-          int CH = kChroma420>
-__global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
+          int CH = kChroma420, bool UPADD = false>
+__global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParamsOf<UPADD> p) {
   static_assert(PX == kPxRGB || (CIN == 3 && COUT == 3 && sizeof(TI) < 4), "pixel formats: integer frames, 3 -> 3");
   constexpr bool PLANAR = PX == kPxYuvPlanar;  // the input is a planar YUV surface: three planes
   constexpr bool YUV = PX == kPxYuv || PLANAR;  // the input is a YUV surface; the frame the kernel stores is RGB
@@ -475,6 +489,10 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
   static_assert(CH == kChroma420 || YUV, "a chroma layout belongs to a YUV surface");
   static_assert(CH != kChroma444 || PLANAR, "4:4:4: planar surfaces only");
   constexpr bool ROWPAIR = SURFOUT && CH == kChroma420;
+  // UPADD (apply_fwd_io_upadd_yuv.hip): the pyramid's finest level -- the coarser level's output, up-sampled, is added to
+  // the lane's pixels BEFORE any store, so the clip, the luma code and the chroma sums see the sum
+  static_assert(!UPADD || (YUV && CH == kChroma420 && (GUIDE == kGuideMap || GUIDE == kGuideNN)),
+                "the up-add: 4:2:0 surfaces, a guide map or the guide network");
   constexpr bool PACKED = PX != kPxRGB && !YUV;  // BGR / RGBA / BGRA
   constexpr int SPX = PACKED ? px_stored(PX) : CIN;  // samples per stored pixel of the frame
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
@@ -584,6 +602,7 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParams p) {
 #pragma unroll
         for (int i = 0; i < COUT; ++i) of[k * COUT + i] = o[i];
       }
+      if constexpr (UPADD) upadd_quad<COUT>(p.up, b, y, x, of);  // (once per row of a pair, with that row's y)
     }
 
     if constexpr (SURFOUT) {
@@ -750,11 +769,11 @@ RowGeom io_geom(const ApplyIoArgs& a) {
 }
 
 template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, int PX = kPxRGB, int OUT = kOutFrame,
-          int CH = kChroma420>
-hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
+          int CH = kChroma420, bool UPADD = false>
+hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s, const UpAdd* up = nullptr) {
   constexpr int C = COUT * (CIN + (OFFSET ? 1 : 0));
   const RowGeom g = io_geom(a);
-  IoParams p;
+  IoParamsOf<UPADD> p;
   p.grid = a.grid;
   p.guide = a.guide;
   p.input = a.input;
@@ -776,6 +795,7 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   p.code_max = 0.0f;
   p.code_shift = 0;
   p.pin = p.pout = YuvPlanarSurface{};
+  if constexpr (UPADD) p.up = *up;
   if constexpr (PX == kPxYuvPlanar) {
     p.pin = a.yuvp->in;
     p.to_rgb = a.yuvp->to_rgb;
@@ -795,7 +815,7 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s) {
   }
   // a 4:2:0 surface output: one workgroup per row PAIR of a segment (H % 2 == 0); 4:2:2 / 4:4:4: per row, as a frame
   const dim3 grid3((unsigned)g.pl.nseg, (unsigned)(OUT != kOutFrame && CH == kChroma420 ? a.H / 2 : a.H), (unsigned)a.B);
-  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT, CH><<<grid3, g.pl.threads, g.lds, s>>>(p);
+  apply_fwd_io_rows<CIN, COUT, OFFSET, GUIDE, TI, TO, PX, OUT, CH, UPADD><<<grid3, g.pl.threads, g.lds, s>>>(p);
   return hipGetLastError();
 }
 
@@ -901,5 +921,6 @@ hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
 // apply_fwd_io_u16.hip (launch.hip.h): the same launch with a 16-bit output (a.output_dtype == 2)
 // apply_fwd_io_yuv_planar.hip (launch.hip.h): the same launch for a planar YUV surface (a.yuvp)
 // apply_fwd_io_yuv_422.hip, apply_fwd_io_yuv_planar_422.hip / _444.hip (launch.hip.h): ... of another chroma layout
+// apply_fwd_io_upadd_yuv.hip (launch.hip.h): the same launch for a 4:2:0 surface + the pyramid's up-add (`coarse`)
 
 }  // namespace hdrnet_amd

@@ -17,6 +17,7 @@
 #include "../../include/hdrnet_amd_yuv_chroma.h"
 #include "../../include/hdrnet_amd_u16_out.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
+#include "../../include/hdrnet_amd_pyramid_yuv.h"
 #include "../../include/hdrnet_amd_train.h"
 #include "launch.hip.h"
 
@@ -167,6 +168,19 @@ int check_upadd_values(int Hc, int Wc, const float* guide, const float* conv1, c
     return fail(HDRNET_INVALID_ARGUMENT, "give either a guide map or the guide network, not both / neither");
   if (conv1 && (!conv2 || n_feats <= 0 || n_feats > 4096))
     return fail(HDRNET_INVALID_ARGUMENT, "guide network needs conv1, conv2 and 0 < n_feats <= 4096");
+  return HDRNET_OK;
+}
+
+// ... and on a YUV surface (include/hdrnet_amd_pyramid_yuv.h): the coarse level as the surface entry points' bodies take it,
+// and the one rule of its pointer (the float ops' coarse level sits in 16-B aligned tensors; here it is read dword by dword)
+struct IoCoarse {
+  const float* coarse;
+  int Hc, Wc;
+};
+
+int check_coarse_pointer(const char* what, const float* coarse) {
+  if (!coarse || ((uintptr_t)coarse & 3u))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: coarse must be a 4-B aligned buffer ([B][Hc][Wc][3] float32)", what);
   return HDRNET_OK;
 }
 
@@ -598,7 +612,7 @@ extern "C" {
 //          yuv420p16le surfaces in, RGB or a planar surface out)
 // 0.2.9.0: + include/hdrnet_amd_yuv_chroma.h: the eight entry points of the three headers above with a `chroma` argument (4:2:2
 //          NV16 / P210 / P216 / yuv422p..., 4:4:4 yuv444p... surfaces in, RGB or a surface of the input's container and layout out)
-int hdrnet_version(void) { return 290; }
+int hdrnet_version(void) { return 291; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -1330,17 +1344,23 @@ int hdrnet_yuv_to_rgb_f32(const void* y, const void* uv, int sample_dtype, int p
 // The four fused entry points (`what`): a surface in with either guide; `io`: the call's surfaces as given, io.out.y the
 // RGB frame where the output is one; `p016`: an entry point of hdrnet_amd_u16_out.h (io.out_kind is then kYuvOutP016,
 // which the others refuse as a caller's output kind).  Either guide's values answer before the surfaces'.
+// `up`: the call is an up-add entry point of hdrnet_amd_pyramid_yuv.h (a guide map or the network, never the curves): the
+// coarse level's rules answer after the surfaces', its pointer after theirs.
 static int apply_io_yuv_impl(const char* what, bool p016, const float* grid, const IoGuide& g, hdrnet_amd::YuvIo io,
                              int sample_dtype, int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset,
-                             void* stream) {
+                             void* stream, const IoCoarse* up = nullptr) {
   using namespace hdrnet_amd;
   char prefix[96];
   snprintf(prefix, sizeof prefix, "%s: ", what);
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = g.curves ? check_curves_knots(prefix, g.n) : check_guide_flags(g.flags)) return rc;
   if (int rc = check_yuv_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset, p016)) return rc;
+  if (up)
+    if (int rc = check_upadd_values(up->Hc, up->Wc, g.guide, g.conv1, g.conv2, g.n)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (int rc = check_yuv_io_pointers(what, io)) return rc;
+  if (up)
+    if (int rc = check_coarse_pointer(what, up->coarse)) return rc;
   if (g.curves) {
     if (!grid || !g.conv1 || !g.shifts || !g.slopes || !g.conv2)
       return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
@@ -1358,6 +1378,10 @@ static int apply_io_yuv_impl(const char* what, bool p016, const float* grid, con
     io.from_rgb = nullptr;
   }
   a.yuv = &io;
+  if (up)
+    return launch_io(a, up->coarse, up->Hc, up->Wc, "BilateralSliceApplyUpAddIOYuv",
+                     "the YUV slice-apply + up-add supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned buffers",
+                     stream);
   return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuv" : "BilateralSliceApplyIOYuv",
                    io.chroma != HDRNET_CHROMA_420
                        ? "the 4:2:2 YUV forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned buffers"
@@ -1479,17 +1503,22 @@ int hdrnet_yuv_planar_to_rgb_f32(const void* y, const void* u, const void* v, in
 
 // The two fused entry points (`what`): a planar surface in with either guide; `io`: the call's surfaces as given, io.out.y
 // the RGB frame where the output is one.  apply_io_yuv_impl's checks in its order.
+// (`up`: as there)
 static int apply_io_yuv_planar_impl(const char* what, const float* grid, const IoGuide& g, hdrnet_amd::YuvPlanarIo io,
                                     int sample_dtype, int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout,
-                                    int has_offset, void* stream) {
+                                    int has_offset, void* stream, const IoCoarse* up = nullptr) {
   using namespace hdrnet_amd;
   char prefix[96];
   snprintf(prefix, sizeof prefix, "%s: ", what);
   if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
   if (int rc = g.curves ? check_curves_knots(prefix, g.n) : check_guide_flags(g.flags)) return rc;
   if (int rc = check_yuv_planar_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
+  if (up)
+    if (int rc = check_upadd_values(up->Hc, up->Wc, g.guide, g.conv1, g.conv2, g.n)) return rc;
   if ((long long)B * H * W == 0) return finish_noop();
   if (int rc = check_yuv_planar_io_pointers(what, io, sample_dtype)) return rc;
+  if (up)
+    if (int rc = check_coarse_pointer(what, up->coarse)) return rc;
   if (g.curves) {
     if (!grid || !g.conv1 || !g.shifts || !g.slopes || !g.conv2)
       return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
@@ -1509,6 +1538,10 @@ static int apply_io_yuv_planar_impl(const char* what, const float* grid, const I
     io.out_bits = 0;
   }
   a.yuvp = &io;
+  if (up)
+    return launch_io(a, up->coarse, up->Hc, up->Wc, "BilateralSliceApplyUpAddIOYuvPlanar",
+                     "the planar YUV slice-apply + up-add supports Cin = Cout = 3 with offset, H % 2 == 0, W % 4 == 0, aligned "
+                     "buffers", stream);
   return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuvPlanar" : "BilateralSliceApplyIOYuvPlanar",
                    io.chroma != HDRNET_CHROMA_420
                        ? "the 4:2:2 / 4:4:4 planar YUV forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned buffers"
@@ -1605,6 +1638,119 @@ int hdrnet_bilateral_slice_apply_upadd_io_ex(const float* grid, const float* gui
   return launch_io(a, coarse, Hc, Wc, "BilateralSliceApplyUpAddIO",
                    "the wire-format slice-apply + up-add supports Cin = Cout = 3 with offset, W % 4 == 0, aligned "
                    "buffers; convert on the caller's side and use hdrnet_bilateral_slice_apply_upadd_f32", stream);
+}
+
+// ---- include/hdrnet_amd_pyramid_yuv.h: the pyramid model on YUV 4:2:0 surfaces -------------------------------------------
+// The resize: the surface's rules (check_yuv_extents / check_yuv_surface / check_yuv_pointers and their planar twins), then
+// the output's.  An empty OUTPUT is the no-op; an empty surface under a non-empty output has nothing to read.
+namespace {
+int check_resize_yuv_output(const char* what, int B, int H, int W, int Hout, int Wout) {
+  if (Hout < 0 || Wout < 0) return fail(HDRNET_INVALID_ARGUMENT, "%s: negative output extent (%d x %d)", what, Hout, Wout);
+  if ((long long)B * Hout * Wout != 0 && (long long)H * W == 0)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: an empty surface (H=%d, W=%d) has no pixel to resize", what, H, W);
+  if ((long long)B * Hout * Wout * 12 >= (1LL << 40)) return fail(HDRNET_INVALID_ARGUMENT, "%s: output too large", what);
+  return HDRNET_OK;
+}
+int check_resize_yuv_out(const char* what, const float* out) {
+  if (!out || ((uintptr_t)out & 3u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: out must be a 4-B aligned buffer", what);
+  return HDRNET_OK;
+}
+}  // namespace
+
+int hdrnet_resize_bilinear_yuv(const void* y, const void* uv, int sample_dtype, int pitch_y, int pitch_uv,
+                               long long image_stride_y, long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                               float* out, int Hout, int Wout, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_resize_bilinear_yuv";
+  const YuvSurface in{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if (int rc = check_resize_yuv_output(what, B, H, W, Hout, Wout)) return rc;
+  if ((long long)B * Hout * Wout == 0) return finish_noop();
+  if (int rc = check_yuv_pointers(what, "input", in, to_rgb)) return rc;
+  if (int rc = check_resize_yuv_out(what, out)) return rc;
+  const char* name = "";
+  const hipError_t e = launch_resize_bilinear_yuv(in, sample_dtype, to_rgb, out, B, H, W, Hout, Wout,
+                                                  static_cast<hipStream_t>(stream), &name);
+  if (e == hipErrorInvalidValue) return fail(HDRNET_INVALID_ARGUMENT, "%s: output too large", what);
+  return finish_launch(e, what, name);
+}
+
+int hdrnet_resize_bilinear_yuv_planar(const void* y, const void* u, const void* v, int sample_dtype, int pitch_y, int pitch_u,
+                                      int pitch_v, long long image_stride_y, long long image_stride_u,
+                                      long long image_stride_v, int B, int H, int W, const float* to_rgb, float* out,
+                                      int Hout, int Wout, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_resize_bilinear_yuv_planar";
+  const YuvPlanarSurface in{y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v};
+  if (int rc = check_yuv_extents(what, B, H, W)) return rc;
+  if (int rc = check_yuv_planar_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if (int rc = check_resize_yuv_output(what, B, H, W, Hout, Wout)) return rc;
+  if ((long long)B * Hout * Wout == 0) return finish_noop();
+  if (int rc = check_yuv_planar_pointers(what, "input", sample_dtype, in, to_rgb)) return rc;
+  if (int rc = check_resize_yuv_out(what, out)) return rc;
+  const char* name = "";
+  const hipError_t e = launch_resize_bilinear_yuv_planar(in, sample_dtype, to_rgb, out, B, H, W, Hout, Wout,
+                                                         static_cast<hipStream_t>(stream), &name);
+  if (e == hipErrorInvalidValue) return fail(HDRNET_INVALID_ARGUMENT, "%s: output too large", what);
+  return finish_launch(e, what, name);
+}
+
+// The finest level: the single-level surface entry points' bodies (apply_io_yuv_impl / apply_io_yuv_planar_impl: the same
+// checks in the same order) with the coarse level beside them.
+int hdrnet_bilateral_slice_apply_upadd_io_yuv(const float* grid, const float* guide, const void* y, const void* uv,
+                                              int sample_dtype, int pitch_y, int pitch_uv, long long image_stride_y,
+                                              long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                                              const float* coarse, int Hc, int Wc, int GH, int GW, int GD, int Cin, int Cout,
+                                              int has_offset, const float* guide_conv1, const float* guide_conv2, int n_feats,
+                                              unsigned flags, int output_kind, void* out, void* out_uv, int out_pitch_y,
+                                              int out_pitch_uv, long long out_image_stride_y, long long out_image_stride_uv,
+                                              const float* from_rgb, void* stream) {
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, output_kind,
+                             {out, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb};
+  const IoCoarse up{coarse, Hc, Wc};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_upadd_io_yuv", false, grid,
+                           io_guide_network(guide, guide_conv1, guide_conv2, n_feats, nullptr, flags), io, sample_dtype, B, H,
+                           W, GH, GW, GD, Cin, Cout, has_offset, stream, &up);
+}
+
+int hdrnet_bilateral_slice_apply_upadd_io_yuv_p016(const float* grid, const float* guide, const void* y, const void* uv,
+                                                   int sample_dtype, int pitch_y, int pitch_uv, long long image_stride_y,
+                                                   long long image_stride_uv, int B, int H, int W, const float* to_rgb,
+                                                   const float* coarse, int Hc, int Wc, int GH, int GW, int GD, int Cin,
+                                                   int Cout, int has_offset, const float* guide_conv1,
+                                                   const float* guide_conv2, int n_feats, unsigned flags, void* out_y,
+                                                   void* out_uv, int out_pitch_y, int out_pitch_uv,
+                                                   long long out_image_stride_y, long long out_image_stride_uv,
+                                                   const float* from_rgb, int out_bits, void* stream) {
+  const hdrnet_amd::YuvIo io{{y, uv, pitch_y, pitch_uv, image_stride_y, image_stride_uv}, to_rgb, hdrnet_amd::kYuvOutP016,
+                             {out_y, out_uv, out_pitch_y, out_pitch_uv, out_image_stride_y, out_image_stride_uv}, from_rgb,
+                             out_bits};
+  const IoCoarse up{coarse, Hc, Wc};
+  return apply_io_yuv_impl("hdrnet_bilateral_slice_apply_upadd_io_yuv_p016", true, grid,
+                           io_guide_network(guide, guide_conv1, guide_conv2, n_feats, nullptr, flags), io, sample_dtype, B, H,
+                           W, GH, GW, GD, Cin, Cout, has_offset, stream, &up);
+}
+
+int hdrnet_bilateral_slice_apply_upadd_io_yuv_planar(const float* grid, const float* guide, const void* y, const void* u,
+                                                     const void* v, int sample_dtype, int pitch_y, int pitch_u, int pitch_v,
+                                                     long long image_stride_y, long long image_stride_u,
+                                                     long long image_stride_v, int B, int H, int W, const float* to_rgb,
+                                                     const float* coarse, int Hc, int Wc, int GH, int GW, int GD, int Cin,
+                                                     int Cout, int has_offset, const float* guide_conv1,
+                                                     const float* guide_conv2, int n_feats, unsigned flags, int output_kind,
+                                                     void* out, void* out_u, void* out_v, int out_pitch_y, int out_pitch_u,
+                                                     int out_pitch_v, long long out_image_stride_y,
+                                                     long long out_image_stride_u, long long out_image_stride_v,
+                                                     const float* from_rgb, int out_bits, void* stream) {
+  const hdrnet_amd::YuvPlanarIo io{
+      {y, u, v, pitch_y, pitch_u, pitch_v, image_stride_y, image_stride_u, image_stride_v}, to_rgb, output_kind,
+      {out, out_u, out_v, out_pitch_y, out_pitch_u, out_pitch_v, out_image_stride_y, out_image_stride_u, out_image_stride_v},
+      from_rgb, out_bits};
+  const IoCoarse up{coarse, Hc, Wc};
+  return apply_io_yuv_planar_impl("hdrnet_bilateral_slice_apply_upadd_io_yuv_planar", grid,
+                                  io_guide_network(guide, guide_conv1, guide_conv2, n_feats, nullptr, flags), io, sample_dtype,
+                                  B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream, &up);
 }
 
 // ---- sample preparation (sample_prep.hip): hdrnet_prepare_batch* of include/hdrnet_amd_train.h, and the low-res network

@@ -308,7 +308,18 @@ hipError_t launch_apply_fwd_io_u16(const ApplyIoArgs& a, hipStream_t s, const ch
 bool apply_fwd_io_upadd_supported(const ApplyIoArgs& a, const float* coarse);
 hipError_t launch_apply_fwd_io_upadd(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
                                      const char** name);
-// apply_fwd_io.hip -- what the C ABI calls: the pair of whichever of the four families above the call belongs to (the
+// apply_fwd_io_upadd_yuv.hip -- ... and the same up-add on a 4:2:0 surface (a.yuv / a.yuvp; include/hdrnet_amd_pyramid_yuv.h):
+// every output kind of the single-level surface forwards, a.yuv->out_kind == kYuvOutP016 among them
+bool apply_fwd_io_upadd_yuv_supported(const ApplyIoArgs& a, const float* coarse);
+hipError_t launch_apply_fwd_io_upadd_yuv(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,
+                                         const char** name);
+// resize_bilinear_yuv.hip -- resize_bilinear of the frame launch_yuv_to_rgb / launch_yuv_planar_to_rgb write, read from the
+// surface (sample_dtype 1 u8 / 2 u16; an empty output is a no-op)
+hipError_t launch_resize_bilinear_yuv(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* out, int B, int Hin,
+                                      int Win, int Hout, int Wout, hipStream_t s, const char** name);
+hipError_t launch_resize_bilinear_yuv_planar(const YuvPlanarSurface& in, int sample_dtype, const float* to_rgb, float* out,
+                                             int B, int Hin, int Win, int Hout, int Wout, hipStream_t s, const char** name);
+// apply_fwd_io.hip -- what the C ABI calls: the pair of whichever of the families above the call belongs to (the
 // 16-bit output's, else the pixel source's; `coarse`: the up-add's coarser level, or null)
 bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse);
 hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse, int Hc, int Wc, hipStream_t s,

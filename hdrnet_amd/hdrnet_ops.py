@@ -1381,10 +1381,11 @@ def yuv_to_rgb(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, chroma: 
 
 def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, guide_curves,
                       return_guide, fast_sigmoid, prescaled, curves_prepared, from_rgb, out_planes, out_bits=None,
-                      chroma: str = "420"):
+                      chroma: str = "420", coarse=None):
     """The body of ``bilateral_slice_apply_io_yuv`` and ``bilateral_slice_apply_io_yuv_deep`` (``what``), once each has
     checked the arguments that say what comes out.  ``surface_dtype``: None for an RGB frame of ``out_dtype``, uint8 for an
-    NV12 surface, uint16 for a P010 / P016 surface of ``out_bits`` from a uint16 surface."""
+    NV12 surface, uint16 for a P010 / P016 surface of ``out_bits`` from a uint16 surface.  ``coarse``: the call is
+    ``bilateral_slice_apply_upadd_io_yuv`` (4:2:0, a guide map or the network): the coarser pyramid level to up-add."""
     deep = surface_dtype == torch.uint16
     y, uv, B, H, W, surf = _yuv_surface(y, uv, what, chroma=chroma)
     if deep and y.dtype != torch.uint16:
@@ -1399,6 +1400,8 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
                          f"{tuple(grid.shape)}")
     GH, GW, GD = grid.shape[1:4]
     tensors = [("grid", grid), ("y", y), ("uv", uv), ("to_rgb", to_rgb)]
+    if coarse is not None:
+        tensors.append(("coarse", _check_coarse(what, coarse, B)))
     oy = ouv = None
     if surface_dtype is not None:
         if not deep:
@@ -1438,9 +1441,14 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
         if chroma != "420":
             output += (0,)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), uv.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W, k_in.data_ptr(),
-            GH, GW, GD, 3, 3, 1)
-    if curves:
+    surface = (y.data_ptr(), uv.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W, k_in.data_ptr())
+    head = (*surface, GH, GW, GD, 3, 3, 1)
+    if coarse is not None:  # (the up-add entry points: the coarse level after to_rgb, no guide_out)
+        coarse = coarse.detach().contiguous()
+        fn = "hdrnet_bilateral_slice_apply_upadd_io_yuv"
+        args = (grid.data_ptr(), _ptr(g[0]), *surface, coarse.data_ptr(), coarse.shape[1], coarse.shape[2], GH, GW, GD, 3, 3, 1,
+                _ptr(g[1]), _ptr(g[2]), n, _guide_flags(fast_sigmoid, prescaled and g[0] is None))
+    elif curves:
         fn = "hdrnet_bilateral_slice_apply_io_curves_yuv"
         args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
     else:
@@ -1449,7 +1457,7 @@ def _apply_io_surface(what, surface_dtype, out_dtype, grid, y, uv, to_rgb, guide
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
         rc = getattr(_lib.load(), fn + ("_chroma" if chroma != "420" else "_p016" if deep else ""))(*args, *output, _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOYuv")
+    _lib.check(rc, "BilateralSliceApplyUpAddIOYuv" if coarse is not None else "BilateralSliceApplyIOYuv")
     return (result, gout) if return_guide else result
 
 
@@ -1658,7 +1666,15 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
     ``chroma`` (include/hdrnet_amd_yuv_chroma.h): ``"422"`` -- yuv422p / yuv422p10le / yuv422p16le, ``u`` and ``v``
     ``[B, H, W / 2]`` -- or ``"444"`` -- yuv444p..., ``[B, H, W]`` -- with any H; ``out="planar"`` is then a surface of the
     same layout, U and V from the mean of each horizontal pair (4:2:2) or per pixel (4:4:4)."""
-    what = "bilateral_slice_apply_io_yuv_planar"
+    return _apply_io_planar("bilateral_slice_apply_io_yuv_planar", grid, y, u, v, to_rgb, guide, guide_conv1, guide_conv2,
+                            guide_curves, return_guide, fast_sigmoid, prescaled, curves_prepared, out, out_dtype, from_rgb,
+                            out_bits, out_planes, chroma)
+
+
+def _apply_io_planar(what, grid, y, u, v, to_rgb, guide, guide_conv1, guide_conv2, guide_curves, return_guide, fast_sigmoid,
+                     prescaled, curves_prepared, out, out_dtype, from_rgb, out_bits, out_planes, chroma, coarse=None):
+    """The body of ``bilateral_slice_apply_io_yuv_planar`` (``what``).  ``coarse``: the call is
+    ``bilateral_slice_apply_upadd_io_yuv_planar`` (4:2:0, a guide map or the network): the coarser pyramid level to up-add."""
     chroma = _check_chroma(what, chroma, True)
     if out not in ("rgb", "planar"):
         raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
@@ -1686,6 +1702,8 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
                          f"{tuple(grid.shape)}")
     GH, GW, GD = grid.shape[1:4]
     tensors = [("grid", grid), ("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)]
+    if coarse is not None:
+        tensors.append(("coarse", _check_coarse(what, coarse, B)))
     planes = osurf = None
     if planar:
         from_rgb = _yuv_constants("from_rgb", from_rgb, what)
@@ -1726,9 +1744,15 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
         output = (_lib.YUV_PLANAR_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), None, None,
                   0, 0, 0, 0, 0, 0, None, 0)
     gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
-    head = (y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W,
-            k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
-    if curves:
+    surface = (y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, *(() if chroma == "420" else (_lib.CHROMA[chroma],)), B, H, W,
+               k_in.data_ptr())
+    head = (*surface, GH, GW, GD, 3, 3, 1)
+    if coarse is not None:  # (the up-add entry point: the coarse level after to_rgb, no guide_out)
+        coarse = coarse.detach().contiguous()
+        fn = "hdrnet_bilateral_slice_apply_upadd_io_yuv_planar"
+        args = (grid.data_ptr(), _ptr(g[0]), *surface, coarse.data_ptr(), coarse.shape[1], coarse.shape[2], GH, GW, GD, 3, 3, 1,
+                _ptr(g[1]), _ptr(g[2]), n, _guide_flags(fast_sigmoid, prescaled and g[0] is None))
+    elif curves:
         fn = "hdrnet_bilateral_slice_apply_io_curves_yuv_planar"
         args = (grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout))
     else:
@@ -1737,7 +1761,7 @@ def bilateral_slice_apply_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: 
                 _guide_flags(fast_sigmoid, prescaled and g[0] is None))
     with torch.cuda.device(dev):
         rc = getattr(_lib.load(), fn + ("_chroma" if chroma != "420" else ""))(*args, *output, _stream(dev))
-    _lib.check(rc, "BilateralSliceApplyIOYuvPlanar")
+    _lib.check(rc, "BilateralSliceApplyUpAddIOYuvPlanar" if coarse is not None else "BilateralSliceApplyIOYuvPlanar")
     return (result, gout) if return_guide else result
 
 
@@ -1806,3 +1830,141 @@ def bilateral_slice_apply_upadd_io(grid: torch.Tensor, input: torch.Tensor, coar
             _guide_flags(fast_sigmoid, prescaled and guide is None), _stream(dev))
     _lib.check(rc, "BilateralSliceApplyUpAddIO")
     return out
+
+
+# ---- the pyramid model on YUV 4:2:0 surfaces (include/hdrnet_amd_pyramid_yuv.h) ---------------------------------------------
+def _check_coarse(what: str, coarse, B: int) -> torch.Tensor:
+    """The coarser pyramid level of an up-add on a surface: float32 ``[B, Hc, Wc, 3]`` with Hc, Wc >= 1."""
+    _require_f32("coarse", coarse)
+    if coarse.dim() != 4 or coarse.shape[0] != B or coarse.shape[3] != 3 or min(coarse.shape[1], coarse.shape[2]) < 1:
+        raise ValueError(f"{what}: coarse should be [B, Hc, Wc, 3] = [{B}, >= 1, >= 1, 3], got {tuple(coarse.shape)}")
+    return coarse
+
+
+def _resize_extents(what: str, height, width):
+    if int(height) < 0 or int(width) < 0:
+        raise ValueError(f"{what}: bad output extents {height} x {width}")
+    return int(height), int(width)
+
+
+def resize_bilinear_yuv(y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """``resize_bilinear(yuv_to_rgb(y, uv, to_rgb), height, width)`` in one pass, without the RGB frame
+    (``hdrnet_resize_bilinear_yuv``, include/hdrnet_amd_pyramid_yuv.h): ``y`` ``[B, H, W]``, ``uv`` ``[B, H / 2, W]``, uint8
+    (NV12) or uint16 (P010 / P016), float32 ``[B, height, width, 3]`` out -- level 1 of ``HDRNetGaussianPyrNN``'s input
+    pyramid from a decoder surface.  Taps and lerps are ``resize_bilinear``'s; each tap is a pixel converted as
+    ``yuv_to_rgb`` converts it (chroma from ``(row >> 1, x >> 1)``, clamped before the blend).  Planes may be pitched (taken
+    as views); padding is not read.  An empty output is a no-op.  No autograd.  Out of scope: 4:2:2 / 4:4:4 surfaces."""
+    what = "resize_bilinear_yuv"
+    y, uv, B, H, W, surf = _yuv_surface(y, uv, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    height, width = _resize_extents(what, height, width)
+    for nm, t in (("y", y), ("uv", uv), ("to_rgb", to_rgb)):
+        _require_gpu(nm, t)
+    dev = y.device
+    k = to_rgb.detach().contiguous()
+    out = torch.empty((B, height, width, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().hdrnet_resize_bilinear_yuv(y.data_ptr(), uv.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
+                                                    height, width, _stream(dev))
+    _lib.check(rc, "ResizeBilinearYuv")
+    return out
+
+
+def resize_bilinear_yuv_planar(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, to_rgb: torch.Tensor, height: int,
+                               width: int) -> torch.Tensor:
+    """``resize_bilinear_yuv`` for a PLANAR 4:2:0 surface (``hdrnet_resize_bilinear_yuv_planar``): ``y`` ``[B, H, W]``, ``u``
+    and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with the code in the low bits; ``to_rgb`` of
+    ``yuv.yuv_coefficients(..., msb_aligned=False)``.  The bits of ``resize_bilinear_yuv`` on the interleaved surface.  No
+    autograd.  Out of scope: 4:2:2 / 4:4:4 surfaces."""
+    what = "resize_bilinear_yuv_planar"
+    B, H, W, surf = _yuv_planar_surface(y, u, v, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    height, width = _resize_extents(what, height, width)
+    for nm, t in (("y", y), ("u", u), ("v", v), ("to_rgb", to_rgb)):
+        _require_gpu(nm, t)
+    dev = y.device
+    k = to_rgb.detach().contiguous()
+    out = torch.empty((B, height, width, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().hdrnet_resize_bilinear_yuv_planar(y.data_ptr(), u.data_ptr(), v.data_ptr(), *surf, B, H, W,
+                                                           k.data_ptr(), out.data_ptr(), height, width, _stream(dev))
+    _lib.check(rc, "ResizeBilinearYuvPlanar")
+    return out
+
+
+def bilateral_slice_apply_upadd_io_yuv(grid: torch.Tensor, y: torch.Tensor, uv: torch.Tensor, to_rgb: torch.Tensor,
+                                       coarse: torch.Tensor,
+                                       guide: Optional[torch.Tensor] = None,
+                                       guide_conv1: Optional[torch.Tensor] = None,
+                                       guide_conv2: Optional[torch.Tensor] = None,
+                                       fast_sigmoid: bool = False, prescaled: bool = False,
+                                       out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                                       from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
+                                       out_planes=None, guide_curves=None):
+    """The finest level of ``HDRNetGaussianPyrNN._output`` on a semi-planar YUV 4:2:0 surface
+    (include/hdrnet_amd_pyramid_yuv.h): ``bilateral_slice_apply_upadd_io`` with the load and the stores of
+    ``bilateral_slice_apply_io_yuv`` / ``..._yuv_deep`` --
+    ``wire_out(bilateral_slice_apply(grid, guide, yuv_to_rgb(y, uv, to_rgb)) + resize_bilinear(coarse -> H x W))`` in one pass,
+    without the RGB frame.  ``coarse`` float32 ``[B, Hc, Wc, 3]``.  ``out="rgb"``: ``[B, H, W, 3]``, ``out_dtype`` float32
+    (default) or uint8; ``out="nv12"``: an NV12 uint8 surface ``(y_out, uv_out)`` encoded by ``from_rgb``; ``out="p010"`` /
+    ``"p016"`` (from a uint16 surface): a uint16 surface of 10- / 16-bit codes in the high bits, ``from_rgb`` of
+    ``yuv.yuv_encode_coefficients`` (``out_bits`` may repeat the depth).  The clip, the luma code and the 2 x 2 chroma sums
+    see the value after the add.  ``out_planes``: the pair to write into (pitched planes are fine).  The guide is a ``guide``
+    map or the folded guide network (``fast_sigmoid`` / ``prescaled`` as everywhere); the curves guide belongs to the
+    single-level models and is refused.  Cin = Cout = 3 with offset, H even, W % 4 == 0.  No autograd.  Out of scope:
+    4:2:2 / 4:4:4 surfaces, a uint16 RGB frame out, BGR / RGBA frames, the curves guide, training."""
+    what = "bilateral_slice_apply_upadd_io_yuv"
+    if guide_curves is not None:
+        raise ValueError(f"{what} takes a guide map or the guide network: the curves guide has no up-add form")
+    if out not in ("rgb", "nv12", "p010", "p016"):
+        raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12', 'p010', 'p016')")
+    if coarse is None:
+        raise ValueError(f"{what}: needs coarse, the coarser pyramid level [B, Hc, Wc, 3]")
+    if out in ("p010", "p016"):
+        bits = 10 if out == "p010" else 16
+        if out_bits not in (None, bits):
+            raise ValueError(f"{what}: out={out!r} has out_bits = {bits}, got {out_bits!r}")
+        if out_dtype not in (None, torch.uint16):
+            raise TypeError(f"{what}: a {out.upper()} output is uint16, got out_dtype = {out_dtype}")
+        if from_rgb is None:
+            raise ValueError(f"{what}: out={out!r} needs from_rgb (yuv.yuv_encode_coefficients)")
+        return _apply_io_surface(what, torch.uint16, None, grid, y, uv, to_rgb, guide, guide_conv1, guide_conv2, None, False,
+                                 fast_sigmoid, prescaled, None, from_rgb, out_planes, bits, coarse=coarse)
+    if out_bits is not None:
+        raise ValueError(f"{what}: out_bits belongs to out='p010' / 'p016'")
+    if out == "rgb":
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"{what}: out_dtype must be float32 or uint8, got {out_dtype}")
+        if from_rgb is not None or out_planes is not None:
+            raise ValueError(f"{what}: from_rgb / out_planes belong to a surface output")
+    else:
+        if out_dtype not in (None, torch.uint8):
+            raise TypeError(f"{what}: an NV12 output is uint8, got out_dtype = {out_dtype}")
+        if from_rgb is None:
+            raise ValueError(f"{what}: out='nv12' needs from_rgb (yuv.yuv_coefficients)")
+    return _apply_io_surface(what, None if out == "rgb" else torch.uint8, out_dtype, grid, y, uv, to_rgb, guide, guide_conv1,
+                             guide_conv2, None, False, fast_sigmoid, prescaled, None, from_rgb, out_planes, coarse=coarse)
+
+
+def bilateral_slice_apply_upadd_io_yuv_planar(grid: torch.Tensor, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                                              to_rgb: torch.Tensor, coarse: torch.Tensor,
+                                              guide: Optional[torch.Tensor] = None,
+                                              guide_conv1: Optional[torch.Tensor] = None,
+                                              guide_conv2: Optional[torch.Tensor] = None,
+                                              fast_sigmoid: bool = False, prescaled: bool = False,
+                                              out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                                              from_rgb: Optional[torch.Tensor] = None, out_bits: Optional[int] = None,
+                                              out_planes=None, guide_curves=None):
+    """``bilateral_slice_apply_upadd_io_yuv`` for a PLANAR 4:2:0 surface (I420, yuv420p10le / yuv420p16le): the load and the
+    stores of ``bilateral_slice_apply_io_yuv_planar`` with the up-add of ``coarse`` before any store -- the bits of the
+    semi-planar op on the interleaved surface.  ``out="rgb"`` (float32 / uint8) or ``out="planar"``: a planar surface
+    ``(y_out, u_out, v_out)`` of the input's dtype, ``from_rgb`` / ``out_bits`` / ``out_planes`` as there.  No autograd.  Out
+    of scope: 4:2:2 / 4:4:4 surfaces, a uint16 RGB frame out, the curves guide, training."""
+    what = "bilateral_slice_apply_upadd_io_yuv_planar"
+    if guide_curves is not None:
+        raise ValueError(f"{what} takes a guide map or the guide network: the curves guide has no up-add form")
+    if coarse is None:
+        raise ValueError(f"{what}: needs coarse, the coarser pyramid level [B, Hc, Wc, 3]")
+    return _apply_io_planar(what, grid, y, u, v, to_rgb, guide, guide_conv1, guide_conv2, None, False, fast_sigmoid, prescaled,
+                            None, out, out_dtype, from_rgb, out_bits, out_planes, "420", coarse=coarse)

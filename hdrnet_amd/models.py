@@ -989,3 +989,108 @@ class HDRNetGaussianPyrNN(HDRNetPointwiseNNGuide):
             return hdrnet_ops.bilateral_slice_apply_upadd_io(
                 grids[2], frame, cur, guide_conv1=gp[0][0], guide_conv2=gp[0][1], input_white_level=white_level,
                 out_dtype=out_dtype, has_offset=True, fast_sigmoid=self.fast_sigmoid, prescaled=gp[0][2])
+
+    # ---- YUV 4:2:0 surface in, frame or surface out (include/hdrnet_amd_pyramid_yuv.h) -------------------------------------
+    def _wire_yuv_tail(self, lowres, l1, fine_op, pixels, **fine_kwargs):
+        """``process_wire``'s launches after level 1: the coefficient network, level 2, the two coarser levels on float32,
+        then ``fine_op(grids[2], *pixels, coarse, guide network, **fine_kwargs)`` on the surface itself."""
+        from . import hdrnet_ops
+        grids = self.coefficients.levels(lowres)
+        l2 = hdrnet_ops.resize_bilinear(l1, l1.shape[1] // 2, l1.shape[2] // 2)
+        gp = [g.inference_params(self.prescale_guide) for g in self.guide]  # guide[0]: the finest level (models.py:278)
+        cur = hdrnet_ops.bilateral_slice_apply_nnguide(grids[0], l2, gp[2][0], gp[2][1], has_offset=True,
+                                                       fast_sigmoid=self.fast_sigmoid, prescaled=gp[2][2])
+        cur = hdrnet_ops.bilateral_slice_apply_upadd(grids[1], l1, cur, guide_conv1=gp[1][0], guide_conv2=gp[1][1],
+                                                     has_offset=True, fast_sigmoid=self.fast_sigmoid, prescaled=gp[1][2])
+        return fine_op(grids[2], *pixels, cur, guide_conv1=gp[0][0], guide_conv2=gp[0][1], fast_sigmoid=self.fast_sigmoid,
+                       prescaled=gp[0][2], **fine_kwargs)
+
+    def process_wire_yuv(self, y: torch.Tensor, uv: torch.Tensor, standard: str = "bt709", full_range: bool = False,
+                         bits: Optional[int] = None, out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                         out_planes=None, chroma: str = "420"):
+        """``process_wire`` for a semi-planar YUV 4:2:0 surface (include/hdrnet_amd_pyramid_yuv.h), with the arguments of
+        the single-level models' ``process_yuv``: ``y`` ``[B, H, W]`` and ``uv`` ``[B, H / 2, W]`` on the device, uint8 (NV12)
+        or uint16 (P010 ``bits=10`` / P016 ``bits=16``).  ``process_wire`` launch for launch -- ``data.lowres_input_yuv`` ->
+        the coefficient network -> level 1 by ``hdrnet_ops.resize_bilinear_yuv`` -> level 2 -> the two coarser levels on
+        float32 -> ``hdrnet_ops.bilateral_slice_apply_upadd_io_yuv`` on the surface -- so no RGB frame exists in memory.
+        ``out="rgb"``: ``[B, H, W, 3]`` float32 (default) or uint8; ``out="nv12"``: an NV12 uint8 surface ``(y_out, uv_out)``;
+        ``out="p010"`` / ``"p016"``: a uint16 surface, from a uint16 surface (``out_planes``: the pair to write into).
+        Inference only; capturable.  The fused pyramid's own condition holds: W % 16 == 0.  ``process_yuv`` keeps refusing
+        the pyramid model.  Out of scope: 4:2:2 / 4:4:4 surfaces
+        (``chroma`` other than ``"420"`` is refused), a uint16 RGB frame out, BGR / RGBA frames, the curves guide, training."""
+        from . import data, hdrnet_ops, yuv
+        what = f"{type(self).__name__}.process_wire_yuv"
+        if self.training:
+            raise RuntimeError("process_wire_yuv() is inference: call eval() first")
+        if standard not in yuv.STANDARDS:
+            raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
+        if chroma != "420":
+            raise ValueError(f"{what}: the pyramid model takes 4:2:0 surfaces only (chroma='420'), got chroma = {chroma!r}: its "
+                             "resize and up-add kernels have no 4:2:2 / 4:4:4 form")
+        if out not in ("rgb", "nv12", "p010", "p016"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'nv12', 'p010', 'p016')")
+        y, uv, B, H, W, _ = hdrnet_ops._yuv_surface(y, uv, what)
+        if W % 16 != 0:
+            raise ValueError(f"{what} runs the fused pyramid kernels, which need W % 16 == 0, got W = {W}")
+        deep = out in ("p010", "p016")
+        if deep and y.dtype != torch.uint16:
+            raise TypeError(f"{what}: out={out!r} needs a uint16 surface in (P010 / P016), got {y.dtype}")
+        if deep and out_dtype not in (None, torch.uint16):
+            raise TypeError(f"{what}: a {out.upper()} output is uint16, got out_dtype = {out_dtype}")
+        if bits is None:
+            bits = 8 if y.dtype == torch.uint8 else 16
+        if bits not in yuv.BITS or (bits == 8) != (y.dtype == torch.uint8):
+            raise ValueError(f"{what}: bits = {bits!r} does not fit {y.dtype} planes (uint8: 8; uint16: 10 or 16)")
+        hdrnet_ops._require_gpu("y", y)
+        with torch.no_grad():
+            to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, y.device)
+            lowres = data.lowres_input_yuv(y, uv, to_rgb, self.params["net_input_size"])
+            l1 = hdrnet_ops.resize_bilinear_yuv(y, uv, to_rgb, H // 2, W // 2)
+            if deep:
+                out_bits = 10 if out == "p010" else 16
+                kw = {"from_rgb": self._yuv_encode_constants(standard, full_range, out_bits, y.device)}
+            else:
+                kw = {"out_dtype": out_dtype, "from_rgb": from_rgb if out == "nv12" else None}
+            return self._wire_yuv_tail(lowres, l1, hdrnet_ops.bilateral_slice_apply_upadd_io_yuv, (y, uv, to_rgb), out=out,
+                                       out_planes=out_planes, **kw)
+
+    def process_wire_yuv_planar(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, standard: str = "bt709",
+                                full_range: bool = False, bits: Optional[int] = None, out: str = "rgb",
+                                out_dtype: Optional[torch.dtype] = None, out_planes=None, chroma: str = "420"):
+        """``process_wire_yuv`` for a PLANAR 4:2:0 surface, with the arguments of the single-level models'
+        ``process_yuv_planar``: ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]``, uint8 (I420) or uint16 with the code
+        in the low bits (yuv420p10le ``bits=10`` / yuv420p16le ``bits=16``).  ``out="rgb"`` (float32 / uint8) or
+        ``out="planar"``: a planar surface ``(y_out, u_out, v_out)`` of the input's dtype, depth, standard and range.
+        Inference only; capturable; W % 16 == 0.  Out of scope: 4:2:2 / 4:4:4 surfaces, a uint16 RGB frame out, training."""
+        from . import data, hdrnet_ops, yuv
+        what = f"{type(self).__name__}.process_wire_yuv_planar"
+        if self.training:
+            raise RuntimeError("process_wire_yuv_planar() is inference: call eval() first")
+        if standard not in yuv.STANDARDS:
+            raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
+        if chroma != "420":
+            raise ValueError(f"{what}: the pyramid model takes 4:2:0 surfaces only (chroma='420'), got chroma = {chroma!r}: its "
+                             "resize and up-add kernels have no 4:2:2 / 4:4:4 form")
+        if out not in ("rgb", "planar"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'planar')")
+        B, H, W, _ = hdrnet_ops._yuv_planar_surface(y, u, v, what)
+        if W % 16 != 0:
+            raise ValueError(f"{what} runs the fused pyramid kernels, which need W % 16 == 0, got W = {W}")
+        if out == "planar" and out_dtype not in (None, y.dtype):
+            raise TypeError(f"{what}: a planar output has the input's dtype ({y.dtype}), got out_dtype = {out_dtype}")
+        if bits is None:
+            bits = 8 if y.dtype == torch.uint8 else 16
+        if bits not in yuv.BITS or (bits == 8) != (y.dtype == torch.uint8):
+            raise ValueError(f"{what}: bits = {bits!r} does not fit {y.dtype} planes (uint8: 8; uint16: 10 or 16)")
+        hdrnet_ops._require_gpu("y", y)
+        with torch.no_grad():
+            to_rgb, _ = self._yuv_constants(standard, full_range, bits, y.device, msb_aligned=False)
+            lowres = data.lowres_input_yuv_planar(y, u, v, to_rgb, self.params["net_input_size"])
+            l1 = hdrnet_ops.resize_bilinear_yuv_planar(y, u, v, to_rgb, H // 2, W // 2)
+            if out == "planar":
+                kw = {"out_bits": bits, "out_planes": out_planes,
+                      "from_rgb": self._yuv_encode_constants(standard, full_range, bits, y.device)}
+            else:
+                kw = {"out_dtype": out_dtype}
+            return self._wire_yuv_tail(lowres, l1, hdrnet_ops.bilateral_slice_apply_upadd_io_yuv_planar, (y, u, v, to_rgb),
+                                       out=out, **kw)

@@ -121,6 +121,10 @@ class _ProcessYuv(torch.nn.Module):
         self.layout = {} if chroma == "420" else {"chroma": chroma}
 
     def forward(self, y: torch.Tensor, uv: torch.Tensor):
+        # a model whose process_yuv() refuses surfaces offers them as process_wire_yuv() (HDRNetGaussianPyrNN), as _Process does
+        if hasattr(self.model, "process_wire_yuv"):
+            return self.model.process_wire_yuv(y, uv, standard=self.standard, full_range=self.full_range, bits=self.bits,
+                                               out=self.out, out_dtype=self.out_dtype, **self.layout)
         return self.model.process_yuv(y, uv, standard=self.standard, full_range=self.full_range, bits=self.bits,
                                       out=self.out, out_dtype=self.out_dtype, **self.layout)
 
@@ -153,6 +157,9 @@ class _ProcessYuvPlanar(torch.nn.Module):
         self.layout = {} if chroma == "420" else {"chroma": chroma}
 
     def forward(self, y: torch.Tensor, u: torch.Tensor, v: torch.Tensor):
+        if hasattr(self.model, "process_wire_yuv_planar"):  # (the pyramid model, as above)
+            return self.model.process_wire_yuv_planar(y, u, v, standard=self.standard, full_range=self.full_range,
+                                                      bits=self.bits, out=self.out, out_dtype=self.out_dtype, **self.layout)
         return self.model.process_yuv_planar(y, u, v, standard=self.standard, full_range=self.full_range, bits=self.bits,
                                              out=self.out, out_dtype=self.out_dtype, **self.layout)
 

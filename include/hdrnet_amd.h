@@ -104,7 +104,11 @@ extern "C" {
  *   285  + hdrnet_resize_bilinear_io / hdrnet_bilateral_slice_apply_upadd_io_ex in hdrnet_amd_pyramid_io.h (a header of
  *        its own, beside this one): the pyramid model's uint8 / uint16 wire formats.
  *   286  + hdrnet_lowres_input_px / hdrnet_bilateral_slice_apply_io_px / hdrnet_bilateral_slice_apply_io_curves_px in
- *        hdrnet_amd_pixel_formats.h (a header of its own): uint8 / uint16 frames in BGR, RGBA and BGRA order. */
+ *        hdrnet_amd_pixel_formats.h (a header of its own): uint8 / uint16 frames in BGR, RGBA and BGRA order.
+ *   287 .. 290  + the surface headers, each a header of its own: hdrnet_amd_yuv.h (287), hdrnet_amd_u16_out.h (288),
+ *        hdrnet_amd_yuv_planar.h (289), hdrnet_amd_yuv_chroma.h (290).
+ *   291  + hdrnet_resize_bilinear_yuv[_planar] / hdrnet_bilateral_slice_apply_upadd_io_yuv[_p016 | _planar] in
+ *        hdrnet_amd_pyramid_yuv.h (a header of its own): the pyramid model on YUV 4:2:0 surfaces. */
 int hdrnet_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

@@ -35,7 +35,8 @@
  * P210 / P216 surfaces out (4:2:2) are include/hdrnet_amd_yuv_chroma.h's: the surface entry points below with a `chroma`
  * argument.
  * Out of scope (the kernels are instantiated for the cases above only): uint8 frames or NV12 surfaces to a 16-bit output,
- * float32 frames in other orders than RGB, a uint16 RGB frame out of a YUV surface, the pyramid model. */
+ * float32 frames in other orders than RGB, a uint16 RGB frame out of a YUV surface, the pyramid model's uint16 RGB frame (its
+ * P010 / P016 surface out is include/hdrnet_amd_pyramid_yuv.h's). */
 #ifndef HDRNET_AMD_U16_OUT_H_
 #define HDRNET_AMD_U16_OUT_H_
 

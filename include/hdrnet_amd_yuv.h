@@ -36,8 +36,8 @@
  * Planar surfaces (I420, yuv420p10le / yuv420p16le: three planes) are include/hdrnet_amd_yuv_planar.h's.
  * 4:2:2 surfaces (NV16, P210 / P216) and planar 4:4:4 ones are include/hdrnet_amd_yuv_chroma.h's: these entry points with a
  * `chroma` argument.  The entry points below keep refusing them (H % 2, the UV plane's rows).
- * Out of scope: sited / bilinear chroma, a uint16 RGB frame out of a surface, NV12 in -> P010 / P016 out, the pyramid
- * model. */
+ * The pyramid model on these surfaces is include/hdrnet_amd_pyramid_yuv.h's.
+ * Out of scope: sited / bilinear chroma, a uint16 RGB frame out of a surface, NV12 in -> P010 / P016 out. */
 #ifndef HDRNET_AMD_YUV_H_
 #define HDRNET_AMD_YUV_H_
 

@@ -38,7 +38,7 @@
  * 4:2:2 and 4:4:4 planar surfaces (yuv422p..., yuv444p...) are include/hdrnet_amd_yuv_chroma.h's: these entry points with a
  * `chroma` argument.  The entry points below keep refusing them.
  * Out of scope: 12-bit depth, sited or bilinear chroma, uint16 planar in -> uint8 planar out, planar in -> semi-planar out
- * and semi-planar in -> planar out, the pyramid model. */
+ * and semi-planar in -> planar out.  The pyramid model on these surfaces is include/hdrnet_amd_pyramid_yuv.h's. */
 #ifndef HDRNET_AMD_YUV_PLANAR_H_
 #define HDRNET_AMD_YUV_PLANAR_H_
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|yuv_chroma|u16_out] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|yuv_chroma|u16_out|pyramid_yuv] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -29,7 +29,10 @@ pair for yuv420p10le (the chain shifts by 6 each way around P010), and the fused
 NV12 -> NV12, all alternating; `yuv_chroma` = 4:2:2 / 4:4:4 surfaces (include/hdrnet_amd_yuv_chroma.h): a hipGraph of
 process_yuv_planar(..., chroma=..., out="planar") against a hipGraph of the stock chain (replicate chroma -> affine + clamp
 -> process -> affine -> footprint mean -> quantise) for yuv422p10le and yuv444p at 4K and 1080p, and the fused kernel alone at
-4K, yuv422p -> yuv422p and yuv444p -> yuv444p against NV12 -> NV12, all alternating.  --tools loads the tools build and adds the un-fused
+4K, yuv422p -> yuv422p and yuv444p -> yuv444p against NV12 -> NV12, all alternating; `pyramid_yuv` = HDRNetGaussianPyrNN on
+decoder surfaces (include/hdrnet_amd_pyramid_yuv.h): a hipGraph of process_wire_yuv, NV12 -> NV12 and P010 -> P010 at 4K and
+1080p, against a hipGraph of yuv_to_rgb -> process -> stock encode, and the finest level's kernel alone at 4K against its RGB
+sibling, all alternating.  --tools loads the tools build and adds the un-fused
 gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -112,6 +115,8 @@ def main():
         return yuv_planar(lib, dev, args)
     if args.workload == "yuv_chroma":
         return yuv_chroma(lib, dev, args)
+    if args.workload == "pyramid_yuv":
+        return pyramid_yuv(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -754,6 +759,140 @@ def yuv_surfaces(lib, dev, args):
         del sets
     if args.json:
         json.dump(dict(workload="yuv", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _PyramidYuvChain(torch.nn.Module):
+    """What a caller with a decoder surface and the pyramid model wrote before process_wire_yuv: hdrnet_ops.yuv_to_rgb into a
+    float32 RGB frame, process (the float32 pyramid), and the stock encode half of _YuvStockChain -- an affine to Y, U, V, the
+    2 x 2 mean of the chroma, quantise to ``bits`` bits (codes in the high bits of a uint16 sample), interleave."""
+
+    def __init__(self, model, to_rgb, from_rgb, bits):
+        super().__init__()
+        self.model, self.bits = model, bits
+        self.register_buffer("to_rgb", to_rgb, persistent=False)
+        self.register_buffer("m_out", from_rgb[:9].reshape(3, 3).t().contiguous(), persistent=False)
+        self.register_buffer("b_out", from_rgb[9:].contiguous(), persistent=False)
+
+    def forward(self, y, uv):
+        from hdrnet_amd import hdrnet_ops
+        B, H, W = y.shape
+        top = float(2 ** self.bits - 1)
+        out = self.model.process(hdrnet_ops.yuv_to_rgb(y, uv, self.to_rgb)).clamp_(0.0, 1.0)
+        enc = out @ self.m_out
+        yq = (enc[..., 0] + self.b_out[0]).clamp_(0.0, top)
+        cm = (enc[..., 1:].reshape(B, H // 2, 2, W // 2, 2, 2).mean(dim=(2, 4)) + self.b_out[1:]).clamp_(0.0, top).reshape(B, H // 2, W)
+        if self.bits == 8:
+            return yq.to(torch.uint8), cm.to(torch.uint8)
+        sh = 16 - self.bits
+        return (yq.to(torch.int32) << sh).to(torch.uint16), (cm.to(torch.int32) << sh).to(torch.uint16)
+
+
+def pyramid_yuv(lib, dev, args):
+    """HDRNetGaussianPyrNN on decoder surfaces at 4K and 1080p, NV12 -> NV12 and P010 -> P010: one hipGraph of
+    process_wire_yuv (YuvFrameInference: the resize and the finest level read the surface, the finest level stores one)
+    against one hipGraph of _PyramidYuvChain, the chain a caller had.  Both are warmed, then run ALTERNATING three times each
+    in one process; reported: the mean of the three and their range (device events around `steps` replays).  Beside it,
+    without a bar, at 4K: the finest level's kernel alone, nv12 -> nv12 + nnguide + upadd (3 bytes per pixel) against
+    u8 -> u8 + nnguide + upadd on an RGB frame (6), over buffer sets that together exceed the Infinity Cache, alternating the
+    same way."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import GraphedInference, YuvFrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetGaussianPyrNN(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def samples(bits, *shape):
+        t = torch.randint(0, 2 ** bits, shape, device=dev, dtype=torch.int32, generator=gen)
+        return t.to(torch.uint8) if bits == 8 else (t << (16 - bits)).to(torch.uint16)
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        for bits, out in ((8, "nv12"), (10, "p010")):
+            to_rgb = torch.from_numpy(yuv.yuv_coefficients("bt709", False, bits)[0]).to(dev)
+            from_rgb = torch.from_numpy(yuv.yuv_encode_coefficients("bt709", False, bits)).to(dev)
+            surfaces = [(samples(bits, 1, H, W), samples(bits, 1, H // 2, W)) for _ in range(3)]
+            new = YuvFrameInference(m, *surfaces[0], bits=bits, out=out)
+            base = GraphedInference(_PyramidYuvChain(m, to_rgb, from_rgb, bits), list(surfaces[0]))
+            (ny, nuv), (by, buv) = new(*surfaces[1]), base(*surfaces[1])
+            sh = 16 - bits if bits > 8 else 0
+            dy = ((ny.int() >> sh) - (by.int() >> sh)).abs()
+            duv = ((nuv.int() >> sh) - (buv.int() >> sh)).abs()
+            # (the chain rounds its affine ops in another order: it is a timing opponent, not the reference of the tests)
+            print(f"{H}x{W} {out}: fused vs chain, codes that differ: Y {int((dy > 0).sum())} (max {int(dy.max())}), "
+                  f"UV {int((duv > 0).sum())} (max {int(duv.max())}) of {dy.numel()} + {duv.numel()}")
+            assert int(dy.max()) <= 1 and int(duv.max()) <= 1, "the two paths encode the same surface to within a code"
+            b, n = alternate(lambda k: base(*surfaces[k % 3]), lambda k: new(*surfaces[k % 3]))
+            mb, mn = statistics.mean(b), statistics.mean(n)
+            spread = max(b) - min(b)
+            name = f"{H}x{W} pyramid model, {out} -> {out}"
+            rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                             us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                             below_chain_beyond_its_spread=bool(mb - mn > spread)))
+            print(f"{name:44s} chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_wire_yuv {mn:8.2f} us "
+                  f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+                  f"below the chain by more than its spread: {mb - mn > spread}")
+            del new, base, surfaces
+
+    # the finest level's kernel alone at 4K: the same grid, guide network and coarse level over two frame layouts
+    H, W = 2160, 3840
+    GH, GW, GD = 16, 16, 8
+    nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 3)))
+    to_rgb, from_rgb = (torch.from_numpy(a).to(dev) for a in yuv.yuv_coefficients("bt709", False, 8))
+    grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+    conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+    conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+    coarse = (0.3 * torch.randn((1, H // 2, W // 2, 3), device=dev, generator=gen)).contiguous()
+    sets = [dict(rgb=samples(8, 1, H, W, 3), y=samples(8, 1, H, W), uv=samples(8, 1, H // 2, W),
+                 out3=torch.empty((1, H, W, 3), device=dev, dtype=torch.uint8),
+                 oy=torch.empty((1, H, W), device=dev, dtype=torch.uint8),
+                 ouv=torch.empty((1, H // 2, W), device=dev, dtype=torch.uint8)) for _ in range(nsets)]
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(lib.hdrnet_last_error().decode())
+
+    def rgb_kernel(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_upadd_io_ex(grid.data_ptr(), None, t["rgb"].data_ptr(), coarse.data_ptr(), H // 2,
+                                                           W // 2, t["out3"].data_ptr(), 1, H, W, GH, GW, GD, 3, 3, 1, 1, 255.0, 1,
+                                                           conv1.data_ptr(), conv2.data_ptr(), 16, _lib.GUIDE_SIGMOID_FAST, stream))
+
+    def yuv_kernel(k):
+        t = sets[k % nsets]
+        check(lib.hdrnet_bilateral_slice_apply_upadd_io_yuv(grid.data_ptr(), None, t["y"].data_ptr(), t["uv"].data_ptr(), 1, W, W,
+                                                            H * W, H // 2 * W, 1, H, W, to_rgb.data_ptr(), coarse.data_ptr(),
+                                                            H // 2, W // 2, GH, GW, GD, 3, 3, 1, conv1.data_ptr(),
+                                                            conv2.data_ptr(), 16, _lib.GUIDE_SIGMOID_FAST, 2, t["oy"].data_ptr(),
+                                                            t["ouv"].data_ptr(), W, W, H * W, H // 2 * W, from_rgb.data_ptr(),
+                                                            stream))
+
+    rgb_kernel(0)
+    k_rgb = lib.hdrnet_last_kernel().decode()
+    yuv_kernel(0)
+    k_yuv = lib.hdrnet_last_kernel().decode()
+    r, q = alternate(rgb_kernel, yuv_kernel)
+    name = f"{H}x{W} kernel, +nnguide+upadd"
+    row = dict(op=name, kernels=[k_rgb, k_yuv])
+    text = []
+    for key, label, t in (("rgb_u8_u8", f"{k_rgb} (6 B/px)", r), ("nv12_nv12", f"{k_yuv} (3 B/px)", q)):
+        row.update({f"us_{key}": round(statistics.mean(t), 2), f"us_{key}_min": round(min(t), 2), f"us_{key}_max": round(max(t), 2)})
+        text.append(f"{label} {statistics.mean(t):8.2f} us ({min(t):8.2f} .. {max(t):8.2f})")
+    rows.append(row)
+    print(f"{name:36s} " + "   ".join(text))
+    if args.json:
+        json.dump(dict(workload="pyramid_yuv", rows=rows), open(args.json, "w"), indent=1)
 
 
 class _PlanarChain(torch.nn.Module):
