@@ -249,6 +249,21 @@ YUV_CHROMA_SIGNATURES = {
                                                                  [_FP] * 4 + [_I, _VP, _FP] + _PLANAR_OUTPUT + [_VP]),
 }
 
+# include/hdrnet_amd_yuv_packed.h: packed 4:2:2 surfaces (YUY2 / UYVY / YVYU, Y210 / Y216) -- the semi-planar 4:2:2 entry points
+# above on one plane.  A surface travels as (surface, sample_dtype, pitch, image_stride, order); the output as (output_kind,
+# out, out_pitch, out_image_stride, from_rgb, out_bits).
+PACKED_ORDER = {"yuy2": 0, "yuyv": 0, "uyvy": 1, "yvyu": 2, "y210": 0, "y216": 0}  # HDRNET_PACKED_*
+_PACKED_SURFACE = [_FP, _I, _I, _LL, _I]
+_PACKED_OUTPUT = [_I, _FP, _I, _LL, _FP, _I]
+YUV_PACKED_SIGNATURES = {
+    "hdrnet_yuv_packed_to_rgb_f32": (_I, _PACKED_SURFACE + [_I] * 3 + [_FP, _FP, _VP]),
+    "hdrnet_lowres_input_yuv_packed": (_I, _PACKED_SURFACE + [_I] * 3 + [_FP, _FP, _I, _VP]),
+    "hdrnet_bilateral_slice_apply_io_yuv_packed": (_I, [_FP, _FP] + _PACKED_SURFACE + [_I] * 3 + [_FP] + [_I] * 6 +
+                                                   [_FP, _FP, _I, _FP, _U] + _PACKED_OUTPUT + [_VP]),
+    "hdrnet_bilateral_slice_apply_io_curves_yuv_packed": (_I, [_FP] + _PACKED_SURFACE + [_I] * 3 + [_FP] + [_I] * 6 + [_FP] * 4 +
+                                                          [_I, _VP, _FP] + _PACKED_OUTPUT + [_VP]),
+}
+
 # include/hdrnet_amd_pyramid_yuv.h: the pyramid model on YUV 4:2:0 surfaces -- the resize that reads a surface (the
 # surface, B, H, W, to_rgb, out, Hout, Wout) and the finest level's slice-apply + up-add: the single-level surface entry
 # points with (coarse, Hc, Wc) after to_rgb and without guide_out.
@@ -321,6 +336,7 @@ def _open(tools: bool) -> ctypes.CDLL:
     table.update(U16_OUT_SIGNATURES)
     table.update(YUV_PLANAR_SIGNATURES)
     table.update(YUV_CHROMA_SIGNATURES)
+    table.update(YUV_PACKED_SIGNATURES)
     table.update(PYRAMID_YUV_SIGNATURES)
     if tools:
         table.update(TOOLS_SIGNATURES)

@@ -48,6 +48,8 @@ SOURCES = [
     ("apply_fwd_io_yuv_422.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_yuv_planar_422.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_yuv_planar_444.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
+    # ... and for packed 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h): YUY2 / UYVY / YVYU / Y210 / Y216
+    ("apply_fwd_io_yuv_packed.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     # ... and with a 16-bit output: a uint16 frame, a P010 / P016 surface (include/hdrnet_amd_u16_out.h)
     ("apply_fwd_io_u16.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]),
     ("apply_fwd_io_upadd.hip", ["-fno-slp-vectorize"]),
@@ -121,6 +123,7 @@ def _deps() -> List[str]:
            os.path.join(INCLUDE, "hdrnet_amd_pyramid_io.h"), os.path.join(INCLUDE, "hdrnet_amd_pixel_formats.h"),
            os.path.join(INCLUDE, "hdrnet_amd_yuv.h"), os.path.join(INCLUDE, "hdrnet_amd_u16_out.h"),
            os.path.join(INCLUDE, "hdrnet_amd_yuv_planar.h"), os.path.join(INCLUDE, "hdrnet_amd_yuv_chroma.h"),
+           os.path.join(INCLUDE, "hdrnet_amd_yuv_packed.h"),
            os.path.join(INCLUDE, "hdrnet_amd_pyramid_yuv.h"),
            os.path.abspath(__file__)]
     for f in os.listdir(CSRC):

@@ -15,9 +15,10 @@ bool apply_fwd_io_supported(const ApplyIoArgs& a) {
 // source's (a.yuv, a.yuvp, or `coarse` for the pyramid's up-add).
 namespace {
 enum IoFamily { kFamilyFrame, kFamilyYuv, kFamilyU16, kFamilyUpAdd, kFamilyYuvPlanar, kFamilyYuv422, kFamilyYuvPlanarChroma,
-                kFamilyUpAddYuv };
+                kFamilyUpAddYuv, kFamilyYuvPacked };
 IoFamily io_family(const ApplyIoArgs& a, const float* coarse) {
   // (a 4:2:2 / 4:4:4 surface carries every output kind of its own, as a planar one does)
+  if (a.yuvk) return kFamilyYuvPacked;  // (a packed 4:2:2 surface: every output kind of its own)
   if (a.yuvp && a.yuvp->chroma != kChroma420) return kFamilyYuvPlanarChroma;
   if (a.yuv && a.yuv->chroma != kChroma420) return kFamilyYuv422;
   if (coarse && (a.yuv || a.yuvp)) return kFamilyUpAddYuv;  // (the pyramid's finest level on a 4:2:0 surface, any output kind)
@@ -32,6 +33,7 @@ bool apply_fwd_io_family_supported(const ApplyIoArgs& a, const float* coarse) {
     case kFamilyYuv: return apply_fwd_io_yuv_supported(a);
     case kFamilyYuvPlanar: return !coarse && apply_fwd_io_yuv_planar_supported(a);
     case kFamilyYuv422: return !coarse && apply_fwd_io_yuv_422_supported(a);
+    case kFamilyYuvPacked: return !coarse && apply_fwd_io_yuv_packed_supported(a);
     case kFamilyYuvPlanarChroma: return !coarse && apply_fwd_io_yuv_planar_chroma_supported(a);
     case kFamilyUpAdd: return apply_fwd_io_upadd_supported(a, coarse);
     case kFamilyUpAddYuv: return apply_fwd_io_upadd_yuv_supported(a, coarse);
@@ -46,6 +48,7 @@ hipError_t launch_apply_fwd_io_family(const ApplyIoArgs& a, const float* coarse,
     case kFamilyYuv: return launch_apply_fwd_io_yuv(a, s, name);
     case kFamilyYuvPlanar: return launch_apply_fwd_io_yuv_planar(a, s, name);
     case kFamilyYuv422: return launch_apply_fwd_io_yuv_422(a, s, name);
+    case kFamilyYuvPacked: return launch_apply_fwd_io_yuv_packed(a, s, name);
     case kFamilyYuvPlanarChroma:
       return a.yuvp->chroma == kChroma422 ? launch_apply_fwd_io_yuv_planar_422(a, s, name)
                                           : launch_apply_fwd_io_yuv_planar_444(a, s, name);

@@ -25,6 +25,12 @@
 // PAIR, runs the stage-image / pixel phase twice over the same LDS region and keeps the 2 x 2 blocks' chroma sums in
 // registers in between.  Neither changes a line of what the other instantiations compile.
 //
+// PACKED 4:2:2 SURFACES (include/hdrnet_amd_yuv_packed.h): YUY2 / UYVY / YVYU / Y210 / Y216, the NV16 / P210 surface with its
+// two planes woven into one.  PX = kPxYuvPacked is the surface load from ONE plane -- a lane's 4 pixels are 8 contiguous bytes
+// of uint8 samples, 16 of uint16 -- and OUT = kOutYuy2 / kOutY216 a store of its own that weaves the 4:2:2 code words back; the
+// byte order is a wave-uniform v_perm_b32 selector, not an instantiation.  Their instantiations are
+// apply_fwd_io_yuv_packed.hip's; every instantiation above compiles to the code it was.
+//
 // This header holds the kernel, its launch and what the front ends share (label, guide-form dispatch, common predicate
 // rules); the RGB instantiations are compiled by apply_fwd_io.hip, those of the
 // other formats by apply_fwd_io_px.hip (a translation unit of its own: they are twice as many), those of the YUV
@@ -92,6 +98,9 @@ constexpr int kPxYuvPlanar = 5;  // ... or a PLANAR one (IoParams::pin): the sam
 constexpr int kOutFrame = 0, kOutNV12 = 1, kOutP016 = 2;
 // ... or a planar surface (IoParams::pout): I420 (uint8 code words) / uint16 code words in the LOW bits (code_shift = 0)
 constexpr int kOutI420 = 3, kOutI016 = 4;
+// ... or a PACKED 4:2:2 one (IoParams::kin / kout): YUY2 / UYVY / YVYU (uint8), Y210 / Y216 (uint16, the code in the high bits)
+constexpr int kPxYuvPacked = 6;
+constexpr int kOutYuy2 = 5, kOutY216 = 6;
 
 struct GuideNet {
   const float* conv1;  // NN: [n][CIN + 1]            curves: ccm [CIN][CIN + 1] (row = output channel)
@@ -446,7 +455,16 @@ struct IoParams {
   SegTab tab;      // (cmin, ncols) per segment, from the host (seg_common.hip.h)
   GuideNet gn;
   // YUV surfaces (PX == kPxYuv / OUT == kOutNV12; unused by every other instantiation)
-  YuvSurface yin, yout;
+  // (a packed 4:2:2 surface, PX == kPxYuvPacked / OUT == kOutYuy2, kOutY216, SHARES their bytes: it is one plane of the pair,
+  // and a longer IoParams moves the kernel-argument loads of every instantiation -- see IoUpParams below)
+  union {
+    YuvSurface yin;
+    YuvPackedSurface kin;
+  };
+  union {
+    YuvSurface yout;
+    YuvPackedSurface kout;
+  };
   const float* to_rgb;    // 12 floats each (yuv_convert.hip.h)
   const float* from_rgb;
   // 16-bit output (TO = uint16_t / OUT == kOutP016; read by no other instantiation)
@@ -474,7 +492,8 @@ template <int CIN, int COUT, bool OFFSET, int GUIDE, typename TI, typename TO, i
 __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParamsOf<UPADD> p) {
   static_assert(PX == kPxRGB || (CIN == 3 && COUT == 3 && sizeof(TI) < 4), "pixel formats: integer frames, 3 -> 3");
   constexpr bool PLANAR = PX == kPxYuvPlanar;  // the input is a planar YUV surface: three planes
-  constexpr bool YUV = PX == kPxYuv || PLANAR;  // the input is a YUV surface; the frame the kernel stores is RGB
+  constexpr bool YUVPACKED = PX == kPxYuvPacked;  // ... a packed 4:2:2 one: one plane
+  constexpr bool YUV = PX == kPxYuv || PLANAR || YUVPACKED;  // the input is a YUV surface; the frame the kernel stores is RGB
   constexpr bool NV12OUT = OUT == kOutNV12;   // ... unless the output is an NV12 surface: a workgroup owns a row pair
   static_assert(!NV12OUT || (YUV && sizeof(TO) == 1), "NV12 out: uint8 planes, from a YUV surface");
   constexpr bool P016OUT = OUT == kOutP016;   // ... or a P010 / P016 surface: the same row pair, uint16 code words
@@ -484,6 +503,10 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParamsOf<UPADD>
   static_assert(!I016OUT || (PLANAR && sizeof(TI) == 2 && sizeof(TO) == 2), "uint16 planar out: from a uint16 planar surface");
   constexpr bool PLANAROUT = I420OUT || I016OUT;
   constexpr bool SURFOUT = NV12OUT || P016OUT || PLANAROUT;
+  constexpr bool PACKEDOUT = OUT == kOutYuy2 || OUT == kOutY216;  // ... or a packed 4:2:2 one, of the input's width and order
+  static_assert(!YUVPACKED || CH == kChroma422, "a packed surface is 4:2:2");
+  static_assert(!PACKEDOUT || (YUVPACKED && sizeof(TI) == sizeof(TO) && (OUT == kOutYuy2) == (sizeof(TO) == 1)),
+                "a packed surface out: from a packed surface of the same sample width");
   // CH: the surfaces' chroma layout (yuv_convert.hip.h).  4:2:2 and 4:4:4 have a chroma row per image row: a surface
   // output is then ONE row per workgroup, as a frame is, and its chroma is stored after that row.
   static_assert(CH == kChroma420 || YUV, "a chroma layout belongs to a YUV surface");
@@ -551,7 +574,8 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParamsOf<UPADD>
         const float4 g4 = *reinterpret_cast<const float4*>(p.guide + px);
         gs[0] = g4.x; gs[1] = g4.y; gs[2] = g4.z; gs[3] = g4.w;
       }
-      if constexpr (PLANAR) yuv_load_quad<TI, CH>(p.pin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      if constexpr (YUVPACKED) yuv_load_quad<TI>(p.kin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
+      else if constexpr (PLANAR) yuv_load_quad<TI, CH>(p.pin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
       else if constexpr (YUV) yuv_load_quad<TI, CH>(p.yin, yuv_load_matrix(p.to_rgb), b, y, x, inf);
       else load_pixels<TI, NI, FOLD_WL, PX>(input, px * SPX, p.white, inf, nullptr, alpha);
     }
@@ -605,7 +629,44 @@ __global__ __launch_bounds__(256) void apply_fwd_io_rows(const IoParamsOf<UPADD>
       if constexpr (UPADD) upadd_quad<COUT>(p.up, b, y, x, of);  // (once per row of a pair, with that row's y)
     }
 
-    if constexpr (SURFOUT) {
+    if constexpr (PACKEDOUT) {
+      // A packed 4:2:2 surface: the NV16 / P210 code words of the branch below -- luma per pixel, chroma from the horizontal
+      // pair's sum with weight 0.5, expression for expression -- woven into the lane's two groups Y0 U Y1 V: 2 dwords of
+      // uint8 code words (each put into the surface's byte order by the load's selector, which is its own inverse), 4 of
+      // uint16 ([Y U][Y V] per group).  8 or 16 contiguous bytes per lane, as dwords.  Padding beyond the row is not written.
+      constexpr int S = (int)sizeof(TO);
+      if (active) {
+        const YuvMatrix fk = yuv_load_matrix(p.from_rgb);
+        const float cmax = S == 1 ? 255.0f : p.code_max;  // (YUY2: compile-time constants)
+        const int sh = S == 1 ? 0 : p.code_shift;
+        uint32_t* wo = reinterpret_cast<uint32_t*>(static_cast<char*>(const_cast<void*>(p.kout.p)) + (long long)b * p.kout.image +
+                                                   (long long)y * p.kout.pitch + (size_t)x * 2 * sizeof(TO));
+        [[maybe_unused]] const uint32_t sel = yuv_packed_selector(p.kout.order);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          uint32_t ly[2];
+          float pu[2], pv[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int k = 2 * h + i;
+            float c[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) c[j] = __builtin_amdgcn_fmed3f(of[k * COUT + j], 0.0f, 1.0f);
+            ly[i] = yuv_luma_code(fk, c, cmax, sh);
+            pu[i] = yuv_chroma_linear(fk, 1, c);
+            pv[i] = yuv_chroma_linear(fk, 2, c);
+          }
+          const uint32_t cu = yuv_chroma_code(fk, 1, pu[0] + pu[1], cmax, sh, 0.5f);  // the horizontal pair is the whole footprint
+          const uint32_t cv = yuv_chroma_code(fk, 2, pv[0] + pv[1], cmax, sh, 0.5f);
+          if constexpr (S == 1) {
+            wo[h] = yuv_packed_perm(ly[0] | (cu << 8) | (ly[1] << 16) | (cv << 24), sel);
+          } else {
+            wo[2 * h] = ly[0] | (cu << 16);
+            wo[2 * h + 1] = ly[1] | (cv << 16);
+          }
+        }
+      }
+    } else if constexpr (SURFOUT) {
       // A semi-planar surface, NV12 (uint8 code words) or P010 / P016 (uint16, IoParams::code_max / code_shift): sizeof(TO)
       // dwords of Y per lane and row; the chroma of the lane's two 2 x 2 blocks after the second row, as many dwords (U0 V0
       // U1 V1) into the pair's interleaved UV row (block x / 2 starts at sample x of its row, as the luma does).  Padding
@@ -803,6 +864,16 @@ hipError_t launch_io(const ApplyIoArgs& a, hipStream_t s, const UpAdd* up = null
     p.from_rgb = a.yuvp->from_rgb;
     if constexpr (OUT == kOutI016) p.code_max = (float)((1 << a.yuvp->out_bits) - 1);  // code_shift stays 0: low bits
   }
+  if constexpr (PX == kPxYuvPacked) {
+    p.kin = a.yuvk->in;
+    p.to_rgb = a.yuvk->to_rgb;
+    p.kout = a.yuvk->out;
+    p.from_rgb = a.yuvk->from_rgb;
+    if constexpr (OUT == kOutY216) {
+      p.code_max = (float)((1 << a.yuvk->out_bits) - 1);
+      p.code_shift = 16 - a.yuvk->out_bits;
+    }
+  }
   if constexpr (PX == kPxYuv) {
     p.yin = a.yuv->in;
     p.to_rgb = a.yuv->to_rgb;
@@ -874,7 +945,13 @@ inline const char* io_label(const ApplyIoArgs& a) {
   static thread_local char label[64];
   // a 4:2:2 / 4:4:4 surface (include/hdrnet_amd_yuv_chroma.h): container, layout and sample width -- nv16 / p216 semi-planar,
   // i422 / i216 / i444 / i416 planar
-  if (a.yuvp && a.yuvp->chroma != kChroma420) {
+  // a packed 4:2:2 surface (include/hdrnet_amd_yuv_packed.h): byte order and sample width -- yuy2 / uyvy / yvyu, y216
+  if (a.yuvk) {
+    static const char* const order[3] = {"yuy2", "uyvy", "yvyu"};
+    const char* const in = a.input_dtype == 2 ? "y216" : order[a.yuvk->in.order];
+    snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", in, a.yuvk->out_kind >= 2 ? in : surface[a.yuvk->out_kind],
+             suffix[io_guide_form(a)]);
+  } else if (a.yuvp && a.yuvp->chroma != kChroma420) {
     static const char* const planar[2][2] = {{"i422", "i216"}, {"i444", "i416"}};
     const char* const in = planar[a.yuvp->chroma == kChroma444][a.input_dtype == 2];
     snprintf(label, sizeof label, "apply_fwd_io/%s->%s%s", in,
@@ -921,6 +998,7 @@ hipError_t launch_apply_fwd_io_px(const ApplyIoArgs& a, hipStream_t s);
 // apply_fwd_io_u16.hip (launch.hip.h): the same launch with a 16-bit output (a.output_dtype == 2)
 // apply_fwd_io_yuv_planar.hip (launch.hip.h): the same launch for a planar YUV surface (a.yuvp)
 // apply_fwd_io_yuv_422.hip, apply_fwd_io_yuv_planar_422.hip / _444.hip (launch.hip.h): ... of another chroma layout
+// apply_fwd_io_yuv_packed.hip (launch.hip.h): the same launch for a packed 4:2:2 surface (a.yuvk)
 // apply_fwd_io_upadd_yuv.hip (launch.hip.h): the same launch for a 4:2:0 surface + the pyramid's up-add (`coarse`)
 
 }  // namespace hdrnet_amd

@@ -15,6 +15,7 @@
 #include "../../include/hdrnet_amd_yuv.h"
 #include "../../include/hdrnet_amd_yuv_planar.h"
 #include "../../include/hdrnet_amd_yuv_chroma.h"
+#include "../../include/hdrnet_amd_yuv_packed.h"
 #include "../../include/hdrnet_amd_u16_out.h"
 #include "../../include/hdrnet_amd_pyramid_io.h"
 #include "../../include/hdrnet_amd_pyramid_yuv.h"
@@ -612,7 +613,10 @@ extern "C" {
 //          yuv420p16le surfaces in, RGB or a planar surface out)
 // 0.2.9.0: + include/hdrnet_amd_yuv_chroma.h: the eight entry points of the three headers above with a `chroma` argument (4:2:2
 //          NV16 / P210 / P216 / yuv422p..., 4:4:4 yuv444p... surfaces in, RGB or a surface of the input's container and layout out)
-int hdrnet_version(void) { return 291; }
+// 0.2.9.2: + include/hdrnet_amd_yuv_packed.h: hdrnet_yuv_packed_to_rgb_f32, hdrnet_lowres_input_yuv_packed,
+//          hdrnet_bilateral_slice_apply_io_yuv_packed, hdrnet_bilateral_slice_apply_io_curves_yuv_packed (YUY2 / UYVY / YVYU /
+//          Y210 / Y216 surfaces in, RGB or a packed surface of the input's width and order out)
+int hdrnet_version(void) { return 292; }
 
 const char* hdrnet_last_error(void) { return g_error; }
 
@@ -2151,6 +2155,176 @@ int hdrnet_bilateral_slice_apply_io_curves_yuv_planar_chroma(const float* grid, 
   return apply_io_yuv_planar_impl(what, grid,
                                   io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out),
                                   io, sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+// ---- include/hdrnet_amd_yuv_packed.h: packed 4:2:2 surfaces -- the semi-planar 4:2:2 entry points above on ONE plane ------------
+// The extents are check_yuv_extents' for HDRNET_CHROMA_422, the guides' rules and the launch tail those of every wire-format
+// forward; what one woven plane adds is stated once below and shared by the four entry points (`which`: "input" / "output").
+namespace {
+
+int check_yuv_packed_surface(const char* what, const char* which, int sample_dtype, const hdrnet_amd::YuvPackedSurface& s, int B,
+                             int H, int W) {
+  if (sample_dtype != 1 && sample_dtype != 2)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown sample dtype code of the %s surface (%d; 1 u8, 2 u16: packed surfaces "
+                "hold integer samples)", what, which, sample_dtype);
+  if (s.order < HDRNET_PACKED_YUYV || s.order > HDRNET_PACKED_YVYU)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: unknown byte order code %d of the %s surface (0 YUYV, 1 UYVY, 2 YVYU)", what, s.order,
+                which);
+  if (sample_dtype == 2 && s.order != HDRNET_PACKED_YUYV)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: uint16 samples (Y210 / Y216) take HDRNET_PACKED_YUYV only (order %d of the %s "
+                "surface: UYVY and YVYU are 8-bit orders)", what, s.order, which);
+  const long long row = 2LL * W * sample_dtype;
+  if (s.pitch < row)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitch of the %s surface is below the row's %lld bytes (pitch=%d; a packed row "
+                "holds 2 W samples)", what, which, row, s.pitch);
+  if (s.pitch & 3)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the pitch of the %s surface must be a multiple of 4 (pitch=%d)", what, which, s.pitch);
+  if (s.image < 0 || (s.image & 3))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image stride of the %s surface must be a non-negative multiple of 4", what, which);
+  if (B > 1 && s.image < (long long)s.pitch * H)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the image stride of the %s surface is below its plane (pitch * H)", what, which);
+  return HDRNET_OK;
+}
+
+int check_yuv_packed_pointers(const char* what, const char* which, const hdrnet_amd::YuvPackedSurface& s, const float* coef) {
+  if (!s.p) return fail(HDRNET_INVALID_ARGUMENT, "%s: null %s surface", what, which);
+  if (!coef) return fail(HDRNET_INVALID_ARGUMENT, "%s: null constants of the %s surface (the 12 floats)", what, which);
+  if (((uintptr_t)s.p | (uintptr_t)coef) & 3u)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: the %s surface and its constants must be 4-B aligned", what, which);
+  return HDRNET_OK;
+}
+
+// ... and of a fused forward's surfaces and output.  io.out.p is `out` whatever the output kind.
+int check_yuv_packed_io_values(const char* what, const hdrnet_amd::YuvPackedIo& io, int sample_dtype, int B, int H, int W,
+                               int Cin, int Cout, int has_offset) {
+  if (int rc = check_yuv_extents(what, B, H, W, HDRNET_CHROMA_422)) return rc;
+  if (int rc = check_yuv_packed_surface(what, "input", sample_dtype, io.in, B, H, W)) return rc;
+  if (int rc = check_chroma_out_kind(what, io.out_kind, sample_dtype, false)) return rc;
+  const bool surface_out = io.out_kind >= HDRNET_CHROMA_OUT_SURFACE_U8;
+  if (surface_out && (io.out_kind == HDRNET_CHROMA_OUT_SURFACE_U8) != (sample_dtype == 1))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a packed surface output has the input's sample width (output kind %d, a %s surface, "
+                "for sample_dtype %d)", what, io.out_kind, io.out_kind == HDRNET_CHROMA_OUT_SURFACE_U8 ? "uint8" : "uint16",
+                sample_dtype);
+  if (io.out_kind == HDRNET_CHROMA_OUT_SURFACE_U16 && io.out_bits != 10 && io.out_bits != 16)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: out_bits must be 10 (Y210) or 16 (Y216), got %d", what, io.out_bits);
+  if (Cin != 3 || Cout != 3 || !has_offset)
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: a YUV surface needs Cin = Cout = 3 with offset (the op sees R, G, B)", what);
+  if (surface_out) return check_yuv_packed_surface(what, "output", sample_dtype, io.out, B, H, W);
+  return HDRNET_OK;
+}
+
+int check_yuv_packed_io_pointers(const char* what, const hdrnet_amd::YuvPackedIo& io) {
+  if (int rc = check_yuv_packed_pointers(what, "input", io.in, io.to_rgb)) return rc;
+  if (io.out_kind >= HDRNET_CHROMA_OUT_SURFACE_U8) return check_yuv_packed_pointers(what, "output", io.out, io.from_rgb);
+  if (!io.out.p || ((uintptr_t)io.out.p & (io.out_kind == HDRNET_CHROMA_OUT_RGB_F32 ? 15u : 3u)))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: null or misaligned out (float32 frames 16-B, uint8 frames 4-B aligned)", what);
+  return HDRNET_OK;
+}
+
+// The two fused entry points (`what`): apply_io_yuv_impl's checks in its order.  `io`: the call's surfaces as given, io.out.p
+// the RGB frame where the output is one.  A guide map AND a guide network is refused here (the entry points this mirrors let
+// the map win): a caller who passes both has made a mistake one of them would hide.
+int apply_io_yuv_packed_impl(const char* what, const float* grid, const IoGuide& g, hdrnet_amd::YuvPackedIo io, int sample_dtype,
+                             int B, int H, int W, int GH, int GW, int GD, int Cin, int Cout, int has_offset, void* stream) {
+  using namespace hdrnet_amd;
+  char prefix[96];
+  snprintf(prefix, sizeof prefix, "%s: ", what);
+  if (int rc = check_common(B, H, W, GH, GW, GD)) return rc;
+  if (int rc = g.curves ? check_curves_knots(prefix, g.n) : check_guide_flags(g.flags)) return rc;
+  if (int rc = check_yuv_packed_io_values(what, io, sample_dtype, B, H, W, Cin, Cout, has_offset)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_packed_io_pointers(what, io)) return rc;
+  if (g.curves) {
+    if (!grid || !g.conv1 || !g.shifts || !g.slopes || !g.conv2)
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid or a curves parameter)", what);
+  } else {
+    if (!grid) return fail(HDRNET_INVALID_ARGUMENT, "%s: null buffer (grid)", what);
+    if (g.guide && (g.conv1 || g.conv2))
+      return fail(HDRNET_INVALID_ARGUMENT, "%s: either a guide map or the guide network must be given, not both", what);
+    if (int rc = check_guide_given(prefix, g.guide, g.conv1, g.conv2, g.n)) return rc;
+  }
+  const bool surface_out = io.out_kind >= HDRNET_CHROMA_OUT_SURFACE_U8;
+  ApplyIoArgs a{grid, g.guide, nullptr, nullptr, B, H, W, GH, GW, GD, Cin, Cout, true,
+                sample_dtype, surface_out ? sample_dtype : io.out_kind == HDRNET_CHROMA_OUT_RGB_F32 ? 0 : 1, 1.0f, g.conv1,
+                g.conv2, g.n, g.guide_out, g.shifts, g.slopes};
+  if (int rc = set_io_guide(a, g, prefix, "npts <= 16")) return rc;
+  if (surface_out) {
+    io.out.order = io.in.order;  // a surface out has the input's byte order
+    if (io.out_kind == HDRNET_CHROMA_OUT_SURFACE_U8) io.out_bits = 0;
+  } else {  // an RGB frame out: a.out
+    a.out = const_cast<void*>(io.out.p);
+    io.out = YuvPackedSurface{};
+    io.from_rgb = nullptr;
+    io.out_bits = 0;
+  }
+  a.yuvk = &io;
+  return launch_io(a, nullptr, 0, 0, g.curves ? "BilateralSliceApplyIOCurvesYuvPacked" : "BilateralSliceApplyIOYuvPacked",
+                   "the packed 4:2:2 YUV forward supports Cin = Cout = 3 with offset, W % 4 == 0, aligned buffers", stream);
+}
+
+}  // namespace
+
+int hdrnet_yuv_packed_to_rgb_f32(const void* surface, int sample_dtype, int pitch, long long image_stride, int order, int B,
+                                 int H, int W, const float* to_rgb, float* rgb, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_yuv_packed_to_rgb_f32";
+  const YuvPackedSurface in{surface, pitch, order, image_stride};
+  if (int rc = check_yuv_extents(what, B, H, W, HDRNET_CHROMA_422)) return rc;
+  if (int rc = check_yuv_packed_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if ((long long)B * H * W == 0) return finish_noop();
+  if (int rc = check_yuv_packed_pointers(what, "input", in, to_rgb)) return rc;
+  if (!rgb || ((uintptr_t)rgb & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: rgb must be a 16-B aligned buffer", what);
+  return finish_launch(launch_yuv_packed_to_rgb(in, sample_dtype, to_rgb, rgb, B, H, W, static_cast<hipStream_t>(stream)), what,
+                       "yuv_packed_to_rgb");
+}
+
+int hdrnet_lowres_input_yuv_packed(const void* surface, int sample_dtype, int pitch, long long image_stride, int order, int B,
+                                   int H, int W, const float* to_rgb, float* lowres, int net_input_size, void* stream) {
+  using namespace hdrnet_amd;
+  const char* what = "hdrnet_lowres_input_yuv_packed";
+  const YuvPackedSurface in{surface, pitch, order, image_stride};
+  if (int rc = check_yuv_extents(what, B, H, W, HDRNET_CHROMA_422)) return rc;
+  if (int rc = check_yuv_packed_surface(what, "input", sample_dtype, in, B, H, W)) return rc;
+  if (H <= 0 || W <= 0 || net_input_size <= 0 || (long long)net_input_size * net_input_size * 12 >= (1LL << 31))
+    return fail(HDRNET_INVALID_ARGUMENT, "%s: non-positive extent (H=%d, W=%d, net_input_size=%d)", what, H, W, net_input_size);
+  if (B == 0) return finish_noop();
+  if (int rc = check_yuv_packed_pointers(what, "input", in, to_rgb)) return rc;
+  if (!lowres || ((uintptr_t)lowres & 15u)) return fail(HDRNET_INVALID_ARGUMENT, "%s: lowres must be a 16-B aligned buffer", what);
+  SamplePrepArgs a{surface, nullptr, sample_dtype, 0, 1.0f, 1.0f, B, H, W, nullptr, B, H, W, nullptr, nullptr, lowres,
+                   net_input_size, false};
+  a.yuv_packed = &in;
+  a.yuv_to_rgb = to_rgb;
+  a.yuv_chroma = HDRNET_CHROMA_422;
+  return finish_launch(launch_sample_prep(a, static_cast<hipStream_t>(stream)), what, "sample_prep");
+}
+
+int hdrnet_bilateral_slice_apply_io_yuv_packed(const float* grid, const float* guide, const void* surface, int sample_dtype,
+                                               int pitch, long long image_stride, int order, int B, int H, int W,
+                                               const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                               int has_offset, const float* guide_conv1, const float* guide_conv2,
+                                               int n_feats, float* guide_out, unsigned flags, int output_kind, void* out,
+                                               int out_pitch, long long out_image_stride, const float* from_rgb,
+                                               int out_bits, void* stream) {
+  const hdrnet_amd::YuvPackedIo io{{surface, pitch, order, image_stride}, to_rgb, output_kind,
+                                   {out, out_pitch, order, out_image_stride}, from_rgb, out_bits};
+  return apply_io_yuv_packed_impl("hdrnet_bilateral_slice_apply_io_yuv_packed", grid,
+                                  io_guide_network(guide, guide_conv1, guide_conv2, n_feats, guide_out, flags), io, sample_dtype,
+                                  B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
+}
+
+int hdrnet_bilateral_slice_apply_io_curves_yuv_packed(const float* grid, const void* surface, int sample_dtype, int pitch,
+                                                      long long image_stride, int order, int B, int H, int W,
+                                                      const float* to_rgb, int GH, int GW, int GD, int Cin, int Cout,
+                                                      int has_offset, const float* guide_ccm, const float* guide_shifts,
+                                                      const float* guide_slopes, const float* guide_mix, int npts,
+                                                      const void* prepared, float* guide_out, int output_kind, void* out,
+                                                      int out_pitch, long long out_image_stride, const float* from_rgb,
+                                                      int out_bits, void* stream) {
+  const hdrnet_amd::YuvPackedIo io{{surface, pitch, order, image_stride}, to_rgb, output_kind,
+                                   {out, out_pitch, order, out_image_stride}, from_rgb, out_bits};
+  return apply_io_yuv_packed_impl("hdrnet_bilateral_slice_apply_io_curves_yuv_packed", grid,
+                                  io_guide_curves(guide_ccm, guide_shifts, guide_slopes, guide_mix, npts, prepared, guide_out), io,
+                                  sample_dtype, B, H, W, GH, GW, GD, Cin, Cout, has_offset, stream);
 }
 
 size_t hdrnet_bilateral_slice_apply_grad_workspace_bytes(int B, int H, int W, int GH, int GW,

@@ -65,6 +65,10 @@ struct ApplyIoArgs {
   // (1 u8 = I420, 2 u16), `out` the RGB frame of output_dtype -- or, with yuvp->out_kind == kYuvPlanarOutPlanar
   // (output_dtype = input_dtype), unused
   const struct YuvPlanarIo* yuvp = nullptr;
+  // ... or a PACKED 4:2:2 one (include/hdrnet_amd_yuv_packed.h; apply_fwd_io_yuv_packed.hip): input_dtype is the sample dtype
+  // (1 u8 = YUY2 / UYVY / YVYU, 2 u16 = Y210 / Y216), `out` the RGB frame of output_dtype -- or, with a surface output
+  // (output_dtype = input_dtype), unused
+  const struct YuvPackedIo* yuvk = nullptr;
   // output_dtype == 2 (include/hdrnet_amd_u16_out.h): the white level of the uint16 frame, which has the input's pixel format
   float output_white_level = 0.0f;
 };
@@ -95,6 +99,17 @@ struct YuvPlanarIo {
   const float* from_rgb;  // device, 12 floats
   int out_bits = 0;       // kYuvPlanarOutPlanar: 8 (uint8 samples), 10 or 16 (uint16): the code's bits, in the LOW bits
   int chroma = kChroma420;  // both surfaces' chroma layout (include/hdrnet_amd_yuv_chroma.h): kChroma420 / 422 / 444
+};
+
+// The packed 4:2:2 counterpart (include/hdrnet_amd_yuv_packed.h): out_kind is HDRNET_CHROMA_OUT_* -- a float32 / uint8 RGB
+// frame, or a packed surface of the input's sample width and order
+struct YuvPackedIo {
+  YuvPackedSurface in;
+  const float* to_rgb;    // device, 12 floats
+  int out_kind;           // HDRNET_CHROMA_OUT_*
+  YuvPackedSurface out;   // out_kind == HDRNET_CHROMA_OUT_SURFACE_U8 / _U16
+  const float* from_rgb;  // device, 12 floats
+  int out_bits = 0;       // HDRNET_CHROMA_OUT_SURFACE_U16: 10 (Y210) or 16 (Y216) significant bits, in the high bits
 };
 
 // Gradients of BilateralSliceApply, and of BilateralSlice as the apply op without an input: slice = true,
@@ -268,6 +283,8 @@ struct SamplePrepArgs {
   const YuvPlanarSurface* yuv_planar = nullptr;
   // the surface's chroma layout (include/hdrnet_amd_yuv_chroma.h): kChroma420 / kChroma422 / kChroma444 (planar only)
   int yuv_chroma = kChroma420;
+  // ... or of a packed 4:2:2 one (hdrnet_lowres_input_yuv_packed): yuv_to_rgb as above
+  const YuvPackedSurface* yuv_packed = nullptr;
 };
 hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s);
 
@@ -292,6 +309,11 @@ bool apply_fwd_io_yuv_422_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io_yuv_422(const ApplyIoArgs& a, hipStream_t s, const char** name);
 hipError_t launch_yuv_422_to_rgb(const YuvSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H, int W,
                                  hipStream_t s);
+// apply_fwd_io_yuv_packed.hip -- ... and for packed 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h: a.yuvk)
+bool apply_fwd_io_yuv_packed_supported(const ApplyIoArgs& a);
+hipError_t launch_apply_fwd_io_yuv_packed(const ApplyIoArgs& a, hipStream_t s, const char** name);
+hipError_t launch_yuv_packed_to_rgb(const YuvPackedSurface& in, int sample_dtype, const float* to_rgb, float* rgb, int B, int H,
+                                    int W, hipStream_t s);
 bool apply_fwd_io_yuv_planar_chroma_supported(const ApplyIoArgs& a);
 hipError_t launch_apply_fwd_io_yuv_planar_422(const ApplyIoArgs& a, hipStream_t s, const char** name);
 hipError_t launch_apply_fwd_io_yuv_planar_444(const ApplyIoArgs& a, hipStream_t s, const char** name);

@@ -61,7 +61,7 @@ struct PrepJob {
   WhiteLevel white;
   int dtype;   // 0 f32 (copied unscaled), 1 u8, 2 u16
   int lowres;  // 0: [B][H][W][3];  1: [B][n][n][3];  2: [B][n][n][3] gathered from a YUV surface (PrepParams::yuv);
-               // 3: ... from a planar YUV surface (PrepParams::yuv_planar)
+               // 3: ... from a planar YUV surface (PrepParams::yuv_planar);  4: ... from a packed 4:2:2 one (::yuv_packed)
 };
 
 struct PrepParams {
@@ -78,7 +78,12 @@ struct PrepParams {
   int px_stride, px_b_first;
   // the low-res gather of a semi-planar YUV surface (hdrnet_lowres_input_yuv, job kind 2): the planes and the 12 constants
   // of yuv_convert.hip.h; the job's dtype is the sample dtype
-  YuvSurface yuv;
+  // (... or of a packed 4:2:2 one, hdrnet_lowres_input_yuv_packed, job kind 4: one plane of the pair, in the pair's bytes --
+  // the parameter block of every other job stays what it was)
+  union {
+    YuvSurface yuv;
+    YuvPackedSurface yuv_packed;
+  };
   const float* yuv_to_rgb;
   // ... of a planar one (hdrnet_lowres_input_yuv_planar, job kind 3): three planes, the same constants
   YuvPlanarSurface yuv_planar;
@@ -350,6 +355,7 @@ __device__ __forceinline__ void lowres_job(const PrepParams& p, const PrepJob& j
 // bits of lowres_job on the float32 frame hdrnet_yuv_to_rgb_f32 writes.
 // (`surf`: p.yuv, or p.yuv_planar for a planar surface -- the chroma then comes from two planes)
 // (CH: the surface's chroma layout -- 4:2:2 takes the chroma from (y, x >> 1), 4:4:4 from (y, x))
+// (a packed 4:2:2 surface, p.yuv_packed: luma and chroma from the pixel's group of ONE plane)
 template <typename T, int CH, typename SURF>
 __device__ __forceinline__ void lowres_job_yuv(const PrepParams& p, const SURF& surf, const PrepJob& job, int b) {
   const int npx = p.n * p.n;
@@ -378,7 +384,10 @@ __global__ __launch_bounds__(kThreads) void sample_prep_kernel(const PrepParams 
   const int b = blockIdx.y;
   if (job.lowres >= 2) {  // a YUV surface, semi-planar (2) or planar (3): no geometry record, no packed source
     if constexpr (!RAGGED) {
-      if (job.lowres == 2) {
+      if (job.lowres == 4) {
+        if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma422>(p, p.yuv_packed, job, b);
+        else lowres_job_yuv<uint16_t, kChroma422>(p, p.yuv_packed, job, b);
+      } else if (job.lowres == 2) {
         if (p.yuv_chroma == kChroma422) {
           if (job.dtype == 1) lowres_job_yuv<uint8_t, kChroma422>(p, p.yuv, job, b);
           else lowres_job_yuv<uint16_t, kChroma422>(p, p.yuv, job, b);
@@ -419,7 +428,8 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   if (a.image_input) { p.job[nj++] = PrepJob{a.src_input, a.image_input, io_white_level(a.input_white_level), a.input_dtype, 0}; full = true; }
   if (a.image_target) { p.job[nj++] = PrepJob{a.src_target, a.image_target, io_white_level(a.target_white_level), a.target_dtype, 0}; full = true; }
   if (a.lowres_input)
-    p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype, a.yuv_planar ? 3 : a.yuv ? 2 : 1};
+    p.job[nj++] = PrepJob{a.src_input, a.lowres_input, io_white_level(a.input_white_level), a.input_dtype,
+                           a.yuv_packed ? 4 : a.yuv_planar ? 3 : a.yuv ? 2 : 1};
   if (nj == 0 || a.B == 0) return hipSuccess;
   p.ops = a.ops;
   p.N = a.N; p.Hs = a.Hs; p.Ws = a.Ws; p.B = a.B; p.H = a.H; p.W = a.W; p.n = a.n;
@@ -435,6 +445,10 @@ hipError_t launch_sample_prep(const SamplePrepArgs& a, hipStream_t s) {
   p.yuv_chroma = a.yuv_chroma;
   if (a.yuv) {
     p.yuv = *a.yuv;
+    p.yuv_to_rgb = a.yuv_to_rgb;
+  }
+  if (a.yuv_packed) {
+    p.yuv_packed = *a.yuv_packed;
     p.yuv_to_rgb = a.yuv_to_rgb;
   }
   if (a.yuv_planar) {

@@ -1,7 +1,8 @@
 // Semi-planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv.h): NV12 (uint8) and P010 / P016 (uint16) in, NV12 out -- and
 // P010 / P016 out (include/hdrnet_amd_u16_out.h) -- and planar surfaces, I420 / yuv420p10le / yuv420p16le, in and out
 // (include/hdrnet_amd_yuv_planar.h): the same functions with the chroma in two planes -- and 4:2:2 / 4:4:4 surfaces
-// (include/hdrnet_amd_yuv_chroma.h): the same functions with a compile-time chroma layout, 4:2:0 by default.
+// (include/hdrnet_amd_yuv_chroma.h): the same functions with a compile-time chroma layout, 4:2:0 by default -- and packed
+// 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h): YUY2 / UYVY / YVYU / Y210 / Y216, the 4:2:2 pair woven into one plane.
 //
 // Every kernel that reads a surface -- hdrnet_yuv_to_rgb_f32 (apply_fwd_io_yuv.hip), the low-res gather
 // (sample_prep.hip) and the fused forward (apply_fwd_io.hip.h) -- converts a pixel with the ONE function below, and the
@@ -176,6 +177,73 @@ __device__ __forceinline__ void yuv_load_px(const YuvPlanarSurface& s, const Yuv
                                              (long long)yuv_chroma_row(CH, row) * s.pitch_v);
   const int xc = CH == kChroma444 ? x : x >> 1;
   yuv_to_rgb_px(k, (float)yp[x], (float)up[xc], (float)vp[xc], rgb);
+}
+
+// ---- packed 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h): YUY2 / UYVY / YVYU (uint8) and Y210 / Y216 (uint16) ------------
+// ONE plane [B][H][2 W] samples: the NV16 / P210 surface with its two planes woven into one, a group of four samples
+// (Y0 U Y1 V in HDRNET_PACKED_YUYV order) per horizontal pixel pair.  Padding is never read and never written.
+struct YuvPackedSurface {
+  const void* p;
+  int pitch;   // bytes per row
+  int order;   // HDRNET_PACKED_*: uint8 samples take all three, uint16 samples YUYV only
+  long long image;  // bytes between images
+};
+constexpr int kPackedYUYV = 0, kPackedUYVY = 1, kPackedYVYU = 2;
+
+// The byte order costs no instantiation: a uint8 group's dword is normalised to Y0 U Y1 V by one v_perm_b32 whose selector
+// is wave-uniform (result byte i = source byte sel[i]).  UYVY swaps bytes 0 <-> 1 and 2 <-> 3, YVYU bytes 1 <-> 3: both are
+// their own inverse, so the store applies the SAME selector to the Y0 U Y1 V dword it has built.
+__device__ __forceinline__ uint32_t yuv_packed_selector(int order) {
+  return order == kPackedUYVY ? 0x02030001u : order == kPackedYVYU ? 0x01020300u : 0x03020100u;
+}
+__device__ __forceinline__ uint32_t yuv_packed_perm(uint32_t w, uint32_t sel) { return __builtin_amdgcn_perm(w, w, sel); }
+
+// yuv_load_quad of a packed surface: a lane's 4 pixels x .. x + 3 (x % 4 == 0) are two groups, 8 contiguous bytes of uint8
+// samples (two dwords) or 16 of uint16 (four: [Y0 U][Y1 V][Y2 U'][Y3 V'], the code in the high bits as P210 / P216).  The
+// same yuv_to_rgb_px on the same samples: the bits of yuv_load_quad<TI, kChroma422> on the unwoven (y, uv) pair.
+template <typename TI>
+__device__ __forceinline__ void yuv_load_quad(const YuvPackedSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                              float* __restrict__ rgb) {
+  static_assert(sizeof(TI) == 1 || sizeof(TI) == 2, "uint8 or uint16 samples");
+  const uint32_t* wp = reinterpret_cast<const uint32_t*>(static_cast<const char*>(s.p) + (long long)b * s.image +
+                                                         (long long)row * s.pitch + (size_t)x * 2 * sizeof(TI));
+  float Y[4], U[2], V[2];
+  if constexpr (sizeof(TI) == 1) {
+    const uint32_t sel = yuv_packed_selector(s.order);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {  // (dwords: the surface promises 4-byte alignment, not 8)
+      const uint32_t w = yuv_packed_perm(wp[h], sel);
+      Y[2 * h] = (float)(w & 0xffu); U[h] = (float)((w >> 8) & 0xffu);
+      Y[2 * h + 1] = (float)((w >> 16) & 0xffu); V[h] = (float)(w >> 24);
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t w0 = wp[2 * h], w1 = wp[2 * h + 1];
+      Y[2 * h] = (float)(w0 & 0xffffu); U[h] = (float)(w0 >> 16);
+      Y[2 * h + 1] = (float)(w1 & 0xffffu); V[h] = (float)(w1 >> 16);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) yuv_to_rgb_px(k, Y[q], U[q >> 1], V[q >> 1], rgb + 3 * q);
+}
+
+// One pixel (row, x) of a packed surface, any x (the low-res gather): the pixel's group is samples 4 (x >> 1) .. + 3 of its
+// row -- one aligned dword for uint8 samples, normalised as above; three scalar sample loads for uint16.  (CH: for callers
+// written on the chroma layout; a packed surface is 4:2:2.)
+template <typename TI, int CH = kChroma422>
+__device__ __forceinline__ void yuv_load_px(const YuvPackedSurface& s, const YuvMatrix& k, int b, int row, int x,
+                                            float* __restrict__ rgb) {
+  static_assert(CH == kChroma422, "a packed surface is 4:2:2");
+  const char* rp = static_cast<const char*>(s.p) + (long long)b * s.image + (long long)row * s.pitch;
+  const int g = x >> 1;
+  if constexpr (sizeof(TI) == 1) {
+    const uint32_t w = yuv_packed_perm(reinterpret_cast<const uint32_t*>(rp)[g], yuv_packed_selector(s.order));
+    yuv_to_rgb_px(k, (float)((w >> (16 * (x & 1))) & 0xffu), (float)((w >> 8) & 0xffu), (float)(w >> 24), rgb);
+  } else {
+    const TI* sp = reinterpret_cast<const TI*>(rp) + 4 * (size_t)g;
+    yuv_to_rgb_px(k, (float)sp[2 * (x & 1)], (float)sp[1], (float)sp[3], rgb);
+  }
 }
 
 // Surface output: code values clamped to code_max and truncated (the + 0.5 of the rounding is in the bias of from_rgb),

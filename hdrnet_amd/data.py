@@ -192,6 +192,36 @@ def lowres_input_yuv_planar(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, t
     return out
 
 
+def lowres_input_yuv_packed(surface: torch.Tensor, to_rgb: torch.Tensor, format: str,  # noqa: A002
+                            net_input_size: int = 256, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``lowres_input_yuv(..., chroma="422")`` of a PACKED 4:2:2 surface (``hdrnet_lowres_input_yuv_packed``,
+    include/hdrnet_amd_yuv_packed.h): ``surface`` ``[B, H, 2 W]`` in the NAMED ``format`` (``"yuy2"`` / ``"uyvy"`` /
+    ``"yvyu"`` uint8, ``"y210"`` / ``"y216"`` uint16), possibly pitched; ``to_rgb`` the 12 floats of
+    ``yuv.yuv_coefficients`` on the device.  The bits of ``lowres_input_yuv`` on the de-interleaved planes.  One launch on
+    the current stream; capturable."""
+    from . import hdrnet_ops
+    what = "lowres_input_yuv_packed"
+    format = hdrnet_ops.packed_format(what, format)  # noqa: A001
+    surface, B, H, W, surf = hdrnet_ops._yuv_packed_surface(surface, format, what)
+    to_rgb = hdrnet_ops._yuv_constants("to_rgb", to_rgb, what)
+    n = int(net_input_size)
+    if n <= 0:
+        raise ValueError(f"{what}: net_input_size must be positive, got {net_input_size}")
+    for nm, t in (("surface", surface), ("to_rgb", to_rgb)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{nm} is on {t.device}: sample preparation runs on an MI355X (HIP) device only")
+    k = to_rgb.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, n, n, 3), dtype=torch.float32, device=surface.device)
+    else:
+        _check_out("lowres_input", out, (B, n, n, 3), surface.device)
+    with torch.cuda.device(surface.device):
+        rc = _lib.load().hdrnet_lowres_input_yuv_packed(surface.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(), n,
+                                                        _stream(surface.device))
+    _lib.check(rc, "LowresInput")
+    return out
+
+
 def _rotate_mode(rotate) -> str:
     if rotate == "even":
         return "even"

@@ -1544,6 +1544,163 @@ def bilateral_slice_apply_io_yuv_deep(grid: torch.Tensor, y: torch.Tensor, uv: t
                              chroma=chroma)
 
 
+# ---- packed YUV 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h) -----------------------------------------------------------
+_PACKED_DTYPE = {"yuy2": torch.uint8, "yuyv": torch.uint8, "uyvy": torch.uint8, "yvyu": torch.uint8,
+                 "y210": torch.uint16, "y216": torch.uint16}
+
+
+def packed_format(what: str, format) -> str:  # noqa: A002
+    """The ``format`` of a packed 4:2:2 surface: ``"yuy2"`` (= ``"yuyv"``), ``"uyvy"``, ``"yvyu"`` (uint8) or ``"y210"`` /
+    ``"y216"`` (uint16).  NAMED by the caller; it is never guessed from the tensor."""
+    if not isinstance(format, str) or format not in _lib.PACKED_ORDER:
+        raise ValueError(f"{what}: unknown format {format!r} (takes {', '.join(repr(k) for k in _lib.PACKED_ORDER)})")
+    return format
+
+
+def _yuv_packed_surface(surface, format, what: str, name: str = "surface"):  # noqa: A002
+    """The rules of a packed surface, on the host: ``[B, H, 2 W]`` samples (or ``[B, H, W, 2]`` viewed as that) of the
+    format's dtype, last-dimension stride 1, row stride >= 2 W samples, pitches multiples of 4 bytes, W % 4 == 0.  Returns
+    ``(surface, B, H, W, (sample_dtype, pitch, image_stride, order))``, pitches in bytes."""
+    if not isinstance(surface, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(surface).__name__}")
+    want = _PACKED_DTYPE[format]
+    if surface.dtype != want:
+        raise TypeError(f"{what}: format={format!r} is a {str(want).replace('torch.', '')} format, {name} is {surface.dtype} "
+                        "('yuy2' / 'uyvy' / 'yvyu' need uint8, 'y210' / 'y216' need uint16)")
+    if surface.dim() == 4 and surface.shape[3] == 2 and surface.stride(3) == 1 and surface.stride(2) == 2:
+        surface = surface.as_strided((surface.shape[0], surface.shape[1], 2 * surface.shape[2]),
+                                     (surface.stride(0), surface.stride(1), 1))
+    if surface.dim() != 3 or surface.shape[2] % 2:
+        raise ValueError(f"{what}: {name} should be [B, H, 2 W] samples (or [B, H, W, 2] with unit sample strides), got "
+                         f"{tuple(surface.shape)} with strides {tuple(surface.stride())}")
+    B, H, W = surface.shape[0], surface.shape[1], surface.shape[2] // 2
+    if W % 4 != 0:
+        raise ValueError(f"{what}: W % 4 != 0 (W = {W})")
+    size = surface.element_size()
+    if B * H * W and (surface.stride(2) != 1 or surface.stride(1) < 2 * W or (surface.stride(1) * size) % 4
+                      or (surface.stride(0) * size) % 4):
+        raise ValueError(f"{what}: {name} must have last-dimension stride 1, a row stride >= 2 W samples and pitches that are "
+                         f"multiples of 4 bytes, got strides {tuple(surface.stride())}")
+    return surface, B, H, W, (_YUV_SAMPLE[want], surface.stride(1) * size, surface.stride(0) * size, _lib.PACKED_ORDER[format])
+
+
+def packed_default_bits(format: str) -> int:  # noqa: A002
+    """Significant bits per sample a packed format implies: 8, 10 (``"y210"``) or 16 (``"y216"``)."""
+    return 10 if format == "y210" else 16 if format == "y216" else 8
+
+
+def yuv_packed_to_rgb(surface: torch.Tensor, to_rgb: torch.Tensor, format: str) -> torch.Tensor:  # noqa: A002
+    """A packed YUV 4:2:2 surface -> float32 ``[B, H, W, 3]`` RGB in [0, 1] (``hdrnet_yuv_packed_to_rgb_f32``): ``surface``
+    ``[B, H, 2 W]`` (or ``[B, H, W, 2]``), ``format`` ``"yuy2"`` / ``"uyvy"`` / ``"yvyu"`` (uint8) or ``"y210"`` / ``"y216"``
+    (uint16, the code in the high bits); ``to_rgb`` the 12 floats of ``yuv.yuv_coefficients`` on the device.  Exactly
+    ``yuv_to_rgb(y, uv, to_rgb, chroma="422")`` on the de-interleaved planes, bit for bit.  The surface may be pitched;
+    padding is not read.  No autograd."""
+    what = "yuv_packed_to_rgb"
+    format = packed_format(what, format)  # noqa: A001
+    surface, B, H, W, surf = _yuv_packed_surface(surface, format, what)
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    for nm, t in (("surface", surface), ("to_rgb", to_rgb)):
+        _require_gpu(nm, t)
+    dev = surface.device
+    k = to_rgb.detach().contiguous()
+    out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().hdrnet_yuv_packed_to_rgb_f32(surface.data_ptr(), *surf, B, H, W, k.data_ptr(), out.data_ptr(),
+                                                      _stream(dev))
+    _lib.check(rc, "YuvPackedToRgb")
+    return out
+
+
+def bilateral_slice_apply_io_yuv_packed(grid: torch.Tensor, surface: torch.Tensor, to_rgb: torch.Tensor, format: str,  # noqa: A002
+                                        guide: Optional[torch.Tensor] = None,
+                                        guide_conv1: Optional[torch.Tensor] = None,
+                                        guide_conv2: Optional[torch.Tensor] = None,
+                                        guide_curves: Optional[Tuple[torch.Tensor, ...]] = None,
+                                        return_guide: bool = False, fast_sigmoid: bool = False, prescaled: bool = False,
+                                        curves_prepared: Optional[torch.Tensor] = None,
+                                        out: str = "rgb", out_dtype: Optional[torch.dtype] = None,
+                                        from_rgb: Optional[torch.Tensor] = None, out_surface=None,
+                                        out_bits: Optional[int] = None):
+    """``bilateral_slice_apply_io_yuv(..., chroma="422")`` for a PACKED 4:2:2 surface (include/hdrnet_amd_yuv_packed.h):
+    ``surface`` ``[B, H, 2 W]`` in the NAMED ``format`` -- the NV16 / P210 pair woven into one plane, read as it is; the same
+    bits as that call on the de-interleaved planes.  The guide arguments are those of ``bilateral_slice_apply_io``.
+
+    ``out="rgb"``: ``[B, H, W, 3]`` RGB, ``out_dtype`` float32 (default) or uint8.  ``out="packed"``: a packed surface of the
+    input's format ``[B, H, 2 W]``, encoded by ``from_rgb`` (12 floats; for uint16 formats those of
+    ``yuv.yuv_encode_coefficients(..., out_bits)``): Y per pixel, U and V from the mean of each horizontal pair, truncated.
+    ``out_bits``: 10 or 16 for ``"y210"`` / ``"y216"`` (default: the format's), 8 otherwise.  ``out_surface``: a surface to
+    write into (pitched is fine; padding is not written).  ``return_guide`` appends the guide map.  Cin = Cout = 3 with
+    offset, any H, W % 4 == 0.  No autograd."""
+    what = "bilateral_slice_apply_io_yuv_packed"
+    format = packed_format(what, format)  # noqa: A001
+    if out not in ("rgb", "packed"):
+        raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'packed')")
+    surface, B, H, W, surf = _yuv_packed_surface(surface, format, what)
+    deep = surface.dtype == torch.uint16
+    if out == "rgb":
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"{what}: out_dtype must be float32 or uint8, got {out_dtype}")
+        if from_rgb is not None or out_surface is not None or out_bits is not None:
+            raise ValueError(f"{what}: from_rgb / out_surface / out_bits belong to out='packed'")
+    else:
+        if out_dtype not in (None, surface.dtype):
+            raise TypeError(f"{what}: a packed output has the input's sample dtype {surface.dtype}, got out_dtype = {out_dtype}")
+        if from_rgb is None:
+            raise ValueError(f"{what}: out='packed' needs from_rgb (yuv.yuv_encode_coefficients)")
+        out_bits = packed_default_bits(format) if out_bits is None else out_bits
+        if out_bits not in ((10, 16) if deep else (8,)):
+            raise ValueError(f"{what}: out_bits must be {'10 (Y210) or 16 (Y216)' if deep else '8'} for format={format!r}, got "
+                             f"{out_bits!r}")
+    to_rgb = _yuv_constants("to_rgb", to_rgb, what)
+    _require_f32("grid", grid)
+    if grid.dim() != 5 or grid.shape[0] != B or grid.shape[4] != 12:
+        raise ValueError(f"{what}: grid should be [B, GH, GW, GD, 12] (the 3 -> 3 op with offset) with B = {B}, got "
+                         f"{tuple(grid.shape)}")
+    GH, GW, GD = grid.shape[1:4]
+    tensors = [("grid", grid), ("surface", surface), ("to_rgb", to_rgb)]
+    osurf = None
+    if out == "packed":
+        from_rgb = _yuv_constants("from_rgb", from_rgb, what)
+        tensors.append(("from_rgb", from_rgb))
+        if out_surface is not None:
+            out_surface, oB, oH, oW, osurf = _yuv_packed_surface(out_surface, format, what, "out_surface")
+            if (oB, oH, oW) != (B, H, W):
+                raise ValueError(f"{what}: out_surface should be a surface of {[B, H, 2 * W]}, got {list(out_surface.shape)}")
+            tensors.append(("out_surface", out_surface))
+    curves, g, n = _guide_source(guide, guide_conv1, guide_conv2, guide_curves, curves_prepared, return_guide, (B, H, W), 3,
+                                 map_or_network=_ONE_GUIDE, lone_conv_ok=False, prepared_name="curves_prepared")
+    for nm, t in tensors:
+        _require_gpu(nm, t)
+    dev = surface.device
+    grid = grid.detach().contiguous()
+    k_in = to_rgb.detach().contiguous()
+    if out == "packed":
+        if out_surface is None:  # a tight surface
+            size = surface.element_size()
+            out_surface = torch.empty((B, H, 2 * W), dtype=surface.dtype, device=dev)
+            osurf = (surf[0], 2 * W * size, 2 * W * H * size, surf[3])
+        k_out = from_rgb.detach().contiguous()
+        output = (_lib.CHROMA_OUT["surface_u16" if deep else "surface_u8"], out_surface.data_ptr(), osurf[1], osurf[2],
+                  k_out.data_ptr(), int(out_bits) if deep else 0)
+        result = out_surface
+    else:
+        result = torch.empty((B, H, W, 3), dtype=out_dtype, device=dev)
+        output = (_lib.CHROMA_OUT["rgb_f32" if out_dtype == torch.float32 else "rgb_u8"], result.data_ptr(), 0, 0, None, 0)
+    gout = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_guide else None
+    head = (surface.data_ptr(), *surf, B, H, W, k_in.data_ptr(), GH, GW, GD, 3, 3, 1)
+    with torch.cuda.device(dev):
+        if curves:
+            rc = _lib.load().hdrnet_bilateral_slice_apply_io_curves_yuv_packed(
+                grid.data_ptr(), *head, *(t.data_ptr() for t in g[:4]), n, _ptr(g[4]), _ptr(gout), *output, _stream(dev))
+        else:
+            rc = _lib.load().hdrnet_bilateral_slice_apply_io_yuv_packed(
+                grid.data_ptr(), _ptr(g[0]), *head, _ptr(g[1]), _ptr(g[2]), n, _ptr(gout),
+                _guide_flags(fast_sigmoid, prescaled and g[0] is None), *output, _stream(dev))
+    _lib.check(rc, "BilateralSliceApplyIOYuvPacked")
+    return (result, gout) if return_guide else result
+
+
 # ---- planar YUV 4:2:0 surfaces (include/hdrnet_amd_yuv_planar.h) -----------------------------------------------------------
 def _yuv_planar_surface(y, u, v, what: str, names=("y", "u", "v"), chroma: str = "420"):
     """The rules of a planar surface, on the host: ``y`` ``[B, H, W]``, ``u`` and ``v`` ``[B, H / 2, W / 2]`` of one dtype,

@@ -771,6 +771,57 @@ class HDRNetCurves(nn.Module):
             return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_planar, lowres, y, u, v, to_rgb, out="rgb",
                                           out_dtype=out_dtype, **layout)
 
+    def process_yuv_packed(self, surface: torch.Tensor, format: str, standard: str = "bt709",  # noqa: A002
+                           full_range: bool = False, bits: Optional[int] = None, out: str = "rgb",
+                           out_dtype: Optional[torch.dtype] = None, out_surface=None):
+        """``process_yuv(chroma="422")`` for a PACKED 4:2:2 surface as a capture card or a webcam delivers it
+        (include/hdrnet_amd_yuv_packed.h): ``surface`` ``[B, H, 2 W]`` (or ``[B, H, W, 2]``) on the device in the NAMED
+        ``format`` -- ``"yuy2"`` (= ``"yuyv"``), ``"uyvy"``, ``"yvyu"`` (uint8) or ``"y210"`` / ``"y216"`` (uint16, the code in
+        the high bits).  ``bits=None`` is 8 for the uint8 formats, 10 for ``"y210"`` and 16 for ``"y216"``.
+        ``process_yuv`` step for step -- ``data.lowres_input_yuv_packed`` -> the coefficient network ->
+        ``hdrnet_ops.bilateral_slice_apply_io_yuv_packed`` -- with no de-interleaving pass.  ``out="rgb"``: ``[B, H, W, 3]``
+        float32 (default) or uint8; ``out="packed"``: a surface of the input's format, depth, standard and range
+        (``out_surface``: the surface to write into).  The surface may be pitched.  Capturable."""
+        from . import data, hdrnet_ops, yuv
+        what = f"{type(self).__name__}.process_yuv_packed"
+        if self._process_dtypes == (torch.float32,):
+            raise ValueError(f"{what}: the pyramid model has no packed 4:2:2 path: its surface path is process_wire_yuv "
+                             "(NV12 / P010 / P016; de-interleave and drop to 4:2:0 first), the single-level models' "
+                             "process_yuv_packed takes YUY2 / UYVY / YVYU / Y210 / Y216")
+        if standard not in yuv.STANDARDS:
+            raise ValueError(f"{what}: unknown standard {standard!r} (takes {', '.join(repr(k) for k in yuv.STANDARDS)})")
+        format = hdrnet_ops.packed_format(what, format)  # noqa: A001
+        if out not in ("rgb", "packed"):
+            raise ValueError(f"{what}: unknown out {out!r} (takes 'rgb', 'packed')")
+        surface = hdrnet_ops._yuv_packed_surface(surface, format, what)[0]
+        if out == "packed" and out_dtype not in (None, surface.dtype):
+            raise TypeError(f"{what}: a packed output has the input's dtype ({surface.dtype}), got out_dtype = {out_dtype}")
+        bits = self._packed_bits(what, format, bits)
+        if self.training:
+            raise RuntimeError("process_yuv_packed() is inference: call eval() first")
+        hdrnet_ops._require_gpu("surface", surface)
+        with torch.no_grad():
+            to_rgb, from_rgb = self._yuv_constants(standard, full_range, bits, surface.device)
+            lowres = data.lowres_input_yuv_packed(surface, to_rgb, format, self.params["net_input_size"])
+            if out == "packed":
+                if bits != 8:
+                    from_rgb = self._yuv_encode_constants(standard, full_range, bits, surface.device)
+                return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_packed, lowres, surface, to_rgb, format,
+                                              out="packed", from_rgb=from_rgb, out_bits=bits, out_surface=out_surface)
+            return self._slice_apply_wire(hdrnet_ops.bilateral_slice_apply_io_yuv_packed, lowres, surface, to_rgb, format,
+                                          out="rgb", out_dtype=out_dtype)
+
+    @staticmethod
+    def _packed_bits(what: str, format: str, bits) -> int:  # noqa: A002
+        """``bits`` of a packed format: the format's own where None, else checked against its sample width."""
+        from . import hdrnet_ops, yuv
+        if bits is None:
+            return hdrnet_ops.packed_default_bits(format)
+        if bits not in yuv.BITS or (bits == 8) != (hdrnet_ops.packed_default_bits(format) == 8):
+            raise ValueError(f"{what}: bits = {bits!r} does not fit format={format!r} (uint8 formats: 8; 'y210' / 'y216': 10 "
+                             "or 16)")
+        return int(bits)
+
 
 class HDRNetPointwiseNNGuide(HDRNetCurves):
     """``hdrnet/models.py:199-210``.  The guide network is FUSED into the slice-apply kernel

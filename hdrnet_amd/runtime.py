@@ -180,6 +180,34 @@ class PlanarYuvFrameInference(GraphedInference):
                          [y_like, u_like, v_like], warmup=warmup, check_parameters=check_parameters)
 
 
+class _ProcessYuvPacked(torch.nn.Module):
+    """``model.process_yuv_packed`` as the module a ``GraphedInference`` captures."""
+
+    def __init__(self, model: torch.nn.Module, format, standard, full_range, bits, out, out_dtype):  # noqa: A002
+        super().__init__()
+        self.model, self.format, self.standard, self.full_range, self.bits = model, format, standard, full_range, bits
+        self.out, self.out_dtype = out, out_dtype
+
+    def forward(self, surface: torch.Tensor):
+        return self.model.process_yuv_packed(surface, self.format, standard=self.standard, full_range=self.full_range,
+                                             bits=self.bits, out=self.out, out_dtype=self.out_dtype)
+
+
+class PackedYuvFrameInference(GraphedInference):
+    """``YuvFrameInference`` for PACKED 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h): the captured callable is
+    ``model.process_yuv_packed``.  One input, the surface ``[B, H, 2 W]`` in the NAMED ``format`` (``"yuy2"`` / ``"uyvy"`` /
+    ``"yvyu"`` uint8, ``"y210"`` / ``"y216"`` uint16), copied into a static surface unless it IS the static surface (a
+    capture card can write into it in place).  ``out="packed"``: the static output is a surface of the input's format and
+    depth; ``out="rgb"``: a ``[B, H, W, 3]`` frame of ``out_dtype``.  ``standard``, ``full_range``, ``bits``: as
+    ``process_yuv_packed``.  Beside ``YuvFrameInference``, which keeps its signature."""
+
+    def __init__(self, model: torch.nn.Module, surface_like: torch.Tensor, format: str, standard: str = "bt709",  # noqa: A002
+                 full_range: bool = False, bits=None, out: str = "packed", out_dtype=None, warmup: int = 3,
+                 check_parameters: bool = True):
+        super().__init__(_ProcessYuvPacked(model.eval(), format, standard, full_range, bits, out, out_dtype), [surface_like],
+                         warmup=warmup, check_parameters=check_parameters)
+
+
 class FramePipeline:
     """Independent frames round-robin over ``depth`` HIP streams.
 

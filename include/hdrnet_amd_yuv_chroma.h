@@ -50,6 +50,8 @@
  * Kernel names state container, layout and sample width: nv16 / p216 (semi-planar 4:2:2, uint8 / uint16), i422 / i216 (planar
  * 4:2:2), i444 / i416 (planar 4:4:4) -- e.g. apply_fwd_io/nv16->nv16+nnguide, apply_fwd_io/p216->u8, apply_fwd_io/i422->i422,
  * apply_fwd_io/i444->f32+curvesguide/cells, apply_fwd_io/i416->i416.
+ * (The entry points of include/hdrnet_amd_yuv_packed.h read and write the semi-planar 4:2:2 surface with its two planes woven
+ * into one, under these rules.)
  * Out of scope: packed 4:2:2 / 4:4:4 (YUY2, UYVY, Y210, AYUV, Y410), semi-planar 4:4:4 (NV24, P410), 12-bit depth, sited or
  * bilinear chroma, a surface out in another container, chroma layout or (planar) sample width than the input's, the pyramid
  * model. */

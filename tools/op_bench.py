@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every entry point of the C-ABI on one MI355X (HIP events, rotating buffer sets).
 
-    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|yuv_chroma|u16_out|pyramid_yuv] [--steps 50] [--json out.json] [--tools] [--ragged]
+    python tools/op_bench.py [--workload 4k|1080p|hdrp|refbench|prep|metrics|pyramid_io|pixel_formats|yuv|yuv_planar|yuv_chroma|u16_out|pyramid_yuv|yuv_packed] [--steps 50] [--json out.json] [--tools] [--ragged]
 
 `hdrp` = BASELINE config #5 per GPU (4000x3000, grid 32x32x8x12; also the uint16 / 32767 -> f32 wire
 format of hdrnet/data_pipeline.py:267-274); `refbench` = the reference's own micro-benchmark shape
@@ -32,7 +32,10 @@ process_yuv_planar(..., chroma=..., out="planar") against a hipGraph of the stoc
 4K, yuv422p -> yuv422p and yuv444p -> yuv444p against NV12 -> NV12, all alternating; `pyramid_yuv` = HDRNetGaussianPyrNN on
 decoder surfaces (include/hdrnet_amd_pyramid_yuv.h): a hipGraph of process_wire_yuv, NV12 -> NV12 and P010 -> P010 at 4K and
 1080p, against a hipGraph of yuv_to_rgb -> process -> stock encode, and the finest level's kernel alone at 4K against its RGB
-sibling, all alternating.  --tools loads the tools build and adds the un-fused
+sibling, all alternating; `yuv_packed` = packed 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h): a hipGraph of
+process_yuv_packed(..., out="packed"), yuy2 -> yuy2 and y210 -> y210 at 4K and 1080p, against a hipGraph of the chain a caller
+had before it (strided de-interleave -> process_yuv(chroma="422") -> re-interleave), and the fused kernel alone at 4K against
+its NV16 / P210 sibling, all alternating.  --tools loads the tools build and adds the un-fused
 gradient kernels (variant 3 of the gradient entry points) for A/B.
 
 Reports per-launch microseconds and algorithmic GB/s (SURVEY.md section 8d byte counts):
@@ -117,6 +120,8 @@ def main():
         return yuv_chroma(lib, dev, args)
     if args.workload == "pyramid_yuv":
         return pyramid_yuv(lib, dev, args)
+    if args.workload == "yuv_packed":
+        return yuv_packed(lib, dev, args)
     B, H, W, GH, GW, GD, desc = WORKLOADS[args.workload]
     if args.luma_bins:
         desc = desc.replace(f"x{GD}x12", f"x{args.luma_bins}x12")
@@ -1138,6 +1143,121 @@ def yuv_chroma(lib, dev, args):
     print(f"{name:28s} " + "   ".join(text))
     if args.json:
         json.dump(dict(workload="yuv_chroma", rows=rows), open(args.json, "w"), indent=1)
+
+
+class _PackedDeinterleaveChain(torch.nn.Module):
+    """What a caller with a packed 4:2:2 surface (YUY2, Y210) writes around process_yuv today: a strided de-interleave into the
+    NV16 / P210 pair, process_yuv(chroma="422") with a surface out, and the strided re-interleave."""
+
+    def __init__(self, model, bits):
+        super().__init__()
+        self.model, self.bits, self.out = model, bits, ("nv16" if bits == 8 else "p210")
+
+    def forward(self, surface):
+        B, H, W2 = surface.shape
+        y = surface[:, :, 0::2].contiguous()
+        uv = surface[:, :, 1::2].contiguous()
+        oy, ouv = self.model.process_yuv(y, uv, bits=self.bits, out=self.out, chroma="422")
+        out = torch.empty_like(surface)
+        out[:, :, 0::2] = oy
+        out[:, :, 1::2] = ouv
+        return out
+
+
+def yuv_packed(lib, dev, args):
+    """Packed 4:2:2 surfaces (include/hdrnet_amd_yuv_packed.h) through HDRNetPointwiseNNGuide at 4K and 1080p, yuy2 -> yuy2 and
+    y210 -> y210: one hipGraph of process_yuv_packed(..., out="packed") against one hipGraph of _PackedDeinterleaveChain; both
+    warmed, then run ALTERNATING three times each in one process; reported: the mean of the three and their range.  Beside it,
+    at 4K: the fused guide-network kernel alone, yuy2 -> yuy2 against nv16 -> nv16 and y210 -> y210 against p210 -> p210 (the
+    same bytes per pixel, one plane against two), over buffer sets that together exceed the Infinity Cache, alternating the
+    same way."""
+    from hdrnet_amd import models, yuv
+    from hdrnet_amd.runtime import GraphedInference, PackedYuvFrameInference
+    torch.manual_seed(7)
+    m = models.HDRNetPointwiseNNGuide(dict(batch_norm=False)).to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = []
+
+    def alternate(*runs):
+        for k in range(30):  # all warmed with their shapes
+            for run in runs:
+                run(k)
+        torch.cuda.synchronize()
+        out = [[] for _ in runs]
+        for _ in range(3):
+            for o, run in zip(out, runs):
+                o.append(timeit(run, args.steps, rounds=1)[0])
+        return out
+
+    def samples(bits, *shape):
+        t = torch.randint(0, 2 ** bits, shape, device=dev, dtype=torch.int32, generator=gen)
+        return t.to(torch.uint8) if bits == 8 else (t << (16 - bits)).to(torch.uint16)
+
+    for H, W in ((2160, 3840), (1080, 1920)):
+        for fmt, bits in (("yuy2", 8), ("y210", 10)):
+            surfaces = [samples(bits, 1, H, 2 * W) for _ in range(3)]
+            new = PackedYuvFrameInference(m, surfaces[0], fmt, out="packed")
+            base = GraphedInference(_PackedDeinterleaveChain(m, bits), [surfaces[0]])
+            assert torch.equal(new(surfaces[1]), base(surfaces[1])), "the two paths write the same surface, bit for bit"
+            b, n = alternate(lambda k: base(surfaces[k % 3]), lambda k: new(surfaces[k % 3]))
+            mb, mn = statistics.mean(b), statistics.mean(n)
+            spread = max(b) - min(b)
+            name = f"{H}x{W} model, {fmt} -> {fmt}"
+            rows.append(dict(op=name, us_chain=round(mb, 2), us_chain_min=round(min(b), 2), us_chain_max=round(max(b), 2),
+                             us_fused=round(mn, 2), us_fused_min=round(min(n), 2), us_fused_max=round(max(n), 2),
+                             faster_beyond_chain_spread=bool(mb - mn > spread)))
+            print(f"{name:40s} de-interleave chain {mb:8.2f} us ({min(b):8.2f} .. {max(b):8.2f})   process_yuv_packed {mn:8.2f} us "
+                  f"({min(n):8.2f} .. {max(n):8.2f})   fused / chain {mn / mb:6.3f}   "
+                  f"faster by more than the chain's spread: {mb - mn > spread}")
+            del new, base, surfaces
+
+    # the kernel alone at 4K: the same grid and guide network, one plane against the plane pair
+    H, W = 2160, 3840
+    GH, GW, GD = 16, 16, 8
+    grid = torch.rand((1, GH, GW, GD, 12), device=dev, generator=gen)
+    conv1 = (torch.randn((16, 4), device=dev, generator=gen) * 0.8).contiguous()
+    conv2 = (torch.randn((17,), device=dev, generator=gen) * 0.5).contiguous()
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(lib.hdrnet_last_error().decode())
+
+    for fmt, bits, semi in (("yuy2", 8, "nv16"), ("y210", 10, "p210")):
+        S = 1 if bits == 8 else 2
+        dt = torch.uint8 if bits == 8 else torch.uint16
+        to_rgb = torch.from_numpy(yuv.yuv_coefficients("bt709", False, bits)[0]).to(dev)
+        from_rgb = torch.from_numpy(yuv.yuv_encode_coefficients("bt709", False, bits)).to(dev)
+        nsets = max(3, -(-int(CACHE_BYTES * 1.5) // (H * W * 4 * S)))
+        e = lambda *shape: torch.empty(shape, device=dev, dtype=dt)  # noqa: E731
+        sets = [dict(s=samples(bits, 1, H, 2 * W), y=samples(bits, 1, H, W), uv=samples(bits, 1, H, W), os=e(1, H, 2 * W),
+                     oy=e(1, H, W), ouv=e(1, H, W)) for _ in range(nsets)]
+        kind, out_bits = (2, 0) if bits == 8 else (3, bits)
+
+        def packed_kernel(k):
+            t = sets[k % nsets]
+            check(lib.hdrnet_bilateral_slice_apply_io_yuv_packed(
+                grid.data_ptr(), None, t["s"].data_ptr(), S, 2 * W * S, H * 2 * W * S, 0, 1, H, W, to_rgb.data_ptr(), GH, GW, GD, 3,
+                3, 1, conv1.data_ptr(), conv2.data_ptr(), 16, None, _lib.GUIDE_SIGMOID_FAST, kind, t["os"].data_ptr(), 2 * W * S,
+                H * 2 * W * S, from_rgb.data_ptr(), out_bits, stream))
+
+        def semi_kernel(k):
+            t = sets[k % nsets]
+            check(lib.hdrnet_bilateral_slice_apply_io_yuv_chroma(
+                grid.data_ptr(), None, t["y"].data_ptr(), t["uv"].data_ptr(), S, W * S, W * S, H * W * S, H * W * S, 1, 1, H, W,
+                to_rgb.data_ptr(), GH, GW, GD, 3, 3, 1, conv1.data_ptr(), conv2.data_ptr(), 16, None, _lib.GUIDE_SIGMOID_FAST, kind,
+                t["oy"].data_ptr(), t["ouv"].data_ptr(), W * S, W * S, H * W * S, H * W * S, from_rgb.data_ptr(), out_bits, stream))
+
+        q, p = alternate(semi_kernel, packed_kernel)
+        name = f"{H}x{W} kernel, +nnguide, {fmt} -> {fmt} against {semi} -> {semi}"
+        rows.append({"op": name, "us_semi": round(statistics.mean(q), 2), "us_semi_min": round(min(q), 2),
+                     "us_semi_max": round(max(q), 2), "us_packed": round(statistics.mean(p), 2), "us_packed_min": round(min(p), 2),
+                     "us_packed_max": round(max(p), 2), "packed_over_semi": round(statistics.mean(p) / statistics.mean(q), 3)})
+        print(f"{name:60s} {semi} {statistics.mean(q):8.2f} us ({min(q):8.2f} .. {max(q):8.2f})   {fmt} {statistics.mean(p):8.2f} us "
+              f"({min(p):8.2f} .. {max(p):8.2f})   packed / semi-planar {statistics.mean(p) / statistics.mean(q):6.3f}")
+        del sets
+    if args.json:
+        json.dump(dict(workload="yuv_packed", rows=rows), open(args.json, "w"), indent=1)
 
 
 class _QuantiseChain(torch.nn.Module):
